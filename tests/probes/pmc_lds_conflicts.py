@@ -1,7 +1,7 @@
 """LDS bank-conflict fraction per kernel from two rocprofv3 PMC passes (evidence tooling, not a test).
 
-    rocprofv3 --pmc SQ_LDS_BANK_CONFLICT --output-format csv -d out_c -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
-    rocprofv3 --pmc SQ_LDS_IDX_ACTIVE   --output-format csv -d out_a -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --pmc SQ_LDS_BANK_CONFLICT --output-format csv -d out_c -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --pmc SQ_LDS_IDX_ACTIVE   --output-format csv -d out_a -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
     python3 tests/probes/pmc_lds_conflicts.py <conflict csv> <active csv> [out.json]
 
 Sums over the batch launches (grid > 10^5 threads) of each library kernel; conflict_fraction = SQ_LDS_BANK_CONFLICT /
@@ -24,7 +24,7 @@ def agg(path, counter):
 def main():
     c = agg(sys.argv[1], "SQ_LDS_BANK_CONFLICT")
     a = agg(sys.argv[2], "SQ_LDS_IDX_ACTIVE")
-    rec = {"command": "rocprofv3 --pmc SQ_LDS_BANK_CONFLICT (and, separately, --pmc SQ_LDS_IDX_ACTIVE) --output-format csv -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline",
+    rec = {"command": "rocprofv3 --pmc SQ_LDS_BANK_CONFLICT (and, separately, --pmc SQ_LDS_IDX_ACTIVE) --output-format csv -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline",
            "kernels": {}}
     for k in sorted(a, key=lambda k: -a[k][1]):
         if k in c and a[k][1] > 0:

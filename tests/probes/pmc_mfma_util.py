@@ -1,8 +1,8 @@
 """f64 matrix-pipe utilisation of the two MFMA kernels from two rocprofv3 PMC passes (evidence tooling, not a test).
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d out_b -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
-    rocprofv3 --pmc GRBM_GUI_ACTIVE          --output-format csv -d out_g -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d out_b -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --pmc GRBM_GUI_ACTIVE          --output-format csv -d out_g -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
     python3 tests/probes/pmc_mfma_util.py <busy counter_collection.csv> <gui counter_collection.csv> [out.json]
 
 One counter per pass.  For each kernel only its largest-grid launches are taken (the panel-0 update / the J*Q1 of a pipelined

@@ -1,8 +1,8 @@
 """HBM traffic of the level-0 trailing update from two rocprofv3 PMC passes (diagnostic / evidence tooling, not a test).
 
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out_f -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
-    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out_w -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --pmc FETCH_SIZE --output-format csv -d out_f -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --pmc WRITE_SIZE --output-format csv -d out_w -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline
     python3 tests/probes/pmc_update_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> [out.json] [batch=384]
 
 Counters are collected in separate passes (one counter per run) and corrected as MI355X_MICROARCH.md's HBM / rocprofv3 section
@@ -54,7 +54,7 @@ def main():
     assert len(fetch) == nl and len(write) == nl, (len(fetch), len(write), nl)
     hbm = (2.0 * sum(fetch) + sum(write)) * 1024.0 / L
     alg = sum(per_launch_alg) / L
-    rec = {"command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) -- python3 bench.py --steps 1 --warmup 1 --cpu-budget 0 --no-roofline",
+    rec = {"command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) -- python3 bench.py --full --steps 1 --warmup 1 --cpu-budget 0 --no-roofline",
            "kernel": KERNEL, "FETCH_SIZE_KB_per_launch": fetch, "WRITE_SIZE_KB_per_launch": write,
            "correction": "gfx950: FETCH_SIZE doubled (128-B requests tallied at 64 B), WRITE_SIZE as reported",
            "hbm_bytes_per_launch_avg": hbm, "algorithmic_bytes_per_launch_avg": alg, "ratio": hbm / alg,

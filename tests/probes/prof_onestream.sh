@@ -3,7 +3,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/onestream}; mkdir -p $O
 export ENLSIP_GN_PIPELINE=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python3 bench.py --steps 4 --warmup 1 --cpu-budget 0 --no-roofline ${@:2} > $O/bench.json 2> $O/ks.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python3 bench.py --full --steps 4 --warmup 1 --cpu-budget 0 --no-roofline ${@:2} > $O/bench.json 2> $O/ks.err
 cp $O/ks/*/*kernel_stats.csv $O/kernel_stats.csv
 python3 - <<PY
 import csv, glob, collections

@@ -11,9 +11,9 @@ UB_M=4032 UB_PAIR_ONLY=1 $B 384 0 0 | grep PAIRONLY >> $O/sweep_other.txt
 UB_M=4224 UB_PAIR_ONLY=1 $B 384 6 0 | grep PAIRONLY >> $O/sweep_other.txt
 UB_M=3968 UB_PAIR_ONLY=1 $B 384 0 0 | grep PAIRONLY >> $O/sweep_other.txt
 cat $O/sweep_m4096.txt $O/sweep_other.txt
-python3 bench.py --cpu-budget 0 > $O/c2.json 2> $O/c2.err
+python3 bench.py --full --cpu-budget 0 > $O/c2.json 2> $O/c2.err
 python3 tests/probes/bench_fields.py base < $O/c2.json || true
 export ENLSIP_GN_PIPELINE=0
-rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 bench.py --batch 1 --steps 3 --warmup 1 --cpu-budget 0 --no-roofline > $O/single.json 2> $O/kt.err
+rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 bench.py --full --batch 1 --steps 3 --warmup 1 --cpu-budget 0 --no-roofline > $O/single.json 2> $O/kt.err
 cp $O/kt/*/*kernel_trace.csv $O/single_kernel_trace.csv; rm -rf $O/kt
 echo done

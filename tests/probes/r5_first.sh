@@ -5,7 +5,7 @@ echo "[1] pytest -m gpu"; timeout -k 10 900 python3 -m pytest tests -m gpu -q --
 echo "[2] C4 A/B"
 for i in 1 2; do
   for d in 0 1; do
-    ENLSIP_GN_LA_DEEP=$d timeout -k 10 300 python3 bench.py --config C4 --steps 5 --cpu-budget 0 2> $O/c4_deep${d}_$i.err | python3 tests/probes/bench_fields.py deep $d >> $O/c4_ab.txt
+    ENLSIP_GN_LA_DEEP=$d timeout -k 10 300 python3 bench.py --full --config C4 --steps 5 --cpu-budget 0 2> $O/c4_deep${d}_$i.err | python3 tests/probes/bench_fields.py deep $d >> $O/c4_ab.txt
   done
 done
 cat $O/c4_ab.txt

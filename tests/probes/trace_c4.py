@@ -1,5 +1,5 @@
 """Kernel timeline of C4's local stage from a rocprofv3 kernel trace (diagnostic tooling, not a test):
-    rocprofv3 --kernel-trace --output-format csv -d out -- python3 bench.py --config C4 --steps 2 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --kernel-trace --output-format csv -d out -- python3 bench.py --full --config C4 --steps 2 --warmup 1 --cpu-budget 0 --no-roofline
     python3 tests/probes/trace_c4.py out
 Per kernel class of the LAST solve: launches, busy time, share that ran beside a kernel of the other queue; span / union / idle."""
 import csv, glob, sys

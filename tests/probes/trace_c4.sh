@@ -2,7 +2,7 @@
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=${1:-gpurun_out/c4trace}; mkdir -p $O
-rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 bench.py --config C4 --steps 2 --warmup 1 --cpu-budget 0 --no-roofline > $O/bench.json 2> $O/kt.err
+rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 bench.py --full --config C4 --steps 2 --warmup 1 --cpu-budget 0 --no-roofline > $O/bench.json 2> $O/kt.err
 python3 tests/probes/trace_c4.py $O/kt > $O/summary.txt
 cat $O/summary.txt
 python3 - <<PY

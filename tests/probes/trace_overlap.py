@@ -1,6 +1,6 @@
 """Timeline of the two pipelined halves of a default bench.py step from a rocprofv3 kernel trace (diagnostic tooling, not a test).
 
-    rocprofv3 --kernel-trace --output-format csv -d out -- python3 bench.py --steps 3 --warmup 1 --cpu-budget 0 --no-roofline
+    rocprofv3 --kernel-trace --output-format csv -d out -- python3 bench.py --full --steps 3 --warmup 1 --cpu-budget 0 --no-roofline
     python3 tests/probes/trace_overlap.py out
 
 For the launches of the timed steps (grids of batch/2 problems) it prints, per kernel class, its busy time per step, the time during

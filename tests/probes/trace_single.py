@@ -1,5 +1,5 @@
 """Kernel timeline of ONE C2 solve (batch 1) from a rocprofv3 kernel trace (diagnostic tooling, not a test):
-    rocprofv3 --kernel-trace --output-format csv -d out -- python3 bench.py --config C2 --batch 1 --steps 6 --warmup 3 --cpu-budget 0 --no-roofline --no-live-pmc
+    rocprofv3 --kernel-trace --output-format csv -d out -- python3 bench.py --full --config C2 --batch 1 --steps 6 --warmup 3 --cpu-budget 0 --no-roofline --no-live-pmc
     python3 tests/probes/trace_single.py out
 Takes the last solve (the kernels after the last k_vt / k_constraint launch): per kernel class launches, busy time, and the idle
 time in front of its launches (start - end of the previous kernel on any queue)."""

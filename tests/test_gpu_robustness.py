@@ -93,7 +93,7 @@ def test_bench_two_rank_control_flow_rehearsal():
     env = dict(os.environ, ENLSIP_BENCH_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "32", "--cpu-budget", "0"]
+           "--batch", "32", "--cpu-budget", "0", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -117,7 +117,7 @@ def test_bench_starts_its_own_ranks(config):
     env = dict(os.environ, ENLSIP_BENCH_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", config, "--steps", "2", "--warmup", "1",
-           "--cpu-budget", "0"]
+           "--cpu-budget", "0", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-2500:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -131,6 +131,30 @@ def test_bench_starts_its_own_ranks(config):
         assert rec["scaling"] == "strong" and rec["metric"].startswith("GN subproblem solves/sec at (m=262144,n=1024)")
         assert rec["results_check"]["rankJ2"] == 1024 and rec["roofline"]["bound"] == "mfma"
         assert rec["stage_ms"]["local"] > 0 and rec["stage_ms"]["combine"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline line only (no results check, roofline or CPU leg) and `--dump-outputs` writes
+    what its last timed step returned: float64 arrays of the bench's own shapes, problem 0's p equal to the LAPACK oracle's."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, m, n, t = 8, 4096, 512, 64
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+           "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2500:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and rec["value"] > 0 and rec["unit"] == "solves/s"
+    assert rec["dtype"] == "f64" and rec["higher_is_better"] is True
+    assert not {"results_check", "roofline", "cpu_baseline", "single_problem_latency_ms"} & set(rec)
+    arrays = {name: np.load(tmp_path / f"{name}.npy") for name in ("p", "b", "d", "jpvtJ2")}
+    assert {k: v.shape for k, v in arrays.items()} == {"p": (B, n), "b": (B, t), "d": (B, m), "jpvtJ2": (B, n)}
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in arrays.values())
+    ref = go.gn_subproblem(*synth.make_problem(0, m, n, t))
+    assert rel(arrays["p"][0], ref.p) <= 1e-11
 
 
 @pytest.mark.gpu
