@@ -250,14 +250,28 @@ static void big_lds(KernelT k, size_t bytes) {
 // dispatch helpers over the rows-per-lane instantiations of the single-workgroup kernels
 // Problems with at most 64 rows run with 256 or 512 threads and an LDS carve sized to the problem, so that batches of
 // small problems (C3, C5) keep several workgroups resident per CU; larger ones use 1024 threads.
-static void launch_constraint(int rows, int batch, hipStream_t s, ConstraintArgs a) {
-    if (launch_constraint_small(batch, s, a)) return;
+// tk: each problem's own t of a ragged batch (device), NULL for a uniform batch
+static void launch_constraint(int rows, int batch, hipStream_t s, ConstraintArgs a, const int* tk = nullptr) {
+    if (launch_constraint_small(batch, s, a, tk)) return;
     constraint_carve(a.n, a.t, a.fa_done, a.nv, a.blkd, a.gld, a.matd, a.need_T, a.fl_done);
     const size_t lds = constraint_lds_bytes(a.nv, a.blkd, a.gld, a.matd);
     if (!a.fa_done && (size_t)a.n * a.t > (size_t)CMAT_DOUBLES) GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_GLOBAL);
     GN_ROUTE(rows <= 32 ? ENLSIP_GN_ROUTE_CONSTRAINT_LDS_R1_256 : rows <= 64 ? ENLSIP_GN_ROUTE_CONSTRAINT_LDS_R1_512 :
              rows <= 128 ? ENLSIP_GN_ROUTE_CONSTRAINT_LDS_R2 : rows <= 256 ? ENLSIP_GN_ROUTE_CONSTRAINT_LDS_R4 :
              rows <= 512 ? ENLSIP_GN_ROUTE_CONSTRAINT_LDS_R8 : ENLSIP_GN_ROUTE_CONSTRAINT_LDS_R16);
+    if (tk) {       // ragged batch: the same instantiations reading each problem's own t (gn_kernels_constraint.hpp)
+        auto launch_ragged = [&](void (*k)(ConstraintArgs, const int*), int nth) {
+            big_lds(k, lds);
+            hipLaunchKernelGGL(k, dim3(batch), dim3(nth), lds, s, a, tk);
+        };
+        if (rows <= 32) launch_ragged(k_constraint_ragged<1, 8, 256>, 256);
+        else if (rows <= 64) launch_ragged(k_constraint_ragged<1, 8, 512>, 512);
+        else if (rows <= 128) launch_ragged(k_constraint_ragged<2, 8, 1024>, 1024);
+        else if (rows <= 256) launch_ragged(k_constraint_ragged<4, 8, 1024>, 1024);
+        else if (rows <= 512) launch_ragged(k_constraint_ragged<8, 4, 1024>, 1024);
+        else launch_ragged(k_constraint_ragged<16, 2, 1024>, 1024);
+        return;
+    }
     if (rows <= 32) GN_LAUNCH_BIG((k_constraint<1, 8, 256>), dim3(batch), dim3(256), lds, s, a);
     else if (rows <= 64) GN_LAUNCH_BIG((k_constraint<1, 8, 512>), dim3(batch), dim3(512), lds, s, a);
     else if (rows <= 128) GN_LAUNCH_BIG((k_constraint<2, 8, 1024>), dim3(batch), dim3(1024), lds, s, a);
@@ -906,7 +920,10 @@ static int extreme_shifts(enlsip_gn_handle h, long long m, long long n, long lon
 // ---------------------------------------------------------------------------------------------
 // Constraint stage with many constraints: both pivoted factorisations through the distributed QR (one launch per pivot step),
 // then k_constraint only does the rank decisions, the triangular solves and the T blocks.
-static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long batch, long long n, long long t) {
+// Ragged batch (tk != NULL): the launch shapes stay those of t_max; each problem's records carry its own column counts, F_L11 is
+// factored as the t_max x kA matrix [L11; 0] (its padded rows and carried entries are zero, so they change nothing), and the copies
+// out of the working storage take each problem's own sizes and write F_A's zero columns.
+static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long batch, long long n, long long t, const int* tk = nullptr) {
     const Plan& P = h->plan;
     hipStream_t s = h->stream;
     const int kA = P.kA;
@@ -938,8 +955,13 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
     ProbState* stA = (ProbState*)carve((size_t)batch * sizeof(ProbState));
     ProbState* stL = (ProbState*)carve((size_t)batch * sizeof(ProbState));
     const unsigned gb = (unsigned)((batch + 255) / 256);
-    hipLaunchKernelGGL(k_fake_state, dim3(gb), dim3(256), 0, s, stA, (int)batch, kA, (int)t);
-    hipLaunchKernelGGL(k_fake_state, dim3(gb), dim3(256), 0, s, stL, (int)batch, kA, kA);
+    if (tk) {
+        hipLaunchKernelGGL(k_fake_state_ragged, dim3(gb), dim3(256), 0, s, stA, (int)batch, (int)n, tk, 0);
+        hipLaunchKernelGGL(k_fake_state_ragged, dim3(gb), dim3(256), 0, s, stL, (int)batch, (int)n, tk, 1);
+    } else {
+        hipLaunchKernelGGL(k_fake_state, dim3(gb), dim3(256), 0, s, stA, (int)batch, kA, (int)t);
+        hipLaunchKernelGGL(k_fake_state, dim3(gb), dim3(256), 0, s, stL, (int)batch, kA, kA);
+    }
 
     QdArgs q{};
     q.n = (int)n; q.ldw = 0; q.ldr = (int)ldc; q.prob0 = 0;
@@ -965,20 +987,35 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
     q.rows = (int)n; q.in_mode = 1; q.Ain = ca.At; q.ldain = ca.ldat; q.sAin = ca.strideAt;
     q.tau = h->tauA; q.sTau = P.sTauA; q.jpvt = h->jpvtA; q.sJ = P.sJA; q.state = stA;
     factor((int)n, (int)t, kA);
-    hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)t, (unsigned)batch), dim3(256), 0, s, h->FA, n, P.sFA, cRt, ldc, sRtc, (int)n, (int)t);
+    if (tk)
+        hipLaunchKernelGGL(k_copy_cols_ragged, dim3((unsigned)t, (unsigned)batch), dim3(256), 0, s, h->FA, n, P.sFA, (const double*)cRt, ldc,
+                           sRtc, (int)n, (int)t, (int)n, tk, 0);
+    else
+        hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)t, (unsigned)batch), dim3(256), 0, s, h->FA, n, P.sFA, cRt, ldc, sRtc, (int)n, (int)t);
     // ---- F_L11: the t x kA lower trapezoid R_A', carrying b_buff = -cx[F_A.p] ----------------------------------------
-    hipLaunchKernelGGL(k_bbuff, dim3((unsigned)((t + 255) / 256), (unsigned)batch), dim3(256), 0, s, cBq, sVec, ca.cx, ca.stride_cx,
-                       h->jpvtA, P.sJA, (int)t);
+    if (tk)
+        hipLaunchKernelGGL(k_bbuff_ragged, dim3((unsigned)((t + 255) / 256), (unsigned)batch), dim3(256), 0, s, cBq, sVec, ca.cx,
+                           ca.stride_cx, (const long long*)h->jpvtA, P.sJA, (int)t, tk);
+    else
+        hipLaunchKernelGGL(k_bbuff, dim3((unsigned)((t + 255) / 256), (unsigned)batch), dim3(256), 0, s, cBq, sVec, ca.cx, ca.stride_cx,
+                           h->jpvtA, P.sJA, (int)t);
     q.rows = (int)t; q.in_mode = 2; q.Ain = h->FA; q.ldain = n; q.sAin = P.sFA; q.rin = cBq; q.sRin = sVec; q.Lout = cL; q.sLout = sLc;
     q.tau = h->tauL; q.sTau = P.sTauL; q.jpvt = h->jpvtL; q.sJ = P.sJL; q.state = stL;
     factor((int)t, kA, (int)std::min<long long>(t, kA));
-    hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)kA, (unsigned)batch), dim3(256), 0, s, h->FL, t, P.sFL, cRt, ldc, sRtc, (int)t, kA);
-    hipLaunchKernelGGL(k_copy_cols, dim3(1, (unsigned)batch), dim3(256), 0, s, cQb, sVec, sVec, cRt + (size_t)kA * ldc, ldc, sRtc, (int)t, 1);
+    if (tk) {
+        hipLaunchKernelGGL(k_copy_cols_ragged, dim3((unsigned)kA, (unsigned)batch), dim3(256), 0, s, h->FL, t, P.sFL, (const double*)cRt,
+                           ldc, sRtc, (int)t, kA, (int)n, tk, 1);
+        hipLaunchKernelGGL(k_copy_cols_ragged, dim3(1, (unsigned)batch), dim3(256), 0, s, cQb, sVec, sVec, (const double*)cRt, ldc, sRtc,
+                           (int)t, 1, (int)n, tk, 2);
+    } else {
+        hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)kA, (unsigned)batch), dim3(256), 0, s, h->FL, t, P.sFL, cRt, ldc, sRtc, (int)t, kA);
+        hipLaunchKernelGGL(k_copy_cols, dim3(1, (unsigned)batch), dim3(256), 0, s, cQb, sVec, sVec, cRt + (size_t)kA * ldc, ldc, sRtc, (int)t, 1);
+    }
     // ---- ranks, triangular solves, T blocks ---------------------------------------------------------------------------
     ca.fa_done = 1; ca.fl_done = 1; ca.need_T = 1;
     ca.Lmat = cL; ca.ldL = ldc; ca.sL = sLc; ca.qb = cQb; ca.sQb = sVec;
     h->cdist.L = cL; h->cdist.ldL = ldc; h->cdist.sL = sLc; h->cdist.qb = cQb; h->cdist.sQb = sVec; h->cdist.valid = true;
-    launch_constraint((int)std::max(n, t), (int)batch, s, ca);
+    launch_constraint((int)std::max(n, t), (int)batch, s, ca, tk);
     GN_HIP(hipGetLastError());
     return 0;
 }
@@ -1005,10 +1042,11 @@ static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m
     ca.FL = h->FL; ca.sFL = P.sFL; ca.tauL = h->tauL; ca.sTauL = P.sTauL; ca.jpvtL = h->jpvtL; ca.sJL = P.sJL;
     ca.TA = h->TA; ca.sTA = P.sTA; ca.p1 = h->p1; ca.sP1 = P.sP1; ca.bvec = h->bvec; ca.sB = P.sB;
     ca.state = h->state;
+    const int* tk = h->h_tk.empty() ? nullptr : (const int*)h->tkbuf.p;     // ragged batch: each problem's own t
     // many constraints: both factorisations through the distributed pivoted QR
     if (t > 64 && (size_t)n * t > (size_t)CMAT_DOUBLES) {
         GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_DIST);
-        int rcd = run_constraint_dist(h, ca, batch, n, t);
+        int rcd = run_constraint_dist(h, ca, batch, n, t, tk);
         if (rcd) return rcd;
         return scaledA ? unscale_constraint_side(h) : 0;
     }
@@ -1019,12 +1057,15 @@ static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m
         ga.F = h->FA; ga.sF = P.sFA; ga.tau = h->tauA; ga.sTau = P.sTauA; ga.jpvt = h->jpvtA; ga.sJ = P.sJA;
         ga.T = h->TA; ga.sT = P.sTA; ga.prob0 = prob0;
         GN_ROUTE(n <= 256 ? ENLSIP_GN_ROUTE_CONSTRAINT_REG4 : ENLSIP_GN_ROUTE_CONSTRAINT_REG8);
-        if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg<4>, dim3((unsigned)batch), dim3(512), 0, s, ga);
+        if (tk) {
+            if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg_ragged<4>, dim3((unsigned)batch), dim3(512), 0, s, ga, tk);
+            else hipLaunchKernelGGL(k_geqp3_reg_ragged<8>, dim3((unsigned)batch), dim3(512), 0, s, ga, tk);
+        } else if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg<4>, dim3((unsigned)batch), dim3(512), 0, s, ga);
         else hipLaunchKernelGGL(k_geqp3_reg<8>, dim3((unsigned)batch), dim3(512), 0, s, ga);
         ca.fa_done = 1;
     }
     // with F_A done the kernel only factors the t x kA matrix R_A': size its rows-per-lane instantiation (and LDS) for that
-    launch_constraint(ca.fa_done ? (int)std::max<long long>(t, 1) : (int)std::max(n, t), (int)batch, s, ca);
+    launch_constraint(ca.fa_done ? (int)std::max<long long>(t, 1) : (int)std::max(n, t), (int)batch, s, ca, tk);
     GN_HIP(hipGetLastError());
     return scaledA ? unscale_constraint_side(h) : 0;
 }
@@ -1034,7 +1075,8 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
                      const double* dAt, long long ldat, long long strideAt, const double* dcx,
                      double eps_rank, long long dimA_ov, long long dimJ2_ov,
                      double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
-                     long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo = nullptr) {
+                     long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo = nullptr,
+                     const int* htk = nullptr) {
     h->split = 0;   // routing of accessors to the pipeline child is (re)established by the batched entry point
     h->chunk0 = 0;  // ... and to the resident chunk by solve_chunked
     gn_route_acc = 0;
@@ -1060,6 +1102,17 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
     if (!reuse) h->sc_eA = 0;       // (a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it)
     h->rescue_prob.clear();
     hipStream_t s = h->stream;
+    // ragged batch: every problem's own t, kept on the host for the accessors and copied to the device for the constraint kernels
+    int t_min = (int)t;
+    if (htk) {
+        h->h_tk.assign(htk, htk + batch);
+        for (int v : h->h_tk) t_min = std::min(t_min, v);
+        rc = grow(h, h->tkbuf, (size_t)batch * sizeof(int));
+        if (rc) return rc;
+        GN_HIP(hipMemcpyAsync(h->tkbuf.p, h->h_tk.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s));
+    } else if (!reuse) {
+        h->h_tk.clear();
+    }
     if (h->profiling) {
         if (!h->ev_ready) {
             for (int i = 0; i < 8; ++i) GN_HIP(hipEventCreate(&h->ev[i]));
@@ -1086,7 +1139,8 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
 
     // steps 2-4 for the Jacobian side given (the caller's J, rx — or their scaled copies, abs_shift = their power of two)
     auto attempts = [&](const double* dJ, long long ldj, long long strideJ, const double* drx, int abs_shift) -> int {
-    int n2_launch = (int)(n - P.kA);  // speculate rankA = min(n, t); verified after the solve
+    // speculate rankA = min(n, t) (ragged: the smallest min(n, t_k), so that only a rank-deficient A' widens J2); verified after the solve
+    int n2_launch = (int)(n - std::min<long long>(n, t_min));
     for (int attempt = 0; attempt < 2; ++attempt) {
         // 2. JQ1 = J*Q1, d_temp
         JQ1Args qa{};
@@ -1148,7 +1202,10 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
         mark(4);
         GN_TRACE(h, "final kernel done");
         // nominate problems whose largest column norm overflowed or sits at the bottom of the exponent range (gn_rescale.hpp)
-        if (h->rescale_enabled)
+        if (h->rescale_enabled && !h->h_tk.empty())
+            hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt,
+                               P.sRt, (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)batch, (const int*)h->tkbuf.p);
+        else if (h->rescale_enabled)
             hipLaunchKernelGGL(k_extreme_flags, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt, P.sRt,
                                (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)batch);
         GN_HIP(hipGetLastError());
@@ -1168,7 +1225,7 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
         const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
         bool flagged = false;
         for (long long k = 0; k < batch; ++k) flagged = flagged || (h->h_state[k].status & fl);
-        if (flagged && batch == 1) {
+        if (flagged && batch == 1 && !htk) {
             int sJ = 0, sA = 0;
             rc = extreme_shifts(h, m, n, t, dJ, ldj, drx, reuse ? nullptr : dAt, ldat, reuse ? nullptr : dcx, &sJ, &sA);
             if (rc) return rc;
@@ -1203,12 +1260,13 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
                 GN_ROUTE(ENLSIP_GN_ROUTE_RESCALED);
             }
         } else if (flagged) {
-            // a batch: every nominated problem whose inputs are beyond the band goes to a one-problem handle of its own (which
+            // a batch (or a ragged batch of one, whose problem is solved with its own t there): every nominated problem whose inputs are beyond the band goes to a one-problem handle of its own (which
             // rescales in place as above); its outputs land in the caller's slots, the accessors are routed to it
             for (long long k = 0; k < batch; ++k) {
                 if (!(h->h_state[k].status & fl)) continue;
                 int sJ = 0, sA = 0;
-                rc = extreme_shifts(h, m, n, t, dJ + k * strideJ, ldj, drx + k * m, dAt ? dAt + k * strideAt : nullptr, ldat,
+                const long long tk = htk ? htk[k] : t;      // a problem of a ragged batch is rescued with its own t (strides stay t_max)
+                rc = extreme_shifts(h, m, n, tk, dJ + k * strideJ, ldj, drx + k * m, dAt ? dAt + k * strideAt : nullptr, ldat,
                                     dcx ? dcx + k * t : nullptr, &sJ, &sA);
                 if (rc) return rc;
                 if (!sJ && !sA) continue;
@@ -1226,7 +1284,7 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
                 }
                 enlsip_gn_handle r = h->rescue[j];
                 const unsigned long long route_here = gn_route_acc;
-                rc = solve_dev(r, 1, m, n, t, dJ + k * strideJ, ldj, strideJ, drx + k * m, dAt ? dAt + k * strideAt : nullptr, ldat, strideAt,
+                rc = solve_dev(r, 1, m, n, tk, dJ + k * strideJ, ldj, strideJ, drx + k * m, dAt ? dAt + k * strideAt : nullptr, ldat, strideAt,
                                dcx ? dcx + k * t : nullptr, eps_rank, dimA_ov, dimJ2_ov, dp ? dp + k * n : nullptr, db ? db + k * t : nullptr,
                                dd ? dd + k * m : nullptr, nullptr, djA ? djA + k * t : nullptr, djL ? djL + k * P.kA : nullptr,
                                djJ ? djJ + k * n : nullptr, nullptr);
@@ -1302,7 +1360,7 @@ static void tsqr_drop_comm(enlsip_gn_handle h);      // gn_tsqr.inc
 
 extern "C" {
 
-int enlsip_gn_version(void) { return 200; }
+int enlsip_gn_version(void) { return 201; }
 
 // why the last enlsip_gn_create of this thread failed (no handle exists to carry the message): enlsip_gn_last_error(NULL)
 static thread_local std::string g_create_err;
@@ -1585,7 +1643,8 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
                             const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
                             const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
                             double eps_rank, int64_t dimA_ov, int64_t dimJ2_ov, double* dp, double* db, double* dd,
-                            enlsip_gn_info* dinfo, long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo) {
+                            enlsip_gn_info* dinfo, long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo,
+                            const int* htk = nullptr) {
     h->split = 0;
     // one-tile problems of the wave-per-problem pipeline (n <= 64, m <= 512: C3, C5) are a handful of short, uniform launches with
     // nothing latency-bound to hide behind them: the split costs C3 4 % (1.276 -> 1.325 M solves/s without it), C5 nothing
@@ -1616,7 +1675,7 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
                                 ldat, strideAt, dcx ? dcx + b0 * t : nullptr, eps_rank, -1, -1, dp ? dp + b0 * n : nullptr,
                                 db ? db + b0 * t : nullptr, dd ? dd + b0 * m : nullptr, dinfo ? dinfo + b0 : nullptr,
                                 djA ? djA + b0 * t : nullptr, djL ? djL + b0 * kA : nullptr, djJ ? djJ + b0 * n : nullptr,
-                                hinfo ? hinfo + b0 : nullptr);
+                                hinfo ? hinfo + b0 : nullptr, htk ? htk + b0 : nullptr);
             } catch (...) {
                 c->err = "exception in the second pipeline half (out of host memory?)";
                 rc1 = 997;
@@ -1625,7 +1684,7 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
         int rc0;
         try {
             rc0 = solve_dev(h, b0, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, -1, -1, dp, db,
-                            dd, dinfo, djA, djL, djJ, hinfo);
+                            dd, dinfo, djA, djL, djJ, hinfo, htk);
         } catch (...) {
             worker.join();
             throw;
@@ -1638,7 +1697,7 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
         return 0;
     }
     return solve_dev(h, batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, dimA_ov, dimJ2_ov, dp, db,
-                     dd, dinfo, djA, djL, djJ, hinfo);
+                     dd, dinfo, djA, djL, djJ, hinfo, htk);
 }
 
 // Any batch: consecutive chunks of at most GN_MAX_LAUNCH_BATCH problems (the problem index is a grid y / z dimension).  The
@@ -1648,7 +1707,8 @@ static int solve_chunked(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n
                          const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
                          const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
                          double eps_rank, int64_t dimA_ov, int64_t dimJ2_ov, double* dp, double* db, double* dd,
-                         enlsip_gn_info* dinfo, long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo) {
+                         enlsip_gn_info* dinfo, long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo,
+                         const int* htk = nullptr) {
     h->chunk0 = 0;
     const int64_t kA = std::min(n, t);
     const int64_t nchunks = (batch + GN_MAX_LAUNCH_BATCH - 1) / GN_MAX_LAUNCH_BATCH;
@@ -1660,7 +1720,8 @@ static int solve_chunked(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n
                                   dAt ? dAt + c0 * strideAt : nullptr, ldat, strideAt, dcx ? dcx + c0 * t : nullptr, eps_rank,
                                   dimA_ov, dimJ2_ov, dp ? dp + c0 * n : nullptr, db ? db + c0 * t : nullptr,
                                   dd ? dd + c0 * m : nullptr, dinfo ? dinfo + c0 : nullptr, djA ? djA + c0 * t : nullptr,
-                                  djL ? djL + c0 * kA : nullptr, djJ ? djJ + c0 * n : nullptr, hinfo ? hinfo + c0 : nullptr);
+                                  djL ? djL + c0 * kA : nullptr, djJ ? djJ + c0 * n : nullptr, hinfo ? hinfo + c0 : nullptr,
+                                  htk ? htk + c0 : nullptr);
         if (rc) return rc;
         h->chunk0 = c0;
         route_all |= h->route;
@@ -1690,7 +1751,7 @@ static int solve_host(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, i
                       int64_t ldj, int64_t strideJ, const double* rx, const double* At, int64_t ldat,
                       int64_t strideAt, const double* cx, double eps_rank, int64_t dimA_ov, int64_t dimJ2_ov,
                       double* p, double* b, double* d, enlsip_gn_info* info, int64_t* jA, int64_t* jL, int64_t* jJ,
-                      bool factored = false) {
+                      bool factored = false, const int* htk = nullptr) {
     if (!h) return -1;
     GN_TRY
     int rc = check_limits(h, batch, m, n, t);
@@ -1745,7 +1806,7 @@ static int solve_host(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, i
     if (t > 0 && !factored) GN_HIP(hipMemcpyAsync(dcx, cx, (size_t)batch * t * 8, hipMemcpyHostToDevice, s));
     h->reuse_once = factored;      // A', cx (same staging slots) and the constraint factors are resident
     rc = solve_chunked(h, batch, m, n, t, dJ, m, m * n, drx, dAt, n, n * t, dcx, eps_rank, dimA_ov, dimJ2_ov, dp, db, dd,
-                       nullptr, djA, djL, djJ, info);
+                       nullptr, djA, djL, djJ, info, htk);
     if (rc) return rc;
     if (p) GN_HIP(hipMemcpyAsync(p, dp, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
     if (b && t > 0) GN_HIP(hipMemcpyAsync(b, db, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
@@ -1788,6 +1849,7 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
     h->last_At = dAt; h->last_ldat = n; h->last_strideAt = (long long)n * t;
     h->sc_eJ = 0; h->sc_eA = 0;
     h->rescue_prob.clear();
+    h->h_tk.clear();
     rc = run_constraint_stage(h, 1, m, n, t, dAt, n, (long long)n * t, dcx, eps_rank, -1);
     if (rc) return rc;
     if (h->rescale_enabled && t > 0)
@@ -1841,6 +1903,62 @@ int enlsip_gn_solve_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
                             enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
     return solve_host(h, batch, m, n, t, J, ldj, strideJ, rx, At, ldat, strideAt, cx, eps_rank, -1, -1, p, b, d,
                       info, jpvtA, jpvtL, jpvtJ2);
+}
+
+// ---- ragged batch: one t per problem (update_working_set, src/enlsip_functions.jl:686-795, gives every problem its own W.t and
+// calls gn_search_direction with it, :725, :743, :762, :771, :789).  The batch is planned and launched with t_max; the constraint
+// kernels read each problem's t and write the identity padding up to t_max, so that everything downstream runs unchanged.
+// Argument errors are LAPACK-style (position in the argument list), all checked before anything is launched.
+static int check_ragged(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t, const double* J,
+                        int64_t ldj, const double* rx, const double* At, int64_t ldat, int64_t strideAt, const double* cx,
+                        std::vector<int>& tk) {
+    int rc = check_limits(h, batch, m, n, t_max);
+    if (rc) return rc;
+    if (!t) { h->err = "t is NULL"; return -6; }
+    if (!J) { h->err = "J is NULL"; return -7; }
+    if (ldj < m) { h->err = "ldj < m"; return -8; }
+    if (!rx) { h->err = "rx is NULL"; return -10; }
+    if (t_max > 0 && !At) { h->err = "At is NULL with t_max > 0"; return -11; }
+    if (t_max > 0 && ldat < n) { h->err = "ldat < n"; return -12; }
+    if (t_max > 0 && strideAt < ldat * t_max) { h->err = "strideAt < ldat * t_max"; return -13; }
+    if (t_max > 0 && !cx) { h->err = "cx is NULL with t_max > 0"; return -14; }
+    tk.resize((size_t)batch);
+    for (int64_t k = 0; k < batch; ++k) {
+        if (t[k] < 0 || t[k] > t_max) {
+            h->err = "t[" + std::to_string(k) + "] = " + std::to_string(t[k]) + " is outside 0..t_max";
+            return -6;
+        }
+        tk[(size_t)k] = (int)t[k];
+    }
+    return 0;
+}
+
+int enlsip_gn_solve_batched_ragged(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                   const double* J, int64_t ldj, int64_t strideJ, const double* rx, const double* At, int64_t ldat,
+                                   int64_t strideAt, const double* cx, double eps_rank, double* p, double* b, double* d,
+                                   enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    int rc = check_ragged(h, batch, m, n, t_max, t, J, ldj, rx, At, ldat, strideAt, cx, tk);
+    if (rc) return rc;
+    return solve_host(h, batch, m, n, t_max, J, ldj, strideJ, rx, At, ldat, strideAt, cx, eps_rank, -1, -1, p, b, d, info, jpvtA,
+                      jpvtL, jpvtJ2, false, tk.data());
+    GN_CATCH(h)
+}
+
+int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                       const double* dJ, int64_t ldj, int64_t strideJ, const double* drx, const double* dAt,
+                                       int64_t ldat, int64_t strideAt, const double* dcx, double eps_rank, double* dp, double* db,
+                                       double* dd, enlsip_gn_info* dinfo, int64_t* djpvtA, int64_t* djpvtL, int64_t* djpvtJ2) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    int rc = check_ragged(h, batch, m, n, t_max, t, dJ, ldj, drx, dAt, ldat, strideAt, dcx, tk);
+    if (rc) return rc;
+    return solve_chunked(h, batch, m, n, t_max, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, -1, -1, dp, db, dd,
+                         dinfo, (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data());
+    GN_CATCH(h)
 }
 
 int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* J, int64_t ldj,

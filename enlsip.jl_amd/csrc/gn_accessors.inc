@@ -27,6 +27,11 @@ int need_factors(enlsip_gn_handle& h, int64_t& prob) {
     return 0;
 }
 
+// the constraint count of problem `prob` of the resident batch: its own t after a ragged solve, the batch's t otherwise
+int prob_t(enlsip_gn_handle h, int64_t prob) {
+    return h->h_tk.empty() ? (int)h->plan.t : h->h_tk[(size_t)prob];
+}
+
 struct FactorView {
     const double* F; int ld; int rows, cols, k; const double* tau; const long long* jpvt;
 };
@@ -36,13 +41,14 @@ struct FactorView {
 int view(enlsip_gn_handle h, int which, int64_t prob, FactorView& v) {
     const Plan& P = h->plan;
     const ProbState& st = h->h_state[prob];
+    const int t = prob_t(h, prob), kA = (int)std::min<long long>(P.n, t);     // F_L11 of a ragged batch has ld t (its own)
     switch (which) {
         case ENLSIP_GN_FACTOR_A:
-            v = {h->FA + prob * P.sFA, (int)P.n, (int)P.n, (int)P.t, P.kA, h->tauA + prob * P.sTauA,
+            v = {h->FA + prob * P.sFA, (int)P.n, (int)P.n, t, kA, h->tauA + prob * P.sTauA,
                  h->jpvtA + prob * P.sJA};
             return 0;
         case ENLSIP_GN_FACTOR_L11:
-            v = {h->FL + prob * P.sFL, (int)P.t, (int)P.t, P.kA, (int)std::min<long long>(P.t, P.kA),
+            v = {h->FL + prob * P.sFL, t, t, kA, std::min(t, kA),
                  h->tauL + prob * P.sTauL, h->jpvtL + prob * P.sJL};
             return 0;
         case ENLSIP_GN_FACTOR_J2:
@@ -217,9 +223,10 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
     if (h->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
     const Plan& P = h->plan;
     const ProbState st0 = h->h_state[prob];
-    if (dimA < 0 || dimA > P.kA) { h->err = "dimA out of range"; return -3; }
+    const int tk = prob_t(h, prob);       // the problem's own t (ragged batch); the stage below runs with the batch's t_max
+    if (dimA < 0 || dimA > std::min<long long>(P.n, tk)) { h->err = "dimA out of range"; return -3; }
     if (dimJ2 < 0 || dimJ2 > st0.kp) { h->err = "dimJ2 out of range"; return -4; }
-    if (code == 1 && st0.rankA != P.t) { h->err = "code 1 requires rankA == t"; return -5; }
+    if (code == 1 && st0.rankA != tk) { h->err = "code 1 requires rankA == t"; return -5; }
     GN_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int m = (int)P.m, n = (int)P.n, t = (int)P.t;
@@ -238,7 +245,7 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
         ca.state = h->state;
         ca.fa_done = 1; ca.fl_done = 1; ca.need_T = 0;
         ca.Lmat = h->cdist.L; ca.ldL = h->cdist.ldL; ca.sL = h->cdist.sL; ca.qb = h->cdist.qb; ca.sQb = h->cdist.sQb;
-        launch_constraint((int)std::max<long long>(n, t), 1, s, ca);
+        launch_constraint((int)std::max<long long>(n, t), 1, s, ca, h->h_tk.empty() ? nullptr : (const int*)h->tkbuf.p);
     } else {
         rc = run_constraint_stage(h, 1, m, n, t, h->last_At, h->last_ldat, h->last_strideAt, h->last_cx, h->eps_rank, dimA, (int)prob,
                                   (int)code);
@@ -285,7 +292,7 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
     launch_pivot((int)std::min<long long>(m, n), 1, s, fa);
     GN_HIP(hipGetLastError());
     if (p) GN_HIP(hipMemcpyAsync(p, dp, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    if (b && t > 0) GN_HIP(hipMemcpyAsync(b, db, (size_t)t * 8, hipMemcpyDeviceToHost, s));
+    if (b && tk > 0) GN_HIP(hipMemcpyAsync(b, db, (size_t)tk * 8, hipMemcpyDeviceToHost, s));
     if (d) GN_HIP(hipMemcpyAsync(d, dd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
     GN_HIP(hipMemcpyAsync(h->h_state + prob, h->state + prob, sizeof(ProbState), hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));

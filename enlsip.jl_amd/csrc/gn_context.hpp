@@ -125,6 +125,10 @@ struct enlsip_gn_context {
     bool is_rescue = false;
     std::vector<enlsip_gn_context*> rescue;     // one-problem handles of rescaled problems of the last batch
     std::vector<long long> rescue_prob;          // their problem indices (same length while the batch is resident)
+    // Ragged batch (enlsip_gn_solve_batched_ragged*): each problem's own constraint count (plan.t = t_max); empty after a uniform
+    // solve.  The device copy is what the RAGGED forms of the constraint kernels read; the host copy answers the accessors.
+    std::vector<int> h_tk;
+    gn::DevBuf tkbuf;
     unsigned long long route = 0;       // ENLSIP_GN_ROUTE_* bits of the last solve (enlsip_gn_get_route)
     long long chunk0 = 0;               // first problem (index in the caller's batch) of the resident chunk: batches above the launch limit run in chunks
     long long tsqr_n2 = -1;             // n2 of the last tsqr_local on this handle

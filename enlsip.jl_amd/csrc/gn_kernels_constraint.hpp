@@ -62,8 +62,11 @@ inline void constraint_carve(long long n, long long t, int fa_done, int& nv, int
 }
 inline size_t constraint_lds_bytes(int nv, int blkd, int gld, int matd) { return (size_t)(3 * nv + blkd + gld + matd + 8) * 8; }
 
-template <int RPL, int G, int NTH>
-__global__ __launch_bounds__(NTH) void k_constraint(ConstraintArgs a) {
+// RAGGED (ragged batch, enlsip_gn_solve_batched_ragged): a.t, a.kA are the batch's t_max and min(n, t_max), the problem's own
+// t = tk[prob] (kA = min(n, t)); every slot between its sizes and the batch's is written as the identity padding the downstream
+// kernels rely on (end of the body).
+template <int RPL, int G, int NTH, bool RAGGED>
+__device__ __forceinline__ void constraint_body(const ConstraintArgs& a, const int* tk) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* vn1 = smem;
     double* vn2 = vn1 + a.nv;
@@ -74,7 +77,9 @@ __global__ __launch_bounds__(NTH) void k_constraint(ConstraintArgs a) {
     int* sh_i = reinterpret_cast<int*>(mat + a.matd);
 
     const int prob = blockIdx.x + a.prob0;
-    const int n = a.n, t = a.t, kA = a.kA;
+    const int n = a.n;
+    const int t = RAGGED ? tk[prob] : a.t;
+    const int kA = RAGGED ? (n < t ? n : t) : a.kA;
     const double* At = a.At + prob * a.strideAt;
     const double* cx = a.cx + prob * a.stride_cx;
     double* FA = a.FA + prob * a.sFA;
@@ -219,6 +224,15 @@ __global__ __launch_bounds__(NTH) void k_constraint(ConstraintArgs a) {
         __syncthreads();
     }
 
+    if constexpr (RAGGED) {
+        // identity padding up to the batch's sizes: zero reflector columns (V and R parts), tau = 0 and zero T rows / columns make
+        // the padded reflectors exactly I in I - V T V'; zero pivots, b and p1 entries are what the outputs carry past t
+        for (long long e = tid; e < (long long)n * (a.t - t); e += nt) FA[(size_t)t * n + e] = 0.0;
+        for (int i = kA + tid; i < a.kA; i += nt) { tauA[i] = 0.0; tauL[i] = 0.0; jpvtL[i] = 0; }
+        for (int i = t + tid; i < a.t; i += nt) { jpvtA[i] = 0; bvec[i] = 0.0; p1[i] = 0.0; }
+        const int nblk_all = (a.fa_done && !a.need_T) ? 0 : (a.kA + KBLK - 1) / KBLK;
+        for (long long e = (long long)nblk * KBLK * KBLK + tid; e < (long long)nblk_all * KBLK * KBLK; e += nt) TA[e] = 0.0;
+    }
     if (tid == 0) {
         st->rankA = rankA;
         st->n2 = n - rankA;
@@ -230,5 +244,10 @@ __global__ __launch_bounds__(NTH) void k_constraint(ConstraintArgs a) {
         st->status = sh_i[2];
     }
 }
+
+template <int RPL, int G, int NTH>
+__global__ __launch_bounds__(NTH) void k_constraint(ConstraintArgs a) { constraint_body<RPL, G, NTH, false>(a, nullptr); }
+template <int RPL, int G, int NTH>
+__global__ __launch_bounds__(NTH) void k_constraint_ragged(ConstraintArgs a, const int* tk) { constraint_body<RPL, G, NTH, true>(a, tk); }
 
 }  // namespace gn

@@ -16,16 +16,19 @@ namespace gn {
 // LDS (doubles): tmp[kA * 65] vbuf[64] dg[64] gcol[64] tail[64] Tl[64 * kA]
 inline size_t constraint_small_lds_bytes(int kA) { return (size_t)((kA > 0 ? kA : 1) * (65 + 64) + 4 * 64 + 8) * 8; }
 
-template <int NR>
 #ifndef ENLSIP_CS_OCC
 #define ENLSIP_CS_OCC 3           // NR = 32: 168 registers without spills, 3 waves per SIMD instead of 2 (C5 constraint stage 0.117 -> 0.098 ms)
 #endif
 #ifndef ENLSIP_CS64_OCC
 #define ENLSIP_CS64_OCC 0         // measured: 2 waves per SIMD = 420 spilled registers, C3 constraint stage 0.07 -> 0.13 ms
 #endif
-__global__ __launch_bounds__(64, (NR == 32 && ENLSIP_CS_OCC) ? ENLSIP_CS_OCC : ((NR == 64 && ENLSIP_CS64_OCC) ? ENLSIP_CS64_OCC : 1)) void k_constraint_small(ConstraintArgs a) {
+// RAGGED: the problem's own t = tk[prob]; the slots up to the batch's t_max / kA_max get the identity padding (k_constraint)
+template <int NR, bool RAGGED>
+__device__ __forceinline__ void constraint_small_body(const ConstraintArgs& a, const int* tk) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int n = a.n, t = a.t, kA = a.kA;
+    const int n = a.n;
+    const int t = RAGGED ? tk[blockIdx.x + a.prob0] : a.t;
+    const int kA = RAGGED ? (n < t ? n : t) : a.kA;
     const int kd = kA > 0 ? kA : 1;
     double* tmp = smem;
     double* vbuf = tmp + kd * 65;
@@ -64,13 +67,14 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_CS_OCC) ? ENLSIP_CS_OCC : (
     wave_mem_sync();
     const int lp = (ln < t) ? lpos[ln] : 0;          // lane i: the lane (= column of A') that sits at position i
     wave_qrcp_store_upper(q, ln, lp, t, FA, n);
-    if (kA > 0) {
+    const int kAb = RAGGED ? a.kA : kA;       // the batch's kA: J*Q1 picks its form (and the T columns it reads) by it
+    if (kAb > 0) {
         // block T factor (one block: kA <= 63), zero outside the upper triangle.  The compact-WY kernels of J*Q1 pad a block to 64
         // reflectors and need the zeros of all 64 columns; with at most 16 reflectors J*Q1 runs reflector by reflector
         // (k_jq1_rows*, k_jq1_factor_small: the diagonal; launch_jq1 of the accessors: the upper triangle of the first kA columns),
         // so only those columns are written — 30 of the 32 KB per problem at C5 (t = 4) were zeros nobody reads: 250 MB per step
         double* T = a.TA + prob * a.sTA;
-        const int jcols = jq1_by_reflectors(n, kA) ? kA : KBLK;       // the predicate of launch_jq1_rows
+        const int jcols = jq1_by_reflectors(n, kAb) ? kAb : KBLK;     // the predicate of launch_jq1_rows
         for (int jc = 0; jc < jcols; ++jc) T[ln + jc * KBLK] = (jc < kA && ln <= jc) ? Tl[ln + 64 * jc] : 0.0;
     }
     const int rankA = wave_pseudo_rank(dg, kA, a.eps_rank, ln, pseudo_rank_abs_threshold(a.eps_rank, a.abs_shift));
@@ -144,6 +148,13 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_CS_OCC) ? ENLSIP_CS_OCC : (
         if (ln < t) p1[ln] = 0.0;
         if (ln < kA) p1[lpL] = (ln < dimA) ? zw : 0.0;    // distinct targets; lanes >= kA wrote zeros to other entries
     }
+    if constexpr (RAGGED) {
+        // identity padding up to the batch's sizes (see k_constraint): lane = row of the zero columns of F_A
+        for (int c = t; c < a.t; ++c)
+            if (ln < n) FA[ln + (size_t)c * n] = 0.0;
+        for (int i = kA + ln; i < a.kA; i += 64) { tauA[i] = 0.0; tauL[i] = 0.0; jpvtL[i] = 0; }
+        for (int i = t + ln; i < a.t; i += 64) { jpvtA[i] = 0; bvec[i] = 0.0; p1[i] = 0.0; }
+    }
     if (ln == 0) {
         st->rankA = rankA;
         st->n2 = n - rankA;
@@ -156,12 +167,29 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_CS_OCC) ? ENLSIP_CS_OCC : (
     }
 }
 
+template <int NR>
+__global__ __launch_bounds__(64, (NR == 32 && ENLSIP_CS_OCC) ? ENLSIP_CS_OCC : ((NR == 64 && ENLSIP_CS64_OCC) ? ENLSIP_CS64_OCC : 1)) void k_constraint_small(ConstraintArgs a) {
+    constraint_small_body<NR, false>(a, nullptr);
+}
+template <int NR>
+__global__ __launch_bounds__(64, (NR == 32 && ENLSIP_CS_OCC) ? ENLSIP_CS_OCC : ((NR == 64 && ENLSIP_CS64_OCC) ? ENLSIP_CS64_OCC : 1)) void k_constraint_small_ragged(ConstraintArgs a, const int* tk) {
+    constraint_small_body<NR, true>(a, tk);
+}
+
 // Returns false when the shape is outside the kernel's range (the caller uses k_constraint).
-inline bool launch_constraint_small(int batch, hipStream_t s, const ConstraintArgs& a) {
+// tk: each problem's own t (ragged batch), NULL for a uniform one
+inline bool launch_constraint_small(int batch, hipStream_t s, const ConstraintArgs& a, const int* tk = nullptr) {
     if (a.n > 64 || a.t > 63 || a.fa_done) return false;
     const size_t lds = constraint_small_lds_bytes(a.kA);
-    if (a.n <= 32 && a.t <= 32) { GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_WAVE32); hipLaunchKernelGGL(k_constraint_small<32>, dim3(batch), dim3(64), lds, s, a); }
-    else { GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_WAVE64); hipLaunchKernelGGL(k_constraint_small<64>, dim3(batch), dim3(64), lds, s, a); }
+    if (a.n <= 32 && a.t <= 32) {
+        GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_WAVE32);
+        if (tk) hipLaunchKernelGGL(k_constraint_small_ragged<32>, dim3(batch), dim3(64), lds, s, a, tk);
+        else hipLaunchKernelGGL(k_constraint_small<32>, dim3(batch), dim3(64), lds, s, a);
+    } else {
+        GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_WAVE64);
+        if (tk) hipLaunchKernelGGL(k_constraint_small_ragged<64>, dim3(batch), dim3(64), lds, s, a, tk);
+        else hipLaunchKernelGGL(k_constraint_small<64>, dim3(batch), dim3(64), lds, s, a);
+    }
     return true;
 }
 

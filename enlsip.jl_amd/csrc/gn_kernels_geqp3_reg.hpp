@@ -21,8 +21,10 @@ struct Geqp3RegArgs {
     int prob0;
 };
 
-template <int RPL>
-__global__ __launch_bounds__(512) void k_geqp3_reg(Geqp3RegArgs a) {
+// RAGGED: the problem's own column count tk[prob]; the padding of F, tau and jpvt up to a.cols is left to the k_constraint
+// launch that follows (its RAGGED form writes it); the T block is complete here (zero past the last reflector)
+template <int RPL, bool RAGGED>
+__device__ __forceinline__ void geqp3_reg_body(const Geqp3RegArgs& a, const int* tk) {
     constexpr int NWV = 8, NCW = 8;
     __shared__ double vsh[2][64 * RPL];
     __shared__ double cvn1[2][64], cvn2[64], taul[64];
@@ -30,7 +32,8 @@ __global__ __launch_bounds__(512) void k_geqp3_reg(Geqp3RegArgs a) {
     __shared__ double gram[64 * 65];
     __shared__ double tau_s[2], beta_s[2];
     const int prob = blockIdx.x + a.prob0;
-    const int rows = a.rows, cols = a.cols;
+    const int rows = a.rows;
+    const int cols = RAGGED ? tk[prob] : a.cols;
     const int tid = threadIdx.x, ln = lane_id();
     const int w = __builtin_amdgcn_readfirstlane(wave_id());
     const double* A = a.A + prob * a.strideA;
@@ -240,5 +243,10 @@ __global__ __launch_bounds__(512) void k_geqp3_reg(Geqp3RegArgs a) {
         }
     }
 }
+
+template <int RPL>
+__global__ __launch_bounds__(512) void k_geqp3_reg(Geqp3RegArgs a) { geqp3_reg_body<RPL, false>(a, nullptr); }
+template <int RPL>
+__global__ __launch_bounds__(512) void k_geqp3_reg_ragged(Geqp3RegArgs a, const int* tk) { geqp3_reg_body<RPL, true>(a, tk); }
 
 }  // namespace gn

@@ -39,7 +39,7 @@ int enlsip_gn_jacobian_times(enlsip_gn_handle h, int64_t prob, const double* p, 
     if (!Jp && !Ap) return -4;
     if (!h->last_J) { h->err = "J of the last solve is not available"; return -1; }
     const Plan& P = h->plan;
-    const int n = (int)P.n, t = (int)P.t, m = (int)P.m;
+    const int n = (int)P.n, t = prob_t(h, prob), m = (int)P.m;       // Ap: the problem's own active rows
     GN_HIP(hipSetDevice(h->device));
     rc = lagrange_scratch(h, m);
     if (rc) return rc;
@@ -133,7 +133,7 @@ int enlsip_gn_matrix_times_QA(enlsip_gn_handle h, int64_t prob, int64_t rows, co
 static int lagrange_common(enlsip_gn_handle h, int64_t prob, int mode, const double* host_vec, const double* diag_scale,
                            double eps_rank, double* lambda, double* grad_res) {
     const Plan& P = h->plan;
-    const int n = (int)P.n, t = (int)P.t, m = (int)P.m;
+    const int n = (int)P.n, t = prob_t(h, prob), m = (int)P.m;       // lambda: the problem's own t (ragged batch)
     if (!lambda) return -6;
     if (h->constraints_only && (mode == 2 || !host_vec)) {
         h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
@@ -154,7 +154,7 @@ static int lagrange_common(enlsip_gn_handle h, int64_t prob, int mode, const dou
     double* d = (double*)h->lag.p;
     hipStream_t s = h->stream;
     LagrangeArgs a{};
-    a.mode = mode; a.n = n; a.t = t; a.kA = P.kA; a.rank_solve = h->h_state[prob].rankA;
+    a.mode = mode; a.n = n; a.t = t; a.kA = std::min(n, t); a.rank_solve = h->h_state[prob].rankA;
     a.FA = h->FA + prob * P.sFA; a.tauA = h->tauA + prob * P.sTauA; a.jpvtA = h->jpvtA + prob * P.sJA;
     a.cx = h->last_cx ? h->last_cx + prob * h->last_stride_cx : nullptr;
     a.eps_rank = eps_rank; a.lambda = d + 2048; a.scal = d + 3072;

@@ -12,7 +12,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
     if (!p) { h->err = "p is NULL"; return -5; }
     if (!h->last_J || !h->last_rx) { h->err = "J / rx of the last solve are not available"; return -1; }
     const Plan& P = h->plan;
-    const int m = (int)P.m, n = (int)P.n, t = (int)P.t;
+    const int m = (int)P.m, n = (int)P.n, t = prob_t(h, prob);      // the problem's own t (ragged batch)
     if (ldg < n) { h->err = "ldg < n"; return -4; }
     const ProbState st0 = h->h_state[prob];
     const int rankA = st0.rankA, n2 = n - rankA;
@@ -31,7 +31,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
     // b, p1 with the default dimensions (a re-solve may have left truncated ones), state record restored afterwards
     if (t > 0) {
         if (h->cdist.valid) { h->err = "newton direction after the distributed constraint stage is not supported"; return -7; }
-        rc = run_constraint_stage(h, 1, m, n, t, h->last_At, h->last_ldat, h->last_strideAt, h->last_cx, h->eps_rank, -1, (int)prob, 0);
+        rc = run_constraint_stage(h, 1, m, n, P.t, h->last_At, h->last_ldat, h->last_strideAt, h->last_cx, h->eps_rank, -1, (int)prob, 0);
         if (rc) return rc;
         GN_HIP(hipMemcpyAsync(h->state + prob, &st0, sizeof(ProbState), hipMemcpyHostToDevice, s));
     }

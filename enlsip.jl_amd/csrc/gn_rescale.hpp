@@ -19,15 +19,17 @@ constexpr int GN_RESCALE_BAND = 400;           // inputs with 2^-400 <= max |ent
 // finite: a sum of squares overflowed (or the inputs held NaN / Inf).  Below 2^-440 (zero included): the squares of the largest
 // column sit at the bottom of the exponent range (or J / A is zero).  Both only nominate the problem: the host looks at the
 // magnitudes of its inputs before anything is redone.
-__global__ __launch_bounds__(256) void k_extreme_flags(ProbState* state, const double* Rt, long long sRt, const double* FA, long long sFA,
-                                                       int kA, int n2cap, int batch) {
+// RAGGED: F_A of problem k has min(kA, tk[k]) reflectors — a problem without constraints has none to look at
+template <bool RAGGED>
+__device__ __forceinline__ void extreme_flags_body(ProbState* state, const double* Rt, long long sRt, const double* FA, long long sFA,
+                                                   int kA, int n2cap, int batch, const int* tk) {
     const int k = blockIdx.x * 256 + threadIdx.x;
     if (k >= batch) return;
     const ProbState st = state[k];
     if (n2cap > 0 && st.n2 > n2cap) return;            // redone by the caller (second attempt): nothing of it is final yet
     const double tiny = 0x1p-440;
     int f = 0;
-    if (kA > 0) {
+    if (RAGGED ? (kA > 0 && tk[k] > 0) : kA > 0) {
         const double a = fabs(FA[k * sFA]);
         if (!(a <= __builtin_huge_val()) || a == __builtin_huge_val()) f |= GN_FLAG_NONFINITE;
         else if (a < tiny) f |= GN_FLAG_TINY;
@@ -38,6 +40,14 @@ __global__ __launch_bounds__(256) void k_extreme_flags(ProbState* state, const d
         else if (r < tiny) f |= GN_FLAG_TINY;
     }
     if (f) state[k].status = st.status | f;
+}
+__global__ __launch_bounds__(256) void k_extreme_flags(ProbState* state, const double* Rt, long long sRt, const double* FA, long long sFA,
+                                                       int kA, int n2cap, int batch) {
+    extreme_flags_body<false>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, nullptr);
+}
+__global__ __launch_bounds__(256) void k_extreme_flags_ragged(ProbState* state, const double* Rt, long long sRt, const double* FA,
+                                                              long long sFA, int kA, int n2cap, int batch, const int* tk) {
+    extreme_flags_body<true>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, tk);
 }
 
 __global__ __launch_bounds__(256) void k_clear_status_bits(ProbState* state, int bits, int batch) {

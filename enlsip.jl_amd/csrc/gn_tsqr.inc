@@ -189,6 +189,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     // same routing as a solve (register / distributed forms of F_A for the shapes that need them)
     h->sc_eJ = 0; h->sc_eA = 0;          // row shards are not rescaled (include/enlsip_gn.h: magnitude range of the TSQR entry points)
     h->rescue_prob.clear();
+    h->h_tk.clear();
     rc = run_constraint_stage(h, 1, m_loc, n, t, dAt, ldat, 0, dcx, eps_rank, -1);
     if (rc) return rc;
     int n2_launch = (int)(n - P.kA);

@@ -380,6 +380,35 @@ function gn_search_direction_batched_hip(h::Handle, Js::Array{Float64,3}, rxs::M
     return P, infos
 end
 
+"""    gn_search_direction_batched_hip(h, Js, rxs, As::Vector{Matrix{Float64}}, cxs, ε_rank) -> (P, infos)
+
+The ragged form: every problem brings its own active Jacobian `As[k]` (`t_k×n`, different row counts after
+update_working_set, src/enlsip_functions.jl:686-795) and `cxs[k]` (`t_k`).  They are packed into `t_max` padding and solved in
+one call of enlsip_gn_solve_batched_ragged; problem `k`'s results are those of its own `t_k`.
+"""
+function gn_search_direction_batched_hip(h::Handle, Js::Array{Float64,3}, rxs::Matrix{Float64}, As::Vector{Matrix{Float64}},
+                                         cxs::Vector{Vector{Float64}}, ε_rank::Float64)
+    m, n, B = size(Js)
+    t = Int64[size(A, 1) for A in As]
+    t_max = B > 0 ? maximum(t) : 0
+    kA = min(n, t_max)
+    Ats = zeros(Float64, n, max(t_max, 1), B)            # n×t_max×B: slice k holds C.A' of problem k in its first t_k columns
+    cxp = zeros(Float64, max(t_max, 1), B)
+    for k in 1:B
+        t[k] > 0 || continue
+        Ats[:, 1:t[k], k] = permutedims(As[k], (2, 1))
+        cxp[1:t[k], k] = cxs[k]
+    end
+    P = zeros(Float64, n, B); b = zeros(Float64, max(t_max, 1), B); d = zeros(Float64, m, B)
+    jA = zeros(Int64, max(t_max, 1), B); jL = zeros(Int64, max(kA, 1), B); jJ = zeros(Int64, n, B)
+    infos = fill(Info(0, 0, 0, 0, 0, 0), B)
+    GC.@preserve Js rxs t Ats cxp P b d jA jL jJ infos check(h, ccall((:enlsip_gn_solve_batched_ragged, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+         Int64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Info}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        h.ptr, B, m, n, t_max, t, Js, m, m * n, rxs, Ats, max(n, 1), n * max(t_max, 1), cxp, ε_rank, P, b, d, infos, jA, jL, jJ))
+    return P, infos
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

@@ -208,6 +208,71 @@ class GNSolver:
         infos = [(int(i.rankA), int(i.rankJ2), int(i.code), int(i.dimA), int(i.dimJ2), int(i.status)) for i in info]
         return p, b, d, infos, jA, jL, jJ
 
+    # ---- ragged batch: one working-set size per problem (src/enlsip_functions.jl:686-795) ---------
+    @staticmethod
+    def pack_ragged(As, cxs, n: Optional[int] = None):
+        """Each problem's own active Jacobian A_k (t_k x n) and cx_k (t_k) -> the padded layout of solve_batched_ragged:
+        At (batch, t_max, n), cx (batch, t_max) with zeros past t_k, and t (int64).  n is taken from the 2-D A_k; pass it when
+        no A_k carries it (an empty batch, or every A_k empty and 1-D)."""
+        As = [np.asarray(A, dtype=np.float64) for A in As]
+        if len(As) != len(cxs):
+            raise ValueError(f"pack_ragged: {len(As)} matrices but {len(cxs)} cx vectors")
+        widths = {A.shape[1] for A in As if A.ndim == 2}
+        if n is None:
+            if not widths:
+                raise ValueError("pack_ragged: n cannot be inferred (no 2-D A_k); pass n")
+            if len(widths) > 1:
+                raise ValueError(f"pack_ragged: the A_k have different column counts {sorted(widths)}")
+            n = widths.pop()
+        elif widths - {n}:
+            raise ValueError(f"pack_ragged: A_k with {sorted(widths - {n})} columns, n = {n}")
+        for A in As:
+            if A.size and A.ndim != 2:
+                raise ValueError("pack_ragged: every non-empty A_k must be a t_k x n matrix")
+        t = np.array([A.shape[0] if A.size else 0 for A in As], dtype=np.int64)
+        t_max = int(t.max()) if len(t) else 0
+        At = np.zeros((len(As), t_max, n))
+        cx = np.zeros((len(As), t_max))
+        for k, (A, c) in enumerate(zip(As, cxs)):
+            if t[k]:
+                At[k, :t[k]] = A
+                cx[k, :t[k]] = np.asarray(c, dtype=np.float64)
+        return At, cx, t
+
+    def solve_batched_ragged(self, J: np.ndarray, rx: np.ndarray, At: np.ndarray, cx: np.ndarray, t,
+                             eps_rank: float = SQRT_EPS):
+        """Like solve_batched, with problem k's own t[k] <= t_max: At (batch, t_max, n) and cx (batch, t_max) are padded
+        (pack_ragged builds them); rows past t[k] are not read.  Outputs have the t_max layout with zeros past t[k]."""
+        batch, n, m = J.shape
+        t = np.ascontiguousarray(t, dtype=np.int64)
+        t_max = At.shape[1] if At is not None and At.ndim == 3 else 0
+        kA = min(n, t_max)
+        J = np.ascontiguousarray(J, dtype=np.float64)
+        rx = np.ascontiguousarray(rx, dtype=np.float64)
+        p, b, d = np.zeros((batch, n)), np.zeros((batch, t_max)), np.zeros((batch, m))
+        jA = np.zeros((batch, t_max), np.int64)
+        jL = np.zeros((batch, kA), np.int64)
+        jJ = np.zeros((batch, n), np.int64)
+        info = (L.Info * batch)()
+        if t_max:
+            At = np.ascontiguousarray(At, dtype=np.float64)
+            cx = np.ascontiguousarray(cx, dtype=np.float64)
+        self._chk(self._lib.enlsip_gn_solve_batched_ragged(
+            self._h, batch, m, n, t_max, t.ctypes.data_as(C.c_void_p), _fptr(J), m, m * n, _fptr(rx),
+            _fptr(At) if t_max else None, max(n, 1), n * t_max, _fptr(cx) if t_max else None, eps_rank,
+            _fptr(p), _fptr(b), _fptr(d), C.cast(info, C.c_void_p), _fptr(jA), _fptr(jL), _fptr(jJ)))
+        infos = [(int(i.rankA), int(i.rankJ2), int(i.code), int(i.dimA), int(i.dimJ2), int(i.status)) for i in info]
+        return p, b, d, infos, jA, jL, jJ
+
+    def solve_batched_ragged_dev(self, batch, m, n, t_max, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx,
+                                 eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):
+        """Device pointers as solve_batched_dev; t stays a host array of batch entries."""
+        v = lambda x: C.c_void_p(x) if x else None
+        t = np.ascontiguousarray(t, dtype=np.int64)
+        self._chk(self._lib.enlsip_gn_solve_batched_ragged_dev(
+            self._h, batch, m, n, t_max, t.ctypes.data_as(C.c_void_p), v(dJ), ldj, strideJ, v(drx), v(dAt), ldat, strideAt,
+            v(dcx), eps_rank, v(dp), v(db), v(dd), v(dinfo), v(djA), v(djL), v(djJ)))
+
     # ---- batch, device buffers (raw pointers, e.g. torch tensor .data_ptr()) ------------------
     def solve_batched_dev(self, batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx,
                           eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):

@@ -11,6 +11,8 @@
  *                               + the QR / rank lines of update_working_set
  *                                                     src/enlsip_functions.jl:700, 768-769
  *                               pseudo_rank           src/enlsip_functions.jl:17-31
+ *   enlsip_gn_solve_batched_ragged*   the same per problem with its own working-set size W.t
+ *                               update_working_set    src/enlsip_functions.jl:686-795 (:725, :743, :762, :771, :789)
  *   enlsip_gn_resolve           sub_search_direction re-entry with truncated dimA/dimJ2
  *                                                     src/enlsip_functions.jl:1249-1253
  *   enlsip_gn_get_R / _diagR / _jpvt / _apply_qt / _apply_q / _get_JQ1
@@ -158,6 +160,37 @@ int enlsip_gn_solve_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
                                 double eps_rank,
                                 double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
                                 int64_t* djpvtA, int64_t* djpvtL, int64_t* djpvtJ2);
+
+/*
+ * Ragged batch: one shape (m, n) and a working set of its own per problem.  update_working_set (src/enlsip_functions.jl:686-795)
+ * adds and drops constraints per problem and calls gn_search_direction with that problem's W.t (:725, :743, :762, :771, :789).
+ * t holds `batch` entries 0 <= t[k] <= t_max and is a HOST array in both variants (the working set is host bookkeeping).
+ * Problem k: A'_k = the n x t[k] matrix at At + k*strideAt (ld ldat, strideAt >= ldat*t_max), cx_k = the first t[k] entries of
+ * cx + k*t_max.  Outputs use the strides of enlsip_gn_solve_batched with t = t_max: p + k*n, b + k*t_max, d + k*m, info[k],
+ * jpvtA + k*t_max, jpvtL + k*min(n,t_max), jpvtJ2 + k*n; entries past t[k] in b and jpvtA and past min(n,t[k]) in jpvtL are 0.
+ * Every problem's results are those of enlsip_gn_solve on (J_k, rx_k, A'_k[:, :t[k]], cx_k[:t[k]]), the magnitude contract above
+ * included; with all t[k] == t_max they are bitwise those of enlsip_gn_solve_batched.  The accessors answer for each problem's
+ * own t[k] (F_A: min(n,t[k]) x t[k], F_L11: min(t[k],kA) x kA with kA = min(n,t[k]); lambda, Ap, L11 vectors: t[k]).
+ * Work is padded to t_max.  Known cliff: the J-side kernels are chosen with n2 = n - min(n, min_k t[k]), so one t[k] = 0 member
+ * of a C5-shaped batch (n = 32) makes n2 = 32 and the whole batch leaves the fused one-launch J*Q1 + panel path; in a C3-shaped
+ * batch (n = 64) it makes n2 + 1 = 65 and the whole batch leaves the one-wave pivoted QR (measured: 0.41x the uniform throughput).
+ * A ragged batch of one problem whose magnitudes need the rescaling is solved with its own t[0] (the padding is never read).
+ * Errors before any launch: -6 t NULL or some t[k] outside 0..t_max, -5 t_max beyond the build limit, -12 ldat < n,
+ * -13 strideAt < ldat*t_max, -11 / -14 At / cx NULL while t_max > 0.
+ */
+int enlsip_gn_solve_batched_ragged(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                   const double* J, int64_t ldj, int64_t strideJ, const double* rx,
+                                   const double* At, int64_t ldat, int64_t strideAt, const double* cx,
+                                   double eps_rank,
+                                   double* p, double* b, double* d, enlsip_gn_info* info,
+                                   int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2);
+/* Same, DEVICE buffers in and out (t stays a HOST array), as enlsip_gn_solve_batched_dev. */
+int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                       const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
+                                       const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
+                                       double eps_rank,
+                                       double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
+                                       int64_t* djpvtA, int64_t* djpvtL, int64_t* djpvtJ2);
 
 /* ---- accessors on the resident factors of problem `prob` of the last solve (host buffers) ---- */
 
