@@ -25,6 +25,7 @@
 #include "gn_kernels_update_v4.hpp"
 #include "gn_kernels_misc.hpp"
 #include "gn_kernels_lagrange.hpp"
+#include "gn_kernels_lagrange_batched.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
 #include "gn_kernels_qrcp_block.hpp"
@@ -1424,6 +1425,8 @@ int enlsip_gn_create(enlsip_gn_handle* out, const enlsip_gn_opts* opts) {
         const char* pl = getenv("ENLSIP_GN_PIPELINE");       // 0: never split a batch over two streams
         if (pl && pl[0] == '0') h->pipeline = false;
         if (pl && pl[0] == '1') h->pipeline_forced = true;    // 1: split even the small uniform shapes (A/B)
+        const char* ls = getenv("ENLSIP_GN_LAGRANGE_SMALL");  // 0: batched multiplier estimates always in the general form (A/B)
+        if (ls && ls[0] == '0') h->lagrange_small = false;
     }
     if (opts && opts->panel_width != 0 && opts->panel_width != PB) {
         delete h;
@@ -1460,6 +1463,9 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->out_stage.p) (void)hipFree(h->out_stage.p);
     if (h->lag.p) (void)hipFree(h->lag.p);
     if (h->newton.p) (void)hipFree(h->newton.p);
+    if (h->lagb_io.p) (void)hipFree(h->lagb_io.p);
+    if (h->lagb_scr.p) (void)hipFree(h->lagb_scr.p);
+    if (h->h_lagflag) (void)hipHostFree(h->h_lagflag);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);
     if (h->xbuf.p) (void)hipFree(h->xbuf.p);
@@ -1974,4 +1980,5 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_accessors.inc"
 #include "gn_tsqr.inc"
 #include "gn_lagrange.inc"
+#include "gn_lagrange_batched.inc"
 #include "gn_newton.inc"

@@ -147,6 +147,12 @@ struct enlsip_gn_context {
     gn::ProbState* state = nullptr;
     // staging for the host-pointer API
     gn::DevBuf in_stage, out_stage, scratch, lag, newton;
+    // batched consumers (gn_lagrange_batched.inc): staging of the host-buffer forms, device temporaries, pinned "some problem
+    // flagged" word of the last launch; never a buffer the resident solve reads
+    gn::DevBuf lagb_io, lagb_scr;
+    int* h_lagflag = nullptr;
+    bool lagrange_small = true;         // ENLSIP_GN_LAGRANGE_SMALL=0: batched multiplier estimates in the general form only (A/B)
+    int consumer_form = -1;             // form of the last batched multiplier estimate (enlsip_gn_get_consumer_form), -1: none yet
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (needed by resolve / get_JQ1 paths)

@@ -46,12 +46,11 @@ struct LagrangeArgs {
     double* scal;          // [0] grad_res (mode 1), [1] status (1: singular diagonal, 2: rank beyond the resident J1)
 };
 
-// one workgroup; LDS vectors of up to 1024 entries (n, t <= 1024 in this build)
-__global__ __launch_bounds__(256) void k_lagrange(LagrangeArgs a) {
-    __shared__ double bq[1024], v[1024], u[1024];
-    __shared__ double blk[64 * 65];
-    __shared__ double red[4];
-    __shared__ int sh[2];
+// The general form of both estimates on one workgroup (256 threads): shared by the per-problem kernel k_lagrange and the batched
+// k_lagrange_batched (gn_kernels_lagrange_batched.hpp).  LDS vectors of up to 1024 entries (n, t <= 1024 in this build); blk: 64 x 65.
+// grad_res (mode 1) is stored to *gres by thread 0; the status bits end in sh[1] (final after the last barrier).
+__device__ __forceinline__ void lagrange_wg_body(const LagrangeArgs& a, double* bq, double* v, double* u, double* blk, double* red,
+                                                 int* sh, double* gres) {
     const int tid = threadIdx.x, ln = lane_id(), w = wave_id();
     const int n = a.n, t = a.t, kA = a.kA;
     if (tid == 0) {
@@ -74,7 +73,7 @@ __global__ __launch_bounds__(256) void k_lagrange(LagrangeArgs a) {
         s = wave_allsum(s);
         if (ln == 0) red[w] = s;
         __syncthreads();
-        if (tid == 0) a.scal[0] = (n > pr) ? sqrt((red[0] + red[1]) + (red[2] + red[3])) : 0.0;
+        if (tid == 0) *gres = (n > pr) ? sqrt((red[0] + red[1]) + (red[2] + red[3])) : 0.0;
     } else if (pr > a.rank_solve && tid == 0) {
         sh[1] |= 2;       // columns rank_solve .. pr-1 of J1 were overwritten by the factorisation of J2
     }
@@ -108,7 +107,16 @@ __global__ __launch_bounds__(256) void k_lagrange(LagrangeArgs a) {
         if (a.diag_scale) lam *= a.diag_scale[dst];
         a.lambda[dst] = lam;
     }
-    if (tid == 0) a.scal[1] = (double)sh[1];
+}
+
+// one workgroup, one problem (enlsip_gn_first_lagrange / enlsip_gn_second_lagrange)
+__global__ __launch_bounds__(256) void k_lagrange(LagrangeArgs a) {
+    __shared__ double bq[1024], v[1024], u[1024];
+    __shared__ double blk[64 * 65];
+    __shared__ double red[4];
+    __shared__ int sh[2];
+    lagrange_wg_body(a, bq, v, u, blk, red, sh, a.scal);
+    if (threadIdx.x == 0) a.scal[1] = (double)sh[1];
 }
 
 }  // namespace gn

@@ -1,0 +1,402 @@
+// Batched consumers of a solve: gradient, J p / A p and the two multiplier estimates over a contiguous range of the resident batch
+// (kernels: gn_kernels_lagrange_batched.hpp).  Included at the end of enlsip_gn.hip, after gn_lagrange.inc.
+
+namespace {
+
+enum { CONS_GRADIENT = 0, CONS_JTIMES = 1, CONS_FIRST = 2, CONS_SECOND = 3 };
+
+// device buffers of one call; slot 0 = problem prob0 of the caller's batch
+struct ConsumerIO {
+    const double* in;       // grad_fx (first estimate, may be null), p (jacobian_times), p_gn (second estimate)
+    const double* diag;     // diag_scale (estimates), may be null
+    double eps_rank;
+    double* out0;           // grad / Jp / lambda
+    double* out1;           // Ap / grad_res
+    int* status;            // estimates, may be null
+};
+
+// the part of a range that lives on one handle: problems k0 .. k0+cnt-1 of hh in the caller's slots j0 .. j0+cnt-1
+struct ConsumerSeg {
+    enlsip_gn_handle hh;
+    long long k0, j0, cnt;
+};
+
+// Splits prob0 .. prob0+count-1 (indices in the caller's whole batch) over the pipeline halves, with the checks of need_factors.
+int consumer_range(enlsip_gn_handle h, int64_t prob0, int64_t count, ConsumerSeg seg[2], int& nseg) {
+    nseg = 0;
+    if (count < 1) { h->err = "count must be >= 1"; return -2; }
+    long long p = prob0;
+    if (h->chunk0 > 0) {       // the batch ran in chunks (solve_chunked): only the last chunk is resident
+        if (p < h->chunk0) { h->err = "problem belongs to an earlier chunk of a batch above the launch limit: its factors are no longer resident"; return -3; }
+        p -= h->chunk0;
+    }
+    const bool split = h->split > 0 && h->child;
+    if (!h->factors_valid || (split && !h->child->factors_valid)) { h->err = "no resident factors: call a solve first"; return -1; }
+    const long long b0 = split ? h->split : h->plan.batch;
+    const long long total = split ? b0 + h->child->plan.batch : b0;
+    if (p < 0 || count > total || p > total - count) { h->err = "problem range out of range: prob0 .. prob0+count-1 must lie in the resident batch"; return -3; }
+    const long long e = p + count;
+    if (p < b0) seg[nseg++] = {h, p, 0, std::min(e, b0) - p};
+    if (e > b0) {
+        const long long s0 = std::max(p, b0);
+        seg[nseg++] = {h->child, s0 - b0, s0 - p, e - s0};
+    }
+    return 0;
+}
+
+// what every handle of the range must hold for the consumer (the per-problem entry points' checks)
+int consumer_needs(enlsip_gn_handle h, enlsip_gn_handle hh, int kind, const ConsumerIO& io) {
+    const char* no_j = "J / rx of the last solve are not available";
+    switch (kind) {
+        case CONS_GRADIENT:
+            if (!hh->last_J || !hh->last_rx) { h->err = no_j; return -1; }
+            return 0;
+        case CONS_JTIMES:
+            if (!hh->last_J) { h->err = "J of the last solve is not available"; return -1; }
+            if (io.out1 && hh->plan.t > 0 && !hh->last_At) { h->err = "A' of the last solve is not available"; return -1; }
+            return 0;
+        case CONS_FIRST:
+            if (hh->constraints_only && !io.in) {
+                h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
+                return -1;
+            }
+            if (hh->plan.t > 0 && !hh->last_cx) { h->err = "cx of the last solve is not available"; return -1; }
+            if (!io.in && (!hh->last_J || !hh->last_rx)) { h->err = no_j; return -1; }
+            return 0;
+        default:
+            if (hh->constraints_only) {
+                h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
+                return -1;
+            }
+            if (!hh->last_J || !hh->last_rx) { h->err = no_j; return -1; }
+            return 0;
+    }
+}
+
+// Enqueues the consumer for one segment on its handle's stream: at most three launches whatever the segment's size.
+int consumer_launch(enlsip_gn_handle hh, int kind, const ConsumerSeg& sg, const ConsumerIO& io, bool small) {
+    enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
+    const Plan& P = hh->plan;
+    const long long m = P.m, n = P.n, tmax = P.t, k0 = sg.k0, j0 = sg.j0, cnt = sg.cnt;
+    const int* tk = hh->h_tk.empty() ? nullptr : (const int*)hh->tkbuf.p + k0;
+    const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
+    // temporaries: flag word | status (when the caller passes none) | grad (first, no grad_fx) | rx + J p (m) | J1'(.) (t_max)
+    const size_t o_st = 256, o_g = o_st + rup((long long)cnt * 4, 256);
+    const size_t o_y = o_g + (size_t)cnt * n * 8, o_b = o_y + (size_t)cnt * m * 8, bytes = o_b + (size_t)cnt * std::max(tmax, 1LL) * 8;
+    int rc = grow(hh, hh->lagb_scr, bytes);
+    if (rc) return rc;
+    if (est && !hh->h_lagflag) GN_HIP(hipHostMalloc((void**)&hh->h_lagflag, sizeof(int), hipHostMallocDefault));
+    char* scr = (char*)hh->lagb_scr.p;
+    hipStream_t s = hh->stream;
+    const unsigned cn = (unsigned)cnt;
+    auto jt = [&](const double* x, long long sx, double* y) {          // J' x
+        hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(n + 3) / 4, cn), dim3(256), 0, s, hh->last_J + k0 * hh->last_strideJ,
+                           hh->last_ldj, hh->last_strideJ, (int)m, (int)n, (const int*)nullptr, x, sx, y, n);
+    };
+    switch (kind) {
+        case CONS_GRADIENT:
+            jt(hh->last_rx + k0 * hh->last_stride_rx, hh->last_stride_rx, io.out0 + j0 * n);
+            break;
+        case CONS_JTIMES:
+            if (io.out0)
+                hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s,
+                                   hh->last_J + k0 * hh->last_strideJ, hh->last_ldj, hh->last_strideJ, (int)m, (int)n, io.in + j0 * n, n,
+                                   (const double*)nullptr, 0LL, io.out0 + j0 * m, m);
+            if (io.out1 && tmax > 0)     // (A p)[i] = sum_r At[r + i * ldat] p[r]: A' is stored n x t; slots past t_k are 0
+                hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(tmax + 3) / 4, cn), dim3(256), 0, s,
+                                   hh->last_At + k0 * hh->last_strideAt, hh->last_ldat, hh->last_strideAt, (int)n, (int)tmax, tk,
+                                   io.in + j0 * n, n, io.out1 + j0 * tmax, tmax);
+            break;
+        default: {
+            LagrangeBatchArgs a{};
+            a.mode = kind == CONS_FIRST ? 1 : 2;
+            a.count = (int)cnt; a.n = (int)n; a.t_max = (int)tmax; a.tk = tk; a.state = hh->state + k0;
+            a.FA = hh->FA + k0 * P.sFA; a.sFA = P.sFA; a.tauA = hh->tauA + k0 * P.sTauA; a.sTauA = P.sTauA;
+            a.jpvtA = hh->jpvtA + k0 * P.sJA; a.sJA = P.sJA;
+            a.cx = hh->last_cx ? hh->last_cx + k0 * hh->last_stride_cx : nullptr; a.scx = hh->last_stride_cx;
+            a.diag_scale = io.diag ? io.diag + j0 * tmax : nullptr;
+            a.eps_rank = io.eps_rank;
+            a.lambda = io.out0 + j0 * tmax;
+            a.grad_res = (kind == CONS_FIRST && io.out1) ? io.out1 + j0 : nullptr;
+            a.status = io.status ? io.status + j0 : (int*)(scr + o_st);
+            a.flag = (int*)scr;
+            GN_HIP(hipMemsetAsync(scr, 0, sizeof(int), s));
+            if (kind == CONS_FIRST) {
+                if (io.in) {
+                    a.vec = io.in + j0 * n;
+                } else {       // gradient from the resident J, rx
+                    double* g = (double*)(scr + o_g);
+                    jt(hh->last_rx + k0 * hh->last_stride_rx, hh->last_stride_rx, g);
+                    a.vec = g;
+                }
+                a.svec = n;
+            } else {
+                double* y = (double*)(scr + o_y);
+                double* bv = (double*)(scr + o_b);
+                hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s,
+                                   hh->last_J + k0 * hh->last_strideJ, hh->last_ldj, hh->last_strideJ, (int)m, (int)n, io.in + j0 * n,
+                                   n, hh->last_rx + k0 * hh->last_stride_rx, hh->last_stride_rx, y, m);       // rx + J p
+                if (tmax > 0)
+                    hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(tmax + 3) / 4, cn), dim3(256), 0, s, (const double*)hh->W + k0 * P.sW,
+                                       (long long)P.ldw, P.sW, (int)m, (int)tmax, tk, (const double*)y, m, bv, tmax);   // J1' (.)
+                a.vec = bv;
+                a.svec = tmax;
+            }
+            if (small)
+                hipLaunchKernelGGL(k_lagrange_wave, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, s, a);
+            else
+                hipLaunchKernelGGL(k_lagrange_batched, dim3(cn), dim3(256), 0, s, a);
+            GN_HIP(hipMemcpyAsync(hh->h_lagflag, scr, sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+    }
+    GN_HIP(hipGetLastError());
+    return 0;
+}
+
+// rc of a per-problem estimate -> the batched status (0, 1 singular, 2 rank beyond the solve's); other codes are errors
+int per_problem_status(int rc, int& st) {
+    st = rc == 0 ? 0 : rc == 1 ? 1 : rc == -7 ? 2 : -1;
+    return st < 0 ? rc : 0;
+}
+
+// Problems of the range that live on a rescue handle (or on a handle whose one problem was rescaled in place) are answered by the
+// per-problem entry point; their slots are overwritten with its results.  Returns the status OR of the whole range in *flagged.
+int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const ConsumerSeg* seg, int nseg,
+                         const ConsumerIO& io, const std::vector<long long>& slots, bool& flagged) {
+    const Plan& P = seg[0].hh->plan;
+    const long long m = P.m, n = P.n, tmax = P.t;
+    hipStream_t s = h->stream;
+    std::vector<double> in((size_t)n), dg((size_t)std::max(tmax, 1LL)), o0((size_t)std::max({m, n, tmax, 1LL})),
+        o1((size_t)std::max(tmax, 1LL));
+    std::vector<int> st_all;
+    const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
+    if (est) {      // statuses of the batched launch: the rescued slots' entries are replaced below
+        st_all.assign((size_t)count, 0);
+        for (int q = 0; q < nseg; ++q) {
+            const ConsumerSeg& sg = seg[q];
+            const int* src = io.status ? io.status + sg.j0 : (const int*)((char*)sg.hh->lagb_scr.p + 256);
+            GN_HIP(hipMemcpy(st_all.data() + sg.j0, src, (size_t)sg.cnt * sizeof(int), hipMemcpyDeviceToHost));
+        }
+    }
+    for (long long j : slots) {
+        const int64_t gp = prob0 + j;
+        if (io.in) GN_HIP(hipMemcpy(in.data(), io.in + j * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+        if (io.diag && tmax > 0) GN_HIP(hipMemcpy(dg.data(), io.diag + j * tmax, (size_t)tmax * 8, hipMemcpyDeviceToHost));
+        std::fill(o0.begin(), o0.end(), 0.0);
+        std::fill(o1.begin(), o1.end(), 0.0);
+        int rc = 0, st = 0;
+        switch (kind) {
+            case CONS_GRADIENT:
+                rc = enlsip_gn_gradient(h, gp, o0.data());
+                if (rc) return rc;
+                GN_HIP(hipMemcpyAsync(io.out0 + j * n, o0.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+                break;
+            case CONS_JTIMES:
+                rc = enlsip_gn_jacobian_times(h, gp, in.data(), io.out0 ? o0.data() : nullptr, io.out1 ? o1.data() : nullptr);
+                if (rc) return rc;
+                if (io.out0) GN_HIP(hipMemcpyAsync(io.out0 + j * m, o0.data(), (size_t)m * 8, hipMemcpyHostToDevice, s));
+                if (io.out1 && tmax > 0) GN_HIP(hipMemcpyAsync(io.out1 + j * tmax, o1.data(), (size_t)tmax * 8, hipMemcpyHostToDevice, s));
+                break;
+            default: {
+                double gres = 0.0;
+                rc = kind == CONS_FIRST
+                         ? enlsip_gn_first_lagrange(h, gp, io.in ? in.data() : nullptr, io.diag ? dg.data() : nullptr, io.eps_rank,
+                                                    o0.data(), &gres)
+                         : enlsip_gn_second_lagrange(h, gp, in.data(), io.diag ? dg.data() : nullptr, io.eps_rank, o0.data());
+                rc = per_problem_status(rc, st);
+                if (rc) return rc;
+                st_all[(size_t)j] = st;
+                if (tmax > 0) GN_HIP(hipMemcpyAsync(io.out0 + j * tmax, o0.data(), (size_t)tmax * 8, hipMemcpyHostToDevice, s));
+                if (kind == CONS_FIRST && io.out1) GN_HIP(hipMemcpyAsync(io.out1 + j, &gres, 8, hipMemcpyHostToDevice, s));
+                if (io.status) GN_HIP(hipMemcpyAsync(io.status + j, &st, sizeof(int), hipMemcpyHostToDevice, s));
+                GN_HIP(hipStreamSynchronize(s));       // gres / st live on this frame
+            }
+        }
+    }
+    GN_HIP(hipStreamSynchronize(s));
+    flagged = false;
+    for (int v : st_all) flagged = flagged || v != 0;
+    return 0;
+}
+
+// The batched consumer on device buffers: validation, launches on the halves that own the range, one synchronisation per half,
+// then the per-problem route for rescued problems.  0, 1 (some estimate flagged) or a negative argument / state error.
+int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const ConsumerIO& io) {
+    if (!h) return -1;
+    ConsumerSeg seg[2];
+    int nseg = 0;
+    int rc = consumer_range(h, prob0, count, seg, nseg);
+    if (rc) return rc;
+    const Plan& P = seg[0].hh->plan;
+    const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
+    switch (kind) {
+        case CONS_GRADIENT: if (!io.out0) { h->err = "dgrad is NULL"; return -4; } break;
+        case CONS_JTIMES:
+            if (!io.in) { h->err = "dp is NULL"; return -4; }
+            if (!io.out0 && !io.out1) { h->err = "dJp and dAp are both NULL"; return -4; }
+            break;
+        case CONS_FIRST: if (!io.out0 && P.t > 0) { h->err = "dlambda is NULL"; return -4; } break;
+        default:
+            if (!io.in) { h->err = "dp_gn is NULL"; return -4; }
+            if (!io.out0 && P.t > 0) { h->err = "dlambda is NULL"; return -4; }
+    }
+    for (int q = 0; q < nseg; ++q) {
+        rc = consumer_needs(h, seg[q].hh, kind, io);
+        if (rc) return rc;
+    }
+    GN_HIP(hipSetDevice(h->device));
+    const bool small = h->lagrange_small && P.n <= 64 && P.t <= 64;
+    if (est) h->consumer_form = small ? 1 : 0;
+    // slots answered by the per-problem entry point: problems on rescue handles, or the one problem of a handle rescaled in place
+    std::vector<long long> slots;
+    for (int q = 0; q < nseg; ++q) {
+        const ConsumerSeg& sg = seg[q];
+        if (sg.hh->sc_eJ || sg.hh->sc_eA) {
+            for (long long k = sg.k0; k < sg.k0 + sg.cnt; ++k) slots.push_back(sg.j0 + k - sg.k0);
+            continue;
+        }
+        for (long long k : sg.hh->rescue_prob)
+            if (k >= sg.k0 && k < sg.k0 + sg.cnt) slots.push_back(sg.j0 + k - sg.k0);
+    }
+    for (int q = 0; q < nseg; ++q) {
+        if (seg[q].hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
+            if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+            GN_HIP(hipEventRecord(h->ev_fork, h->stream));
+            GN_HIP(hipStreamWaitEvent(seg[q].hh->stream, h->ev_fork, 0));
+        }
+        rc = consumer_launch(seg[q].hh, kind, seg[q], io, small);
+        if (rc) {
+            if (seg[q].hh != h) h->err = seg[q].hh->err;
+            return rc;
+        }
+    }
+    bool flagged = false;
+    for (int q = 0; q < nseg; ++q) {
+        GN_HIP(hipStreamSynchronize(seg[q].hh->stream));
+        if (est) flagged = flagged || *seg[q].hh->h_lagflag != 0;
+    }
+    if (!slots.empty()) {
+        rc = consumer_per_problem(h, kind, prob0, count, seg, nseg, io, slots, flagged);
+        if (rc) return rc;
+    }
+    return flagged ? 1 : 0;
+}
+
+// The host-buffer forms: inputs staged into lagb_io (never in_stage, which the resident J / rx of a host solve live in), the
+// device form, outputs copied back.
+int consumer_host(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const double* in, const double* diag, double eps_rank,
+                  double* out0, double* out1, int* status) {
+    if (!h) return -1;
+    ConsumerSeg seg[2];
+    int nseg = 0;
+    int rc = consumer_range(h, prob0, count, seg, nseg);
+    if (rc) return rc;
+    const Plan& P = seg[0].hh->plan;
+    const long long m = P.m, n = P.n, tmax = P.t;
+    const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
+    const size_t c = (size_t)count;
+    const size_t n_in = in ? c * n : 0, n_dg = (diag && est) ? c * tmax : 0;
+    const size_t n_o0 = !out0 ? 0 : kind == CONS_GRADIENT ? c * n : kind == CONS_JTIMES ? c * m : c * tmax;
+    const size_t n_o1 = !out1 ? 0 : kind == CONS_JTIMES ? c * tmax : kind == CONS_FIRST ? c : 0;
+    const size_t n_st = (status && est) ? c : 0;
+    GN_HIP(hipSetDevice(h->device));
+    rc = grow(h, h->lagb_io, (n_in + n_dg + n_o0 + n_o1 + n_st + 8) * 8);
+    if (rc) return rc;
+    double* d_in = (double*)h->lagb_io.p;
+    double* d_dg = d_in + n_in;
+    double* d_o0 = d_dg + n_dg;
+    double* d_o1 = d_o0 + n_o0;
+    int* d_st = (int*)(d_o1 + n_o1);
+    hipStream_t s = h->stream;
+    if (n_in) GN_HIP(hipMemcpyAsync(d_in, in, n_in * 8, hipMemcpyHostToDevice, s));
+    if (n_dg) GN_HIP(hipMemcpyAsync(d_dg, diag, n_dg * 8, hipMemcpyHostToDevice, s));
+    // a NULL pointer keeps its meaning; an output of zero entries (t_max = 0) still passes the NULL checks
+    const ConsumerIO io{in ? d_in : nullptr, (diag && est) ? d_dg : nullptr, eps_rank, out0 ? d_o0 : nullptr,
+                        (out1 && (kind == CONS_JTIMES || kind == CONS_FIRST)) ? d_o1 : nullptr, n_st ? d_st : nullptr};
+    rc = consumer_dev(h, kind, prob0, count, io);
+    if (rc < 0) return rc;
+    if (n_o0) GN_HIP(hipMemcpyAsync(out0, d_o0, n_o0 * 8, hipMemcpyDeviceToHost, s));
+    if (n_o1) GN_HIP(hipMemcpyAsync(out1, d_o1, n_o1 * 8, hipMemcpyDeviceToHost, s));
+    if (n_st) GN_HIP(hipMemcpyAsync(status, d_st, n_st * sizeof(int), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipStreamSynchronize(s));
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int enlsip_gn_gradient_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, double* dgrad) {
+    if (!h) return -1;
+    GN_TRY
+    return consumer_dev(h, CONS_GRADIENT, prob0, count, {nullptr, nullptr, 0.0, dgrad, nullptr, nullptr});
+    GN_CATCH(h)
+}
+
+int enlsip_gn_jacobian_times_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dp, double* dJp,
+                                         double* dAp) {
+    if (!h) return -1;
+    GN_TRY
+    return consumer_dev(h, CONS_JTIMES, prob0, count, {dp, nullptr, 0.0, dJp, dAp, nullptr});
+    GN_CATCH(h)
+}
+
+int enlsip_gn_first_lagrange_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dgrad_fx,
+                                         const double* ddiag_scale, double eps_rank, double* dlambda, double* dgrad_res,
+                                         int* dstatus) {
+    if (!h) return -1;
+    GN_TRY
+    return consumer_dev(h, CONS_FIRST, prob0, count, {dgrad_fx, ddiag_scale, eps_rank, dlambda, dgrad_res, dstatus});
+    GN_CATCH(h)
+}
+
+int enlsip_gn_second_lagrange_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dp_gn,
+                                          const double* ddiag_scale, double eps_rank, double* dlambda, int* dstatus) {
+    if (!h) return -1;
+    GN_TRY
+    return consumer_dev(h, CONS_SECOND, prob0, count, {dp_gn, ddiag_scale, eps_rank, dlambda, nullptr, dstatus});
+    GN_CATCH(h)
+}
+
+int enlsip_gn_gradient_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, double* grad) {
+    if (!h) return -1;
+    GN_TRY
+    if (!grad) { h->err = "grad is NULL"; return -4; }
+    return consumer_host(h, CONS_GRADIENT, prob0, count, nullptr, nullptr, 0.0, grad, nullptr, nullptr);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_jacobian_times_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* p, double* Jp, double* Ap) {
+    if (!h) return -1;
+    GN_TRY
+    if (!p) { h->err = "p is NULL"; return -4; }
+    if (!Jp && !Ap) { h->err = "Jp and Ap are both NULL"; return -4; }
+    return consumer_host(h, CONS_JTIMES, prob0, count, p, nullptr, 0.0, Jp, Ap, nullptr);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_first_lagrange_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* grad_fx,
+                                     const double* diag_scale, double eps_rank, double* lambda, double* grad_res, int* status) {
+    if (!h) return -1;
+    GN_TRY
+    return consumer_host(h, CONS_FIRST, prob0, count, grad_fx, diag_scale, eps_rank, lambda, grad_res, status);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_second_lagrange_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* p_gn,
+                                      const double* diag_scale, double eps_rank, double* lambda, int* status) {
+    if (!h) return -1;
+    GN_TRY
+    if (!p_gn) { h->err = "p_gn is NULL"; return -4; }
+    return consumer_host(h, CONS_SECOND, prob0, count, p_gn, diag_scale, eps_rank, lambda, nullptr, status);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_get_consumer_form(enlsip_gn_handle h, int* form) {
+    if (!h) return -1;
+    if (!form) { h->err = "form is NULL"; return -2; }
+    *form = h->consumer_form;
+    return 0;
+}
+
+}  // extern "C"

@@ -409,6 +409,70 @@ function gn_search_direction_batched_hip(h::Handle, Js::Array{Float64,3}, rxs::M
     return P, infos
 end
 
+# ---- the consumers of a batched solve over a range of its problems (one call, a fixed number of launches) ----------------------
+#
+# A batched outer iteration: solve (ragged), first estimate over the batch, the host deletion test of update_working_set
+# (src/enlsip_functions.jl:700-704), then a ragged re-solve of the problems whose working set changed.  Problem `prob0 + j`
+# (0-based, as the C ABI counts) is column `j + 1` of every array; lambda and Ap have `t_max` rows, zero past a problem's own t.
+# status: 0, 1 singular triangular system, 2 pseudo-rank beyond the solve's rank (the per-problem -7).
+
+batched_check(h::Handle, rc::Integer) = (rc == 0 || rc == 1 || check(h, rc); rc)
+
+"""    gradient_batched_hip(h, n, prob0, count) -> G (n×count): J' rx of every problem of the range (src/enlsip_functions.jl:2690)"""
+function gradient_batched_hip(h::Handle, n::Integer, prob0::Integer, count::Integer)
+    G = zeros(Float64, n, count)
+    GC.@preserve G check(h, ccall((:enlsip_gn_gradient_batched, LIB), Cint, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}),
+                                  h.ptr, prob0, count, G))
+    return G
+end
+
+"""    jacobian_times_batched_hip(h, m, t_max, P, prob0) -> (JP (m×count), AP (t_max×count)): the line-search products
+(src/enlsip_functions.jl:2226-2229) of the directions in the columns of `P` (n×count)"""
+function jacobian_times_batched_hip(h::Handle, m::Integer, t_max::Integer, P::Matrix{Float64}, prob0::Integer)
+    count = size(P, 2)
+    JP = zeros(Float64, m, count); AP = zeros(Float64, max(t_max, 1), count)
+    GC.@preserve P JP AP check(h, ccall((:enlsip_gn_jacobian_times_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h.ptr, prob0, count, P, JP, AP))
+    return JP, AP[1:t_max, :]
+end
+
+"""    first_lagrange_mult_estimate_batched_hip(h, t_max, prob0, count, grads, diag_scales, ε_rank) -> (Λ, grad_res, status)
+
+first_lagrange_mult_estimate! (src/enlsip_functions.jl:461-508) of every problem of the range.  `grads` (n×count) = nothing: J' rx
+of the resident J, rx; `diag_scales` (t_max×count) = nothing: no back-transform."""
+function first_lagrange_mult_estimate_batched_hip(h::Handle, t_max::Integer, prob0::Integer, count::Integer,
+                                                  grads::Union{Nothing,Matrix{Float64}},
+                                                  diag_scales::Union{Nothing,Matrix{Float64}}, ε_rank::Float64)
+    Λ = zeros(Float64, max(t_max, 1), count); gres = zeros(Float64, count); st = zeros(Cint, count)
+    g = grads === nothing ? C_NULL : pointer(grads)
+    ds = diag_scales === nothing ? C_NULL : pointer(diag_scales)
+    GC.@preserve grads diag_scales Λ gres st batched_check(h, ccall((:enlsip_gn_first_lagrange_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+        h.ptr, prob0, count, g, ds, ε_rank, Λ, gres, st))
+    return Λ[1:t_max, :], gres, st
+end
+
+"""    second_lagrange_mult_estimate_batched_hip(h, t_max, prob0, P_gn, diag_scales, ε_rank) -> (Λ, status)
+
+second_lagrange_mult_estimate! (src/enlsip_functions.jl:514-537) of every problem of the range; `P_gn` is n×count."""
+function second_lagrange_mult_estimate_batched_hip(h::Handle, t_max::Integer, prob0::Integer, P_gn::Matrix{Float64},
+                                                   diag_scales::Union{Nothing,Matrix{Float64}}, ε_rank::Float64)
+    count = size(P_gn, 2)
+    Λ = zeros(Float64, max(t_max, 1), count); st = zeros(Cint, count)
+    ds = diag_scales === nothing ? C_NULL : pointer(diag_scales)
+    GC.@preserve P_gn diag_scales Λ st batched_check(h, ccall((:enlsip_gn_second_lagrange_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Cint}),
+        h.ptr, prob0, count, P_gn, ds, ε_rank, Λ, st))
+    return Λ[1:t_max, :], st
+end
+
+"""    consumer_form_hip(h) -> 0 general, 1 wave per problem, -1 none yet: the form of the last batched estimate on `h`"""
+function consumer_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_consumer_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

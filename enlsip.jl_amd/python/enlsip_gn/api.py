@@ -347,6 +347,77 @@ class GNSolver:
         self._chk(self._lib.enlsip_gn_second_lagrange(self._h, prob, _fptr(p), _fptr(ds), eps_rank, _fptr(lam)))
         return lam
 
+    # ---- the same consumers over a range of the resident batch (one call, a fixed number of launches) ----------------------
+    # Slot j of every array holds problem prob0 + j; lambda / Ap have t_max entries per problem (zero past a ragged problem's t).
+    # The estimates return per-problem status (0, 1 singular triangular system, 2 pseudo-rank beyond the solve's rank).
+    def _chk_batched(self, rc: int) -> int:
+        if rc < 0 or rc > 1:
+            self._chk(rc)
+        return rc
+
+    def gradient_batched(self, n: int, prob0: int = 0, count: int = 1) -> np.ndarray:
+        """J' rx of problems prob0 .. prob0+count-1: (count, n)."""
+        g = np.zeros((count, n))
+        self._chk(self._lib.enlsip_gn_gradient_batched(self._h, prob0, count, _fptr(g)))
+        return g
+
+    def jacobian_times_batched(self, m: int, t_max: int, p: np.ndarray, prob0: int = 0, jp: bool = True, ap: bool = True):
+        """(J p, A_active p) per problem; p: (count, n).  Returns (Jp (count, m) or None, Ap (count, t_max) or None)."""
+        pv = np.ascontiguousarray(p, dtype=np.float64)
+        count = pv.shape[0]
+        Jp = np.zeros((count, m)) if jp else None
+        Ap = np.zeros((count, t_max)) if ap else None
+        self._chk(self._lib.enlsip_gn_jacobian_times_batched(self._h, prob0, count, _fptr(pv), _fptr(Jp), _fptr(Ap)))
+        return Jp, Ap
+
+    def first_lagrange_batched(self, t_max: int, prob0: int = 0, count: int = 1, grad_fx: Optional[np.ndarray] = None,
+                               diag_scale: Optional[np.ndarray] = None, eps_rank: float = SQRT_EPS):
+        """first_lagrange_mult_estimate! per problem: (lambda (count, t_max), grad_res (count,), status (count,), rc)."""
+        g = None if grad_fx is None else np.ascontiguousarray(grad_fx, dtype=np.float64)
+        ds = None if diag_scale is None else np.ascontiguousarray(diag_scale, dtype=np.float64)
+        lam, gres, st = np.zeros((count, t_max)), np.zeros(count), np.zeros(count, dtype=np.int32)
+        rc = self._chk_batched(self._lib.enlsip_gn_first_lagrange_batched(
+            self._h, prob0, count, _fptr(g), _fptr(ds), eps_rank, _fptr(lam), _fptr(gres), st.ctypes.data_as(C.c_void_p)))
+        return lam, gres, st, rc
+
+    def second_lagrange_batched(self, t_max: int, p_gn: np.ndarray, prob0: int = 0, diag_scale: Optional[np.ndarray] = None,
+                                eps_rank: float = SQRT_EPS):
+        """second_lagrange_mult_estimate! per problem; p_gn: (count, n).  Returns (lambda (count, t_max), status, rc)."""
+        p = np.ascontiguousarray(p_gn, dtype=np.float64)
+        count = p.shape[0]
+        ds = None if diag_scale is None else np.ascontiguousarray(diag_scale, dtype=np.float64)
+        lam, st = np.zeros((count, t_max)), np.zeros(count, dtype=np.int32)
+        rc = self._chk_batched(self._lib.enlsip_gn_second_lagrange_batched(
+            self._h, prob0, count, _fptr(p), _fptr(ds), eps_rank, _fptr(lam), st.ctypes.data_as(C.c_void_p)))
+        return lam, st, rc
+
+    # device forms: raw device pointers (e.g. torch tensor .data_ptr(), 0 = NULL); return the call's rc (0 or 1)
+    def gradient_batched_dev(self, prob0: int, count: int, dgrad: int) -> int:
+        v = lambda x: C.c_void_p(x) if x else None
+        return self._chk_batched(self._lib.enlsip_gn_gradient_batched_dev(self._h, prob0, count, v(dgrad)))
+
+    def jacobian_times_batched_dev(self, prob0: int, count: int, dp: int, dJp: int = 0, dAp: int = 0) -> int:
+        v = lambda x: C.c_void_p(x) if x else None
+        return self._chk_batched(self._lib.enlsip_gn_jacobian_times_batched_dev(self._h, prob0, count, v(dp), v(dJp), v(dAp)))
+
+    def first_lagrange_batched_dev(self, prob0: int, count: int, dlambda: int, dgrad_fx: int = 0, ddiag_scale: int = 0,
+                                   eps_rank: float = SQRT_EPS, dgrad_res: int = 0, dstatus: int = 0) -> int:
+        v = lambda x: C.c_void_p(x) if x else None
+        return self._chk_batched(self._lib.enlsip_gn_first_lagrange_batched_dev(
+            self._h, prob0, count, v(dgrad_fx), v(ddiag_scale), eps_rank, v(dlambda), v(dgrad_res), v(dstatus)))
+
+    def second_lagrange_batched_dev(self, prob0: int, count: int, dp_gn: int, dlambda: int, ddiag_scale: int = 0,
+                                    eps_rank: float = SQRT_EPS, dstatus: int = 0) -> int:
+        v = lambda x: C.c_void_p(x) if x else None
+        return self._chk_batched(self._lib.enlsip_gn_second_lagrange_batched_dev(
+            self._h, prob0, count, v(dp_gn), v(ddiag_scale), eps_rank, v(dlambda), v(dstatus)))
+
+    def consumer_form(self) -> int:
+        """Form of the last batched multiplier estimate: 0 general, 1 wave per problem, -1 none yet."""
+        f = C.c_int(0)
+        self._chk(self._lib.enlsip_gn_get_consumer_form(self._h, C.byref(f)))
+        return int(f.value)
+
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).
         Returns (p, error) as the reference does (error = True: W22 not positive definite, p = 0)."""

@@ -249,6 +249,54 @@ int enlsip_gn_first_lagrange(enlsip_gn_handle h, int64_t prob, const double* gra
 int enlsip_gn_second_lagrange(enlsip_gn_handle h, int64_t prob, const double* p_gn, const double* diag_scale,
                               double eps_rank, double* lambda);
 
+/* ---- the same consumers over a range of the resident batch ----------------------------------------------------------------------
+ * update_working_set needs the first estimate on every outer iteration (src/enlsip_functions.jl:700-704) and the second whenever
+ * t == rankA && rankJ2 == min(m, n - rankA) (:745-747, :773-776); the line search needs J p and A p (:2226-2229).  These forms
+ * answer for problems prob0 .. prob0+count-1 (indices in the caller's whole batch, as the accessors count them) in a fixed number
+ * of launches whatever count is.  Slot j holds problem prob0 + j; strides are those of enlsip_gn_solve_batched with t = t_max:
+ *   grad, p, p_gn, grad_fx: n    Jp: m    Ap, lambda, diag_scale: t_max    grad_res, status: 1
+ * After a ragged solve each problem uses its own t[k]; lambda and Ap entries past t[k] are exactly 0.
+ *
+ * enlsip_gn_gradient_batched*         grad = J' rx                         src/enlsip_functions.jl:2690, :2734, :2830
+ * enlsip_gn_jacobian_times_batched*   Jp = J p, Ap = C.A p (active rows)   src/enlsip_functions.jl:2226-2229
+ *                                     Jp or Ap may be NULL, not both.
+ * enlsip_gn_first_lagrange_batched*   first_lagrange_mult_estimate!        src/enlsip_functions.jl:461-508
+ *                                     grad_fx = NULL: J' rx of the resident J, rx; grad_res and status may be NULL.  A problem with
+ *                                     t[k] = 0 gets grad_res = ||grad|| (grad = grad_fx or J' rx); the per-problem entry point
+ *                                     reports 0 there when grad_fx is NULL (it has no gradient), so that case is checked against the
+ *                                     reference's definition, not against enlsip_gn_first_lagrange.
+ * enlsip_gn_second_lagrange_batched*  second_lagrange_mult_estimate!       src/enlsip_functions.jl:514-537
+ * diag_scale = NULL: no back-transform.  status[j]: 0; 1 singular triangular system (the per-problem return 1); 2 the pseudo-rank
+ * under eps_rank exceeds the rank the solve used, whose J1 columns are no longer resident (the per-problem -7).
+ * Returns 0 when every status is 0, 1 when some problem is flagged; argument and state errors are negative (last_error):
+ *   -1 no resident factors or a resident input missing (as the per-problem entry points; after enlsip_gn_factor_constraints:
+ *      grad_fx is required and there is no second estimate), -2 count < 1, -3 the range leaves the resident batch or reaches into
+ *      an earlier chunk of a batch above the launch limit (need_factors' message), -4 a required pointer is NULL.
+ * The range may straddle the two pipelined halves of a batch; problems solved on a rescue handle (magnitudes beyond the plain
+ * range) are answered by the per-problem entry points, bitwise.  The _dev forms take DEVICE buffers and return after one
+ * synchronisation of each stream that ran a part of the range (the rescue route synchronises more).  The host forms stage through
+ * a buffer of their own, never through a buffer the resident solve reads.
+ * Results: gradient and products bitwise those of the per-problem entry points; estimates bitwise in the general form (one
+ * workgroup per problem, the per-problem kernel's body) and to rounding in the wave-per-problem form, used for n <= 64 and
+ * t_max <= 64 unless ENLSIP_GN_LAGRANGE_SMALL=0 (read at handle creation).
+ */
+int enlsip_gn_gradient_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, double* grad);
+int enlsip_gn_gradient_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, double* dgrad);
+int enlsip_gn_jacobian_times_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* p, double* Jp, double* Ap);
+int enlsip_gn_jacobian_times_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dp,
+                                         double* dJp, double* dAp);
+int enlsip_gn_first_lagrange_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* grad_fx,
+                                     const double* diag_scale, double eps_rank, double* lambda, double* grad_res, int* status);
+int enlsip_gn_first_lagrange_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dgrad_fx,
+                                         const double* ddiag_scale, double eps_rank, double* dlambda,
+                                         double* dgrad_res, int* dstatus);
+int enlsip_gn_second_lagrange_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* p_gn,
+                                      const double* diag_scale, double eps_rank, double* lambda, int* status);
+int enlsip_gn_second_lagrange_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dp_gn,
+                                          const double* ddiag_scale, double eps_rank, double* dlambda, int* dstatus);
+/* form of the last batched multiplier estimate on this handle: 0 general, 1 wave per problem, -1 none yet */
+int enlsip_gn_get_consumer_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
