@@ -885,10 +885,11 @@ static int unscale_jacobian_side(enlsip_gn_handle h, double* dd) {
     return 0;
 }
 // largest |entry| of the four inputs of problem 0 of a one-problem solve -> power-of-two shifts that bring J, rx / A', cx to
-// magnitude ~1 (0: inside the band, zero, or not finite — nothing to rescale)
-static int extreme_shifts(enlsip_gn_handle h, long long m, long long n, long long t, const double* dJ, long long ldj, const double* drx,
-                          const double* dAt, long long ldat, const double* dcx, int* shiftJ, int* shiftA) {
+// magnitude ~1 (0: inside the band, zero, or not finite — nothing to rescale).  A null input side is not looked at.
+static int extreme_shifts(enlsip_gn_handle h, const BatchOperands& v, int* shiftJ, int* shiftA) {
     hipStream_t s = h->stream;
+    const long long m = v.m, n = v.n, t = v.t, ldj = v.ldj, ldat = v.ldat;
+    const double *dJ = v.J, *drx = v.rx, *dAt = v.At, *dcx = v.cx;
     unsigned long long* dmx = (unsigned long long*)(h->small + 32);      // 2 words of the handle's 256-byte scalar area
     GN_HIP(hipMemsetAsync(dmx, 0, 16, s));
     if (dJ && drx) {
@@ -913,6 +914,27 @@ static int extreme_shifts(enlsip_gn_handle h, long long m, long long n, long lon
     };
     *shiftJ = shift_of(hb[0]);
     *shiftA = shift_of(hb[1]);
+    return 0;
+}
+// the copies of a one-problem solve's inputs scaled by 2^sJ (J, rx) and 2^sA (A', cx) in rs_buf; a zero shift copies nothing
+static int scaled_copies(enlsip_gn_handle h, const BatchOperands& v, int sJ, int sA) {
+    const long long m = v.m, n = v.n, t = v.t;
+    const size_t nJ = (size_t)m * n, nA = (size_t)n * t;
+    int rc = grow(h, h->rs_buf, (nJ + (size_t)m + nA + (size_t)t + 8) * 8);
+    if (rc) return rc;
+    h->rs_J = (double*)h->rs_buf.p; h->rs_rx = h->rs_J + nJ; h->rs_At = h->rs_rx + m; h->rs_cx = h->rs_At + nA;
+    auto copy_scaled = [&](double* dst, long long ldd, const double* src, long long lds, long long rows, long long cols, int sh) {
+        hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)std::min<long long>((rows + 255) / 256, 1024), (unsigned)cols), dim3(256), 0,
+                           h->stream, dst, ldd, src, lds, (int)rows, (int)cols, sh);
+    };
+    if (sJ) {
+        copy_scaled(h->rs_J, m, v.J, v.ldj, m, n, sJ);
+        copy_scaled(h->rs_rx, m, v.rx, m, m, 1, sJ);
+    }
+    if (sA) {
+        copy_scaled(h->rs_At, n, v.At, v.ldat, n, t, sA);
+        copy_scaled(h->rs_cx, t, v.cx, t, t, 1, sA);
+    }
     return 0;
 }
 
@@ -1071,13 +1093,52 @@ static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m
     return scaledA ? unscale_constraint_side(h) : 0;
 }
 
-static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long n, long long t,
-                     const double* dJ, long long ldj, long long strideJ, const double* drx,
-                     const double* dAt, long long ldat, long long strideAt, const double* dcx,
-                     double eps_rank, long long dimA_ov, long long dimJ2_ov,
-                     double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
-                     long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo = nullptr,
-                     const int* htk = nullptr) {
+static enlsip_gn_info info_of(const ProbState& st) {
+    return {st.rankA, st.rankJ2, st.code, st.dimA, st.dimJ2, st.status};
+}
+
+// stage times of the last solve from its events and the event pairs around the trailing-update launches (profiling on)
+static int collect_stage_ms(enlsip_gn_handle h) {
+    float ms;
+    GN_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stage_ms[ENLSIP_GN_STAGE_CONSTRAINT] = ms;
+    GN_HIP(hipEventElapsedTime(&ms, h->ev[1], h->ev[2])); h->stage_ms[ENLSIP_GN_STAGE_JQ1] = ms;
+    GN_HIP(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    float upd = 0.f;
+    h->upd_launch_ms.clear();
+    for (size_t i = 0; i + 1 < h->upd_used; i += 2) {
+        float u;
+        GN_HIP(hipEventElapsedTime(&u, h->upd_ev[i], h->upd_ev[i + 1]));
+        upd += u;
+        h->upd_launch_ms.push_back(u);
+    }
+    h->upd_launches = (long long)(h->upd_used / 2);
+    h->upd_avg_ms = h->upd_launches ? upd / (float)h->upd_launches : 0.f;
+    // every trailing-update launch of the sweep is "update" (far level-0 passes AND tree levels / second-panel columns);
+    // "panel" = the factorisations (and whatever else the sweep launches)
+    float oth = 0.f;
+    for (size_t i = 0; i + 1 < h->oth_used; i += 2) {
+        float u;
+        GN_HIP(hipEventElapsedTime(&u, h->oth_ev[i], h->oth_ev[i + 1]));
+        oth += u;
+    }
+    h->oth_ms = oth;
+    h->oth_launches = (long long)(h->oth_used / 2);
+    h->stage_ms[ENLSIP_GN_STAGE_UPDATE] = upd + oth;
+    h->stage_ms[ENLSIP_GN_STAGE_PANEL] = ms - upd - oth;
+    GN_HIP(hipEventElapsedTime(&ms, h->ev[3], h->ev[4])); h->stage_ms[ENLSIP_GN_STAGE_PIVOT] = ms;
+    GN_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[4])); h->stage_ms[ENLSIP_GN_STAGE_TOTAL] = ms;
+    return 0;
+}
+
+// a handle of the library's own (pipeline half, rescue handle, TSQR sub-handle) with h's device, flags and tile rows
+static int create_helper(enlsip_gn_handle h, enlsip_gn_handle* out, hipStream_t stream) {
+    enlsip_gn_opts o{};
+    o.device = h->device; o.flags = h->flags; o.panel_width = 0; o.tile_rows = h->tile_rows; o.stream = (void*)stream;
+    return enlsip_gn_create(out, &o);
+}
+
+static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
+    const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
     h->split = 0;   // routing of accessors to the pipeline child is (re)established by the batched entry point
     h->chunk0 = 0;  // ... and to the resident chunk by solve_chunked
     gn_route_acc = 0;
@@ -1087,27 +1148,24 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
     h->upper_once = false;
     int rc = check_limits(h, batch, m, n, t);
     if (rc) return rc;
-    if (ldj < m) { h->err = "ldj < m"; return -7; }
-    if (t > 0 && ldat < n) { h->err = "ldat < n"; return -11; }
+    if (v.ldj < m) { h->err = "ldj < m"; return -7; }
+    if (t > 0 && v.ldat < n) { h->err = "ldat < n"; return -11; }
     GN_HIP(hipSetDevice(h->device));
     rc = make_plan(h, batch, m, n, t);
     if (rc) return rc;
     const Plan& P = h->plan;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
-    h->last_J = dJ; h->last_ldj = ldj; h->last_strideJ = strideJ;
-    h->last_rx = drx; h->last_stride_rx = m;
-    h->last_cx = dcx; h->last_stride_cx = t;
-    h->last_At = dAt; h->last_ldat = ldat; h->last_strideAt = strideAt;
+    h->last = v.inputs();
     h->sc_eJ = 0;
     if (!reuse) h->sc_eA = 0;       // (a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it)
     h->rescue_prob.clear();
     hipStream_t s = h->stream;
     // ragged batch: every problem's own t, kept on the host for the accessors and copied to the device for the constraint kernels
     int t_min = (int)t;
-    if (htk) {
-        h->h_tk.assign(htk, htk + batch);
-        for (int v : h->h_tk) t_min = std::min(t_min, v);
+    if (v.tk) {
+        h->h_tk.assign(v.tk, v.tk + batch);
+        for (int tk : h->h_tk) t_min = std::min(t_min, tk);
         rc = grow(h, h->tkbuf, (size_t)batch * sizeof(int));
         if (rc) return rc;
         GN_HIP(hipMemcpyAsync(h->tkbuf.p, h->h_tk.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s));
@@ -1132,7 +1190,7 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
     // 1. constraint stage
     GN_TRACE(h, "solve m=%lld n=%lld t=%lld batch=%lld: constraint stage%s", m, n, t, batch, reuse ? " (resident)" : "");
     if (!reuse) {       // enlsip_gn_solve_factored: F_A, F_L11, b, p1, T and the state record are those of enlsip_gn_factor_constraints
-        rc = run_constraint_stage(h, batch, m, n, t, dAt, ldat, strideAt, dcx, eps_rank, dimA_ov);
+        rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov);
         if (rc) return rc;
     }
     mark(1);
@@ -1181,10 +1239,10 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
         fa.W = h->W; fa.sW = P.sW; fa.Rt = h->Rt; fa.sRt = P.sRt; fa.tauJ = h->tauJ; fa.sTauJ = P.sTauJ;
         fa.jpvtJ = h->jpvtJ; fa.sJJ = P.sJJ; fa.FA = h->FA; fa.sFA = P.sFA; fa.tauA = h->tauA; fa.sTauA = P.sTauA;
         fa.p1 = h->p1; fa.sP1 = P.sP1; fa.bvec = h->bvec; fa.sB = P.sB; fa.zsave = h->zsave; fa.sZ = P.sZ;
-        fa.p_out = dp; fa.sPo = n; fa.b_out = db; fa.sBo = t; fa.d_out = dd; fa.sDo = m;
-        fa.jA_out = djA; fa.sJAo = t; fa.jpvtA = h->jpvtA; fa.sJA = P.sJA;
-        fa.jL_out = djL; fa.sJLo = P.kA; fa.jpvtL = h->jpvtL; fa.sJL = P.sJL;
-        fa.jJ_out = djJ; fa.sJJo = n;
+        fa.p_out = v.p; fa.sPo = n; fa.b_out = v.b; fa.sBo = t; fa.d_out = v.d; fa.sDo = m;
+        fa.jA_out = v.jpvtA; fa.sJAo = t; fa.jpvtA = h->jpvtA; fa.sJA = P.sJA;
+        fa.jL_out = v.jpvtL; fa.sJLo = P.kA; fa.jpvtL = h->jpvtL; fa.sJL = P.sJL;
+        fa.jJ_out = v.jpvtJ2; fa.sJJo = n;
         fa.state = h->state;
         fa.n2cap = n2_launch;
         {
@@ -1219,43 +1277,33 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
     }
     return 0;
     };
-    rc = attempts(dJ, ldj, strideJ, drx, 0);
+    rc = attempts(v.J, v.ldj, v.strideJ, v.rx, 0);
     if (rc) return rc;
     // ---- magnitudes beyond the range of plain sums of squares: LAPACK's result through a power-of-two scaling (gn_rescale.hpp) ----
     {
         const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
         bool flagged = false;
         for (long long k = 0; k < batch; ++k) flagged = flagged || (h->h_state[k].status & fl);
-        if (flagged && batch == 1 && !htk) {
+        if (flagged && batch == 1 && !v.tk) {
             int sJ = 0, sA = 0;
-            rc = extreme_shifts(h, m, n, t, dJ, ldj, drx, reuse ? nullptr : dAt, ldat, reuse ? nullptr : dcx, &sJ, &sA);
+            BatchOperands looked = v;
+            if (reuse) { looked.At = nullptr; looked.cx = nullptr; }
+            rc = extreme_shifts(h, looked, &sJ, &sA);
             if (rc) return rc;
             if (sJ || sA) {
                 GN_TRACE(h, "rescale: J, rx by 2^%d, A', cx by 2^%d", sJ, sA);
-                const size_t nJ = (size_t)m * n, nA = (size_t)n * t;
-                rc = grow(h, h->rs_buf, (nJ + (size_t)m + nA + (size_t)t + 8) * 8);
+                rc = scaled_copies(h, v, sJ, sA);
                 if (rc) return rc;
-                h->rs_J = (double*)h->rs_buf.p; h->rs_rx = h->rs_J + nJ; h->rs_At = h->rs_rx + m; h->rs_cx = h->rs_At + nA;
-                auto copy_scaled = [&](double* dst, long long ldd, const double* src, long long lds, long long rows, long long cols, int sh) {
-                    hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)std::min<long long>((rows + 255) / 256, 1024), (unsigned)cols), dim3(256), 0, s,
-                                       dst, ldd, src, lds, (int)rows, (int)cols, sh);
-                };
-                if (sJ) {
-                    copy_scaled(h->rs_J, m, dJ, ldj, m, n, sJ);
-                    copy_scaled(h->rs_rx, m, drx, m, m, 1, sJ);
-                }
                 if (sA) {
-                    copy_scaled(h->rs_At, n, dAt, ldat, n, t, sA);
-                    copy_scaled(h->rs_cx, t, dcx, t, t, 1, sA);
                     h->sc_eA = sA;
-                    rc = run_constraint_stage(h, 1, m, n, t, dAt, ldat, strideAt, dcx, eps_rank, dimA_ov);     // on the scaled copies; scaled back
+                    rc = run_constraint_stage(h, 1, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov);     // on the scaled copies; scaled back
                     if (rc) return rc;
                 }
                 h->sc_eJ = sJ;
-                rc = attempts(sJ ? h->rs_J : dJ, sJ ? m : ldj, sJ ? (long long)nJ : strideJ, sJ ? h->rs_rx : drx, sJ);
+                rc = sJ ? attempts(h->rs_J, m, m * n, h->rs_rx, sJ) : attempts(v.J, v.ldj, v.strideJ, v.rx, 0);
                 if (rc) return rc;
                 if (sJ) {
-                    rc = unscale_jacobian_side(h, dd);
+                    rc = unscale_jacobian_side(h, v.d);
                     if (rc) return rc;
                 }
                 GN_ROUTE(ENLSIP_GN_ROUTE_RESCALED);
@@ -1266,18 +1314,17 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
             for (long long k = 0; k < batch; ++k) {
                 if (!(h->h_state[k].status & fl)) continue;
                 int sJ = 0, sA = 0;
-                const long long tk = htk ? htk[k] : t;      // a problem of a ragged batch is rescued with its own t (strides stay t_max)
-                rc = extreme_shifts(h, m, n, tk, dJ + k * strideJ, ldj, drx + k * m, dAt ? dAt + k * strideAt : nullptr, ldat,
-                                    dcx ? dcx + k * t : nullptr, &sJ, &sA);
+                BatchOperands one = v.slice(k, 1);      // offsets with the batch's strides (t_max) ...
+                if (v.tk) one.t = v.tk[k];              // ... and a problem of a ragged batch rescued with its own t
+                one.dinfo = nullptr; one.hinfo = nullptr; one.tk = nullptr;
+                rc = extreme_shifts(h, one, &sJ, &sA);
                 if (rc) return rc;
                 if (!sJ && !sA) continue;
                 const size_t j = h->rescue_prob.size();
                 if (j >= 64) { h->err = "more than 64 problems of the batch need rescaling (magnitudes beyond 2^+-400): solve them separately"; return -18; }
                 if (j >= h->rescue.size()) {
-                    enlsip_gn_opts o{};
-                    o.device = h->device; o.flags = h->flags; o.panel_width = 0; o.tile_rows = h->tile_rows; o.stream = nullptr;
                     enlsip_gn_handle r = nullptr;
-                    rc = enlsip_gn_create(&r, &o);
+                    rc = create_helper(h, &r, nullptr);
                     if (rc) { h->err = "could not create a handle for a rescaled problem"; return rc; }
                     r->is_rescue = true;
                     r->pipeline = false;
@@ -1285,10 +1332,7 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
                 }
                 enlsip_gn_handle r = h->rescue[j];
                 const unsigned long long route_here = gn_route_acc;
-                rc = solve_dev(r, 1, m, n, tk, dJ + k * strideJ, ldj, strideJ, drx + k * m, dAt ? dAt + k * strideAt : nullptr, ldat, strideAt,
-                               dcx ? dcx + k * t : nullptr, eps_rank, dimA_ov, dimJ2_ov, dp ? dp + k * n : nullptr, db ? db + k * t : nullptr,
-                               dd ? dd + k * m : nullptr, nullptr, djA ? djA + k * t : nullptr, djL ? djL + k * P.kA : nullptr,
-                               djJ ? djJ + k * n : nullptr, nullptr);
+                rc = solve_dev(r, one, eps_rank, dimA_ov, dimJ2_ov);
                 gn_route_acc = route_here | r->route;
                 if (rc) { h->err = r->err; return rc; }
                 GN_HIP(hipSetDevice(h->device));
@@ -1302,52 +1346,18 @@ static int solve_dev(enlsip_gn_handle h, long long batch, long long m, long long
             GN_HIP(hipGetLastError());
         }
     }
-    if (hinfo)
-        for (long long k = 0; k < batch; ++k) {
-            const ProbState& st = h->h_state[k];
-            hinfo[k] = {st.rankA, st.rankJ2, st.code, st.dimA, st.dimJ2, st.status};
-        }
-    if (dinfo) {
+    if (v.hinfo)
+        for (long long k = 0; k < batch; ++k) v.hinfo[k] = info_of(h->h_state[k]);
+    if (v.dinfo) {
         // info records are produced on the host from the state mirror and copied to the device buffer
         std::vector<enlsip_gn_info> tmp((size_t)batch);
-        for (long long k = 0; k < batch; ++k) {
-            const ProbState& st = h->h_state[k];
-            tmp[k] = {st.rankA, st.rankJ2, st.code, st.dimA, st.dimJ2, st.status};
-        }
-        GN_HIP(hipMemcpyAsync(dinfo, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
+        for (long long k = 0; k < batch; ++k) tmp[k] = info_of(h->h_state[k]);
+        GN_HIP(hipMemcpyAsync(v.dinfo, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
         GN_HIP(hipStreamSynchronize(s));
     }
     if (h->profiling) {
-        float ms;
-        const int map[5][2] = {{0, 1}, {1, 2}, {2, 3}, {3, 4}, {0, 4}};
-        GN_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stage_ms[ENLSIP_GN_STAGE_CONSTRAINT] = ms;
-        GN_HIP(hipEventElapsedTime(&ms, h->ev[1], h->ev[2])); h->stage_ms[ENLSIP_GN_STAGE_JQ1] = ms;
-        GN_HIP(hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-        float upd = 0.f;
-        h->upd_launch_ms.clear();
-        for (size_t i = 0; i + 1 < h->upd_used; i += 2) {
-            float u;
-            GN_HIP(hipEventElapsedTime(&u, h->upd_ev[i], h->upd_ev[i + 1]));
-            upd += u;
-            h->upd_launch_ms.push_back(u);
-        }
-        h->upd_launches = (long long)(h->upd_used / 2);
-        h->upd_avg_ms = h->upd_launches ? upd / (float)h->upd_launches : 0.f;
-        // every trailing-update launch of the sweep is "update" (far level-0 passes AND tree levels / second-panel columns);
-        // "panel" = the factorisations (and whatever else the sweep launches)
-        float oth = 0.f;
-        for (size_t i = 0; i + 1 < h->oth_used; i += 2) {
-            float u;
-            GN_HIP(hipEventElapsedTime(&u, h->oth_ev[i], h->oth_ev[i + 1]));
-            oth += u;
-        }
-        h->oth_ms = oth;
-        h->oth_launches = (long long)(h->oth_used / 2);
-        h->stage_ms[ENLSIP_GN_STAGE_UPDATE] = upd + oth;
-        h->stage_ms[ENLSIP_GN_STAGE_PANEL] = ms - upd - oth;
-        GN_HIP(hipEventElapsedTime(&ms, h->ev[3], h->ev[4])); h->stage_ms[ENLSIP_GN_STAGE_PIVOT] = ms;
-        GN_HIP(hipEventElapsedTime(&ms, h->ev[0], h->ev[4])); h->stage_ms[ENLSIP_GN_STAGE_TOTAL] = ms;
-        (void)map;
+        rc = collect_stage_ms(h);
+        if (rc) return rc;
     }
     h->factors_valid = true;
     h->route = gn_route_acc;
@@ -1645,13 +1655,9 @@ int enlsip_gn_get_update_totals(enlsip_gn_handle h, float* far_ms, float* other_
 }
 
 // One launch set over at most GN_MAX_LAUNCH_BATCH problems: either two pipelined halves on two streams or one solve_dev.
-static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t,
-                            const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
-                            const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
-                            double eps_rank, int64_t dimA_ov, int64_t dimJ2_ov, double* dp, double* db, double* dd,
-                            enlsip_gn_info* dinfo, long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo,
-                            const int* htk = nullptr) {
+static int solve_launchable(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
     h->split = 0;
+    const long long batch = v.batch, m = v.m, n = v.n;
     // one-tile problems of the wave-per-problem pipeline (n <= 64, m <= 512: C3, C5) are a handful of short, uniform launches with
     // nothing latency-bound to hide behind them: the split costs C3 4 % (1.276 -> 1.325 M solves/s without it), C5 nothing
     const bool small_uniform = (n <= 64 && m <= 512) && !h->pipeline_forced;
@@ -1661,27 +1667,20 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
         // has enqueued on this handle's stream, and both halves are complete when this call returns
         GN_HIP(hipSetDevice(h->device));
         if (!h->child) {
-            enlsip_gn_opts o{};
-            o.device = h->device; o.flags = h->flags; o.panel_width = 0; o.tile_rows = h->tile_rows; o.stream = nullptr;
-            int rc = enlsip_gn_create(&h->child, &o);
+            int rc = create_helper(h, &h->child, nullptr);
             if (rc) { h->err = "could not create the second pipeline handle"; return rc; }
             h->child->pipeline = false;
         }
         if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
         GN_HIP(hipEventRecord(h->ev_fork, h->stream));
         GN_HIP(hipStreamWaitEvent(h->child->stream, h->ev_fork, 0));
-        const int64_t b0 = (batch + 1) / 2, b1 = batch - b0;
-        const int64_t kA = std::min(n, t);
+        const long long b0 = (batch + 1) / 2, b1 = batch - b0;
         enlsip_gn_handle c = h->child;
         int rc1 = 0;
         std::thread worker([&] {
             (void)hipSetDevice(c->device);
             try {
-                rc1 = solve_dev(c, b1, m, n, t, dJ + b0 * strideJ, ldj, strideJ, drx + b0 * m, dAt ? dAt + b0 * strideAt : nullptr,
-                                ldat, strideAt, dcx ? dcx + b0 * t : nullptr, eps_rank, -1, -1, dp ? dp + b0 * n : nullptr,
-                                db ? db + b0 * t : nullptr, dd ? dd + b0 * m : nullptr, dinfo ? dinfo + b0 : nullptr,
-                                djA ? djA + b0 * t : nullptr, djL ? djL + b0 * kA : nullptr, djJ ? djJ + b0 * n : nullptr,
-                                hinfo ? hinfo + b0 : nullptr, htk ? htk + b0 : nullptr);
+                rc1 = solve_dev(c, v.slice(b0, b1), eps_rank, -1, -1);
             } catch (...) {
                 c->err = "exception in the second pipeline half (out of host memory?)";
                 rc1 = 997;
@@ -1689,8 +1688,7 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
         });
         int rc0;
         try {
-            rc0 = solve_dev(h, b0, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, -1, -1, dp, db,
-                            dd, dinfo, djA, djL, djJ, hinfo, htk);
+            rc0 = solve_dev(h, v.slice(0, b0), eps_rank, -1, -1);
         } catch (...) {
             worker.join();
             throw;
@@ -1702,32 +1700,20 @@ static int solve_launchable(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
         h->route |= c->route | (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
         return 0;
     }
-    return solve_dev(h, batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, dimA_ov, dimJ2_ov, dp, db,
-                     dd, dinfo, djA, djL, djJ, hinfo, htk);
+    return solve_dev(h, v, eps_rank, dimA_ov, dimJ2_ov);
 }
 
 // Any batch: consecutive chunks of at most GN_MAX_LAUNCH_BATCH problems (the problem index is a grid y / z dimension).  The
 // factors that stay resident are those of the LAST chunk; accessors address problems by their index in the whole batch and
-// report an error for the earlier chunks (gn_accessors.inc: need_factors).
-static int solve_chunked(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t,
-                         const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
-                         const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
-                         double eps_rank, int64_t dimA_ov, int64_t dimJ2_ov, double* dp, double* db, double* dd,
-                         enlsip_gn_info* dinfo, long long* djA, long long* djL, long long* djJ, enlsip_gn_info* hinfo,
-                         const int* htk = nullptr) {
+// report an error for the earlier chunks (gn_accessors.inc: map_resident).
+static int solve_chunked(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
     h->chunk0 = 0;
-    const int64_t kA = std::min(n, t);
-    const int64_t nchunks = (batch + GN_MAX_LAUNCH_BATCH - 1) / GN_MAX_LAUNCH_BATCH;
-    const int64_t per = (batch + nchunks - 1) / nchunks;
+    const long long batch = v.batch;
+    const long long nchunks = (batch + GN_MAX_LAUNCH_BATCH - 1) / GN_MAX_LAUNCH_BATCH;
+    const long long per = (batch + nchunks - 1) / nchunks;
     unsigned long long route_all = nchunks > 1 ? (1ull << ENLSIP_GN_ROUTE_CHUNKED) : 0ull;
-    for (int64_t c0 = 0; c0 < batch; c0 += per) {
-        const int64_t nb = std::min(per, batch - c0);
-        int rc = solve_launchable(h, nb, m, n, t, dJ + c0 * strideJ, ldj, strideJ, drx + c0 * m,
-                                  dAt ? dAt + c0 * strideAt : nullptr, ldat, strideAt, dcx ? dcx + c0 * t : nullptr, eps_rank,
-                                  dimA_ov, dimJ2_ov, dp ? dp + c0 * n : nullptr, db ? db + c0 * t : nullptr,
-                                  dd ? dd + c0 * m : nullptr, dinfo ? dinfo + c0 : nullptr, djA ? djA + c0 * t : nullptr,
-                                  djL ? djL + c0 * kA : nullptr, djJ ? djJ + c0 * n : nullptr, hinfo ? hinfo + c0 : nullptr,
-                                  htk ? htk + c0 : nullptr);
+    for (long long c0 = 0; c0 < batch; c0 += per) {
+        int rc = solve_launchable(h, v.slice(c0, std::min(per, batch - c0)), eps_rank, dimA_ov, dimJ2_ov);
         if (rc) return rc;
         h->chunk0 = c0;
         route_all |= h->route;
@@ -1748,23 +1734,22 @@ int enlsip_gn_solve_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
     if (!dJ) { h->err = "dJ is NULL"; return -6; }
     if (!drx) { h->err = "drx is NULL"; return -9; }
     if (t > 0 && (!dAt || !dcx)) { h->err = "dAt / dcx is NULL with t > 0"; return -10; }
-    return solve_chunked(h, batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, -1, -1, dp, db, dd,
-                         dinfo, (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr);
+    return solve_chunked(h, {batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, dp, db, dd, dinfo, (long long*)djpvtA,
+                             (long long*)djpvtL, (long long*)djpvtJ2}, eps_rank, -1, -1);
     GN_CATCH(h)
 }
 
-static int solve_host(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t, const double* J,
-                      int64_t ldj, int64_t strideJ, const double* rx, const double* At, int64_t ldat,
-                      int64_t strideAt, const double* cx, double eps_rank, int64_t dimA_ov, int64_t dimJ2_ov,
-                      double* p, double* b, double* d, enlsip_gn_info* info, int64_t* jA, int64_t* jL, int64_t* jJ,
-                      bool factored = false, const int* htk = nullptr) {
+// hv: the caller's host arrays (hinfo = the info records): staged packed (ld = m / n), solved, outputs copied back
+static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_rank, long long dimA_ov, long long dimJ2_ov,
+                      bool factored = false) {
     if (!h) return -1;
     GN_TRY
+    const long long batch = hv.batch, m = hv.m, n = hv.n, t = hv.t;
     int rc = check_limits(h, batch, m, n, t);
     if (rc) return rc;
-    if (!J) { h->err = "J is NULL"; return -6; }
-    if (ldj < m) { h->err = "ldj < m"; return -7; }
-    if (!rx) { h->err = "rx is NULL"; return -9; }
+    if (!hv.J) { h->err = "J is NULL"; return -6; }
+    if (hv.ldj < m) { h->err = "ldj < m"; return -7; }
+    if (!hv.rx) { h->err = "rx is NULL"; return -9; }
     if (factored) {
         const Plan& P = h->plan;
         if (!(h->factors_valid && h->constraints_only && h->have_plan && P.batch == 1 && P.m == m && P.n == n && P.t == t)) {
@@ -1772,8 +1757,8 @@ static int solve_host(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, i
             return -1;
         }
     } else {
-        if (t > 0 && (!At || !cx)) { h->err = "At / cx is NULL with t > 0"; return -10; }
-        if (t > 0 && ldat < n) { h->err = "ldat < n"; return -11; }
+        if (t > 0 && (!hv.At || !hv.cx)) { h->err = "At / cx is NULL with t > 0"; return -10; }
+        if (t > 0 && hv.ldat < n) { h->err = "ldat < n"; return -11; }
     }
     // truncation dimensions index the triangular factors: dimA <= min(n, t) = rows of F_L11.R, dimJ2 <= min(m, n) >= kp
     // (the kernels clamp dimJ2 to kp = min(m, n - rankA), which is only known on the device)
@@ -1800,26 +1785,26 @@ static int solve_host(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, i
     long long* djA = (long long*)(dd + (size_t)batch * m);
     long long* djL = djA + (size_t)batch * t;
     long long* djJ = djL + (size_t)batch * kA;
+    const BatchOperands dv{batch, m, n, t, dJ, m, m * n, drx, dAt, n, n * t, dcx, dp, db, dd, nullptr, djA, djL, djJ, hv.hinfo, hv.tk};
     hipStream_t s = h->stream;
     for (int64_t k = 0; k < batch; ++k) {
-        GN_HIP(hipMemcpy2DAsync(dJ + (size_t)k * m * n, (size_t)m * 8, J + (size_t)k * strideJ, (size_t)ldj * 8,
+        GN_HIP(hipMemcpy2DAsync(dJ + (size_t)k * m * n, (size_t)m * 8, hv.J + (size_t)k * hv.strideJ, (size_t)hv.ldj * 8,
                                 (size_t)m * 8, (size_t)n, hipMemcpyHostToDevice, s));
         if (t > 0 && !factored)
-            GN_HIP(hipMemcpy2DAsync(dAt + (size_t)k * n * t, (size_t)n * 8, At + (size_t)k * strideAt,
-                                    (size_t)ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
+            GN_HIP(hipMemcpy2DAsync(dAt + (size_t)k * n * t, (size_t)n * 8, hv.At + (size_t)k * hv.strideAt,
+                                    (size_t)hv.ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
     }
-    GN_HIP(hipMemcpyAsync(drx, rx, (size_t)batch * m * 8, hipMemcpyHostToDevice, s));
-    if (t > 0 && !factored) GN_HIP(hipMemcpyAsync(dcx, cx, (size_t)batch * t * 8, hipMemcpyHostToDevice, s));
+    GN_HIP(hipMemcpyAsync(drx, hv.rx, (size_t)batch * m * 8, hipMemcpyHostToDevice, s));
+    if (t > 0 && !factored) GN_HIP(hipMemcpyAsync(dcx, hv.cx, (size_t)batch * t * 8, hipMemcpyHostToDevice, s));
     h->reuse_once = factored;      // A', cx (same staging slots) and the constraint factors are resident
-    rc = solve_chunked(h, batch, m, n, t, dJ, m, m * n, drx, dAt, n, n * t, dcx, eps_rank, dimA_ov, dimJ2_ov, dp, db, dd,
-                       nullptr, djA, djL, djJ, info, htk);
+    rc = solve_chunked(h, dv, eps_rank, dimA_ov, dimJ2_ov);
     if (rc) return rc;
-    if (p) GN_HIP(hipMemcpyAsync(p, dp, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
-    if (b && t > 0) GN_HIP(hipMemcpyAsync(b, db, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
-    if (d) GN_HIP(hipMemcpyAsync(d, dd, (size_t)batch * m * 8, hipMemcpyDeviceToHost, s));
-    if (jA && t > 0) GN_HIP(hipMemcpyAsync(jA, djA, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
-    if (jL && kA > 0) GN_HIP(hipMemcpyAsync(jL, djL, (size_t)batch * kA * 8, hipMemcpyDeviceToHost, s));
-    if (jJ) GN_HIP(hipMemcpyAsync(jJ, djJ, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
+    if (hv.p) GN_HIP(hipMemcpyAsync(hv.p, dp, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
+    if (hv.b && t > 0) GN_HIP(hipMemcpyAsync(hv.b, db, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
+    if (hv.d) GN_HIP(hipMemcpyAsync(hv.d, dd, (size_t)batch * m * 8, hipMemcpyDeviceToHost, s));
+    if (hv.jpvtA && t > 0) GN_HIP(hipMemcpyAsync(hv.jpvtA, djA, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
+    if (hv.jpvtL && kA > 0) GN_HIP(hipMemcpyAsync(hv.jpvtL, djL, (size_t)batch * kA * 8, hipMemcpyDeviceToHost, s));
+    if (hv.jpvtJ2) GN_HIP(hipMemcpyAsync(hv.jpvtJ2, djJ, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
     return 0;
     GN_CATCH(h)
@@ -1848,11 +1833,11 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
         GN_HIP(hipMemcpy2DAsync(dAt, (size_t)n * 8, At, (size_t)ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
         GN_HIP(hipMemcpyAsync(dcx, cx, (size_t)t * 8, hipMemcpyHostToDevice, s));
     }
+    BatchOperands v{1, m, n, t};     // no J, rx: the constraint side only
+    v.At = dAt; v.ldat = n; v.strideAt = n * t; v.cx = dcx;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
-    h->last_J = nullptr; h->last_rx = nullptr;
-    h->last_cx = dcx; h->last_stride_cx = t;
-    h->last_At = dAt; h->last_ldat = n; h->last_strideAt = (long long)n * t;
+    h->last = v;
     h->sc_eJ = 0; h->sc_eA = 0;
     h->rescue_prob.clear();
     h->h_tk.clear();
@@ -1866,16 +1851,11 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
     if (h->h_state[0].status & (GN_FLAG_NONFINITE | GN_FLAG_TINY)) {
         // A', cx beyond the range of plain sums of squares: the stage again on copies scaled by a power of two (gn_rescale.hpp)
         int sJ = 0, sA = 0;
-        rc = extreme_shifts(h, m, n, t, nullptr, 0, nullptr, dAt, n, dcx, &sJ, &sA);
+        rc = extreme_shifts(h, v, &sJ, &sA);
         if (rc) return rc;
         if (sA) {
-            const size_t nJ = (size_t)m * n, nA = (size_t)n * t;
-            rc = grow(h, h->rs_buf, (nJ + (size_t)m + nA + (size_t)t + 8) * 8);
+            rc = scaled_copies(h, v, 0, sA);
             if (rc) return rc;
-            h->rs_J = (double*)h->rs_buf.p; h->rs_rx = h->rs_J + nJ; h->rs_At = h->rs_rx + m; h->rs_cx = h->rs_At + nA;
-            hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)std::min<long long>((n + 255) / 256, 1024), (unsigned)t), dim3(256), 0, s, h->rs_At,
-                               (long long)n, (const double*)dAt, (long long)n, (int)n, (int)t, sA);
-            hipLaunchKernelGGL(k_scale_copy, dim3(1, 1), dim3(256), 0, s, h->rs_cx, (long long)t, (const double*)dcx, (long long)t, (int)t, 1, sA);
             h->sc_eA = sA;
             rc = run_constraint_stage(h, 1, m, n, t, dAt, n, (long long)n * t, dcx, eps_rank, -1);
             if (rc) return rc;
@@ -1890,8 +1870,8 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
     h->factors_valid = true;
     h->constraints_only = true;
     if (info) {
-        const ProbState& st = h->h_state[0];
-        *info = {st.rankA, 0, st.code, st.dimA, 0, st.status};
+        *info = info_of(h->h_state[0]);
+        info->rankJ2 = info->dimJ2 = 0;       // nothing about J is resident
     }
     return 0;
 }
@@ -1899,16 +1879,16 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
 int enlsip_gn_solve_factored(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* J, int64_t ldj,
                              const double* rx, double eps_rank, int64_t dimJ2_override, double* p, double* b, double* d,
                              enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
-    return solve_host(h, 1, m, n, t, J, ldj, (int64_t)ldj * n, rx, nullptr, n, (int64_t)n * t, nullptr, eps_rank, -1,
-                      dimJ2_override, p, b, d, info, jpvtA, jpvtL, jpvtJ2, true);
+    return solve_host(h, {1, m, n, t, J, ldj, ldj * n, rx, nullptr, n, n * t, nullptr, p, b, d, nullptr, (long long*)jpvtA,
+                          (long long*)jpvtL, (long long*)jpvtJ2, info}, eps_rank, -1, dimJ2_override, true);
 }
 
 int enlsip_gn_solve_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t, const double* J,
                             int64_t ldj, int64_t strideJ, const double* rx, const double* At, int64_t ldat,
                             int64_t strideAt, const double* cx, double eps_rank, double* p, double* b, double* d,
                             enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
-    return solve_host(h, batch, m, n, t, J, ldj, strideJ, rx, At, ldat, strideAt, cx, eps_rank, -1, -1, p, b, d,
-                      info, jpvtA, jpvtL, jpvtJ2);
+    return solve_host(h, {batch, m, n, t, J, ldj, strideJ, rx, At, ldat, strideAt, cx, p, b, d, nullptr, (long long*)jpvtA,
+                          (long long*)jpvtL, (long long*)jpvtJ2, info}, eps_rank, -1, -1);
 }
 
 // ---- ragged batch: one t per problem (update_working_set, src/enlsip_functions.jl:686-795, gives every problem its own W.t and
@@ -1948,8 +1928,8 @@ int enlsip_gn_solve_batched_ragged(enlsip_gn_handle h, int64_t batch, int64_t m,
     std::vector<int> tk;
     int rc = check_ragged(h, batch, m, n, t_max, t, J, ldj, rx, At, ldat, strideAt, cx, tk);
     if (rc) return rc;
-    return solve_host(h, batch, m, n, t_max, J, ldj, strideJ, rx, At, ldat, strideAt, cx, eps_rank, -1, -1, p, b, d, info, jpvtA,
-                      jpvtL, jpvtJ2, false, tk.data());
+    return solve_host(h, {batch, m, n, t_max, J, ldj, strideJ, rx, At, ldat, strideAt, cx, p, b, d, nullptr, (long long*)jpvtA,
+                          (long long*)jpvtL, (long long*)jpvtJ2, info, tk.data()}, eps_rank, -1, -1);
     GN_CATCH(h)
 }
 
@@ -1962,8 +1942,8 @@ int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_
     std::vector<int> tk;
     int rc = check_ragged(h, batch, m, n, t_max, t, dJ, ldj, drx, dAt, ldat, strideAt, dcx, tk);
     if (rc) return rc;
-    return solve_chunked(h, batch, m, n, t_max, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, eps_rank, -1, -1, dp, db, dd,
-                         dinfo, (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data());
+    return solve_chunked(h, {batch, m, n, t_max, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, dp, db, dd, dinfo,
+                             (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()}, eps_rank, -1, -1);
     GN_CATCH(h)
 }
 
@@ -1971,8 +1951,8 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
                     const double* rx, const double* At, int64_t ldat, const double* cx, double eps_rank,
                     int64_t dimA_override, int64_t dimJ2_override, double* p, double* b, double* d,
                     enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
-    return solve_host(h, 1, m, n, t, J, ldj, (int64_t)ldj * n, rx, At, ldat, (int64_t)ldat * t, cx, eps_rank,
-                      dimA_override, dimJ2_override, p, b, d, info, jpvtA, jpvtL, jpvtJ2);
+    return solve_host(h, {1, m, n, t, J, ldj, ldj * n, rx, At, ldat, ldat * t, cx, p, b, d, nullptr, (long long*)jpvtA,
+                          (long long*)jpvtL, (long long*)jpvtJ2, info}, eps_rank, dimA_override, dimJ2_override);
 }
 
 }  // extern "C"

@@ -3,27 +3,62 @@
 
 namespace {
 
-// also routes (h, prob) to the pipeline half that owns the problem (gn_context.hpp)
+// the part of a range of the caller's batch that one handle holds: its problems k0 .. k0+cnt-1 in the caller's slots j0 .. j0+cnt-1
+struct ResidentSeg {
+    enlsip_gn_handle hh;
+    long long k0, j0, cnt;
+    bool alone;       // answered on its own: a problem on a rescue handle, or the one problem of a handle rescaled in place
+};
+
+// Maps problems prob0 .. prob0+count-1 of the caller's batch to the handles that hold them, calling each(seg) in slot order:
+// only the last chunk of a batch above the launch limit is resident (solve_chunked); the problems from h->split on live on the
+// pipeline child (solve_launchable); a rescued problem lives on a one-problem rescue handle of its half (gn_rescale.hpp).  Every
+// half gives one segment over its part of the range, followed by an `alone` segment for each of its problems answered on its own.
+// one: a single problem (need_factors): errors past the pipeline split are reported on the half that holds it.
+template <class Each>
+int map_resident(enlsip_gn_handle h, int64_t prob0, int64_t count, bool one, Each&& each) {
+    if (count < 1) { h->err = "count must be >= 1"; return -2; }
+    long long p = prob0;
+    if (h->chunk0 > 0) {
+        if (p < h->chunk0) { h->err = "problem belongs to an earlier chunk of a batch above the launch limit: its factors are no longer resident"; return -3; }
+        p -= h->chunk0;
+    }
+    const enlsip_gn_handle c = h->split > 0 ? h->child : nullptr;
+    const long long b0 = c ? h->split : h->plan.batch;
+    const long long total = c ? b0 + c->plan.batch : b0;
+    const enlsip_gn_handle rh = (one && c && p >= b0) ? c : h;
+    if (!h->factors_valid || (c && !c->factors_valid)) { rh->err = "no resident factors: call a solve first"; return -1; }
+    if (p < 0 || count > total || p > total - count) {
+        rh->err = one ? "problem index out of range" : "problem range out of range: prob0 .. prob0+count-1 must lie in the resident batch";
+        return -3;
+    }
+    const long long e = p + count;
+    const struct { enlsip_gn_handle hh; long long lo, hi; } halves[2] = {{h, 0, b0}, {c, b0, total}};
+    for (const auto& hf : halves) {
+        const long long lo = std::max(p, hf.lo), hi = std::min(e, hf.hi);
+        if (lo >= hi) continue;
+        const ResidentSeg sg = {hf.hh, lo - hf.lo, lo - p, hi - lo, false};
+        each(sg);
+        if (hf.hh->sc_eJ || hf.hh->sc_eA) each(ResidentSeg{hf.hh, sg.k0, sg.j0, sg.cnt, true});
+        for (size_t j = 0; j < hf.hh->rescue_prob.size(); ++j) {
+            const long long k = hf.hh->rescue_prob[j];
+            if (k < sg.k0 || k >= sg.k0 + sg.cnt) continue;
+            const enlsip_gn_handle r = hf.hh->rescue[j];
+            if (!r->factors_valid) { r->err = "no resident factors: call a solve first"; return -1; }
+            each(ResidentSeg{r, 0, sg.j0 + k - sg.k0, 1, true});
+        }
+    }
+    return 0;
+}
+
+// routes (h, prob) to the handle that holds the problem and its index there (the last segment of its map)
 int need_factors(enlsip_gn_handle& h, int64_t& prob) {
     if (!h) return -1;
-    if (h->chunk0 > 0) {       // the batch ran in chunks (solve_chunked): only the last chunk is resident
-        if (prob < h->chunk0) { h->err = "problem belongs to an earlier chunk of a batch above the launch limit: its factors are no longer resident"; return -3; }
-        prob -= h->chunk0;
-    }
-    if (h->split > 0 && h->child && prob >= h->split) {
-        prob -= h->split;
-        h = h->child;
-    }
-    if (!h->factors_valid) { h->err = "no resident factors: call a solve first"; return -1; }
-    if (prob < 0 || prob >= h->plan.batch) { h->err = "problem index out of range"; return -3; }
-    // a problem of the batch that was solved on rescaled copies of its inputs lives on a one-problem handle of its own (gn_rescale.hpp)
-    for (size_t j = 0; j < h->rescue_prob.size(); ++j)
-        if (h->rescue_prob[j] == prob) {
-            h = h->rescue[j];
-            prob = 0;
-            if (!h->factors_valid) { h->err = "no resident factors: call a solve first"; return -1; }
-            break;
-        }
+    ResidentSeg at{};
+    const int rc = map_resident(h, prob, 1, true, [&](const ResidentSeg& sg) { at = sg; });
+    if (rc) return rc;
+    h = at.hh;
+    prob = at.k0;
     return 0;
 }
 
@@ -198,13 +233,13 @@ int enlsip_gn_get_JQ1(enlsip_gn_handle h, int64_t prob, double* out, int64_t ld)
     if (!out) return -3;
     const Plan& P = h->plan;
     if (ld < P.m) return -4;
-    if (!h->last_J) { h->err = "J of the last solve is not available"; return -1; }
+    if (!h->last.J) { h->err = "J of the last solve is not available"; return -1; }
     GN_HIP(hipSetDevice(h->device));
     rc = grow(h, h->scratch, (size_t)P.ldw * (P.n + 1) * 8);
     if (rc) return rc;
     JQ1Args qa{};
     qa.m = (int)P.m; qa.n = (int)P.n; qa.kA = P.kA; qa.ldw = P.ldw;
-    qa.J = h->last_J; qa.ldj = h->last_ldj; qa.strideJ = h->last_strideJ; qa.rx = h->last_rx; qa.stride_rx = P.m;
+    qa.J = h->last.J; qa.ldj = h->last.ldj; qa.strideJ = h->last.strideJ; qa.rx = h->last.rx; qa.stride_rx = P.m;
     qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
     qa.W = (double*)h->scratch.p; qa.sW = 0; qa.state = h->state; qa.prob0 = (int)prob;
     launch_jq1(qa, 1, h->stream);
@@ -238,7 +273,7 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
         ConstraintArgs ca{};
         ca.n = n; ca.t = t; ca.kA = P.kA; ca.m = m; ca.eps_rank = h->eps_rank;
         ca.dimA_override = (int)dimA; ca.code_override = (int)code; ca.prob0 = (int)prob;
-        ca.At = h->last_At; ca.ldat = h->last_ldat; ca.strideAt = h->last_strideAt; ca.cx = h->last_cx; ca.stride_cx = t;
+        ca.At = h->last.At; ca.ldat = h->last.ldat; ca.strideAt = h->last.strideAt; ca.cx = h->last.cx; ca.stride_cx = t;
         ca.FA = h->FA; ca.sFA = P.sFA; ca.tauA = h->tauA; ca.sTauA = P.sTauA; ca.jpvtA = h->jpvtA; ca.sJA = P.sJA;
         ca.FL = h->FL; ca.sFL = P.sFL; ca.tauL = h->tauL; ca.sTauL = P.sTauL; ca.jpvtL = h->jpvtL; ca.sJL = P.sJL;
         ca.TA = h->TA; ca.sTA = P.sTA; ca.p1 = h->p1; ca.sP1 = P.sP1; ca.bvec = h->bvec; ca.sB = P.sB;
@@ -247,14 +282,14 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
         ca.Lmat = h->cdist.L; ca.ldL = h->cdist.ldL; ca.sL = h->cdist.sL; ca.qb = h->cdist.qb; ca.sQb = h->cdist.sQb;
         launch_constraint((int)std::max<long long>(n, t), 1, s, ca, h->h_tk.empty() ? nullptr : (const int*)h->tkbuf.p);
     } else {
-        rc = run_constraint_stage(h, 1, m, n, t, h->last_At, h->last_ldat, h->last_strideAt, h->last_cx, h->eps_rank, dimA, (int)prob,
+        rc = run_constraint_stage(h, 1, m, n, t, h->last.At, h->last.ldat, h->last.strideAt, h->last.cx, h->eps_rank, dimA, (int)prob,
                                   (int)code);
         if (rc) return rc;
     }
     // (2) d_temp = -J1 p1 - rx into the vector buffer, (3) Q0' d, (4) Qt' on the leading kp entries
     double* dv = h->vec + prob * P.sVec;
     hipLaunchKernelGGL(k_dtemp, dim3((P.ldw + 255) / 256), dim3(256), 0, s, h->W + prob * P.sW, P.ldw, m,
-                       st0.rankA, h->p1 + prob * P.sP1, h->last_rx + prob * h->last_stride_rx, dv);
+                       st0.rankA, h->p1 + prob * P.sP1, h->last.slice(prob, 1).rx, dv);
     const int kp = st0.kp, npan = (kp + PB - 1) / PB;
     for (int k = 0; k < npan; ++k)
         for (const LevelPlan& L : P.panels[k].levels) {

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -44,6 +45,36 @@ struct Plan {
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+};
+
+// The operands of one batched solve: shape, inputs, outputs (device pointers, or host pointers before solve_host stages them).
+// Problem k's part of each array starts at a fixed stride, and slice() is the one place that knows them: J, A' by strideJ,
+// strideAt; rx, d by m; p, jpvtJ2 by n; cx, b, jpvtA by t (t_max of a ragged batch); jpvtL by min(n, t); the info records and
+// tk by 1.  A null pointer is an absent operand and stays null.
+struct BatchOperands {
+    long long batch = 0, m = 0, n = 0, t = 0;
+    const double* J = nullptr; long long ldj = 0, strideJ = 0;
+    const double* rx = nullptr;
+    const double* At = nullptr; long long ldat = 0, strideAt = 0;
+    const double* cx = nullptr;
+    double *p = nullptr, *b = nullptr, *d = nullptr;
+    enlsip_gn_info* dinfo = nullptr;    // device info records
+    long long *jpvtA = nullptr, *jpvtL = nullptr, *jpvtJ2 = nullptr;
+    enlsip_gn_info* hinfo = nullptr;    // host info records
+    const int* tk = nullptr;            // ragged batch: each problem's own t (host)
+
+    BatchOperands slice(long long k0, long long count) const {
+        auto at = [k0](auto* x, long long stride) { return x ? x + k0 * stride : nullptr; };
+        BatchOperands s = *this;
+        s.batch = count;
+        s.J = at(J, strideJ); s.rx = at(rx, m); s.At = at(At, strideAt); s.cx = at(cx, t);
+        s.p = at(p, n); s.b = at(b, t); s.d = at(d, m); s.dinfo = at(dinfo, 1);
+        s.jpvtA = at(jpvtA, t); s.jpvtL = at(jpvtL, std::min(n, t)); s.jpvtJ2 = at(jpvtJ2, n);
+        s.hinfo = at(hinfo, 1); s.tk = at(tk, 1);
+        return s;
+    }
+    // what a handle keeps of its last solve: shape and inputs, no output or host array of the caller
+    BatchOperands inputs() const { return {batch, m, n, t, J, ldj, strideJ, rx, At, ldat, strideAt, cx}; }
 };
 
 }  // namespace gn
@@ -155,11 +186,8 @@ struct enlsip_gn_context {
     int consumer_form = -1;             // form of the last batched multiplier estimate (enlsip_gn_get_consumer_form), -1: none yet
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
-    // device-pointer inputs of the last solve (needed by resolve / get_JQ1 paths)
-    const double* last_J = nullptr; long long last_ldj = 0, last_strideJ = 0;
-    const double* last_rx = nullptr; long long last_stride_rx = 0;
-    const double* last_cx = nullptr; long long last_stride_cx = 0;
-    const double* last_At = nullptr; long long last_ldat = 0, last_strideAt = 0;
+    // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)
+    gn::BatchOperands last;
 
     // profiling
     bool profiling = false;

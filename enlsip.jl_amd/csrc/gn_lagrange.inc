@@ -17,15 +17,15 @@ int enlsip_gn_gradient(enlsip_gn_handle h, int64_t prob, double* grad) {
     int rc = need_factors(h, prob);
     if (rc) return rc;
     if (!grad) return -3;
-    if (!h->last_J || !h->last_rx) { h->err = "J / rx of the last solve are not available"; return -1; }
+    if (!h->last.J || !h->last.rx) { h->err = "J / rx of the last solve are not available"; return -1; }
     const Plan& P = h->plan;
+    const BatchOperands in = h->last.slice(prob, 1);
     GN_HIP(hipSetDevice(h->device));
     rc = lagrange_scratch(h, P.m);
     if (rc) return rc;
     double* d = (double*)h->lag.p;
     hipStream_t s = h->stream;
-    hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)P.n + 3) / 4), dim3(256), 0, s, h->last_J + prob * h->last_strideJ,
-                       h->last_ldj, (int)P.m, (int)P.n, h->last_rx + prob * h->last_stride_rx, d);
+    hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)P.n + 3) / 4), dim3(256), 0, s, in.J, in.ldj, (int)P.m, (int)P.n, in.rx, d);
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpyAsync(grad, d, (size_t)P.n * 8, hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
@@ -37,8 +37,9 @@ int enlsip_gn_jacobian_times(enlsip_gn_handle h, int64_t prob, const double* p, 
     if (rc) return rc;
     if (!p) return -3;
     if (!Jp && !Ap) return -4;
-    if (!h->last_J) { h->err = "J of the last solve is not available"; return -1; }
+    if (!h->last.J) { h->err = "J of the last solve is not available"; return -1; }
     const Plan& P = h->plan;
+    const BatchOperands in = h->last.slice(prob, 1);
     const int n = (int)P.n, t = prob_t(h, prob), m = (int)P.m;       // Ap: the problem's own active rows
     GN_HIP(hipSetDevice(h->device));
     rc = lagrange_scratch(h, m);
@@ -50,15 +51,14 @@ int enlsip_gn_jacobian_times(enlsip_gn_handle h, int64_t prob, const double* p, 
     hipStream_t s = h->stream;
     GN_HIP(hipMemcpyAsync(dp, p, (size_t)n * 8, hipMemcpyHostToDevice, s));
     if (Jp) {
-        hipLaunchKernelGGL(k_gemv_n_add, dim3(((unsigned)m + 255) / 256), dim3(256), 0, s, h->last_J + prob * h->last_strideJ,
-                           h->last_ldj, m, n, dp, (const double*)nullptr, dJp);
+        hipLaunchKernelGGL(k_gemv_n_add, dim3(((unsigned)m + 255) / 256), dim3(256), 0, s, in.J, in.ldj, m, n, dp,
+                           (const double*)nullptr, dJp);
         GN_HIP(hipMemcpyAsync(Jp, dJp, (size_t)m * 8, hipMemcpyDeviceToHost, s));
     }
     if (Ap && t > 0) {
-        if (!h->last_At) { h->err = "A' of the last solve is not available"; return -1; }
+        if (!in.At) { h->err = "A' of the last solve is not available"; return -1; }
         // (A p)[i] = sum_r At[r + i * ldat] p[r]: A' is stored n x t
-        hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)t + 3) / 4), dim3(256), 0, s, h->last_At + prob * h->last_strideAt,
-                           h->last_ldat, n, t, dp, dAp);
+        hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)t + 3) / 4), dim3(256), 0, s, in.At, in.ldat, n, t, dp, dAp);
         GN_HIP(hipMemcpyAsync(Ap, dAp, (size_t)t * 8, hipMemcpyDeviceToHost, s));
     }
     GN_HIP(hipGetLastError());
@@ -156,7 +156,8 @@ static int lagrange_common(enlsip_gn_handle h, int64_t prob, int mode, const dou
     LagrangeArgs a{};
     a.mode = mode; a.n = n; a.t = t; a.kA = std::min(n, t); a.rank_solve = h->h_state[prob].rankA;
     a.FA = h->FA + prob * P.sFA; a.tauA = h->tauA + prob * P.sTauA; a.jpvtA = h->jpvtA + prob * P.sJA;
-    a.cx = h->last_cx ? h->last_cx + prob * h->last_stride_cx : nullptr;
+    const BatchOperands in = h->last.slice(prob, 1);
+    a.cx = in.cx;
     a.eps_rank = eps_rank; a.lambda = d + 2048; a.scal = d + 3072;
     a.diag_scale = nullptr;
     if (diag_scale) {
@@ -168,17 +169,16 @@ static int lagrange_common(enlsip_gn_handle h, int64_t prob, int mode, const dou
         if (host_vec) {
             GN_HIP(hipMemcpyAsync(d, host_vec, (size_t)n * 8, hipMemcpyHostToDevice, s));
         } else {   // gradient from the resident J, rx
-            if (!h->last_J || !h->last_rx) { h->err = "J / rx of the last solve are not available"; return -1; }
-            hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)n + 3) / 4), dim3(256), 0, s, h->last_J + prob * h->last_strideJ,
-                               h->last_ldj, m, n, h->last_rx + prob * h->last_stride_rx, d);
+            if (!in.J || !in.rx) { h->err = "J / rx of the last solve are not available"; return -1; }
+            hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)n + 3) / 4), dim3(256), 0, s, in.J, in.ldj, m, n, in.rx, d);
         }
         a.vec = d;
     } else {
         if (!host_vec) return -3;
-        if (!h->last_J || !h->last_rx) { h->err = "J / rx of the last solve are not available"; return -1; }
+        if (!in.J || !in.rx) { h->err = "J / rx of the last solve are not available"; return -1; }
         GN_HIP(hipMemcpyAsync(d, host_vec, (size_t)n * 8, hipMemcpyHostToDevice, s));          // p_gn
-        hipLaunchKernelGGL(k_gemv_n_add, dim3(((unsigned)m + 255) / 256), dim3(256), 0, s, h->last_J + prob * h->last_strideJ,
-                           h->last_ldj, m, n, d, h->last_rx + prob * h->last_stride_rx, d + 5120);   // rx + J p
+        hipLaunchKernelGGL(k_gemv_n_add, dim3(((unsigned)m + 255) / 256), dim3(256), 0, s, in.J, in.ldj, m, n, d, in.rx,
+                           d + 5120);   // rx + J p
         hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)t + 3) / 4), dim3(256), 0, s, h->W + prob * P.sW, (long long)P.ldw, m, t,
                            d + 5120, d + 1024);                                                       // J1' (.)
         a.vec = d + 1024;

@@ -15,70 +15,42 @@ struct ConsumerIO {
     int* status;            // estimates, may be null
 };
 
-// the part of a range that lives on one handle: problems k0 .. k0+cnt-1 of hh in the caller's slots j0 .. j0+cnt-1
-struct ConsumerSeg {
-    enlsip_gn_handle hh;
-    long long k0, j0, cnt;
-};
-
-// Splits prob0 .. prob0+count-1 (indices in the caller's whole batch) over the pipeline halves, with the checks of need_factors.
-int consumer_range(enlsip_gn_handle h, int64_t prob0, int64_t count, ConsumerSeg seg[2], int& nseg) {
-    nseg = 0;
-    if (count < 1) { h->err = "count must be >= 1"; return -2; }
-    long long p = prob0;
-    if (h->chunk0 > 0) {       // the batch ran in chunks (solve_chunked): only the last chunk is resident
-        if (p < h->chunk0) { h->err = "problem belongs to an earlier chunk of a batch above the launch limit: its factors are no longer resident"; return -3; }
-        p -= h->chunk0;
-    }
-    const bool split = h->split > 0 && h->child;
-    if (!h->factors_valid || (split && !h->child->factors_valid)) { h->err = "no resident factors: call a solve first"; return -1; }
-    const long long b0 = split ? h->split : h->plan.batch;
-    const long long total = split ? b0 + h->child->plan.batch : b0;
-    if (p < 0 || count > total || p > total - count) { h->err = "problem range out of range: prob0 .. prob0+count-1 must lie in the resident batch"; return -3; }
-    const long long e = p + count;
-    if (p < b0) seg[nseg++] = {h, p, 0, std::min(e, b0) - p};
-    if (e > b0) {
-        const long long s0 = std::max(p, b0);
-        seg[nseg++] = {h->child, s0 - b0, s0 - p, e - s0};
-    }
-    return 0;
-}
-
 // what every handle of the range must hold for the consumer (the per-problem entry points' checks)
 int consumer_needs(enlsip_gn_handle h, enlsip_gn_handle hh, int kind, const ConsumerIO& io) {
     const char* no_j = "J / rx of the last solve are not available";
     switch (kind) {
         case CONS_GRADIENT:
-            if (!hh->last_J || !hh->last_rx) { h->err = no_j; return -1; }
+            if (!hh->last.J || !hh->last.rx) { h->err = no_j; return -1; }
             return 0;
         case CONS_JTIMES:
-            if (!hh->last_J) { h->err = "J of the last solve is not available"; return -1; }
-            if (io.out1 && hh->plan.t > 0 && !hh->last_At) { h->err = "A' of the last solve is not available"; return -1; }
+            if (!hh->last.J) { h->err = "J of the last solve is not available"; return -1; }
+            if (io.out1 && hh->plan.t > 0 && !hh->last.At) { h->err = "A' of the last solve is not available"; return -1; }
             return 0;
         case CONS_FIRST:
             if (hh->constraints_only && !io.in) {
                 h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
                 return -1;
             }
-            if (hh->plan.t > 0 && !hh->last_cx) { h->err = "cx of the last solve is not available"; return -1; }
-            if (!io.in && (!hh->last_J || !hh->last_rx)) { h->err = no_j; return -1; }
+            if (hh->plan.t > 0 && !hh->last.cx) { h->err = "cx of the last solve is not available"; return -1; }
+            if (!io.in && (!hh->last.J || !hh->last.rx)) { h->err = no_j; return -1; }
             return 0;
         default:
             if (hh->constraints_only) {
                 h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
                 return -1;
             }
-            if (!hh->last_J || !hh->last_rx) { h->err = no_j; return -1; }
+            if (!hh->last.J || !hh->last.rx) { h->err = no_j; return -1; }
             return 0;
     }
 }
 
 // Enqueues the consumer for one segment on its handle's stream: at most three launches whatever the segment's size.
-int consumer_launch(enlsip_gn_handle hh, int kind, const ConsumerSeg& sg, const ConsumerIO& io, bool small) {
+int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const ConsumerIO& io, bool small) {
     enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
     const Plan& P = hh->plan;
     const long long m = P.m, n = P.n, tmax = P.t, k0 = sg.k0, j0 = sg.j0, cnt = sg.cnt;
     const int* tk = hh->h_tk.empty() ? nullptr : (const int*)hh->tkbuf.p + k0;
+    const BatchOperands in = hh->last.slice(k0, cnt);
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
     // temporaries: flag word | status (when the caller passes none) | grad (first, no grad_fx) | rx + J p (m) | J1'(.) (t_max)
     const size_t o_st = 256, o_g = o_st + rup((long long)cnt * 4, 256);
@@ -90,22 +62,20 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ConsumerSeg& sg, const 
     hipStream_t s = hh->stream;
     const unsigned cn = (unsigned)cnt;
     auto jt = [&](const double* x, long long sx, double* y) {          // J' x
-        hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(n + 3) / 4, cn), dim3(256), 0, s, hh->last_J + k0 * hh->last_strideJ,
-                           hh->last_ldj, hh->last_strideJ, (int)m, (int)n, (const int*)nullptr, x, sx, y, n);
+        hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(n + 3) / 4, cn), dim3(256), 0, s, in.J, in.ldj, in.strideJ, (int)m, (int)n,
+                           (const int*)nullptr, x, sx, y, n);
     };
     switch (kind) {
         case CONS_GRADIENT:
-            jt(hh->last_rx + k0 * hh->last_stride_rx, hh->last_stride_rx, io.out0 + j0 * n);
+            jt(in.rx, m, io.out0 + j0 * n);
             break;
         case CONS_JTIMES:
             if (io.out0)
-                hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s,
-                                   hh->last_J + k0 * hh->last_strideJ, hh->last_ldj, hh->last_strideJ, (int)m, (int)n, io.in + j0 * n, n,
-                                   (const double*)nullptr, 0LL, io.out0 + j0 * m, m);
+                hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s, in.J, in.ldj, in.strideJ,
+                                   (int)m, (int)n, io.in + j0 * n, n, (const double*)nullptr, 0LL, io.out0 + j0 * m, m);
             if (io.out1 && tmax > 0)     // (A p)[i] = sum_r At[r + i * ldat] p[r]: A' is stored n x t; slots past t_k are 0
-                hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(tmax + 3) / 4, cn), dim3(256), 0, s,
-                                   hh->last_At + k0 * hh->last_strideAt, hh->last_ldat, hh->last_strideAt, (int)n, (int)tmax, tk,
-                                   io.in + j0 * n, n, io.out1 + j0 * tmax, tmax);
+                hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(tmax + 3) / 4, cn), dim3(256), 0, s, in.At, in.ldat, in.strideAt,
+                                   (int)n, (int)tmax, tk, io.in + j0 * n, n, io.out1 + j0 * tmax, tmax);
             break;
         default: {
             LagrangeBatchArgs a{};
@@ -113,7 +83,7 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ConsumerSeg& sg, const 
             a.count = (int)cnt; a.n = (int)n; a.t_max = (int)tmax; a.tk = tk; a.state = hh->state + k0;
             a.FA = hh->FA + k0 * P.sFA; a.sFA = P.sFA; a.tauA = hh->tauA + k0 * P.sTauA; a.sTauA = P.sTauA;
             a.jpvtA = hh->jpvtA + k0 * P.sJA; a.sJA = P.sJA;
-            a.cx = hh->last_cx ? hh->last_cx + k0 * hh->last_stride_cx : nullptr; a.scx = hh->last_stride_cx;
+            a.cx = in.cx; a.scx = in.t;
             a.diag_scale = io.diag ? io.diag + j0 * tmax : nullptr;
             a.eps_rank = io.eps_rank;
             a.lambda = io.out0 + j0 * tmax;
@@ -126,16 +96,15 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ConsumerSeg& sg, const 
                     a.vec = io.in + j0 * n;
                 } else {       // gradient from the resident J, rx
                     double* g = (double*)(scr + o_g);
-                    jt(hh->last_rx + k0 * hh->last_stride_rx, hh->last_stride_rx, g);
+                    jt(in.rx, m, g);
                     a.vec = g;
                 }
                 a.svec = n;
             } else {
                 double* y = (double*)(scr + o_y);
                 double* bv = (double*)(scr + o_b);
-                hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s,
-                                   hh->last_J + k0 * hh->last_strideJ, hh->last_ldj, hh->last_strideJ, (int)m, (int)n, io.in + j0 * n,
-                                   n, hh->last_rx + k0 * hh->last_stride_rx, hh->last_stride_rx, y, m);       // rx + J p
+                hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s, in.J, in.ldj, in.strideJ,
+                                   (int)m, (int)n, io.in + j0 * n, n, in.rx, m, y, m);       // rx + J p
                 if (tmax > 0)
                     hipLaunchKernelGGL(k_gemv_t_batched, dim3((unsigned)(tmax + 3) / 4, cn), dim3(256), 0, s, (const double*)hh->W + k0 * P.sW,
                                        (long long)P.ldw, P.sW, (int)m, (int)tmax, tk, (const double*)y, m, bv, tmax);   // J1' (.)
@@ -161,7 +130,7 @@ int per_problem_status(int rc, int& st) {
 
 // Problems of the range that live on a rescue handle (or on a handle whose one problem was rescaled in place) are answered by the
 // per-problem entry point; their slots are overwritten with its results.  Returns the status OR of the whole range in *flagged.
-int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const ConsumerSeg* seg, int nseg,
+int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const std::vector<ResidentSeg>& seg,
                          const ConsumerIO& io, const std::vector<long long>& slots, bool& flagged) {
     const Plan& P = seg[0].hh->plan;
     const long long m = P.m, n = P.n, tmax = P.t;
@@ -172,8 +141,7 @@ int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t co
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
     if (est) {      // statuses of the batched launch: the rescued slots' entries are replaced below
         st_all.assign((size_t)count, 0);
-        for (int q = 0; q < nseg; ++q) {
-            const ConsumerSeg& sg = seg[q];
+        for (const ResidentSeg& sg : seg) {
             const int* src = io.status ? io.status + sg.j0 : (const int*)((char*)sg.hh->lagb_scr.p + 256);
             GN_HIP(hipMemcpy(st_all.data() + sg.j0, src, (size_t)sg.cnt * sizeof(int), hipMemcpyDeviceToHost));
         }
@@ -223,9 +191,13 @@ int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t co
 // then the per-problem route for rescued problems.  0, 1 (some estimate flagged) or a negative argument / state error.
 int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const ConsumerIO& io) {
     if (!h) return -1;
-    ConsumerSeg seg[2];
-    int nseg = 0;
-    int rc = consumer_range(h, prob0, count, seg, nseg);
+    // the halves that hold the range get the batched launches; the slots answered on their own, the per-problem entry point
+    std::vector<ResidentSeg> seg;
+    std::vector<long long> slots;
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
+        if (!sg.alone) seg.push_back(sg);
+        else for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) slots.push_back(j);
+    });
     if (rc) return rc;
     const Plan& P = seg[0].hh->plan;
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
@@ -240,43 +212,32 @@ int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, con
             if (!io.in) { h->err = "dp_gn is NULL"; return -4; }
             if (!io.out0 && P.t > 0) { h->err = "dlambda is NULL"; return -4; }
     }
-    for (int q = 0; q < nseg; ++q) {
-        rc = consumer_needs(h, seg[q].hh, kind, io);
+    for (const ResidentSeg& sg : seg) {
+        rc = consumer_needs(h, sg.hh, kind, io);
         if (rc) return rc;
     }
     GN_HIP(hipSetDevice(h->device));
     const bool small = h->lagrange_small && P.n <= 64 && P.t <= 64;
     if (est) h->consumer_form = small ? 1 : 0;
-    // slots answered by the per-problem entry point: problems on rescue handles, or the one problem of a handle rescaled in place
-    std::vector<long long> slots;
-    for (int q = 0; q < nseg; ++q) {
-        const ConsumerSeg& sg = seg[q];
-        if (sg.hh->sc_eJ || sg.hh->sc_eA) {
-            for (long long k = sg.k0; k < sg.k0 + sg.cnt; ++k) slots.push_back(sg.j0 + k - sg.k0);
-            continue;
-        }
-        for (long long k : sg.hh->rescue_prob)
-            if (k >= sg.k0 && k < sg.k0 + sg.cnt) slots.push_back(sg.j0 + k - sg.k0);
-    }
-    for (int q = 0; q < nseg; ++q) {
-        if (seg[q].hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
+    for (const ResidentSeg& sg : seg) {
+        if (sg.hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
             if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
             GN_HIP(hipEventRecord(h->ev_fork, h->stream));
-            GN_HIP(hipStreamWaitEvent(seg[q].hh->stream, h->ev_fork, 0));
+            GN_HIP(hipStreamWaitEvent(sg.hh->stream, h->ev_fork, 0));
         }
-        rc = consumer_launch(seg[q].hh, kind, seg[q], io, small);
+        rc = consumer_launch(sg.hh, kind, sg, io, small);
         if (rc) {
-            if (seg[q].hh != h) h->err = seg[q].hh->err;
+            if (sg.hh != h) h->err = sg.hh->err;
             return rc;
         }
     }
     bool flagged = false;
-    for (int q = 0; q < nseg; ++q) {
-        GN_HIP(hipStreamSynchronize(seg[q].hh->stream));
-        if (est) flagged = flagged || *seg[q].hh->h_lagflag != 0;
+    for (const ResidentSeg& sg : seg) {
+        GN_HIP(hipStreamSynchronize(sg.hh->stream));
+        if (est) flagged = flagged || *sg.hh->h_lagflag != 0;
     }
     if (!slots.empty()) {
-        rc = consumer_per_problem(h, kind, prob0, count, seg, nseg, io, slots, flagged);
+        rc = consumer_per_problem(h, kind, prob0, count, seg, io, slots, flagged);
         if (rc) return rc;
     }
     return flagged ? 1 : 0;
@@ -287,11 +248,10 @@ int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, con
 int consumer_host(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const double* in, const double* diag, double eps_rank,
                   double* out0, double* out1, int* status) {
     if (!h) return -1;
-    ConsumerSeg seg[2];
-    int nseg = 0;
-    int rc = consumer_range(h, prob0, count, seg, nseg);
+    enlsip_gn_handle first = nullptr;       // the half that holds prob0
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) { if (!first) first = sg.hh; });
     if (rc) return rc;
-    const Plan& P = seg[0].hh->plan;
+    const Plan& P = first->plan;
     const long long m = P.m, n = P.n, tmax = P.t;
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
     const size_t c = (size_t)count;

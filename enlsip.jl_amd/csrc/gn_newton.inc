@@ -10,7 +10,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
     if (h->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
     if (!Gamma) { h->err = "Gamma is NULL"; return -3; }
     if (!p) { h->err = "p is NULL"; return -5; }
-    if (!h->last_J || !h->last_rx) { h->err = "J / rx of the last solve are not available"; return -1; }
+    if (!h->last.J || !h->last.rx) { h->err = "J / rx of the last solve are not available"; return -1; }
     const Plan& P = h->plan;
     const int m = (int)P.m, n = (int)P.n, t = prob_t(h, prob);      // the problem's own t (ragged batch)
     if (ldg < n) { h->err = "ldg < n"; return -4; }
@@ -31,7 +31,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
     // b, p1 with the default dimensions (a re-solve may have left truncated ones), state record restored afterwards
     if (t > 0) {
         if (h->cdist.valid) { h->err = "newton direction after the distributed constraint stage is not supported"; return -7; }
-        rc = run_constraint_stage(h, 1, m, n, P.t, h->last_At, h->last_ldat, h->last_strideAt, h->last_cx, h->eps_rank, -1, (int)prob, 0);
+        rc = run_constraint_stage(h, 1, m, n, P.t, h->last.At, h->last.ldat, h->last.strideAt, h->last.cx, h->eps_rank, -1, (int)prob, 0);
         if (rc) return rc;
         GN_HIP(hipMemcpyAsync(h->state + prob, &st0, sizeof(ProbState), hipMemcpyHostToDevice, s));
     }
@@ -66,7 +66,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
     {
         JQ1Args qa{};
         qa.m = m; qa.n = n; qa.kA = P.kA; qa.ldw = P.ldw;
-        qa.J = h->last_J; qa.ldj = h->last_ldj; qa.strideJ = h->last_strideJ; qa.rx = h->last_rx; qa.stride_rx = P.m;
+        qa.J = h->last.J; qa.ldj = h->last.ldj; qa.strideJ = h->last.strideJ; qa.rx = h->last.rx; qa.stride_rx = P.m;
         qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
         qa.W = JQ; qa.sW = 0; qa.state = h->state; qa.prob0 = (int)prob;
         launch_jq1(qa, 1, s);
@@ -92,7 +92,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
                            dE + rankA, (long long)n, dW21, (long long)n2);
     // d = -W21 p1 - J2' rx
     hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)n2 + 3) / 4), dim3(256), 0, s, J2, (long long)P.ldw, m, n2,
-                       h->last_rx + prob * h->last_stride_rx, dg);
+                       h->last.slice(prob, 1).rx, dg);
     hipLaunchKernelGGL(k_newton_rhs, dim3(((unsigned)n2 + 255) / 256), dim3(256), 0, s, n2, rankA, dW21, (long long)n2, p1, dg, dd);
     // cholesky(sW22), the two triangular solves, p = Q [p1; p2]
     hipLaunchKernelGGL(k_newton_chol, dim3(1), dim3(1024), 0, s, n2, dW22, (long long)n2, dUt, dflag);

@@ -182,10 +182,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     hipStream_t s = h->stream;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
-    h->last_J = dJ; h->last_ldj = ldj; h->last_strideJ = 0;
-    h->last_rx = drx; h->last_stride_rx = m_loc;
-    h->last_cx = dcx; h->last_stride_cx = t;
-    h->last_At = dAt; h->last_ldat = ldat; h->last_strideAt = 0;
+    h->last = {1, m_loc, n, t, dJ, ldj, 0, drx, dAt, ldat, 0, dcx};
     // same routing as a solve (register / distributed forms of F_A for the shapes that need them)
     h->sc_eJ = 0; h->sc_eA = 0;          // row shards are not rescaled (include/enlsip_gn.h: magnitude range of the TSQR entry points)
     h->rescue_prob.clear();
@@ -230,8 +227,7 @@ int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank
     int rc;
     if (n2 > 0) {
         if (!h->sub) {
-            enlsip_gn_opts o = {h->device, h->flags, 0, h->tile_rows, (void*)h->stream};
-            rc = enlsip_gn_create(&h->sub, &o);
+            rc = create_helper(h, &h->sub, h->stream);
             if (rc) { h->err = "tsqr_combine: cannot create the sub-handle"; return rc; }
         }
         // jpvt / info of the stacked (unconstrained) problem through the ordinary device-pointer solve
@@ -239,11 +235,10 @@ int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank
         if (rc) return rc;
         long long* djJ = (long long*)h->out_stage.p;
         h->sub->upper_once = (G == 1);      // one rank: the stacked matrix is that rank's triangle
-        rc = solve_dev(h->sub, 1, ms, n2, 0, Jst, ms, 0, rxs, nullptr, 1, 0, nullptr, eps_rank, -1, -1, dp2, nullptr, dd,
-                       nullptr, nullptr, nullptr, djJ);
+        const BatchOperands v{1, ms, n2, 0, Jst, ms, 0, rxs, nullptr, 1, 0, nullptr, dp2, nullptr, dd, nullptr, nullptr, nullptr, djJ};
+        rc = solve_dev(h->sub, v, eps_rank, -1, -1);
         if (rc) { h->err = std::string("tsqr_combine/sub: ") + h->sub->err; return rc; }
-        const ProbState& ss = h->sub->h_state[0];
-        sinfo = {0, ss.rankJ2, 1, 0, ss.dimJ2, ss.status};
+        sinfo = info_of(h->sub->h_state[0]);       // its rankJ2, dimJ2 and status
         if (jpvtJ2) GN_HIP(hipMemcpyAsync(jpvtJ2, djJ, (size_t)n2 * 8, hipMemcpyDeviceToHost, s));
         if (dlead) GN_HIP(hipMemcpyAsync(dlead, dd, (size_t)n2 * 8, hipMemcpyDeviceToHost, s));
         GN_HIP(hipMemsetAsync(h->small + 8, 0, 8, s));
