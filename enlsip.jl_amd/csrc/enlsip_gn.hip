@@ -294,6 +294,25 @@ static void launch_pivot(int rows, int batch, hipStream_t s, FinalArgs a) {
     else GN_LAUNCH_BIG((k_pivot_solve<16, 2, 1024>), dim3(batch), dim3(1024), lds, s, a);
 }
 
+// J*Q1 of a solve: JQ1 = J Q1 into the working matrix W (and d_temp from rx), for the problems of the resident plan
+static JQ1Args jq1_args(enlsip_gn_handle h, const double* J, long long ldj, long long strideJ, const double* rx) {
+    const Plan& P = h->plan;
+    JQ1Args qa{};
+    qa.m = (int)P.m; qa.n = (int)P.n; qa.kA = P.kA; qa.ldw = P.ldw;
+    qa.J = J; qa.ldj = ldj; qa.strideJ = strideJ; qa.rx = rx; qa.stride_rx = P.m;
+    qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
+    qa.W = h->W; qa.sW = P.sW; qa.state = h->state;
+    qa.prob0 = 0;
+    // V T' of the fast path lives in the (still unused) working matrix of the pivoted QR
+    qa.VT = (P.sM >= P.n * KBLK) ? h->qdM : nullptr; qa.sVT = P.sM;
+    return qa;
+}
+static void launch_jq1_any(enlsip_gn_handle h, const JQ1Args& qa, int batch, hipStream_t s) {
+    if (h->flags & ENLSIP_GN_UPDATE_REFLECTORS) launch_jq1(qa, batch, s);   // plain-FMA A/B partner
+    else if (launch_jq1_rows(qa, batch, s)) {}                              // small n, few reflectors
+    else if (!launch_jq1_v2(qa, batch, s)) launch_jq1_mfma(qa, batch, s);   // regular shapes / general shapes
+}
+
 static CaqrArgs caqr_args(enlsip_gn_handle h, int k, const LevelPlan& L) {
     const Plan& P = h->plan;
     CaqrArgs a{};
@@ -333,15 +352,16 @@ static void launch_factor(enlsip_gn_handle h, const CaqrArgs& a, int groups, hip
         else hipLaunchKernelGGL((k_caqr_factor<4, 4>), grid, dim3(256), 0, st, a);
     }
 }
-static void launch_update_refl(enlsip_gn_handle h, const CaqrArgs& a, int groups, int ncols) {
-    dim3 grid(groups, (ncols + 31) / 32, (unsigned)h->plan.batch);
+// nprob: the batch (the sweep), or 1 for one problem addressed through a.prob0 (caqr_apply_ext)
+static void launch_update_refl(enlsip_gn_handle h, const CaqrArgs& a, int groups, int ncols, int nprob) {
+    dim3 grid(groups, (ncols + 31) / 32, (unsigned)nprob);
     if (h->plan.RPL == 8) hipLaunchKernelGGL(k_caqr_update_refl<8>, grid, dim3(256), 0, h->stream, a);
     else hipLaunchKernelGGL(k_caqr_update_refl<4>, grid, dim3(256), 0, h->stream, a);
 }
 
-// Apply Q0' (reverse = 0) or Q0 (reverse = 1) of the resident CAQR factors to the external
-// matrix C (ldw x ncols per problem).
-static void caqr_apply_ext(enlsip_gn_handle h, double* C, long long sC, int ncols, int npan, bool reverse) {
+// Apply Q0' (reverse = 0) or Q0 (reverse = 1) of the resident CAQR factors of problem `prob` to the external
+// vector C (ldw doubles): every (panel, level) in forward or reverse order.
+static void caqr_apply_ext(enlsip_gn_handle h, double* C, int prob, int npan, bool reverse) {
     const Plan& P = h->plan;
     for (int kk = 0; kk < npan; ++kk) {
         const int k = reverse ? npan - 1 - kk : kk;
@@ -349,17 +369,33 @@ static void caqr_apply_ext(enlsip_gn_handle h, double* C, long long sC, int ncol
         for (size_t li = 0; li < lv.size(); ++li) {
             const LevelPlan& L = reverse ? lv[lv.size() - 1 - li] : lv[li];
             CaqrArgs a = caqr_args(h, k, L);
-            a.ext_cols = ncols; a.C = C; a.sC = sC; a.reverse = reverse ? 1 : 0;
-            launch_update_refl(h, a, L.groups, ncols);
+            a.ext_cols = 1; a.C = C; a.sC = 0; a.reverse = reverse ? 1 : 0; a.prob0 = prob;
+            launch_update_refl(h, a, L.groups, 1, 1);
         }
     }
 }
 
+// the next event of a pool that grows on demand
+static int next_event(enlsip_gn_handle h, std::vector<hipEvent_t>& pool, size_t& used, unsigned flags, hipEvent_t& e) {
+    if (used >= pool.size()) {
+        hipEvent_t ne;
+        GN_HIP(hipEventCreateWithFlags(&ne, flags));
+        pool.push_back(ne);
+    }
+    e = pool[used++];
+    return 0;
+}
+
 // the CAQR sweep over [J2 | d]
+// A step is a panel pair (k, k + 1) or one panel k.  Its CHAIN (the factorisations and, for a pair, the first panel's reflectors on
+// the second panel's 32 columns) touches only the step's own columns; its WINDOW UPDATE is everything it applies to the trailing
+// columns, one function of a column sub-window (sub0, subn) and a stream.  The one-stream schedule calls that function once for the
+// whole window; the look-ahead schedule (two_streams) calls it for the near part on the main stream and for the rest on the second.
 static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     const Plan& P = h->plan;
     const int kp_launch = (int)std::min<long long>(P.m, n2_launch);
     const int npan = (kp_launch + PB - 1) / PB;
+    const int nprob = (int)P.batch;
     const bool use_mfma = !(h->flags & ENLSIP_GN_UPDATE_REFLECTORS);
     GN_ROUTE(P.RPL == 8 ? ENLSIP_GN_ROUTE_SWEEP_TILE512 : ENLSIP_GN_ROUTE_SWEEP_TILE256);
     if (!use_mfma) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_REFLECTORS);
@@ -367,25 +403,23 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     // the launch shape is the widest J2 of the batch; narrower ones exist only when some constraint matrix was rank deficient
     // (second attempt of solve_dev) or when the caller's problems differ
     const bool mixed = n2_launch != (int)(P.n - P.kA);
-    // HIP events around the level-0 far updates (the dominant kernel) when profiling is on; `bytes` = SURVEY 8d's
-    // B_trail = 8 (2 m_k n_k + m_k b + b^2) of every panel the launch applies, on the columns it applies them to
-    auto timed = [&](double bytes, hipStream_t st, auto&& launch) -> int {
+    // HIP events around a launch when `on`
+    auto between_events = [&](bool on, std::vector<hipEvent_t>& pool, size_t& used, hipStream_t st, auto&& launch) -> int {
         hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (h->profiling) {
-            if (h->upd_used + 2 > h->upd_ev.size()) {
-                for (int q = 0; q < 2; ++q) {
-                    hipEvent_t e;
-                    GN_HIP(hipEventCreate(&e));
-                    h->upd_ev.push_back(e);
-                }
-            }
-            e0 = h->upd_ev[h->upd_used++];
-            e1 = h->upd_ev[h->upd_used++];
+        if (on) {
+            if (int rc = next_event(h, pool, used, hipEventDefault, e0)) return rc;
+            if (int rc = next_event(h, pool, used, hipEventDefault, e1)) return rc;
             GN_HIP(hipEventRecord(e0, st));
         }
         launch();
-        if (e1) {
-            GN_HIP(hipEventRecord(e1, st));
+        if (on) GN_HIP(hipEventRecord(e1, st));
+        return 0;
+    };
+    // the level-0 far updates (the dominant kernel) are timed when profiling is on; `bytes` = SURVEY 8d's
+    // B_trail = 8 (2 m_k n_k + m_k b + b^2) of every panel the launch applies, on the columns it applies them to
+    auto timed = [&](double bytes, hipStream_t st, auto&& launch) -> int {
+        if (int rc = between_events(h->profiling, h->upd_ev, h->upd_used, st, launch)) return rc;
+        if (h->profiling) {
             h->upd_bytes += (double)P.batch * bytes;
             h->upd_launch_bytes.push_back((double)P.batch * bytes);
         }
@@ -394,36 +428,35 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     // every other trailing-update launch (tree levels, the second panel's own columns): timed too, booked under
     // ENLSIP_GN_STAGE_UPDATE and reported by enlsip_gn_get_update_totals
     auto other = [&](hipStream_t st, auto&& launch) -> int {
-        hipEvent_t e1 = nullptr;
-        if (h->profiling && h->profile_all_updates) {
-            if (h->oth_used + 2 > h->oth_ev.size()) {
-                for (int q = 0; q < 2; ++q) {
-                    hipEvent_t e;
-                    GN_HIP(hipEventCreate(&e));
-                    h->oth_ev.push_back(e);
-                }
-            }
-            hipEvent_t e0 = h->oth_ev[h->oth_used++];
-            e1 = h->oth_ev[h->oth_used++];
-            GN_HIP(hipEventRecord(e0, st));
+        return between_events(h->profiling && h->profile_all_updates, h->oth_ev, h->oth_used, st, launch);
+    };
+    auto btrail = [&](int k, double ncols) { const double mk = mpad - (double)k * PB; return 8.0 * (2.0 * mk * ncols + mk * PB + PB * PB); };
+    // a sub-window [sub0, sub0 + subn) of a trailing window of ntot columns (subn = 0: to its end); the carried right-hand side is
+    // the window's last column, so a sub-window that ends before it has J2 columns only
+    struct Window { int sub0, subn, ncols; bool has_rhs; };
+    auto window = [](int ntot, int sub0, int subn) {
+        const int ncols = subn > 0 ? std::min(subn, ntot - sub0) : ntot - sub0;
+        return Window{sub0, subn, ncols, sub0 + ncols == ntot};
+    };
+    // The level-0 MFMA update of a window, on a grid over ngrid columns.  With the J2 columns filling whole 32-column blocks the
+    // carried right-hand side (the 32 j + 1-th column: every panel of C2) would take a block of its own: it gets its own routine as
+    // the last block index instead.  With a partial last block (C3: 24 columns) it simply rides in that block.
+    auto update_l0 = [&](CaqrArgs a, const LevelPlan& L, const Window& w, int ngrid, hipStream_t st) {
+        a.sub0 = w.sub0; a.subn = w.subn;
+        if (w.has_rhs && (w.ncols - 1) % 32 == 0) {
+            a.skip_rhs = 1;
+            --ngrid;
         }
-        launch();
-        if (e1) GN_HIP(hipEventRecord(e1, st));
-        return 0;
+        launch_update_v4(P.RPL, a, L.groups, ngrid, nprob, st);
+    };
+    // every other update of a window (tree levels, the second panel's own columns): not the dominant kernel, booked as "other"
+    auto update_other = [&](CaqrArgs a, const LevelPlan& L, const Window& w, int ngrid, hipStream_t st) -> int {
+        a.sub0 = w.sub0; a.subn = w.subn;
+        return other(st, [&] { launch_update_v4(P.RPL, a, L.groups, ngrid, nprob, st); });
     };
     // few problems with many tiles each: the far update of a pair reads its grid XCD-locally, so that a tile's V stays in one L2
     // between the tile's column blocks (k_caqr_update_v4_pair); batches keep the native order (a problem's tiles are neighbours)
     auto xmap_tiles = [&](int groups) -> int { return (h->xcd_map && P.batch <= 8 && groups >= 16 && !mixed) ? groups : 0; };
-    auto btrail = [&](int k, double ncols) { const double mk = mpad - (double)k * PB; return 8.0 * (2.0 * mk * ncols + mk * PB + PB * PB); };
-    // the MFMA update of every trailing column of the window; with the J2 columns filling whole 32-column blocks the carried
-    // right-hand side (the 32 j + 1-th column: every panel of C2) would take a block of its own: it gets its own routine as the
-    // last block index instead.  With a partial last block (C3: 24 columns) it simply rides in that block.
-    auto update_l0 = [&](CaqrArgs a, const LevelPlan& L, int ncols_window, int ncols_grid, hipStream_t st) {
-        if ((ncols_window - 1) % 32 == 0) {
-            a.skip_rhs = 1;
-            launch_update_v4(h->plan.RPL, a, L.groups, ncols_grid - 1, (int)P.batch, st);
-        } else launch_update_v4(h->plan.RPL, a, L.groups, ncols_grid, (int)P.batch, st);
-    };
     // Look-ahead (chain-bound sweeps: one or a few problems with many tiles — C4): a pair's far update is split into the NEXT
     // pair's 64 columns (this stream) and the rest (second stream), so that the next pair's chain of small dependent launches
     // (two level-0 factorisations, their trees, the second panel's own columns) runs beside the bulk of the previous far update
@@ -431,18 +464,6 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     const long long far_wgs0 = P.batch * (((long long)mpad + 64 * P.RPL - 1) / (64 * P.RPL)) * ((n2_launch + 31) / 32);
     const bool la = P.pair && use_mfma && h->lookahead && !mixed && !h->pair_debug && h->debug_stage < 0 &&
                     ((P.batch <= 8 && far_wgs0 >= 8192) || h->lookahead_forced);
-    hipStream_t sA = h->stream, sB = nullptr;
-    size_t la_ev = 0;
-    hipEvent_t la_prev = nullptr;                 // E2 of the previous pair's rest (second stream), not yet waited for
-    auto la_event = [&](hipEvent_t& e) -> int {
-        if (la_ev >= h->la_events.size()) {
-            hipEvent_t ne;
-            GN_HIP(hipEventCreateWithFlags(&ne, hipEventDisableTiming));
-            h->la_events.push_back(ne);
-        }
-        e = h->la_events[la_ev++];
-        return 0;
-    };
     // The same idea for the PLAIN sweep of a chain-bound problem (a single C2 problem; a 32768-row shard of C4 where pairs do
     // not pay): the factorisations of a panel (tile level and tree levels: they only read the panel's own columns) run first,
     // its trailing updates are split into the next panel's 32 columns (this stream) and the rest (second stream), and the next
@@ -452,6 +473,8 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     // 4.59 -> 4.80 ms, a 32768 x 1024 shard 15.66 -> 15.63 ms: two event hand-overs per panel cost what the overlap of a ~25 us
     // update with a ~75 us factor chain brings.  Kept behind ENLSIP_GN_LOOKAHEAD=1 (parity-tested in both sweeps), off by default.
     const bool lap = !P.pair && use_mfma && h->lookahead && !mixed && h->debug_stage < 0 && npan >= 3 && h->lookahead_forced;
+    const hipStream_t sA = h->stream;
+    hipStream_t sB = nullptr;
     if (la || lap) {
         if (!h->stream2) {
             // lowest priority: the chain's small kernels on the main stream must not queue behind the thousands of workgroups
@@ -463,208 +486,150 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
         sB = h->stream2;
         GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_LOOKAHEAD);
     }
-    auto la_join = [&]() -> int {                 // this stream goes on only after the second stream's last far update
+    size_t la_used = 0;
+    hipEvent_t la_prev = nullptr;                 // E2 of the previous step's rest (second stream), not yet waited for
+    auto la_join = [&]() -> int {                 // this stream goes on only after the second stream's last window update
         if (la_prev) {
             GN_HIP(hipStreamWaitEvent(sA, la_prev, 0));
             la_prev = nullptr;
         }
         return 0;
     };
-    for (int k = 0; k < npan;) {
-        if (h->debug_maxpan >= 0 && k >= h->debug_maxpan) break;   // ENLSIP_GN_DEBUG_MAXPAN: stop the sweep (debugging aid)
+    // the window update of a step whose chain has just been issued on this stream, in two parts: columns [0, near) (the next
+    // step's own) on this stream, the rest on the second
+    auto two_streams = [&](int ncols, int near, auto&& update) -> int {
+        if (ncols <= near) {                                    // nothing beyond the next step's columns: one part, this stream
+            if (int rc = la_join()) return rc;
+            return update(0, 0, sA);
+        }
+        hipEvent_t e1, e2;
+        if (int rc = next_event(h, h->la_events, la_used, hipEventDisableTiming, e1)) return rc;
+        if (int rc = next_event(h, h->la_events, la_used, hipEventDisableTiming, e2)) return rc;
+        GN_HIP(hipEventRecord(e1, sA));                         // the step's reflectors and T factors are complete
+        if (int rc = la_join()) return rc;                      // the previous step's rest covers the columns `near` touches
+        if (int rc = update(0, near, sA)) return rc;
+        GN_HIP(hipStreamWaitEvent(sB, e1, 0));
+        if (int rc = update(near, 0, sB)) return rc;
+        GN_HIP(hipEventRecord(e2, sB));
+        la_prev = e2;
+        return 0;
+    };
+    // Which parts of a step are issued.  Everything, but for the switches of the laboratory build (ENLSIP_GN_DEBUG_STAGE: parts
+    // 0..7 of a pair in the order of issue; ENLSIP_GN_DEBUG_MAXPAN: stop the sweep) and the A/B form ENLSIP_GN_PAIR=2: the same pair
+    // geometry, the far level-0 pass as two plain passes (first panel, then second).
+    auto live = [&](int part) { return h->debug_stage < 0 || part <= h->debug_stage; };
+    const bool far_pair_pass = live(4) && !h->pair_debug, far_plain_a = live(4) && h->pair_debug, far_plain_b = far_plain_a && live(5);
+    const int npan_run = h->debug_maxpan >= 0 ? std::min(npan, h->debug_maxpan) : npan;
+    for (int k = 0; k < npan_run;) {
         const int bwk = std::min(PB, kp_launch - k * PB);
         const int ntrail = n2_launch + 1 - (k * PB + bwk);  // trailing columns incl. the augmented one
         if (h->profiling && ntrail > 0) h->upd_all_bytes += (double)P.batch * btrail(k, ntrail);   // every column right of the panel
+        const auto& LA = P.panels[k].levels;
         if (P.pair && use_mfma && !(k & 1) && k + 1 < npan) {
             // ---- panel pair (k, k + 1): tiles shared, ONE pass over the far trailing columns for both (gn_kernels_caqr.hpp) ----
             GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_PAIRS);
-            if (P.panels[k].levels.size() > 1) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_TREE);
+            if (LA.size() > 1) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_TREE);
             const int kb = k + 1;
-            const auto& LA = P.panels[k].levels;
             const auto& LB = P.panels[kb].levels;
             const int bwb = std::min(PB, kp_launch - kb * PB);
             const int nfar = ntrail - bwb;                   // columns beyond the pair, incl. the augmented one (>= 1)
             if (h->profiling && nfar > 0) h->upd_all_bytes += (double)P.batch * btrail(kb, nfar);
-            // Grid of the launches over the far window (win = 2).  A problem whose J2 ends inside the pair has bwb fewer pair
+            // chain.  The first panel's level 0, applied to the second panel's columns only (win = 1); level 0 of the second panel:
+            // the same tiles without their first 32 rows; the first panel's tree, applied likewise; the second panel's tree
+            const Window own = window(bwb, 0, 0);
+            auto first_panel_level = [&](const LevelPlan& L) -> int {
+                CaqrArgs a = caqr_args(h, k, L);
+                launch_factor(h, a, L.groups);
+                a.win = 1;
+                return update_other(a, L, own, bwb, sA);
+            };
+            if (live(0))
+                if (int rc = first_panel_level(LA[0])) return rc;
+            if (live(1)) launch_factor(h, caqr_args(h, kb, LB[0]), LB[0].groups);
+            for (size_t li = 1; li < LA.size() && live(2); ++li)
+                if (int rc = first_panel_level(LA[li])) return rc;
+            for (size_t li = 1; li < LB.size() && live(3); ++li) launch_factor(h, caqr_args(h, kb, LB[li]), LB[li].groups);
+            // window update (win = 2): both level-0 reflectors in one pass, then the first panel's tree levels, then the second's.
+            // Grid of the first panel's launches.  A problem whose J2 ends inside the pair has bwb fewer pair
             // columns and as many more far columns than the launch shape says, so with mixed widths the grid spans ntrail and the
             // column block past a problem's last column exits at once.  In a uniform batch that block is ALWAYS empty — and not
             // free: with 8 tiles in x (= the 8 XCDs) a grid whose y extent is a multiple of 4 hands the empty and the light
             // (right-hand side) block of every problem to the same two of an XCD's four dispatch queues, measured 5-20 % on the
             // far launches of pairs 1, 3, 5 of a C2 step (profiles/r4_notes.md).  The exact grid has an odd y extent.
-            const int far_grid = mixed ? ntrail : nfar;
-            auto live = [&](int st) { return h->debug_stage < 0 || st <= h->debug_stage; };   // ENLSIP_GN_DEBUG_STAGE (debugging aid)
-            if (live(0)) {   // level 0 of the first panel, applied to the second panel's columns only
-                CaqrArgs a = caqr_args(h, k, LA[0]);
-                launch_factor(h, a, LA[0].groups);
-                a.win = 1;
-                if (int rc = other(h->stream, [&] { launch_update_v4(h->plan.RPL, a, LA[0].groups, bwb, (int)P.batch, h->stream); })) return rc;
-            }
-            if (live(1)) {   // level 0 of the second panel: the same tiles without their first 32 rows
-                CaqrArgs a = caqr_args(h, kb, LB[0]);
-                launch_factor(h, a, LB[0].groups);
-            }
-            for (size_t li = 1; li < LA.size() && live(2); ++li) {      // tree of the first panel, applied to the second panel's columns
-                CaqrArgs a = caqr_args(h, k, LA[li]);
-                launch_factor(h, a, LA[li].groups);
-                a.win = 1;
-                if (int rc = other(h->stream, [&] { launch_update_v4(h->plan.RPL, a, LA[li].groups, bwb, (int)P.batch, h->stream); })) return rc;
-            }
-            for (size_t li = 1; li < LB.size() && live(3); ++li) {      // tree of the second panel
-                CaqrArgs a = caqr_args(h, kb, LB[li]);
-                launch_factor(h, a, LB[li].groups);
-            }
-            // far columns: both level-0 reflectors in one pass (a problem whose J2 ends inside the pair has more far columns
-            // than the launch shape says: the grid covers ntrail, workgroups past a problem's last column exit at once)
-            if (!live(4)) {
-            } else if (h->pair_debug) {    // A/B: the same pair geometry, far columns in two plain passes (first panel, then second)
+            // (Mixed widths never meet a sub-window: both look-ahead forms need a uniform batch.)
+            auto far_update = [&](int sub0, int subn, hipStream_t st) -> int {
+                const Window w = window(nfar, sub0, subn);
+                const int far_grid = mixed ? ntrail : w.ncols;
                 CaqrArgs a = caqr_args(h, k, LA[0]);
                 a.win = 2;
-                update_l0(a, LA[0], nfar, ntrail, h->stream);
-                CaqrArgs b0 = caqr_args(h, kb, LB[0]);
-                if (live(5)) update_l0(b0, LB[0], nfar, nfar, h->stream);
-            } else if (la) {
-                // far columns of the pair in two parts (see above); `far` launches level 0 and the trees on columns
-                // [sub0, sub0 + subn) of the far window
-                auto far = [&](int sub0, int subn, hipStream_t st) -> int {
-                    const int ncw = (subn > 0 ? std::min(subn, nfar - sub0) : nfar - sub0);     // launch shape of the sub-window
-                    CaqrArgs a = caqr_args(h, k, LA[0]);
-                    a.win = 2; a.pair = 1; a.tOff2 = LB[0].tOff; a.sub0 = sub0; a.subn = subn;
+                if (far_pair_pass) {
+                    a.pair = 1; a.tOff2 = LB[0].tOff;
                     a.xmap = xmap_tiles(LA[0].groups);
-                    // the carried right-hand side is the window's last column: a sub-window that ends before it has J2 columns only
-                    const bool has_rhs = (sub0 + ncw == nfar);
-                    const double by = btrail(k, ncw) + btrail(kb, ncw);
-                    int rc = timed(by, st, [&] {
-                        if (has_rhs) update_l0(a, LA[0], ncw, ncw, st);          // look-ahead sweeps are uniform (la implies !mixed)
-                        else launch_update_v4(h->plan.RPL, a, LA[0].groups, ncw, (int)P.batch, st);
-                    });
+                    int rc = timed(btrail(k, w.ncols) + btrail(kb, w.ncols), st, [&] { update_l0(a, LA[0], w, far_grid, st); });
                     if (rc) return rc;
-                    for (size_t li = 1; li < LA.size(); ++li) {
-                        CaqrArgs t = caqr_args(h, k, LA[li]);
-                        t.win = 2; t.sub0 = sub0; t.subn = subn;
-                        if (int rc2 = other(st, [&] { launch_update_v4(h->plan.RPL, t, LA[li].groups, ncw, (int)P.batch, st); })) return rc2;
+                    if (mixed) {        // problems whose J2 ends before the second panel: the first panel alone, every trailing column
+                        a.pair = 2;
+                        update_l0(a, LA[0], w, ntrail, st);
                     }
-                    for (size_t li = 1; li < LB.size(); ++li) {
-                        CaqrArgs t = caqr_args(h, kb, LB[li]);
-                        t.sub0 = sub0; t.subn = subn;
-                        if (int rc2 = other(st, [&] { launch_update_v4(h->plan.RPL, t, LB[li].groups, ncw, (int)P.batch, st); })) return rc2;
-                    }
-                    return 0;
-                };
-                const int near = 2 * PB;
-                if (nfar <= near) {               // nothing beyond the next pair's columns: one part, this stream
-                    if (int rcj = la_join()) return rcj;
-                    if (int rc = far(0, 0, sA)) return rc;
-                } else {
-                    hipEvent_t e1, e2;
-                    if (int rc = la_event(e1)) return rc;
-                    if (int rc = la_event(e2)) return rc;
-                    GN_HIP(hipEventRecord(e1, sA));                     // the pair's reflectors and T factors are complete
-                    if (int rcj = la_join()) return rcj;                // the previous pair's rest covers the columns `near` touches
-                    if (int rc = far(0, near, sA)) return rc;
-                    GN_HIP(hipStreamWaitEvent(sB, e1, 0));
-                    if (int rc = far(near, 0, sB)) return rc;
-                    GN_HIP(hipEventRecord(e2, sB));
-                    la_prev = e2;
                 }
-                k += 2;
-                continue;
-            } else {
-                CaqrArgs a = caqr_args(h, k, LA[0]);
-                a.win = 2; a.pair = 1; a.tOff2 = LB[0].tOff;
-                a.xmap = xmap_tiles(LA[0].groups);
-                int rc = timed(btrail(k, nfar) + btrail(kb, nfar), h->stream, [&] { update_l0(a, LA[0], nfar, far_grid, h->stream); });
-                if (rc) return rc;
-                if (mixed) {        // problems whose J2 ends before the second panel: the first panel alone, every trailing column
-                    a.pair = 2;
-                    update_l0(a, LA[0], nfar, ntrail, h->stream);
+                if (far_plain_a) update_l0(a, LA[0], w, ntrail, st);
+                if (far_plain_b) update_l0(caqr_args(h, kb, LB[0]), LB[0], w, nfar, st);
+                for (size_t li = 1; li < LA.size() && live(6); ++li) {
+                    CaqrArgs t = caqr_args(h, k, LA[li]);
+                    t.win = 2;
+                    if (int rc = update_other(t, LA[li], w, far_grid, st)) return rc;
                 }
-            }
-            for (size_t li = 1; li < LA.size() && live(6); ++li) {
-                CaqrArgs a = caqr_args(h, k, LA[li]);
-                a.win = 2;
-                if (int rc = other(h->stream, [&] { launch_update_v4(h->plan.RPL, a, LA[li].groups, far_grid, (int)P.batch, h->stream); })) return rc;
-            }
-            for (size_t li = 1; li < LB.size() && live(7); ++li) {
-                CaqrArgs a = caqr_args(h, kb, LB[li]);
-                if (int rc = other(h->stream, [&] { launch_update_v4(h->plan.RPL, a, LB[li].groups, nfar, (int)P.batch, h->stream); })) return rc;
-            }
+                for (size_t li = 1; li < LB.size() && live(7); ++li)
+                    if (int rc = update_other(caqr_args(h, kb, LB[li]), LB[li], w, w.ncols, st)) return rc;
+                return 0;
+            };
+            if (int rc = la ? two_streams(nfar, 2 * PB, far_update) : far_update(0, 0, sA)) return rc;
             k += 2;
             continue;
         }
         // ---- one panel ----
-        // last panel narrower than 32 with d as the only trailing column: d rides through the factor kernels
+        // last panel narrower than 32 with d as the only trailing column: d rides through the factor kernels (no update launch)
         const bool passenger = (ntrail == 1 && bwk < PB && kp_launch == n2_launch);
         GN_ROUTE(passenger ? ENLSIP_GN_ROUTE_SWEEP_PASSENGER : ENLSIP_GN_ROUTE_SWEEP_PLAIN);
-        if (P.panels[k].levels.size() > 1) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_TREE);
-        if (lap && !passenger && ntrail > 0) {
-            const auto& LV = P.panels[k].levels;
-            for (const LevelPlan& L : LV) {                      // every factorisation of the panel first
-                CaqrArgs a = caqr_args(h, k, L);
-                launch_factor(h, a, L.groups);
-            }
-            // updates of the levels, in order, on columns [sub0, sub0 + subn) of the trailing window (subn = 0: to its end)
-            auto upd = [&](int sub0, int subn, hipStream_t st) -> int {
-                const int ncw = (subn > 0 ? std::min(subn, ntrail - sub0) : ntrail - sub0);
-                const bool has_rhs = (sub0 + ncw == ntrail);       // the carried right-hand side is the window's last column
-                for (const LevelPlan& L : LV) {
-                    CaqrArgs a = caqr_args(h, k, L);
-                    a.sub0 = sub0; a.subn = subn;
-                    if (L.level == 0) {
-                        int rc = timed(btrail(k, ncw), st, [&] {
-                            if (has_rhs) update_l0(a, L, ncw, ncw, st);
-                            else launch_update_v4(h->plan.RPL, a, L.groups, ncw, (int)P.batch, st);
-                        });
-                        if (rc) return rc;
-                    } else {
-                        if (int rc = other(st, [&] { launch_update_v4(h->plan.RPL, a, L.groups, ncw, (int)P.batch, st); })) return rc;
-                    }
-                }
+        if (LA.size() > 1) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_TREE);
+        const bool updates = ntrail > 0 && !passenger;
+        // window update of one level
+        auto level_update = [&](const LevelPlan& L, int sub0, int subn, hipStream_t st) -> int {
+            const Window w = window(ntrail, sub0, subn);
+            const CaqrArgs a = caqr_args(h, k, L);
+            if (L.level > 0) return update_other(a, L, w, w.ncols, st);
+            return timed(btrail(k, w.ncols), st, [&] { update_l0(a, L, w, w.ncols, st); });
+        };
+        if (lap && updates) {       // every factorisation of the panel first, then the updates of the levels, in order
+            for (const LevelPlan& L : LA) launch_factor(h, caqr_args(h, k, L), L.groups);
+            int rc = two_streams(ntrail, PB, [&](int sub0, int subn, hipStream_t st) -> int {
+                for (const LevelPlan& L : LA)
+                    if (int rcl = level_update(L, sub0, subn, st)) return rcl;
                 return 0;
-            };
-            if (ntrail <= PB) {                                    // nothing beyond the next panel's columns
-                if (int rcj = la_join()) return rcj;
-                if (int rc = upd(0, 0, sA)) return rc;
-            } else {
-                hipEvent_t e1, e2;
-                if (int rc = la_event(e1)) return rc;
-                if (int rc = la_event(e2)) return rc;
-                GN_HIP(hipEventRecord(e1, sA));                     // the panel's reflectors and T factors are complete
-                if (int rcj = la_join()) return rcj;                // the previous panel's rest covers the columns `near` touches
-                if (int rc = upd(0, PB, sA)) return rc;
-                GN_HIP(hipStreamWaitEvent(sB, e1, 0));
-                if (int rc = upd(PB, 0, sB)) return rc;
-                GN_HIP(hipEventRecord(e2, sB));
-                la_prev = e2;
-            }
+            });
+            if (rc) return rc;
             ++k;
             continue;
         }
-        if (int rcj = la_join()) return rcj;
-        for (const LevelPlan& L : P.panels[k].levels) {
+        if (int rc = la_join()) return rc;
+        for (const LevelPlan& L : LA) {     // one stream: factor and update level by level (F0 U0 F1 U1 ...)
             CaqrArgs a = caqr_args(h, k, L);
             a.npass = passenger ? 1 : 0;
             launch_factor(h, a, L.groups);
-            if (ntrail > 0 && !passenger) {
-                if (use_mfma && L.level == 0) {
-                    int rc = timed(btrail(k, ntrail), h->stream, [&] { update_l0(a, L, ntrail, ntrail, h->stream); });
-                    if (rc) return rc;
-                } else if (use_mfma) {
-                    if (int rc = other(h->stream, [&] { launch_update_v4(h->plan.RPL, a, L.groups, ntrail, (int)P.batch, h->stream); })) return rc;
-                }
-                else launch_update_refl(h, a, L.groups, ntrail);
-            }
+            if (!updates) continue;
+            if (!use_mfma) launch_update_refl(h, a, L.groups, ntrail, nprob);      // reflector by reflector (A/B path)
+            else if (int rc = level_update(L, 0, 0, sA)) return rc;
         }
         ++k;
     }
-    if (int rcj = la_join()) return rcj;
+    if (int rc = la_join()) return rc;
     GN_HIP(hipGetLastError());
     return 0;
 }
 
-// distributed column-pivoted QR of R0 (one launch per pivot step over all problems)
-static int run_qrcp_dist(enlsip_gn_handle h, int n2_launch) {
+// the launch-per-step pivoted QR (gn_kernels_qrcp_dist.hpp): arguments of the stage on R0 out of the CAQR storage
+static QdArgs qd_args_r0(enlsip_gn_handle h, int n2_launch) {
     const Plan& P = h->plan;
-    const int kp_launch = (int)std::min<long long>(P.m, n2_launch);
     QdArgs a{};
     a.n = (int)P.n; a.ldw = P.ldw; a.ldr = P.ldr; a.step = 0; a.prob0 = 0;
     a.W = h->W; a.sW = P.sW; a.M = h->qdM; a.sM = P.sM; a.Vb = h->qdVb; a.sVb = P.sVb; a.Rt = h->Rt; a.sRt = P.sRt;
@@ -674,17 +639,30 @@ static int run_qrcp_dist(enlsip_gn_handle h, int n2_launch) {
     a.cand = (QdCand*)h->qdCand; a.sCand = P.sCand; a.Gmax = P.qdGmax;
     a.jpvt = h->jpvtJ; a.sJ = P.sJJ; a.state = h->state;
     a.n2cap = n2_launch;
-    const int G = (n2_launch + 1 + QD_CPW - 1) / QD_CPW;
-    dim3 grid(G, (unsigned)P.batch);
-    GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_STEPS);
-    const bool big = kp_launch > 512;
-    if (big) hipLaunchKernelGGL(k_qd_init<16>, grid, dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL(k_qd_init<8>, grid, dim3(256), 0, h->stream, a);
-    for (int j = 0; j < kp_launch; ++j) {
+    return a;
+}
+static dim3 qd_grid(int cols, long long batch) { return dim3((cols + 1 + QD_CPW - 1) / QD_CPW, (unsigned)batch); }
+// k_qd_init (with the caller's a.step) and the pivot steps [0, nsteps), in the 16 (big: more than 512 rows) or 8 rows-per-lane
+// form; a.step is left at the last step issued.  k_qd_assemble reads the sign of a.step (negative: the blocked form's single
+// map), so it stays with the callers.
+static void launch_qd_steps(dim3 grid, bool big, hipStream_t s, QdArgs& a, int nsteps) {
+    if (big) hipLaunchKernelGGL(k_qd_init<16>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_qd_init<8>, grid, dim3(256), 0, s, a);
+    for (int j = 0; j < nsteps; ++j) {
         a.step = j;
-        if (big) hipLaunchKernelGGL(k_qd_step<16>, grid, dim3(256), 0, h->stream, a);
-        else hipLaunchKernelGGL(k_qd_step<8>, grid, dim3(256), 0, h->stream, a);
+        if (big) hipLaunchKernelGGL(k_qd_step<16>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(k_qd_step<8>, grid, dim3(256), 0, s, a);
     }
+}
+
+// distributed column-pivoted QR of R0 (one launch per pivot step over all problems)
+static int run_qrcp_dist(enlsip_gn_handle h, int n2_launch) {
+    const Plan& P = h->plan;
+    const int kp_launch = (int)std::min<long long>(P.m, n2_launch);
+    QdArgs a = qd_args_r0(h, n2_launch);
+    GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_STEPS);
+    const dim3 grid = qd_grid(n2_launch, P.batch);
+    launch_qd_steps(grid, kp_launch > 512, h->stream, a, kp_launch);
     hipLaunchKernelGGL(k_qd_assemble, grid, dim3(256), 0, h->stream, a);
     GN_HIP(hipGetLastError());
     return 0;
@@ -703,19 +681,12 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
     GN_ROUTE(jhead > 0 ? ENLSIP_GN_ROUTE_PIVOT_HYBRID : ENLSIP_GN_ROUTE_PIVOT_BLOCKS);
     SbArgs a{};
     QdArgs& q = a.q;
-    q.n = (int)P.n; q.ldw = P.ldw; q.ldr = P.ldr; q.step = -1; q.prob0 = 0;
-    q.W = h->W; q.sW = P.sW; q.M = h->qdM; q.sM = P.sM; q.Vb = h->qdVb; q.sVb = P.sVb; q.Rt = h->Rt; q.sRt = P.sRt;
-    q.tau = h->tauJ; q.sTau = P.sTauJ; q.diag = h->qdDiag; q.sDiag = P.sDiag;
-    q.vn1 = h->qdVn1; q.vn2 = h->qdVn2; q.sVn = P.sVn;
-    q.chosen = h->qdChosen; q.pos = h->qdPos; q.colat = h->qdColat; q.sI = P.sQI;
-    q.cand = (QdCand*)h->qdCand; q.sCand = P.sCand; q.Gmax = P.qdGmax;
-    q.jpvt = h->jpvtJ; q.sJ = P.sJJ; q.state = h->state;
-    q.n2cap = n2_launch;
+    q = qd_args_r0(h, n2_launch);
+    q.step = -1;
     a.info = (SbInfo*)h->sbInfo; a.inblk = h->sbInblk; a.sIn = P.sQI; a.blkid = 0;
     a.Tsb = h->sbT; a.sTsb = PB * PB; a.act = h->sbAct; a.sAct = P.sQI + 32;
     a.dbg = nullptr;
-    const int G = (n2_launch + 1 + QD_CPW - 1) / QD_CPW;
-    dim3 grid(G, (unsigned)P.batch);
+    const dim3 grid = qd_grid(n2_launch, P.batch);
     hipStream_t s = h->stream;
     // Row-count statistics per block id (see SbArgs::rows_stat).  Every block is launched in up to three forms of the select /
     // factor kernel and a problem runs in the one that fits its current row count; in a batch of similar problems two of the
@@ -733,15 +704,9 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
     bool hints = h->sb_form_hints && h->sb_rows_kp == kp_launch && h->sb_rows_batch == P.batch && !h->sb_rows_max.empty();
     const bool hinted = hints;
     bool fell_back = false;
-    if (jhead > 0) {
-        hipLaunchKernelGGL(k_qd_init<16>, grid, dim3(256), 0, s, q);
-        for (int j = 0; j < jhead; ++j) {
-            q.step = j;
-            hipLaunchKernelGGL(k_qd_step<16>, grid, dim3(256), 0, s, q);
-        }
-        q.step = -1;
-        q.hyb = jhead;
-    } else hipLaunchKernelGGL(k_qd_init<8>, grid, dim3(256), 0, s, q);
+    launch_qd_steps(grid, jhead > 0, s, q, jhead);     // the head, if any: more than 512 rows
+    q.step = -1;
+    q.hyb = jhead;
     hipLaunchKernelGGL(k_sb_reset, dim3(((unsigned)P.n + 255) / 256, (unsigned)P.batch), dim3(256), 0, s, a, (int)P.n, jhead);
     const int kp_blk = kp_launch - jhead;           // steps (= rows) left to the blocks
     dim3 ugrid((n2_launch + 1 + SB_UCW - 1) / SB_UCW, (unsigned)P.batch);
@@ -993,16 +958,9 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
     q.chosen = cChosen; q.pos = cPos; q.colat = cColat; q.sI = sIc;
     q.cand = cCand; q.sCand = sCandc; q.Gmax = Gc;
     auto factor = [&](int rows, int cols, int steps) {
-        const dim3 grid((cols + 1 + QD_CPW - 1) / QD_CPW, (unsigned)batch);
-        const bool big = rows > 512;
+        const dim3 grid = qd_grid(cols, batch);
         q.step = 0;
-        if (big) hipLaunchKernelGGL(k_qd_init<16>, grid, dim3(256), 0, s, q);
-        else hipLaunchKernelGGL(k_qd_init<8>, grid, dim3(256), 0, s, q);
-        for (int j = 0; j < steps; ++j) {
-            q.step = j;
-            if (big) hipLaunchKernelGGL(k_qd_step<16>, grid, dim3(256), 0, s, q);
-            else hipLaunchKernelGGL(k_qd_step<8>, grid, dim3(256), 0, s, q);
-        }
+        launch_qd_steps(grid, rows > 512, s, q, steps);
         q.step = 0;
         hipLaunchKernelGGL(k_qd_assemble, grid, dim3(256), 0, s, q);
     };
@@ -1202,14 +1160,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     int n2_launch = (int)(n - std::min<long long>(n, t_min));
     for (int attempt = 0; attempt < 2; ++attempt) {
         // 2. JQ1 = J*Q1, d_temp
-        JQ1Args qa{};
-        qa.m = (int)m; qa.n = (int)n; qa.kA = P.kA; qa.ldw = P.ldw;
-        qa.J = dJ; qa.ldj = ldj; qa.strideJ = strideJ; qa.rx = drx; qa.stride_rx = m;
-        qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
-        qa.W = h->W; qa.sW = P.sW; qa.state = h->state;
-        qa.prob0 = 0;
-        // V T' of the fast path lives in the (still unused) working matrix of the pivoted QR
-        qa.VT = (P.sM >= (long long)n * KBLK) ? h->qdM : nullptr; qa.sVT = P.sM;
+        const JQ1Args qa = jq1_args(h, dJ, ldj, strideJ, drx);
         // one 256-row tile, one narrow panel (C5): J*Q1 and the panel factorisation in ONE launch, the tile handed over in LDS
         const bool fused = h->fuse_small && !upper_in && !(h->flags & ENLSIP_GN_UPDATE_REFLECTORS) &&
                            small_fused_applies(m, n, P.kA, n2_launch);
@@ -1218,9 +1169,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
             ca.npass = 1;
             launch_jq1_factor_small(qa, ca, (int)batch, s);
             GN_HIP(hipGetLastError());
-        } else if (h->flags & ENLSIP_GN_UPDATE_REFLECTORS) launch_jq1(qa, (int)batch, s);   // plain-FMA A/B partner
-        else if (launch_jq1_rows(qa, (int)batch, s)) {}                             // small n, few reflectors
-        else if (!launch_jq1_v2(qa, (int)batch, s)) launch_jq1_mfma(qa, (int)batch, s);      // regular shapes / general shapes
+        } else launch_jq1_any(h, qa, (int)batch, s);
         mark(2);
         GN_TRACE(h, "attempt %d n2_launch=%d: J*Q1 done%s", attempt, n2_launch, fused ? " (fused with the panel factorisation)" : "");
         // 3. CAQR of [J2 | d]

@@ -193,26 +193,12 @@ static int apply_q_common(enlsip_gn_handle h, int which, int64_t prob, double* v
     const int npan = (kp + PB - 1) / PB;
     GN_HIP(hipMemcpyAsync(stage, vhost, (size_t)m * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_pad_copy, dim3((P.ldw + 255) / 256), dim3(256), 0, s, stage, m, P.ldw, dv);
-    auto apply_ext = [&](bool reverse) {
-        for (int kk = 0; kk < npan; ++kk) {
-            const int k = reverse ? npan - 1 - kk : kk;
-            const auto& lv = P.panels[k].levels;
-            for (size_t li = 0; li < lv.size(); ++li) {
-                const LevelPlan& L = reverse ? lv[lv.size() - 1 - li] : lv[li];
-                CaqrArgs a = caqr_args(h, k, L);
-                a.ext_cols = 1; a.C = dv; a.sC = 0; a.reverse = reverse ? 1 : 0; a.prob0 = (int)prob;
-                dim3 grid(L.groups, 1, 1);
-                if (P.RPL == 8) hipLaunchKernelGGL(k_caqr_update_refl<8>, grid, dim3(256), 0, s, a);
-                else hipLaunchKernelGGL(k_caqr_update_refl<4>, grid, dim3(256), 0, s, a);
-            }
-        }
-    };
     if (trans) {
-        apply_ext(false);
+        caqr_apply_ext(h, dv, (int)prob, npan, false);
         if (kp > 0) hipLaunchKernelGGL(k_vec_reflectors<true>, dim3(1), dim3(64), 0, s, v.F, v.ld, v.tau, kp, kp, dv);
     } else {
         if (kp > 0) hipLaunchKernelGGL(k_vec_reflectors<false>, dim3(1), dim3(64), 0, s, v.F, v.ld, v.tau, kp, kp, dv);
-        apply_ext(true);
+        caqr_apply_ext(h, dv, (int)prob, npan, true);
     }
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpyAsync(vhost, dv, (size_t)m * 8, hipMemcpyDeviceToHost, s));
@@ -237,11 +223,8 @@ int enlsip_gn_get_JQ1(enlsip_gn_handle h, int64_t prob, double* out, int64_t ld)
     GN_HIP(hipSetDevice(h->device));
     rc = grow(h, h->scratch, (size_t)P.ldw * (P.n + 1) * 8);
     if (rc) return rc;
-    JQ1Args qa{};
-    qa.m = (int)P.m; qa.n = (int)P.n; qa.kA = P.kA; qa.ldw = P.ldw;
-    qa.J = h->last.J; qa.ldj = h->last.ldj; qa.strideJ = h->last.strideJ; qa.rx = h->last.rx; qa.stride_rx = P.m;
-    qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
-    qa.W = (double*)h->scratch.p; qa.sW = 0; qa.state = h->state; qa.prob0 = (int)prob;
+    JQ1Args qa = jq1_args(h, h->last.J, h->last.ldj, h->last.strideJ, h->last.rx);
+    qa.W = (double*)h->scratch.p; qa.sW = 0; qa.prob0 = (int)prob;
     launch_jq1(qa, 1, h->stream);
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpy2DAsync(out, (size_t)ld * 8, h->scratch.p, (size_t)P.ldw * 8, (size_t)P.m * 8, (size_t)P.n,
@@ -291,14 +274,7 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
     hipLaunchKernelGGL(k_dtemp, dim3((P.ldw + 255) / 256), dim3(256), 0, s, h->W + prob * P.sW, P.ldw, m,
                        st0.rankA, h->p1 + prob * P.sP1, h->last.slice(prob, 1).rx, dv);
     const int kp = st0.kp, npan = (kp + PB - 1) / PB;
-    for (int k = 0; k < npan; ++k)
-        for (const LevelPlan& L : P.panels[k].levels) {
-            CaqrArgs a = caqr_args(h, k, L);
-            a.ext_cols = 1; a.C = dv; a.sC = 0; a.reverse = 0; a.prob0 = (int)prob;
-            dim3 grid(L.groups, 1, 1);
-            if (P.RPL == 8) hipLaunchKernelGGL(k_caqr_update_refl<8>, grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL(k_caqr_update_refl<4>, grid, dim3(256), 0, s, a);
-        }
+    caqr_apply_ext(h, dv, (int)prob, npan, false);
     if (kp > 0)
         hipLaunchKernelGGL(k_vec_reflectors<true>, dim3(1), dim3(64), 0, s, h->Rt + prob * P.sRt, P.ldr,
                            h->tauJ + prob * P.sTauJ, kp, kp, dv);

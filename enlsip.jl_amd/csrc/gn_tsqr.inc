@@ -191,15 +191,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     if (rc) return rc;
     int n2_launch = (int)(n - P.kA);
     for (int attempt = 0; attempt < 2; ++attempt) {
-        JQ1Args qa{};
-        qa.m = (int)m_loc; qa.n = (int)n; qa.kA = P.kA; qa.ldw = P.ldw;
-        qa.J = dJ; qa.ldj = ldj; qa.strideJ = 0; qa.rx = drx; qa.stride_rx = m_loc;
-        qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
-        qa.W = h->W; qa.sW = P.sW; qa.state = h->state; qa.prob0 = 0;
-        qa.VT = (P.sM >= (long long)n * KBLK) ? h->qdM : nullptr; qa.sVT = P.sM;
-        if (h->flags & ENLSIP_GN_UPDATE_REFLECTORS) launch_jq1(qa, 1, s);
-        else if (launch_jq1_rows(qa, 1, s)) {}
-        else if (!launch_jq1_v2(qa, 1, s)) launch_jq1_mfma(qa, 1, s);
+        launch_jq1_any(h, jq1_args(h, dJ, ldj, 0, drx), 1, s);
         rc = run_caqr(h, n2_launch);
         if (rc) return rc;
         GN_HIP(hipMemcpyAsync(h->h_state, h->state, sizeof(ProbState), hipMemcpyDeviceToHost, s));
