@@ -26,6 +26,7 @@
 #include "gn_kernels_misc.hpp"
 #include "gn_kernels_lagrange.hpp"
 #include "gn_kernels_lagrange_batched.hpp"
+#include "gn_kernels_resolve_batched.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
 #include "gn_kernels_qrcp_block.hpp"
@@ -1114,6 +1115,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     const Plan& P = h->plan;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
+    h->held.clear();
     h->last = v.inputs();
     h->sc_eJ = 0;
     if (!reuse) h->sc_eA = 0;       // (a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it)
@@ -1424,6 +1426,10 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->newton.p) (void)hipFree(h->newton.p);
     if (h->lagb_io.p) (void)hipFree(h->lagb_io.p);
     if (h->lagb_scr.p) (void)hipFree(h->lagb_scr.p);
+    if (h->rsb_dims.p) (void)hipFree(h->rsb_dims.p);
+    if (h->rsb_io.p) (void)hipFree(h->rsb_io.p);
+    for (hipEvent_t e : h->rsb_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->h_lagflag) (void)hipHostFree(h->h_lagflag);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);
@@ -1786,6 +1792,7 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
     v.At = dAt; v.ldat = n; v.strideAt = n * t; v.cx = dcx;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
+    h->held.clear();
     h->last = v;
     h->sc_eJ = 0; h->sc_eA = 0;
     h->rescue_prob.clear();
@@ -1910,4 +1917,5 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_tsqr.inc"
 #include "gn_lagrange.inc"
 #include "gn_lagrange_batched.inc"
+#include "gn_resolve_batched.inc"
 #include "gn_newton.inc"

@@ -191,6 +191,7 @@ static int apply_q_common(enlsip_gn_handle h, int which, int64_t prob, double* v
     const ProbState& st = h->h_state[prob];
     const int m = (int)P.m, kp = st.kp;
     const int npan = (kp + PB - 1) / PB;
+    if ((size_t)prob < h->held.size()) h->held[(size_t)prob] = {};      // the vector buffer of a held batched re-solve is overwritten
     GN_HIP(hipMemcpyAsync(stage, vhost, (size_t)m * 8, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_pad_copy, dim3((P.ldw + 255) / 256), dim3(256), 0, s, stage, m, P.ldw, dv);
     if (trans) {
@@ -248,6 +249,7 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
     GN_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const int m = (int)P.m, n = (int)P.n, t = (int)P.t;
+    if ((size_t)prob < h->held.size()) h->held[(size_t)prob] = {};      // p1 and the vector buffer of a held batched re-solve are overwritten
     // (1) b, p1 with the requested dimA / code: the constraint stage of this one problem again, through the SAME kernels that
     //     produced its factors (register / LDS / wave forms rewrite them bit for bit; the distributed form of many constraints
     //     keeps its factors and redoes only b and p1).  The kernels reset rankJ2 / dimJ2 / status in the state record:

@@ -184,6 +184,15 @@ struct enlsip_gn_context {
     int* h_lagflag = nullptr;
     bool lagrange_small = true;         // ENLSIP_GN_LAGRANGE_SMALL=0: batched multiplier estimates in the general form only (A/B)
     int consumer_form = -1;             // form of the last batched multiplier estimate (enlsip_gn_get_consumer_form), -1: none yet
+    // batched re-solve (gn_resolve_batched.inc): per-slot requests on the device, staging of the host-buffer form, the form of the
+    // last call, and per resident problem the (code, dimA) of a held call whose p1 and Q3' d_temp are still in p1 / vec (code 0: none)
+    gn::DevBuf rsb_dims, rsb_io;
+    int resolve_form = -1;
+    hipEvent_t rsb_ev[2] = {};          // profiling on: around the Q0' launches of the last batched re-solve on this handle
+    bool rsb_timed = false;
+    float resolve_q0_ms = 0.f;          // ... summed over the handles that ran a part of the range
+    struct Held { int code = 0, dimA = 0; };
+    std::vector<Held> held;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

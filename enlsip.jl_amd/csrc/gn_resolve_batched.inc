@@ -1,0 +1,333 @@
+// Batched subspace re-solve over a contiguous range of the resident batch (kernels: gn_kernels_resolve_batched.hpp): what
+// search_direction_analys does per problem at src/enlsip_functions.jl:1249-1253 — b = F_L11.Q' (-cx[F_A.p]), the d of
+// choose_subspace_dimensions (:1118-1176, :1156-1163) and sub_search_direction (:116-153) — in a number of launches and
+// synchronisations that does not depend on the size of the range.  Routing as the batched consumers (gn_lagrange_batched.inc).
+// Included at the end of enlsip_gn.hip.
+
+namespace {
+
+struct ResolveIO {       // device buffers, slot 0 = problem prob0; any may be null
+    double *p, *b, *d;
+    enlsip_gn_info* info;
+    int* status;
+};
+
+enum { RS_DIMA = 1, RS_DIMJ2 = 2, RS_NO_HOLD = 3, RS_CODE = 4 };
+
+ResolveBatchArgs resolve_args(enlsip_gn_handle hh, long long k0, long long cnt) {
+    const Plan& P = hh->plan;
+    const BatchOperands in = hh->last.slice(k0, cnt);
+    ResolveBatchArgs a{};
+    a.m = (int)P.m; a.n = (int)P.n; a.t = (int)P.t; a.kA = P.kA; a.ldw = P.ldw; a.ldr = P.ldr;
+    a.nv = (int)rup(std::max<long long>({P.n, P.t, 1}), 8);
+    a.blkd = 65 * (int)std::min<long long>(64, std::max<long long>({P.n, P.t, 1}));
+    a.tk = hh->h_tk.empty() ? nullptr : (const int*)hh->tkbuf.p + k0;
+    a.state = hh->state + k0;
+    a.cx = in.cx; a.scx = in.t; a.rx = in.rx;
+    a.FA = hh->FA + k0 * P.sFA; a.sFA = P.sFA; a.tauA = hh->tauA + k0 * P.sTauA; a.sTauA = P.sTauA;
+    a.jpvtA = hh->jpvtA + k0 * P.sJA; a.sJA = P.sJA;
+    a.FL = hh->FL + k0 * P.sFL; a.sFL = P.sFL; a.tauL = hh->tauL + k0 * P.sTauL; a.sTauL = P.sTauL;
+    a.jpvtL = hh->jpvtL + k0 * P.sJL; a.sJL = P.sJL;
+    a.qb = hh->cdist.valid ? hh->cdist.qb + k0 * hh->cdist.sQb : nullptr; a.sQb = hh->cdist.sQb;
+    a.p1 = hh->p1 + k0 * P.sP1; a.sP1 = P.sP1; a.bvec = hh->bvec + k0 * P.sB; a.sB = P.sB;
+    a.W = hh->W + k0 * P.sW; a.sW = P.sW; a.vec = hh->vec + k0 * P.sVec; a.sVec = P.sVec;
+    a.Rt = hh->Rt + k0 * P.sRt; a.sRt = P.sRt; a.tauJ = hh->tauJ + k0 * P.sTauJ; a.sTauJ = P.sTauJ;
+    a.jpvtJ = hh->jpvtJ + k0 * P.sJJ; a.sJJ = P.sJJ;
+    return a;
+}
+
+// Enqueues the re-solve of one segment on its handle's stream: one copy of the requests, then 4 launches plus one per
+// (panel, level) of the CAQR plan, whatever the segment's size.  dims: the requests of the segment's slots (host).
+int resolve_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDims* dims, const ResolveIO& io, bool small, bool b_only, bool prof) {
+    enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
+    const Plan& P = hh->plan;
+    const long long k0 = sg.k0, j0 = sg.j0, cnt = sg.cnt;
+    int rc = grow(hh, hh->rsb_dims, (size_t)cnt * sizeof(ResolveDims));
+    if (rc) return rc;
+    hipStream_t s = hh->stream;
+    ResolveDims* ddims = (ResolveDims*)hh->rsb_dims.p;
+    GN_HIP(hipMemcpyAsync(ddims, dims, (size_t)cnt * sizeof(ResolveDims), hipMemcpyHostToDevice, s));
+    ResolveBatchArgs a = resolve_args(hh, k0, cnt);
+    a.dims = ddims;
+    a.p_out = io.p ? io.p + j0 * P.n : nullptr;
+    a.b_out = (io.b && P.t > 0) ? io.b + j0 * P.t : nullptr;
+    a.d_out = io.d ? io.d + j0 * P.m : nullptr;
+    a.info_out = io.info ? io.info + j0 : nullptr;
+    a.status_out = io.status ? io.status + j0 : nullptr;
+    // the stages before the tail run for the slots that do not start from a held result
+    int kpmax = -1;
+    for (long long jj = 0; jj < cnt; ++jj) {
+        const ResolveDims& d = dims[jj];
+        if (d.code == 0 || d.status != 0 || d.dimA == RESOLVE_HOLD) continue;
+        kpmax = std::max(kpmax, hh->h_state[k0 + jj].kp);
+    }
+    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
+    const unsigned cn = (unsigned)cnt;
+    hh->rsb_timed = false;
+    if (kpmax >= 0) {
+        if (small) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, s, a);
+        else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, s, a);
+        // b_only (every request of the call stops at HOLD and no d is asked for): b and p1 are all there is to compute
+        if (!b_only) hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
+        const int npan = b_only ? 0 : (kpmax + PB - 1) / PB;
+        const bool timed = prof && npan > 0;       // HIP events around the Q0' launches (enlsip_gn_get_resolve_q0_ms)
+        if (timed) {
+            for (hipEvent_t& e : hh->rsb_ev)
+                if (!e) GN_HIP(hipEventCreate(&e));
+            GN_HIP(hipEventRecord(hh->rsb_ev[0], s));
+        }
+        hh->rsb_timed = timed;
+        for (int k = 0; k < npan; ++k)
+            for (const LevelPlan& L : P.panels[k].levels) {
+                CaqrArgs ca = caqr_args(hh, k, L);
+                ca.ext_cols = 1; ca.C = hh->vec; ca.sC = P.sVec; ca.prob0 = (int)k0;
+                if (P.F == 16) hipLaunchKernelGGL(k_caqr_vec_batched<4>, dim3(L.groups, cn), dim3(256), 0, s, ca, (const ResolveDims*)ddims);
+                else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, (const ResolveDims*)ddims);
+            }
+        if (timed) GN_HIP(hipEventRecord(hh->rsb_ev[1], s));
+        if (kpmax > 0 && !b_only) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
+    }
+    if (small) hipLaunchKernelGGL((k_resolve_tail<1, 64>), dim3(cn), dim3(64), lds, s, a);
+    else if (P.n <= 512) hipLaunchKernelGGL((k_resolve_tail<8, 256>), dim3(cn), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((k_resolve_tail<0, 256>), dim3(cn), dim3(256), lds, s, a);
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipMemcpyAsync(hh->h_state + k0, hh->state + k0, (size_t)cnt * sizeof(ProbState), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+// where a slot answered on its own lives
+struct AloneAt { enlsip_gn_handle hh = nullptr; long long k = 0; };
+
+int resolve_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* dimA, const int64_t* dimJ2, const int64_t* code,
+                const ResolveIO& io) {
+    if (!h) return -1;
+    std::vector<ResidentSeg> seg;
+    std::vector<long long> slots;
+    std::vector<AloneAt> alone;
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
+        if (!sg.alone) { seg.push_back(sg); return; }
+        if (alone.empty()) alone.resize((size_t)count);
+        for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) {
+            slots.push_back(j);
+            alone[(size_t)j] = {sg.hh, sg.k0 + (j - sg.j0)};
+        }
+    });
+    if (rc) return rc;
+    if (!dimA || !dimJ2 || !code) { h->err = "dimA, dimJ2 and code are host arrays of count entries"; return -4; }
+    for (const ResidentSeg& sg : seg) {
+        if (sg.hh->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+        if (!sg.hh->last.rx || (sg.hh->plan.t > 0 && !sg.hh->last.cx)) { h->err = "rx / cx of the last solve are not available"; return -1; }
+    }
+    const Plan& P = seg[0].hh->plan;
+    // per-problem validation (enlsip_gn_resolve's) on the host mirror of the state records
+    std::vector<ResolveDims> dims((size_t)count, ResolveDims{0, 0, 0, 0});
+    bool flagged = false;
+    for (const ResidentSeg& sg : seg) {
+        enlsip_gn_handle hh = sg.hh;
+        if (hh->held.size() < (size_t)hh->plan.batch) hh->held.resize((size_t)hh->plan.batch);
+        for (long long jj = 0; jj < sg.cnt; ++jj) {
+            const long long j = sg.j0 + jj, k = sg.k0 + jj;
+            if (!alone.empty() && alone[(size_t)j].hh) continue;       // left at code 0 here
+            if (code[j] == 0) continue;
+            const ProbState& st = hh->h_state[k];
+            const int tk = prob_t(hh, k);
+            ResolveDims d{(int)dimA[j], (int)dimJ2[j], (int)code[j], 0};
+            if (code[j] != 1 && code[j] != -1) d.status = RS_CODE;
+            else if (dimA[j] == ENLSIP_GN_DIM_HOLD) {
+                const auto& hd = hh->held[(size_t)k];
+                if (hd.code == 0) d.status = RS_NO_HOLD;
+                d.code = hd.code ? hd.code : d.code;
+            } else if (dimA[j] < 0 || dimA[j] > std::min<long long>(P.n, tk)) d.status = RS_DIMA;
+            else if (code[j] == 1 && st.rankA != tk) d.status = RS_CODE;
+            if (!d.status && dimJ2[j] != ENLSIP_GN_DIM_HOLD && (dimJ2[j] < 0 || dimJ2[j] > st.kp)) d.status = RS_DIMJ2;
+            flagged = flagged || d.status != 0;
+            dims[(size_t)j] = d;
+        }
+    }
+    GN_HIP(hipSetDevice(h->device));
+    const bool small = P.n <= 64 && P.t <= 64;
+    h->resolve_form = small ? 1 : 0;
+    // the first call of the reference's flow asks for b alone (:1251): no d pointer and every request held — F_J2.Q' is not applied
+    bool b_only = io.d == nullptr;
+    for (const ResolveDims& d : dims)
+        if (d.code != 0 && d.status == 0 && d.dimJ2 != RESOLVE_HOLD) b_only = false;
+    for (const ResidentSeg& sg : seg) {
+        if (sg.hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
+            if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+            GN_HIP(hipEventRecord(h->ev_fork, h->stream));
+            GN_HIP(hipStreamWaitEvent(sg.hh->stream, h->ev_fork, 0));
+        }
+        rc = resolve_launch(sg.hh, sg, dims.data() + sg.j0, io, small, b_only, h->profiling);
+        if (rc) {
+            if (sg.hh != h) h->err = sg.hh->err;
+            return rc;
+        }
+    }
+    h->resolve_q0_ms = 0.f;
+    for (const ResidentSeg& sg : seg) {
+        GN_HIP(hipStreamSynchronize(sg.hh->stream));
+        if (sg.hh->rsb_timed) {       // the halves fill the device one after the other: their Q0' times add up
+            float ms = 0.f;
+            GN_HIP(hipEventElapsedTime(&ms, sg.hh->rsb_ev[0], sg.hh->rsb_ev[1]));
+            h->resolve_q0_ms += ms;
+        }
+        for (long long jj = 0; jj < sg.cnt; ++jj) {      // which problems now hold p1 and Q3' d_temp for a later dimA = HOLD call
+            const ResolveDims& d = dims[(size_t)(sg.j0 + jj)];
+            if (d.code == 0 || d.status != 0 || d.dimA == RESOLVE_HOLD) continue;
+            auto& hd = sg.hh->held[(size_t)(sg.k0 + jj)];
+            if (d.dimJ2 == RESOLVE_HOLD && !b_only) hd = {d.code, d.dimA};
+            else hd = {};
+        }
+    }
+    // problems answered on their own (rescue handles): enlsip_gn_resolve; a held call is the re-solve with dimJ2 = 0, whose b and d
+    // are the held ones, and dimA = HOLD repeats the held dimA
+    if (!slots.empty()) {
+        std::vector<double> hp((size_t)P.n), hb((size_t)std::max<long long>(P.t, 1)), hd_((size_t)P.m);
+        for (long long j : slots) {
+            if (code[j] == 0) continue;
+            const AloneAt at = alone[(size_t)j];
+            if (at.hh->held.size() <= (size_t)at.k) at.hh->held.resize((size_t)at.k + 1);
+            const auto was = at.hh->held[(size_t)at.k];
+            long long dA = dimA[j], dJ = dimJ2[j], c = code[j];
+            int st = 0;
+            if (dA == ENLSIP_GN_DIM_HOLD) {
+                if (was.code == 0) st = RS_NO_HOLD;
+                dA = was.dimA; c = was.code;
+            }
+            const bool hold2 = dJ == ENLSIP_GN_DIM_HOLD;
+            if (!st) {
+                std::fill(hb.begin(), hb.end(), 0.0);
+                rc = enlsip_gn_resolve(h, prob0 + j, dA, hold2 ? 0 : dJ, c, hp.data(), hb.data(), hd_.data());
+                if (rc == -3) st = RS_DIMA;
+                else if (rc == -4) st = RS_DIMJ2;
+                else if (rc == -5) st = RS_CODE;
+                else if (rc) return rc;
+            }
+            if (!st) {
+                if (io.p && !hold2) GN_HIP(hipMemcpy(io.p + j * P.n, hp.data(), (size_t)P.n * 8, hipMemcpyHostToDevice));
+                if (io.b && P.t > 0) GN_HIP(hipMemcpy(io.b + j * P.t, hb.data(), (size_t)P.t * 8, hipMemcpyHostToDevice));
+                if (io.d) GN_HIP(hipMemcpy(io.d + j * P.m, hd_.data(), (size_t)P.m * 8, hipMemcpyHostToDevice));
+                if (io.info) {
+                    const enlsip_gn_info inf = info_of(at.hh->h_state[at.k]);
+                    GN_HIP(hipMemcpy(io.info + j, &inf, sizeof(inf), hipMemcpyHostToDevice));
+                }
+                if (hold2 && dimA[j] != ENLSIP_GN_DIM_HOLD && !b_only) at.hh->held[(size_t)at.k] = {(int)c, (int)dA};
+                else if (dimA[j] == ENLSIP_GN_DIM_HOLD) at.hh->held[(size_t)at.k] = was;
+            }
+            if (io.status) GN_HIP(hipMemcpy(io.status + j, &st, sizeof(int), hipMemcpyHostToDevice));
+            flagged = flagged || st != 0;
+        }
+    }
+    return flagged ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int enlsip_gn_resolve_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* dimA, const int64_t* dimJ2,
+                                  const int64_t* code, double* dp, double* db, double* dd, enlsip_gn_info* dinfo, int* dstatus) {
+    if (!h) return -1;
+    GN_TRY
+    return resolve_dev(h, prob0, count, dimA, dimJ2, code, {dp, db, dd, dinfo, dstatus});
+    GN_CATCH(h)
+}
+
+int enlsip_gn_resolve_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* dimA, const int64_t* dimJ2,
+                              const int64_t* code, double* p, double* b, double* d, enlsip_gn_info* info, int* status) {
+    if (!h) return -1;
+    GN_TRY
+    enlsip_gn_handle first = nullptr;
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) { if (!first) first = sg.hh; });
+    if (rc) return rc;
+    const Plan& P = first->plan;
+    const size_t c = (size_t)count;
+    // staged through a buffer of its own; the caller's arrays go in first so that the slots the call leaves alone come back as they were
+    const size_t n_p = p ? c * P.n : 0, n_b = b ? c * P.t : 0, n_d = d ? c * P.m : 0;
+    const size_t n_i = info ? c * sizeof(enlsip_gn_info) / 8 : 0, n_s = status ? c : 0;
+    GN_HIP(hipSetDevice(h->device));
+    rc = grow(h, h->rsb_io, (n_p + n_b + n_d + n_i + n_s + 8) * 8);
+    if (rc) return rc;
+    double* d_p = (double*)h->rsb_io.p;
+    double* d_b = d_p + n_p;
+    double* d_d = d_b + n_b;
+    enlsip_gn_info* d_i = (enlsip_gn_info*)(d_d + n_d);
+    int* d_s = (int*)((double*)d_i + n_i);
+    hipStream_t s = h->stream;
+    if (n_p) GN_HIP(hipMemcpyAsync(d_p, p, n_p * 8, hipMemcpyHostToDevice, s));
+    if (n_b) GN_HIP(hipMemcpyAsync(d_b, b, n_b * 8, hipMemcpyHostToDevice, s));
+    if (n_d) GN_HIP(hipMemcpyAsync(d_d, d, n_d * 8, hipMemcpyHostToDevice, s));
+    if (n_i) GN_HIP(hipMemcpyAsync(d_i, info, n_i * 8, hipMemcpyHostToDevice, s));
+    if (n_s) GN_HIP(hipMemcpyAsync(d_s, status, n_s * sizeof(int), hipMemcpyHostToDevice, s));
+    rc = resolve_dev(h, prob0, count, dimA, dimJ2, code,
+                     {n_p ? d_p : nullptr, n_b ? d_b : nullptr, n_d ? d_d : nullptr, n_i ? d_i : nullptr, n_s ? d_s : nullptr});
+    if (rc < 0 || rc > 1) return rc;
+    if (n_p) GN_HIP(hipMemcpyAsync(p, d_p, n_p * 8, hipMemcpyDeviceToHost, s));
+    if (n_b) GN_HIP(hipMemcpyAsync(b, d_b, n_b * 8, hipMemcpyDeviceToHost, s));
+    if (n_d) GN_HIP(hipMemcpyAsync(d, d_d, n_d * 8, hipMemcpyDeviceToHost, s));
+    if (n_i) GN_HIP(hipMemcpyAsync(info, d_i, n_i * 8, hipMemcpyDeviceToHost, s));
+    if (n_s) GN_HIP(hipMemcpyAsync(status, d_s, n_s * sizeof(int), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipStreamSynchronize(s));
+    return rc;
+    GN_CATCH(h)
+}
+
+int enlsip_gn_get_diagR_batched(enlsip_gn_handle h, int which, int64_t prob0, int64_t count, double* diag, int64_t stride) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<ResidentSeg> seg;
+    std::vector<long long> slots;
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
+        if (!sg.alone) seg.push_back(sg);
+        else for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) slots.push_back(j);
+    });
+    if (rc) return rc;
+    if (which != ENLSIP_GN_FACTOR_A && which != ENLSIP_GN_FACTOR_L11 && which != ENLSIP_GN_FACTOR_J2) { h->err = "bad factor selector"; return -2; }
+    if (!diag) { h->err = "diag is NULL"; return -5; }
+    const Plan& P = seg[0].hh->plan;
+    long long need = which == ENLSIP_GN_FACTOR_J2 ? 0 : std::min(P.n, P.t);
+    for (const ResidentSeg& sg : seg) {
+        if (which == ENLSIP_GN_FACTOR_J2 && sg.hh->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+        if (which == ENLSIP_GN_FACTOR_J2)
+            for (long long k = sg.k0; k < sg.k0 + sg.cnt; ++k) need = std::max<long long>(need, sg.hh->h_state[k].kp);
+    }
+    if (stride < need || stride < 1) { h->err = "stride is smaller than the longest diagonal of the range"; return -6; }
+    GN_HIP(hipSetDevice(h->device));
+    for (const ResidentSeg& sg : seg) {
+        enlsip_gn_handle hh = sg.hh;
+        rc = grow(hh, hh->rsb_io, (size_t)sg.cnt * stride * 8);
+        if (rc) { h->err = hh->err; return rc; }
+        const ResolveBatchArgs a = resolve_args(hh, sg.k0, sg.cnt);
+        hipLaunchKernelGGL(k_diag_gather, dim3((unsigned)sg.cnt), dim3(64), 0, hh->stream, a, which, (double*)hh->rsb_io.p, (long long)stride);
+        GN_HIP(hipGetLastError());
+        GN_HIP(hipMemcpyAsync(diag + sg.j0 * stride, hh->rsb_io.p, (size_t)sg.cnt * stride * 8, hipMemcpyDeviceToHost, hh->stream));
+    }
+    for (const ResidentSeg& sg : seg) GN_HIP(hipStreamSynchronize(sg.hh->stream));
+    for (long long j : slots) {      // answered on their own
+        std::fill(diag + j * stride, diag + (j + 1) * stride, 0.0);
+        int64_t r = 0, c = 0;
+        rc = enlsip_gn_factor_shape(h, which, prob0 + j, &r, &c);
+        if (rc) return rc;
+        if (std::min(r, c) > stride) { h->err = "stride is smaller than the longest diagonal of the range"; return -6; }
+        rc = enlsip_gn_get_diagR(h, which, prob0 + j, diag + j * stride);
+        if (rc) return rc;
+    }
+    return 0;
+    GN_CATCH(h)
+}
+
+int enlsip_gn_get_resolve_q0_ms(enlsip_gn_handle h, float* ms) {
+    if (!h) return -1;
+    if (!ms) { h->err = "ms is NULL"; return -2; }
+    *ms = h->resolve_q0_ms;
+    return 0;
+}
+
+int enlsip_gn_get_resolve_form(enlsip_gn_handle h, int* form) {
+    if (!h) return -1;
+    if (!form) { h->err = "form is NULL"; return -2; }
+    *form = h->resolve_form;
+    return 0;
+}
+
+}  // extern "C"

@@ -182,6 +182,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     hipStream_t s = h->stream;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
+    h->held.clear();
     h->last = {1, m_loc, n, t, dJ, ldj, 0, drx, dAt, ldat, 0, dcx};
     // same routing as a solve (register / distributed forms of F_A for the shapes that need them)
     h->sc_eJ = 0; h->sc_eA = 0;          // row shards are not rescaled (include/enlsip_gn.h: magnitude range of the TSQR entry points)
@@ -477,6 +478,7 @@ int enlsip_gn_solve_tsqr(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t
         GN_HIP(hipEventElapsedTime(&ms, ev[6], ev[7])); h->tsqr_ms[1] = ms;
         GN_HIP(hipEventElapsedTime(&ms, ev[7], ev[4])); h->tsqr_ms[2] = ms;
     }
+    h->held.clear();
     h->factors_valid = false;       // the resident pieces are those of a row shard, not of a whole problem
     return 0;
     GN_CATCH(h)

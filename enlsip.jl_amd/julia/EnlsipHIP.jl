@@ -473,6 +473,43 @@ function consumer_form_hip(h::Handle)
     return Int(f[])
 end
 
+const DIM_HOLD = Int64(-2)      # ENLSIP_GN_DIM_HOLD
+
+"""    sub_search_direction_batched_hip(h, m, n, t_max, prob0, dimA, dimJ2, code) -> (P, b, d, infos, status)
+
+`sub_search_direction` (src/enlsip_functions.jl:116-153, called at :1253) of problems `prob0 .. prob0 + length(code) - 1` on the
+resident factors, one call.  `code[j]` = 1 / -1, 0 leaves the problem alone (its columns stay NaN); `dimJ2[j] == DIM_HOLD` stops
+after b (:1251) and d (:1156-1163), `dimA[j] == DIM_HOLD` finishes such a held call with `dimJ2[j]`: the three-call flow of
+search_direction_analys (:1249-1253) around choose_subspace_dimensions (:1118-1176).  status: 0, 1 dimA, 2 dimJ2 out of range,
+3 no held result, 4 code."""
+function sub_search_direction_batched_hip(h::Handle, m::Integer, n::Integer, t_max::Integer, prob0::Integer,
+                                          dimA::Vector{Int64}, dimJ2::Vector{Int64}, code::Vector{Int64})
+    count = length(code)
+    (length(dimA) == count && length(dimJ2) == count) || error("dimA, dimJ2 and code must have the same length")
+    P = fill(NaN, n, count); b = fill(NaN, max(t_max, 1), count); d = fill(NaN, m, count)
+    infos = fill(Info(0, 0, 0, 0, 0, 0), count); st = fill(Cint(-1), count)
+    GC.@preserve dimA dimJ2 code P b d infos st batched_check(h, ccall((:enlsip_gn_resolve_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Info}, Ptr{Cint}),
+        h.ptr, prob0, count, dimA, dimJ2, code, P, b, d, infos, st))
+    return P, b[1:t_max, :], d, infos, st
+end
+
+"""    diagR_batched_hip(h, which, stride, prob0, count) -> D (stride×count): diag(F.R) of every problem of the range, zeros past
+each problem's own length — what choose_subspace_dimensions reads (src/enlsip_functions.jl:1118-1176)"""
+function diagR_batched_hip(h::Handle, which::Integer, stride::Integer, prob0::Integer, count::Integer)
+    D = zeros(Float64, max(stride, 1), count)
+    GC.@preserve D check(h, ccall((:enlsip_gn_get_diagR_batched, LIB), Cint, (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Float64}, Int64),
+                                  h.ptr, which, prob0, count, D, max(stride, 1)))
+    return D
+end
+
+"""    resolve_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last batched re-solve on `h`"""
+function resolve_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_resolve_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

@@ -14,6 +14,7 @@ LIB_PATH = Path(os.environ.get("ENLSIP_GN_LIB", _PKG_ROOT / "lib" / "libenlsip_g
 
 FACTOR_A, FACTOR_L11, FACTOR_J2 = 0, 1, 2
 FLAG_UPDATE_MFMA, FLAG_UPDATE_REFLECTORS = 1, 2
+DIM_HOLD = -2            # ENLSIP_GN_DIM_HOLD: the held forms of resolve_batched
 STAGE_NAMES = ("constraint", "jq1", "panel", "update", "pivot", "total")
 
 
@@ -92,6 +93,13 @@ PROTOTYPES = {
     "enlsip_gn_second_lagrange_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
                                                         C.c_void_p]),
     "enlsip_gn_get_consumer_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_resolve_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_resolve_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_diagR_batched": (C.c_int, [_h, C.c_int, _i64, _i64, C.c_void_p, _i64]),
+    "enlsip_gn_get_resolve_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_get_resolve_q0_ms": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_tsqr_local_dev": (C.c_int, [_h, _i64, _i64, _i64, C.c_void_p, _i64, C.c_void_p, C.c_void_p, _i64,
                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, _dp, _ip]),

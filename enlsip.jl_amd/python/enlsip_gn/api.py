@@ -418,6 +418,73 @@ class GNSolver:
         self._chk(self._lib.enlsip_gn_get_consumer_form(self._h, C.byref(f)))
         return int(f.value)
 
+    # ---- the subspace re-solve over a range of the resident batch (src/enlsip_functions.jl:1249-1253, :1118-1176, :116-153) ------
+    @staticmethod
+    def pack_resolve(count: int, dimA, dimJ2, code=-1):
+        """The three host request arrays of resolve_batched (int64, count entries each) from scalars or sequences.  code 0 leaves a
+        problem alone; DIM_HOLD in dimJ2 stops after b and d, DIM_HOLD in dimA starts from the result such a call left."""
+        def arr(x, name):
+            a = np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.int64), (count,))).copy()
+            if a.shape != (count,):
+                raise ValueError(f"pack_resolve: {name} must have {count} entries")
+            return a
+        dA, dJ, cd = arr(dimA, "dimA"), arr(dimJ2, "dimJ2"), arr(code, "code")
+        if np.any((cd != 0) & (cd != 1) & (cd != -1)):
+            raise ValueError("pack_resolve: code entries are 1, -1 or 0 (leave the problem alone)")
+        return dA, dJ, cd
+
+    @staticmethod
+    def resolve_outputs(count: int, m: int, n: int, t_max: int, fill: float = np.nan, want=("p", "b", "d", "info", "status")):
+        """Output arrays of resolve_batched in its slot layout: p (count, n), b (count, t_max), d (count, m), info (count, 6) int64
+        (rankA, rankJ2, code, dimA, dimJ2, status), status (count,) int32.  Slots of problems the call leaves alone keep `fill`
+        (info and status: -1).  An output not named in `want` is None (a NULL pointer: not computed into)."""
+        return {
+            "p": np.full((count, n), fill) if "p" in want else None,
+            "b": np.full((count, t_max), fill) if "b" in want else None,
+            "d": np.full((count, m), fill) if "d" in want else None,
+            "info": np.full((count, 6), -1, dtype=np.int64) if "info" in want else None,
+            "status": np.full(count, -1, dtype=np.int32) if "status" in want else None,
+        }
+
+    def resolve_batched(self, m: int, n: int, t_max: int, dimA, dimJ2, code=-1, prob0: int = 0, count: Optional[int] = None,
+                        want=("p", "b", "d", "info", "status"), out: Optional[dict] = None):
+        """sub_search_direction per problem of prob0 .. prob0+count-1 on the resident factors, one call.  Returns
+        (out, rc): out as resolve_outputs, rc 0 or 1 (some status non-zero)."""
+        if count is None:
+            count = len(np.atleast_1d(np.asarray(code if np.ndim(code) else dimA)))
+        dA, dJ, cd = self.pack_resolve(count, dimA, dimJ2, code)
+        o = out if out is not None else self.resolve_outputs(count, m, n, t_max, want=want)
+        rc = self._chk_batched(self._lib.enlsip_gn_resolve_batched(
+            self._h, prob0, count, _fptr(dA), _fptr(dJ), _fptr(cd), _fptr(o["p"]), _fptr(o["b"]), _fptr(o["d"]),
+            _fptr(o["info"]), _fptr(o["status"])))
+        return o, rc
+
+    def resolve_batched_dev(self, prob0: int, count: int, dimA, dimJ2, code=-1, dp: int = 0, db: int = 0, dd: int = 0,
+                            dinfo: int = 0, dstatus: int = 0) -> int:
+        """Device form: dimA / dimJ2 / code stay host arrays, the outputs are raw device pointers (0 = NULL)."""
+        v = lambda x: C.c_void_p(x) if x else None
+        dA, dJ, cd = self.pack_resolve(count, dimA, dimJ2, code)
+        return self._chk_batched(self._lib.enlsip_gn_resolve_batched_dev(
+            self._h, prob0, count, _fptr(dA), _fptr(dJ), _fptr(cd), v(dp), v(db), v(dd), v(dinfo), v(dstatus)))
+
+    def diagR_batched(self, which: int, stride: int, prob0: int = 0, count: int = 1) -> np.ndarray:
+        """diag(F.R) of problems prob0 .. prob0+count-1: (count, stride), zeros past each problem's own length."""
+        out = np.zeros((count, max(stride, 1)))
+        self._chk(self._lib.enlsip_gn_get_diagR_batched(self._h, which, prob0, count, _fptr(out), max(stride, 1)))
+        return out
+
+    def resolve_form(self) -> int:
+        """Kernel form of the last resolve_batched: 0 general, 1 one wave per problem, -1 none yet."""
+        f = C.c_int(0)
+        self._chk(self._lib.enlsip_gn_get_resolve_form(self._h, C.byref(f)))
+        return int(f.value)
+
+    def resolve_q0_ms(self) -> float:
+        """HIP-event time of the Q0' launches of the last resolve_batched (set_profiling(True) before it; 0 otherwise)."""
+        ms = C.c_float(0.0)
+        self._chk(self._lib.enlsip_gn_get_resolve_q0_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).
         Returns (p, error) as the reference does (error = True: W22 not positive definite, p = 0)."""

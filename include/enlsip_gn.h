@@ -297,6 +297,55 @@ int enlsip_gn_second_lagrange_batched_dev(enlsip_gn_handle h, int64_t prob0, int
 /* form of the last batched multiplier estimate on this handle: 0 general, 1 wave per problem, -1 none yet */
 int enlsip_gn_get_consumer_form(enlsip_gn_handle h, int* form);
 
+/* ---- the subspace re-solve over a range of the resident batch ----------------------------------------------------------------
+ * search_direction_analys inspects the Gauss-Newton direction of every problem on every outer iteration; where
+ * check_gn_direction asks for subspace minimisation it computes b = F_L11.Q' * (-cx[F_A.p]) (src/enlsip_functions.jl:1249-1253),
+ * lets choose_subspace_dimensions (src/enlsip_functions.jl:1118-1176) pick dimA from b and diag(F_L11.R), form
+ * d = F_J2.Q' * (-(rx + J1*p1(dimA))) (:1156-1163) and pick dimJ2 from d and diag(F_J2.R), and calls sub_search_direction
+ * (src/enlsip_functions.jl:116-153) with them (:1253).  These forms do that for problems prob0 .. prob0+count-1 in a number of
+ * launches and synchronisations that does not depend on count; nothing is factored again (F_A, F_L11, F_J2, their pivots and T
+ * blocks are not rewritten).  Slot j is problem prob0 + j; strides are those of enlsip_gn_solve_batched with t = t_max:
+ * p n, b t_max (zero past a ragged problem's t[k]), d m, info and status 1.  dimA, dimJ2, code are HOST arrays of count entries in
+ * both forms (host bookkeeping, like t of the ragged solve); any output pointer may be NULL.
+ *
+ * enlsip_gn_resolve_batched*   per problem what enlsip_gn_resolve(h, prob0 + j, dimA[j], dimJ2[j], code[j], ...) computes:
+ *     sub_search_direction    src/enlsip_functions.jl:116-153 (called at :1253), with
+ *     code[j] = 1 or -1;  code[j] = 0 leaves the problem alone: none of its output slots is written, its state is untouched.
+ *     dimJ2[j] = ENLSIP_GN_DIM_HOLD   b (:1251) and d = F_J2.Q' d_temp (:1156-1163) only: b and d are written, p is not, and b,
+ *                             p1 and F_J2.Q' d_temp stay resident for the form below.  When every request of a call is
+ *                             held and d is NULL, b alone is computed (F_J2.Q' is not applied) and nothing is held.
+ *     dimA[j]  = ENLSIP_GN_DIM_HOLD   the rest alone: the triangular solve with dimJ2[j], the scatter and p = F_A.Q [p1; p2] on the
+ *                             held p1 and d (code and dimA are the held call's; code[j] only has to be non-zero).
+ *     Together: code = -1, dimA = rankA, dimJ2 = HOLD gives b (:1251); dimA chosen, dimJ2 = HOLD gives d (:1162);
+ *     dimA = HOLD, dimJ2 chosen gives p (:1253) — one F_J2.Q' application per problem where the reference's literal flow has two.
+ *   status[j] (written for code[j] != 0): 0; 1 dimA outside 0..min(n, t[k]); 2 dimJ2 outside 0..min(m, n - rankA);
+ *     3 dimA = HOLD without a held result (a solve, enlsip_gn_resolve, apply_q / apply_qt on F_J2 or a call without HOLD on that
+ *     problem came in between); 4 code not 1 / -1 / 0, or code 1 with rankA < t[k].  A flagged problem is skipped.
+ *   Returns 0, 1 when some problem is flagged; negative: -1 no resident factors (also after enlsip_gn_factor_constraints),
+ *     -2 count < 1, -3 the range leaves the resident batch or reaches into an earlier chunk of a batch above the launch limit,
+ *     -4 dimA, dimJ2 or code is NULL.
+ *   Afterwards the resident p1, b, state record and enlsip_gn_info of a re-solved problem are what enlsip_gn_resolve leaves, so
+ *   enlsip_gn_second_lagrange, enlsip_gn_newton_direction and a later enlsip_gn_resolve behave the same.  Results agree with
+ *   enlsip_gn_resolve to rounding (other summation order in F_J2.Q'; p1 is not recomputed by a factorisation).  The range may
+ *   straddle the pipelined halves; problems on a rescue handle are answered by enlsip_gn_resolve.  The _dev form takes DEVICE
+ *   output buffers and returns after one synchronisation of each stream that ran a part of the range.
+ * enlsip_gn_get_diagR_batched  diag(F.R) of every problem of the range, what choose_subspace_dimensions reads
+ *     (src/enlsip_functions.jl:1118-1176: diag(F_L11.R), diag(F_J2.R)): HOST array, `stride` doubles per slot, zeros past each
+ *     problem's own length; -6 when stride is smaller than the longest diagonal of the range.
+ * enlsip_gn_get_resolve_form   kernel form of the last enlsip_gn_resolve_batched* on this handle: 0 general (a workgroup per
+ *     problem), 1 one wave per problem (n <= 64 and t_max <= 64), -1 none yet.
+ */
+enum { ENLSIP_GN_DIM_HOLD = -2 };
+int enlsip_gn_resolve_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* dimA, const int64_t* dimJ2,
+                              const int64_t* code, double* p, double* b, double* d, enlsip_gn_info* info, int* status);
+int enlsip_gn_resolve_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* dimA, const int64_t* dimJ2,
+                                  const int64_t* code, double* dp, double* db, double* dd, enlsip_gn_info* dinfo, int* dstatus);
+int enlsip_gn_get_diagR_batched(enlsip_gn_handle h, int which, int64_t prob0, int64_t count, double* diag, int64_t stride);
+int enlsip_gn_get_resolve_form(enlsip_gn_handle h, int* form);
+/* HIP-event time (ms) of the F_J2.Q0' launches of the last enlsip_gn_resolve_batched* on this handle, summed over the pipelined
+ * halves that ran a part of the range; 0 unless enlsip_gn_set_profiling was on (the events add stream bubbles) */
+int enlsip_gn_get_resolve_q0_ms(enlsip_gn_handle h, float* ms);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
