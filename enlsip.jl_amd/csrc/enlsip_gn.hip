@@ -28,6 +28,7 @@
 #include "gn_kernels_lagrange_batched.hpp"
 #include "gn_kernels_resolve_batched.hpp"
 #include "gn_kernels_newton.hpp"
+#include "gn_kernels_newton_batched.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
 #include "gn_kernels_qrcp_block.hpp"
 #include "gn_kernels_qrcp_block_reg.hpp"
@@ -1430,6 +1431,11 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->rsb_io.p) (void)hipFree(h->rsb_io.p);
     for (hipEvent_t e : h->rsb_ev)
         if (e) (void)hipEventDestroy(e);
+    if (h->nwb_ws.p) (void)hipFree(h->nwb_ws.p);
+    if (h->nwb_io.p) (void)hipFree(h->nwb_io.p);
+    if (h->h_nwflag) (void)hipHostFree(h->h_nwflag);
+    for (hipEvent_t e : h->nwb_ev)
+        if (e) (void)hipEventDestroy(e);
     if (h->h_lagflag) (void)hipHostFree(h->h_lagflag);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);
@@ -1919,3 +1925,4 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_lagrange_batched.inc"
 #include "gn_resolve_batched.inc"
 #include "gn_newton.inc"
+#include "gn_newton_batched.inc"

@@ -193,6 +193,14 @@ struct enlsip_gn_context {
     float resolve_q0_ms = 0.f;          // ... summed over the handles that ran a part of the range
     struct Held { int code = 0, dimA = 0; };
     std::vector<Held> held;
+    // batched Newton direction (gn_newton_batched.inc): device temporaries of a segment, staging of the host-buffer form, the form of
+    // the last call, HIP events around its four stages (profiling on) and their times summed over the handles that ran a part
+    gn::DevBuf nwb_ws, nwb_io;
+    int* h_nwflag = nullptr;            // pinned "some slot flagged" word of the last launch on this handle
+    int newton_form = -1;
+    hipEvent_t nwb_ev[5] = {};
+    bool nwb_timed = false;
+    float newton_ms[4] = {};
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

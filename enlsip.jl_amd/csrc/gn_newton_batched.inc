@@ -1,0 +1,270 @@
+// Batched Newton direction over a contiguous range of the resident batch (kernels: gn_kernels_newton_batched.hpp): what
+// newton_search_direction does per problem at src/enlsip_functions.jl:371-421 after its Hessian sums, in a number of launches and
+// synchronisations that does not depend on the size of the range.  Routing as the batched re-solve (gn_resolve_batched.inc).
+// Included at the end of enlsip_gn.hip, after gn_newton.inc.
+
+namespace {
+
+struct NewtonIO {        // device buffers, slot 0 = problem prob0
+    const double* Gamma; long long ldg, strideG;
+    double* p;
+    int* status;         // may be null
+};
+
+enum { NW_SKIP = 0, NW_TAKE = 1, NW_RANKDEF = 2 };
+
+// Enqueues the step of one segment on its handle's stream: one copy of the requests, one copy of the state records, the
+// b / p1 / d stages of the batched re-solve with the DEFAULT dimensions (dimA = rankA) into the call's own vec, then 4 launches.
+// req: the requests of the segment's slots (host).  pack: host image of the request copy, owned by the caller so that it outlives
+// the copy.  The segment's "some slot flagged" word lands in the handle's pinned h_nwflag.
+int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, const NewtonIO& io, bool small, bool prof, std::vector<int>& pack) {
+    enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
+    const Plan& P = hh->plan;
+    const long long k0 = sg.k0, j0 = sg.j0, cnt = sg.cnt;
+    const int n = (int)P.n;
+    const size_t nn = (size_t)n * n;
+    // workspace: X nn | E nn | rhs n per slot, vec sVec per slot, state records, status, requests (ResolveDims | req | flag)
+    const size_t dbl = (size_t)cnt * (2 * nn + n + (size_t)P.sVec);
+    const size_t st_b = (size_t)rup(cnt * (long long)sizeof(ProbState), 8), su_b = (size_t)rup(cnt * (long long)sizeof(int), 8);
+    const size_t rq_b = (size_t)cnt * (sizeof(ResolveDims) + sizeof(int)) + sizeof(int);
+    int rc = grow(hh, hh->nwb_ws, dbl * 8 + st_b + su_b + rq_b + 64);
+    if (rc) return rc;
+    if (!hh->h_nwflag) GN_HIP(hipHostMalloc((void**)&hh->h_nwflag, sizeof(int), hipHostMallocDefault));
+    double* dX = (double*)hh->nwb_ws.p;
+    double* dE = dX + (size_t)cnt * nn;
+    double* drhs = dE + (size_t)cnt * nn;
+    double* dvec = drhs + (size_t)cnt * n;
+    ProbState* dst = (ProbState*)(dvec + (size_t)cnt * P.sVec);
+    int* dstatus = (int*)((char*)dst + st_b);
+    ResolveDims* ddims = (ResolveDims*)((char*)dstatus + su_b);
+    int* dreq = (int*)(ddims + cnt);
+    int* dflag = dreq + cnt;
+    hipStream_t s = hh->stream;
+
+    // requests: the re-solve's record with the default dimensions for the slots that take the step
+    pack.assign((size_t)cnt * 5 + 1, 0);
+    ResolveDims* hd = (ResolveDims*)pack.data();
+    int kpmax = -1;
+    for (long long jj = 0; jj < cnt; ++jj) {
+        pack[(size_t)cnt * 4 + jj] = req[jj];
+        if (req[jj] != NW_TAKE) continue;
+        const ProbState& st = hh->h_state[k0 + jj];
+        hd[jj] = {st.rankA, RESOLVE_HOLD, st.rankA == prob_t(hh, k0 + jj) ? 1 : -1, 0};
+        kpmax = std::max(kpmax, st.kp);
+    }
+    GN_HIP(hipMemcpyAsync(ddims, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    GN_HIP(hipMemcpyAsync(dst, hh->state + k0, (size_t)cnt * sizeof(ProbState), hipMemcpyDeviceToDevice, s));
+    const unsigned cn = (unsigned)cnt;
+    const bool timed = prof;
+    if (timed) {
+        for (hipEvent_t& e : hh->nwb_ev)
+            if (!e) GN_HIP(hipEventCreate(&e));
+        GN_HIP(hipEventRecord(hh->nwb_ev[0], s));
+    }
+    hh->nwb_timed = timed;
+    if (kpmax >= 0) {
+        // b, p1 (resident, as the per-problem entry point leaves them) and d = F_J2.Q' d_temp (the call's own vec); the state
+        // records the head stage writes are the copy's, so the resident ones stay what they were (the per-problem call restores them)
+        ResolveBatchArgs a = resolve_args(hh, k0, cnt);
+        a.dims = ddims;
+        a.state = dst;
+        a.vec = dvec;
+        const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
+        if (small && P.t <= 64) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, s, a);
+        else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, s, a);
+        hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
+        const int npan = (kpmax + PB - 1) / PB;
+        for (int k = 0; k < npan; ++k)
+            for (const LevelPlan& L : P.panels[k].levels) {
+                CaqrArgs ca = caqr_args(hh, k, L);
+                ca.ext_cols = 1; ca.C = dvec - k0 * P.sVec; ca.sC = P.sVec; ca.prob0 = (int)k0;
+                if (P.F == 16) hipLaunchKernelGGL(k_caqr_vec_batched<4>, dim3(L.groups, cn), dim3(256), 0, s, ca, (const ResolveDims*)ddims);
+                else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, (const ResolveDims*)ddims);
+            }
+        if (kpmax > 0) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
+    }
+    if (timed) GN_HIP(hipEventRecord(hh->nwb_ev[1], s));
+    NewtonBatchArgs a{};
+    a.n = n; a.t = (int)P.t; a.kA = P.kA; a.ldr = P.ldr;
+    a.req = dreq;
+    a.tk = hh->h_tk.empty() ? nullptr : (const int*)hh->tkbuf.p + k0;
+    a.state = hh->state + k0;
+    a.FA = hh->FA + k0 * P.sFA; a.sFA = P.sFA; a.tauA = hh->tauA + k0 * P.sTauA; a.sTauA = P.sTauA;
+    a.jpvtL = hh->jpvtL + k0 * P.sJL; a.sJL = P.sJL;
+    a.p1 = hh->p1 + k0 * P.sP1; a.sP1 = P.sP1;
+    a.vec = dvec; a.sVec = P.sVec;
+    a.Rt = hh->Rt + k0 * P.sRt; a.sRt = P.sRt; a.jpvtJ = hh->jpvtJ + k0 * P.sJJ; a.sJJ = P.sJJ;
+    a.Gamma = io.Gamma + j0 * io.strideG; a.ldg = io.ldg; a.strideG = io.strideG;
+    a.X = dX; a.sX = (long long)nn; a.E = dE; a.rhs = drhs;
+    a.p_out = io.p + j0 * n;
+    a.status_out = io.status ? io.status + j0 : dstatus;
+    a.flag = dflag;
+    const unsigned nvb = (unsigned)((n + NWB_VEC - 1) / NWB_VEC), nt = (unsigned)((n + 15) / 16);
+    const size_t slds = newton_side_lds(n);
+    if (kpmax >= 0) {
+        GN_LAUNCH_BIG(k_newton_side<false>, dim3(nvb, cn), dim3(256), slds, s, a);
+        GN_LAUNCH_BIG(k_newton_side<true>, dim3(nvb, cn), dim3(256), slds, s, a);
+    }
+    if (timed) GN_HIP(hipEventRecord(hh->nwb_ev[2], s));
+    if (kpmax >= 0) hipLaunchKernelGGL(k_newton_w22, dim3(nt * nt + (unsigned)((n + 63) / 64), cn), dim3(64), 0, s, a);
+    if (timed) GN_HIP(hipEventRecord(hh->nwb_ev[3], s));
+    if (small) hipLaunchKernelGGL(k_newton_chol_batched<64>, dim3(cn), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_newton_chol_batched<256>, dim3(cn), dim3(256), 0, s, a);
+    if (timed) GN_HIP(hipEventRecord(hh->nwb_ev[4], s));
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipMemcpyAsync(hh->h_nwflag, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+int newton_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const NewtonIO& io, const int64_t* take) {
+    if (!h) return -1;
+    std::vector<ResidentSeg> seg;
+    std::vector<long long> slots;
+    std::vector<AloneAt> alone;
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
+        if (!sg.alone) { seg.push_back(sg); return; }
+        if (alone.empty()) alone.resize((size_t)count);
+        for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) {
+            slots.push_back(j);
+            alone[(size_t)j] = {sg.hh, sg.k0 + (j - sg.j0)};
+        }
+    });
+    if (rc) return rc;
+    for (const ResidentSeg& sg : seg) {
+        if (sg.hh->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+        if (!sg.hh->last.rx || (sg.hh->plan.t > 0 && !sg.hh->last.cx)) { h->err = "rx / cx of the last solve are not available"; return -1; }
+    }
+    const Plan& P = seg[0].hh->plan;
+    if (!io.Gamma) { h->err = "Gamma is NULL"; return -4; }
+    if (!io.p) { h->err = "p is NULL"; return -4; }
+    if (io.ldg < P.n) { h->err = "ldg < n"; return -5; }
+    if (io.strideG < io.ldg * P.n) { h->err = "strideG < ldg * n"; return -5; }
+    for (const ResidentSeg& sg : seg)
+        if (P.t > 0 && sg.hh->cdist.valid) { h->err = "newton direction after the distributed constraint stage is not supported"; return -7; }
+    // per-problem validation (enlsip_gn_newton_direction's) on the host mirror of the state records
+    std::vector<int> req((size_t)count, NW_SKIP);
+    for (const ResidentSeg& sg : seg)
+        for (long long jj = 0; jj < sg.cnt; ++jj) {
+            const long long j = sg.j0 + jj, k = sg.k0 + jj;
+            if (!alone.empty() && alone[(size_t)j].hh) continue;       // answered on its own below
+            if (take && take[j] == 0) continue;
+            const int tk = prob_t(sg.hh, k);
+            req[(size_t)j] = (tk != sg.hh->h_state[k].rankA && tk < P.n) ? NW_RANKDEF : NW_TAKE;
+        }
+    GN_HIP(hipSetDevice(h->device));
+    const bool small = P.n <= 64;
+    h->newton_form = small ? 1 : 0;
+    std::vector<std::vector<int>> packs(seg.size());      // alive until the streams are synchronised
+    for (size_t i = 0; i < seg.size(); ++i) {
+        const ResidentSeg& sg = seg[i];
+        if (sg.hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
+            if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+            GN_HIP(hipEventRecord(h->ev_fork, h->stream));
+            GN_HIP(hipStreamWaitEvent(sg.hh->stream, h->ev_fork, 0));
+        }
+        rc = newton_launch(sg.hh, sg, req.data() + sg.j0, io, small, h->profiling, packs[i]);
+        if (rc) {
+            if (sg.hh != h) h->err = sg.hh->err;
+            return rc;
+        }
+    }
+    bool flagged = false;
+    for (float& ms : h->newton_ms) ms = 0.f;
+    for (size_t i = 0; i < seg.size(); ++i) {
+        const ResidentSeg& sg = seg[i];
+        GN_HIP(hipStreamSynchronize(sg.hh->stream));
+        flagged = flagged || *sg.hh->h_nwflag != 0;
+        if (sg.hh->nwb_timed)
+            for (int e = 0; e < 4; ++e) {
+                float ms = 0.f;
+                GN_HIP(hipEventElapsedTime(&ms, sg.hh->nwb_ev[e], sg.hh->nwb_ev[e + 1]));
+                h->newton_ms[e] += ms;
+            }
+        // the resident p1 is the default one again: a result held for dimA = HOLD is gone
+        for (long long jj = 0; jj < sg.cnt; ++jj)
+            if (req[(size_t)(sg.j0 + jj)] == NW_TAKE && sg.hh->held.size() > (size_t)(sg.k0 + jj)) sg.hh->held[(size_t)(sg.k0 + jj)] = {};
+    }
+    // problems answered on their own (rescue handles): enlsip_gn_newton_direction
+    if (!slots.empty()) {
+        std::vector<double> hG((size_t)P.n * P.n), hp((size_t)P.n);
+        for (long long j : slots) {
+            if (take && take[j] == 0) continue;
+            GN_HIP(hipMemcpy2D(hG.data(), (size_t)P.n * 8, io.Gamma + j * io.strideG, (size_t)io.ldg * 8, (size_t)P.n * 8, (size_t)P.n,
+                               hipMemcpyDeviceToHost));
+            int64_t bad = 0;
+            int st = 0;
+            rc = enlsip_gn_newton_direction(h, prob0 + j, hG.data(), P.n, hp.data(), &bad);
+            if (rc == -7) st = NW_RANKDEF;
+            else if (rc) return rc;
+            else st = bad ? 1 : 0;
+            if (st != NW_RANKDEF) GN_HIP(hipMemcpy(io.p + j * P.n, hp.data(), (size_t)P.n * 8, hipMemcpyHostToDevice));
+            if (io.status) GN_HIP(hipMemcpy(io.status + j, &st, sizeof(int), hipMemcpyHostToDevice));
+            flagged = flagged || st != 0;
+        }
+    }
+    return flagged ? 1 : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int enlsip_gn_newton_direction_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dGamma, int64_t ldg,
+                                           int64_t strideG, const int64_t* take, double* dp, int* dstatus) {
+    if (!h) return -1;
+    GN_TRY
+    return newton_dev(h, prob0, count, {dGamma, ldg, strideG, dp, dstatus}, take);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_newton_direction_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* Gamma, int64_t ldg,
+                                       int64_t strideG, const int64_t* take, double* p, int* status) {
+    if (!h) return -1;
+    GN_TRY
+    enlsip_gn_handle first = nullptr;
+    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) { if (!first) first = sg.hh; });
+    if (rc) return rc;
+    const Plan& P = first->plan;
+    if (first->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+    if (!Gamma) { h->err = "Gamma is NULL"; return -4; }
+    if (!p) { h->err = "p is NULL"; return -4; }
+    if (ldg < P.n) { h->err = "ldg < n"; return -5; }
+    if (strideG < ldg * P.n) { h->err = "strideG < ldg * n"; return -5; }
+    const size_t c = (size_t)count;
+    // staged through a buffer of its own, one copy each way; the caller's p and status go in first so that the slots the call
+    // leaves alone come back as they were
+    const size_t n_g = (c - 1) * (size_t)strideG + (size_t)ldg * P.n, n_p = c * P.n, n_s = status ? c : 0;
+    GN_HIP(hipSetDevice(h->device));
+    rc = grow(h, h->nwb_io, (n_g + n_p + n_s + 8) * 8);
+    if (rc) return rc;
+    double* d_g = (double*)h->nwb_io.p;
+    double* d_p = d_g + n_g;
+    int* d_s = (int*)(d_p + n_p);
+    hipStream_t s = h->stream;
+    GN_HIP(hipMemcpyAsync(d_g, Gamma, n_g * 8, hipMemcpyHostToDevice, s));
+    GN_HIP(hipMemcpyAsync(d_p, p, n_p * 8, hipMemcpyHostToDevice, s));
+    if (n_s) GN_HIP(hipMemcpyAsync(d_s, status, n_s * sizeof(int), hipMemcpyHostToDevice, s));
+    rc = newton_dev(h, prob0, count, {d_g, ldg, strideG, d_p, n_s ? d_s : nullptr}, take);
+    if (rc < 0 || rc > 1) return rc;
+    GN_HIP(hipMemcpyAsync(p, d_p, n_p * 8, hipMemcpyDeviceToHost, s));
+    if (n_s) GN_HIP(hipMemcpyAsync(status, d_s, n_s * sizeof(int), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipStreamSynchronize(s));
+    return rc;
+    GN_CATCH(h)
+}
+
+int enlsip_gn_get_newton_form(enlsip_gn_handle h, int* form) {
+    if (!h) return -1;
+    if (!form) { h->err = "form is NULL"; return -2; }
+    *form = h->newton_form;
+    return 0;
+}
+
+int enlsip_gn_get_newton_stage_ms(enlsip_gn_handle h, float* ms) {
+    if (!h) return -1;
+    if (!ms) { h->err = "ms is NULL"; return -2; }
+    for (int e = 0; e < 4; ++e) ms[e] = h->newton_ms[e];
+    return 0;
+}
+
+}  // extern "C"

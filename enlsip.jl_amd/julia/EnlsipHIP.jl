@@ -525,6 +525,33 @@ function newton_search_direction_hip(h::Handle, Γ_mat::Matrix{Float64})
     return p, bad[] != 0
 end
 
+"""    newton_search_direction_batched_hip(h, prob0, Γ, take) -> (P, status)
+
+`newton_search_direction` (src/enlsip_functions.jl:348-423) after its Hessian sums for problems `prob0 .. prob0 + size(Γ, 3) - 1`
+of the resident batch, one call: `Γ[:, :, j]` is `r_mat - c_mat` of problem `prob0 + j - 1`; `take[j] == 0` leaves the problem
+alone (its column of `P` stays NaN, its status -1) — only the members whose `method_code` is 2 take the step.  status: 0; 1 the
+symmetrised W22 is not positive definite (column of zeros: the reference's `error = true`); 2 rank-deficient working set with
+t < n (the reference runs out of bounds there)."""
+function newton_search_direction_batched_hip(h::Handle, prob0::Integer, Γ::Array{Float64,3},
+                                             take::Union{Nothing,Vector{Int64}} = nothing)
+    n = size(Γ, 1); count = size(Γ, 3)
+    size(Γ, 2) == n || error("Γ must be n×n×count")
+    (take === nothing || length(take) == count) || error("take must have one entry per problem")
+    P = fill(NaN, n, count); st = fill(Cint(-1), count)
+    tk = take === nothing ? C_NULL : pointer(take)
+    GC.@preserve Γ take P st batched_check(h, ccall((:enlsip_gn_newton_direction_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Cint}),
+        h.ptr, prob0, count, Γ, n, n * n, tk, P, st))
+    return P, st
+end
+
+"""    newton_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last batched Newton direction on `h`"""
+function newton_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_newton_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 # ---- one tall Jacobian, rows sharded over the GPUs of a node (config C4): the library's TSQR collective -------------------------
 #
 # One Julia process per GPU (Distributed / MPI.jl); every rank creates its Handle on its own device.  Rank 0 obtains the RCCL

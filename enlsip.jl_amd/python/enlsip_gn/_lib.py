@@ -101,6 +101,11 @@ PROTOTYPES = {
     "enlsip_gn_get_resolve_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_get_resolve_q0_ms": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
+    "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]),
+    "enlsip_gn_get_newton_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_get_newton_stage_ms": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "enlsip_gn_tsqr_local_dev": (C.c_int, [_h, _i64, _i64, _i64, C.c_void_p, _i64, C.c_void_p, C.c_void_p, _i64,
                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, _dp, _ip]),
     "enlsip_gn_tsqr_combine_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,

@@ -495,6 +495,64 @@ class GNSolver:
         self._chk(self._lib.enlsip_gn_newton_direction(self._h, prob, _fptr(G), n, _fptr(p), C.byref(bad)))
         return p, bool(bad.value)
 
+    # ---- the Newton direction over a range of the resident batch (src/enlsip_functions.jl:371-421) ---------------------------------
+    @staticmethod
+    def _pack_take(count: int, take):
+        if take is None:
+            return None
+        tk = np.ascontiguousarray(np.asarray(take).astype(np.int64))
+        if tk.shape != (count,):
+            raise ValueError(f"take must have {count} entries")
+        return tk
+
+    def newton_direction_batched(self, Gammas: np.ndarray, prob0: int = 0, count: Optional[int] = None, take=None,
+                                 out_p: Optional[np.ndarray] = None, out_status: Optional[np.ndarray] = None):
+        """newton_search_direction after its Hessian sums for problems prob0 .. prob0+count-1, one call.  Gammas: (count, n, n),
+        Gammas[j] = r_mat - c_mat of problem prob0 + j.  take: per slot, 0 leaves the problem alone (its slots keep what out_p /
+        out_status held: NaN / -1 by default).  Returns (p (count, n), status (count,) int32, rc): status 0, 1 not positive
+        definite (p = 0), 2 rank-deficient working set with t < n; rc 0 or 1 (some status non-zero)."""
+        G = np.asarray(Gammas, dtype=np.float64)
+        if G.ndim != 3 or G.shape[1] != G.shape[2]:
+            raise ValueError("Gammas must be (count, n, n)")
+        if count is None:
+            count = G.shape[0]
+        n = G.shape[1]
+        if count < 1 or count > G.shape[0]:
+            raise ValueError(f"count must be in 1..{G.shape[0]} (the number of Gammas)")
+        Gf = np.ascontiguousarray(np.transpose(G[:count], (0, 2, 1)))      # column-major n x n per slot
+        p = out_p if out_p is not None else np.full((count, n), np.nan)
+        st = out_status if out_status is not None else np.full(count, -1, dtype=np.int32)
+        if p.dtype != np.float64 or p.shape != (count, n) or not p.flags.c_contiguous:
+            raise ValueError(f"out_p must be a C-contiguous float64 array of shape ({count}, {n})")
+        if st.dtype != np.int32 or st.shape != (count,) or not st.flags.c_contiguous:
+            raise ValueError(f"out_status must be a contiguous int32 array of {count} entries")
+        tk = self._pack_take(count, take)
+        rc = self._chk_batched(self._lib.enlsip_gn_newton_direction_batched(
+            self._h, prob0, count, _fptr(Gf), n, n * n, _fptr(tk), _fptr(p), st.ctypes.data_as(C.c_void_p)))
+        return p, st, rc
+
+    def newton_direction_batched_dev(self, prob0: int, count: int, dGamma: int, ldg: int, strideG: int, dp: int, dstatus: int = 0,
+                                     take=None) -> int:
+        """Device form: dGamma (column-major n x n per slot, ldg, strideG), dp (count x n) and dstatus are raw device pointers
+        (0 = NULL); take stays a host array."""
+        v = lambda x: C.c_void_p(x) if x else None
+        tk = self._pack_take(count, take)
+        return self._chk_batched(self._lib.enlsip_gn_newton_direction_batched_dev(
+            self._h, prob0, count, v(dGamma), ldg, strideG, _fptr(tk), v(dp), v(dstatus)))
+
+    def newton_form(self) -> int:
+        """Kernel form of the last newton_direction_batched: 0 general, 1 one wave per problem, -1 none yet."""
+        f = C.c_int(0)
+        self._chk(self._lib.enlsip_gn_get_newton_form(self._h, C.byref(f)))
+        return int(f.value)
+
+    def newton_stage_ms(self):
+        """HIP-event times of the four stages of the last newton_direction_batched (set_profiling(True) before it; zeros otherwise):
+        default b / p1 / d, E, W22 and the right-hand side, factorisation + solves + p."""
+        ms = (C.c_float * 4)()
+        self._chk(self._lib.enlsip_gn_get_newton_stage_ms(self._h, ms))
+        return [float(x) for x in ms]
+
     # ---- instrumentation ------------------------------------------------------------------------
     def set_profiling(self, on: bool, all_updates: bool = False):
         """HIP-event timing of the stages and the level-0 far updates; all_updates: every trailing-update launch (update_totals)."""

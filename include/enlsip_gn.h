@@ -21,6 +21,7 @@
  *                               choose_subspace_dimensions, determine_solving_dim consume
  *                                                     src/enlsip_functions.jl:461-537, 1118-1291
  *   enlsip_gn_newton_direction  newton_search_direction after its Hessian sums    src/enlsip_functions.jl:348-423
+ *   enlsip_gn_newton_direction_batched  the same for a range of the resident batch  src/enlsip_functions.jl:371-421
  *   enlsip_gn_solve_tsqr        (new design, no reference counterpart) the same subproblem with the ROWS of one
  *                               tall J sharded over the GPUs of a node: `JQ1 = J * F_A.Q` ... `qr(J2, ColumnNorm())`
  *                               (src/enlsip_functions.jl:219-223) as a TSQR whose one exchange step is an RCCL
@@ -357,6 +358,55 @@ int enlsip_gn_get_resolve_q0_ms(enlsip_gn_handle h, float* ms);
  * because F_L11.p has min(n, t) entries and :402-403 read rows up to n; with n > t > rankA the reference runs out of bounds and
  * this entry point returns -7. */
 int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* Gamma, int64_t ldg, double* p, int64_t* not_posdef);
+
+/* ---- the Newton direction over a range of the resident batch -----------------------------------------------------------------
+ * newton_search_direction (src/enlsip_functions.jl:348-423) is the direction check_gn_direction picks with method_code == 2; the
+ * members of a multi-start batch reach it together, near convergence.  These forms take the step for problems
+ * prob0 .. prob0+count-1 in a number of launches and synchronisations that does not depend on count.  Slot j is problem
+ * prob0 + j: Gamma_j = r_mat - c_mat (the Hessian sums :391-396 stay with the caller; n x n, column-major, ldg >= n) at
+ * Gamma + j*strideG (strideG >= ldg*n), p_j at p + j*n, status[j].  take is a HOST array of count entries in both forms (NULL =
+ * all): take[j] == 0 leaves the problem alone — no output slot written, no state touched.
+ *
+ * Per taken problem the result is what enlsip_gn_newton_direction(h, prob0 + j, Gamma_j, ldg, p_j, &e) computes, with the
+ * problem's own t[k] after a ragged solve and the DEFAULT p1 (dimA = rankA), also after a truncated re-solve:
+ *     p1 of the rank-deficient working set           :371-373
+ *     rankA == n: p1 returned as it is               :374-376
+ *     E = F_A.Q' Gamma F_A.Q                         :398      by the kA resident reflectors from both sides, Q is not formed
+ *     E = E[F_L11.p, F_L11.p] where t >= n > rankA   :396-399
+ *     W22 = E22 + J2'J2, d = -W21 p1 - J2'rx         :405-411  from the resident F_J2 (J2 Pi = Q R): J2'J2 = Pi R'R Pi' and
+ *                                                              d = -E21 p1 + Pi R' (F_J2.Q' d_temp)[1:kp], d_temp = -(rx + J1 p1);
+ *                                                              no row of J, J*F_A.Q or rx is read for W22
+ *     cholesky((W22 + W22')/2), the two solves       :414-420  LAPACK dpotrf semantics (a pivot <= 0 or NaN: not positive definite)
+ *     p = F_A.Q [p1; p2]                             :421
+ *   status[j] (written for taken problems): 0; 1 the symmetrised W22 is not positive definite (p_j = 0, the reference's
+ *     error = true); 2 rank-deficient working set with t[k] < n (enlsip_gn_newton_direction's -7; p_j is not written).
+ *   Returns 0, 1 when some taken problem is flagged; negative: -1 no resident J-side factors (also after
+ *     enlsip_gn_factor_constraints), -2 count < 1, -3 the range leaves the resident batch or reaches into an earlier chunk of a
+ *     batch above the launch limit, -4 Gamma or p is NULL, -5 ldg < n or strideG < ldg*n, -7 the batch went through the
+ *     distributed constraint stage (as enlsip_gn_newton_direction).  Argument errors are raised before any launch.
+ *   Nothing is factored again: F_A, F_L11, F_J2, their pivots and T blocks are not rewritten; W, Rt and the resident vec are only
+ *   read (F_J2.Q' d_temp goes to a buffer of the call).  Afterwards the resident b and p1 of a taken problem are the default ones
+ *   and its state record is what it was — what the loop of enlsip_gn_newton_direction calls leaves — so
+ *   enlsip_gn_second_lagrange, enlsip_gn_resolve, enlsip_gn_newton_direction and the accessors answer the same.  A result held
+ *   by ENLSIP_GN_DIM_HOLD is DROPPED for a taken problem (its p1 is gone): a later dimA = HOLD reports status 3.  Results agree
+ *   with enlsip_gn_newton_direction to rounding (J2'J2 from R instead of J).  The range may straddle the pipelined halves;
+ *   problems on a rescue handle are answered by enlsip_gn_newton_direction.  The host form stages Gamma in and p, status out
+ *   through a buffer of its own, one copy each way; the _dev form takes DEVICE buffers (take stays a host array) and returns after
+ *   one synchronisation of each stream that ran a part of the range.
+ *   Workspace: 2 n^2 + n + ldw doubles per problem of each pipelined half (1.5 GiB for 384 problems of n = 512), kept on the
+ *   handle until it is destroyed.
+ * enlsip_gn_get_newton_form      kernel form of the last enlsip_gn_newton_direction_batched* on this handle: 0 general (256
+ *     threads per problem in the factorisation), 1 one wave per problem (n <= 64), -1 none yet.
+ * enlsip_gn_get_newton_stage_ms  HIP-event times (ms) of the four stages of the last call (b / p1 / d with the default
+ *     dimensions; E; W22 and the right-hand side; factorisation, solves and p), summed over the pipelined halves that ran a part of
+ *     the range; zeros unless enlsip_gn_set_profiling was on.  ms: 4 floats.
+ */
+int enlsip_gn_newton_direction_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* Gamma, int64_t ldg,
+                                       int64_t strideG, const int64_t* take, double* p, int* status);
+int enlsip_gn_newton_direction_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const double* dGamma, int64_t ldg,
+                                           int64_t strideG, const int64_t* take, double* dp, int* dstatus);
+int enlsip_gn_get_newton_form(enlsip_gn_handle h, int* form);
+int enlsip_gn_get_newton_stage_ms(enlsip_gn_handle h, float* ms);
 
 /* ---- row-sharded TSQR building blocks (multi-GPU config C4) ----------
  * One tall residual Jacobian whose ROWS are sharded over G GPUs; the (small) constraint data
