@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <thread>
 
@@ -913,7 +914,10 @@ static int scaled_copies(enlsip_gn_handle h, const BatchOperands& v, int sJ, int
 // Ragged batch (tk != NULL): the launch shapes stay those of t_max; each problem's records carry its own column counts, F_L11 is
 // factored as the t_max x kA matrix [L11; 0] (its padded rows and carried entries are zero, so they change nothing), and the copies
 // out of the working storage take each problem's own sizes and write F_A's zero columns.
-static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long batch, long long n, long long t, const int* tk = nullptr) {
+// A problem list (ca.plist, `launch` entries): every grid covers the listed problems only; the workspace keeps the whole batch's
+// layout, so that the pieces the re-solve reads (L11, F_L11.Q' b_buff) of the problems left alone stay where they are.
+static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long batch, long long launch, long long n, long long t,
+                               const int* tk = nullptr) {
     const Plan& P = h->plan;
     hipStream_t s = h->stream;
     const int kA = P.kA;
@@ -954,13 +958,15 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
     }
 
     QdArgs q{};
-    q.n = (int)n; q.ldw = 0; q.ldr = (int)ldc; q.prob0 = 0;
+    q.n = (int)n; q.ldw = 0; q.ldr = (int)ldc; q.prob0 = 0; q.plist = ca.plist;
+    const int* plist = ca.plist;
+    const unsigned nl = (unsigned)launch;
     q.M = cM; q.sM = sMc; q.Vb = cVb; q.sVb = sVbc; q.Rt = cRt; q.sRt = sRtc;
     q.diag = cDiag; q.sDiag = sVec; q.vn1 = cVn1; q.vn2 = cVn2; q.sVn = sVec;
     q.chosen = cChosen; q.pos = cPos; q.colat = cColat; q.sI = sIc;
     q.cand = cCand; q.sCand = sCandc; q.Gmax = Gc;
     auto factor = [&](int rows, int cols, int steps) {
-        const dim3 grid = qd_grid(cols, batch);
+        const dim3 grid = qd_grid(cols, launch);
         q.step = 0;
         launch_qd_steps(grid, rows > 512, s, q, steps);
         q.step = 0;
@@ -971,34 +977,34 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
     q.tau = h->tauA; q.sTau = P.sTauA; q.jpvt = h->jpvtA; q.sJ = P.sJA; q.state = stA;
     factor((int)n, (int)t, kA);
     if (tk)
-        hipLaunchKernelGGL(k_copy_cols_ragged, dim3((unsigned)t, (unsigned)batch), dim3(256), 0, s, h->FA, n, P.sFA, (const double*)cRt, ldc,
-                           sRtc, (int)n, (int)t, (int)n, tk, 0);
+        hipLaunchKernelGGL(k_copy_cols_ragged, dim3((unsigned)t, nl), dim3(256), 0, s, h->FA, n, P.sFA, (const double*)cRt, ldc,
+                           sRtc, (int)n, (int)t, (int)n, tk, 0, plist);
     else
-        hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)t, (unsigned)batch), dim3(256), 0, s, h->FA, n, P.sFA, cRt, ldc, sRtc, (int)n, (int)t);
+        hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)t, nl), dim3(256), 0, s, h->FA, n, P.sFA, cRt, ldc, sRtc, (int)n, (int)t, plist);
     // ---- F_L11: the t x kA lower trapezoid R_A', carrying b_buff = -cx[F_A.p] ----------------------------------------
     if (tk)
-        hipLaunchKernelGGL(k_bbuff_ragged, dim3((unsigned)((t + 255) / 256), (unsigned)batch), dim3(256), 0, s, cBq, sVec, ca.cx,
-                           ca.stride_cx, (const long long*)h->jpvtA, P.sJA, (int)t, tk);
+        hipLaunchKernelGGL(k_bbuff_ragged, dim3((unsigned)((t + 255) / 256), nl), dim3(256), 0, s, cBq, sVec, ca.cx,
+                           ca.stride_cx, (const long long*)h->jpvtA, P.sJA, (int)t, tk, plist);
     else
-        hipLaunchKernelGGL(k_bbuff, dim3((unsigned)((t + 255) / 256), (unsigned)batch), dim3(256), 0, s, cBq, sVec, ca.cx, ca.stride_cx,
-                           h->jpvtA, P.sJA, (int)t);
+        hipLaunchKernelGGL(k_bbuff, dim3((unsigned)((t + 255) / 256), nl), dim3(256), 0, s, cBq, sVec, ca.cx, ca.stride_cx,
+                           h->jpvtA, P.sJA, (int)t, plist);
     q.rows = (int)t; q.in_mode = 2; q.Ain = h->FA; q.ldain = n; q.sAin = P.sFA; q.rin = cBq; q.sRin = sVec; q.Lout = cL; q.sLout = sLc;
     q.tau = h->tauL; q.sTau = P.sTauL; q.jpvt = h->jpvtL; q.sJ = P.sJL; q.state = stL;
     factor((int)t, kA, (int)std::min<long long>(t, kA));
     if (tk) {
-        hipLaunchKernelGGL(k_copy_cols_ragged, dim3((unsigned)kA, (unsigned)batch), dim3(256), 0, s, h->FL, t, P.sFL, (const double*)cRt,
-                           ldc, sRtc, (int)t, kA, (int)n, tk, 1);
-        hipLaunchKernelGGL(k_copy_cols_ragged, dim3(1, (unsigned)batch), dim3(256), 0, s, cQb, sVec, sVec, (const double*)cRt, ldc, sRtc,
-                           (int)t, 1, (int)n, tk, 2);
+        hipLaunchKernelGGL(k_copy_cols_ragged, dim3((unsigned)kA, nl), dim3(256), 0, s, h->FL, t, P.sFL, (const double*)cRt,
+                           ldc, sRtc, (int)t, kA, (int)n, tk, 1, plist);
+        hipLaunchKernelGGL(k_copy_cols_ragged, dim3(1, nl), dim3(256), 0, s, cQb, sVec, sVec, (const double*)cRt, ldc, sRtc,
+                           (int)t, 1, (int)n, tk, 2, plist);
     } else {
-        hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)kA, (unsigned)batch), dim3(256), 0, s, h->FL, t, P.sFL, cRt, ldc, sRtc, (int)t, kA);
-        hipLaunchKernelGGL(k_copy_cols, dim3(1, (unsigned)batch), dim3(256), 0, s, cQb, sVec, sVec, cRt + (size_t)kA * ldc, ldc, sRtc, (int)t, 1);
+        hipLaunchKernelGGL(k_copy_cols, dim3((unsigned)kA, nl), dim3(256), 0, s, h->FL, t, P.sFL, cRt, ldc, sRtc, (int)t, kA, plist);
+        hipLaunchKernelGGL(k_copy_cols, dim3(1, nl), dim3(256), 0, s, cQb, sVec, sVec, cRt + (size_t)kA * ldc, ldc, sRtc, (int)t, 1, plist);
     }
     // ---- ranks, triangular solves, T blocks ---------------------------------------------------------------------------
     ca.fa_done = 1; ca.fl_done = 1; ca.need_T = 1;
     ca.Lmat = cL; ca.ldL = ldc; ca.sL = sLc; ca.qb = cQb; ca.sQb = sVec;
     h->cdist.L = cL; h->cdist.ldL = ldc; h->cdist.sL = sLc; h->cdist.qb = cQb; h->cdist.sQb = sVec; h->cdist.valid = true;
-    launch_constraint((int)std::max(n, t), (int)batch, s, ca, tk);
+    launch_constraint((int)std::max(n, t), (int)launch, s, ca, tk);
     GN_HIP(hipGetLastError());
     return 0;
 }
@@ -1006,12 +1012,16 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
 // F_A, rankA, F_L11, b, p1, block T of Q1 for every problem of the batch (plan already made)
 // prob0 / code_ov: the re-solve of ONE resident problem (enlsip_gn_resolve) takes the same route as the solve that produced its
 // factors, so that they are rewritten bit for bit by the same kernels.
+// plist / nlist: a device list of problem indices (enlsip_gn_solve_factored_batched: the problems whose working set changed).  Every
+// kernel of the stage is launched over the listed problems only and touches no slot of another one.
 static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m, long long n, long long t, const double* dAt,
                                 long long ldat, long long strideAt, const double* dcx, double eps_rank, long long dimA_ov,
-                                int prob0 = 0, int code_ov = 0) {
+                                int prob0 = 0, int code_ov = 0, const int* plist = nullptr, long long nlist = 0) {
     const Plan& P = h->plan;
     hipStream_t s = h->stream;
-    if (prob0 == 0 && code_ov == 0) h->cdist.valid = false;
+    const long long launch = plist ? nlist : batch;     // workgroups (grid rows) of every launch
+    h->cstage_problems += launch;
+    if (prob0 == 0 && code_ov == 0 && !plist) h->cdist.valid = false;
     // the resident problem was rescaled (sc_eA != 0: one problem): the stage runs on the scaled copies of A', cx with the absolute
     // rank threshold scaled alike, and what it leaves resident is scaled back below
     const bool scaledA = h->sc_eA != 0 && batch == 1 && prob0 == 0 && t > 0;
@@ -1019,7 +1029,7 @@ static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m
     ConstraintArgs ca{};
     ca.n = (int)n; ca.t = (int)t; ca.kA = P.kA; ca.m = (int)m; ca.eps_rank = eps_rank;
     ca.abs_shift = scaledA ? h->sc_eA : 0;
-    ca.dimA_override = (int)dimA_ov; ca.code_override = code_ov; ca.prob0 = prob0;
+    ca.dimA_override = (int)dimA_ov; ca.code_override = code_ov; ca.prob0 = prob0; ca.plist = plist;
     ca.At = dAt; ca.ldat = ldat; ca.strideAt = strideAt; ca.cx = dcx; ca.stride_cx = t;
     ca.FA = h->FA; ca.sFA = P.sFA; ca.tauA = h->tauA; ca.sTauA = P.sTauA; ca.jpvtA = h->jpvtA; ca.sJA = P.sJA;
     ca.FL = h->FL; ca.sFL = P.sFL; ca.tauL = h->tauL; ca.sTauL = P.sTauL; ca.jpvtL = h->jpvtL; ca.sJL = P.sJL;
@@ -1029,7 +1039,7 @@ static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m
     // many constraints: both factorisations through the distributed pivoted QR
     if (t > 64 && (size_t)n * t > (size_t)CMAT_DOUBLES) {
         GN_ROUTE(ENLSIP_GN_ROUTE_CONSTRAINT_DIST);
-        int rcd = run_constraint_dist(h, ca, batch, n, t, tk);
+        int rcd = run_constraint_dist(h, ca, batch, launch, n, t, tk);
         if (rcd) return rcd;
         return scaledA ? unscale_constraint_side(h) : 0;
     }
@@ -1038,17 +1048,17 @@ static int run_constraint_stage(enlsip_gn_handle h, long long batch, long long m
         Geqp3RegArgs ga{};
         ga.rows = (int)n; ga.cols = (int)t; ga.A = dAt; ga.lda = ldat; ga.strideA = strideAt;
         ga.F = h->FA; ga.sF = P.sFA; ga.tau = h->tauA; ga.sTau = P.sTauA; ga.jpvt = h->jpvtA; ga.sJ = P.sJA;
-        ga.T = h->TA; ga.sT = P.sTA; ga.prob0 = prob0;
+        ga.T = h->TA; ga.sT = P.sTA; ga.prob0 = prob0; ga.plist = plist;
         GN_ROUTE(n <= 256 ? ENLSIP_GN_ROUTE_CONSTRAINT_REG4 : ENLSIP_GN_ROUTE_CONSTRAINT_REG8);
         if (tk) {
-            if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg_ragged<4>, dim3((unsigned)batch), dim3(512), 0, s, ga, tk);
-            else hipLaunchKernelGGL(k_geqp3_reg_ragged<8>, dim3((unsigned)batch), dim3(512), 0, s, ga, tk);
-        } else if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg<4>, dim3((unsigned)batch), dim3(512), 0, s, ga);
-        else hipLaunchKernelGGL(k_geqp3_reg<8>, dim3((unsigned)batch), dim3(512), 0, s, ga);
+            if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg_ragged<4>, dim3((unsigned)launch), dim3(512), 0, s, ga, tk);
+            else hipLaunchKernelGGL(k_geqp3_reg_ragged<8>, dim3((unsigned)launch), dim3(512), 0, s, ga, tk);
+        } else if (n <= 256) hipLaunchKernelGGL(k_geqp3_reg<4>, dim3((unsigned)launch), dim3(512), 0, s, ga);
+        else hipLaunchKernelGGL(k_geqp3_reg<8>, dim3((unsigned)launch), dim3(512), 0, s, ga);
         ca.fa_done = 1;
     }
     // with F_A done the kernel only factors the t x kA matrix R_A': size its rows-per-lane instantiation (and LDS) for that
-    launch_constraint(ca.fa_done ? (int)std::max<long long>(t, 1) : (int)std::max(n, t), (int)batch, s, ca, tk);
+    launch_constraint(ca.fa_done ? (int)std::max<long long>(t, 1) : (int)std::max(n, t), (int)launch, s, ca, tk);
     GN_HIP(hipGetLastError());
     return scaledA ? unscale_constraint_side(h) : 0;
 }
@@ -1097,6 +1107,22 @@ static int create_helper(enlsip_gn_handle h, enlsip_gn_handle* out, hipStream_t 
     return enlsip_gn_create(out, &o);
 }
 
+// the one-problem handle for the next rescaled problem of the batch on h (the rescue_prob.size()-th), created on first use
+static int next_rescue_handle(enlsip_gn_handle h, enlsip_gn_handle* out) {
+    const size_t j = h->rescue_prob.size();
+    if (j >= 64) { h->err = "more than 64 problems of the batch need rescaling (magnitudes beyond 2^+-400): solve them separately"; return -18; }
+    if (j >= h->rescue.size()) {
+        enlsip_gn_handle r = nullptr;
+        int rc = create_helper(h, &r, nullptr);
+        if (rc) { h->err = "could not create a handle for a rescaled problem"; return rc; }
+        r->is_rescue = true;
+        r->pipeline = false;
+        h->rescue.push_back(r);
+    }
+    *out = h->rescue[j];
+    return 0;
+}
+
 static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
     const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
     h->split = 0;   // routing of accessors to the pipeline child is (re)established by the batched entry point
@@ -1104,6 +1130,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     gn_route_acc = 0;
     const bool reuse = h->reuse_once;
     h->reuse_once = false;
+    if (!reuse) h->refit.clear();
     const bool upper_in = h->upper_once && t == 0 && m <= n;      // J is upper triangular (and unconstrained): it IS its own R0, Q0 = I
     h->upper_once = false;
     int rc = check_limits(h, batch, m, n, t);
@@ -1150,8 +1177,18 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     h->constraints_only = false;
     // 1. constraint stage
     GN_TRACE(h, "solve m=%lld n=%lld t=%lld batch=%lld: constraint stage%s", m, n, t, batch, reuse ? " (resident)" : "");
+    h->cstage_problems = 0;
     if (!reuse) {       // enlsip_gn_solve_factored: F_A, F_L11, b, p1, T and the state record are those of enlsip_gn_factor_constraints
+        h->fb.valid = false;
         rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov);
+        if (rc) return rc;
+    } else if (!h->refit.empty()) {     // enlsip_gn_solve_factored_batched: the stage again for the problems whose working set changed
+        const size_t nl = h->refit.size();
+        rc = grow(h, h->plist_buf, nl * sizeof(int));
+        if (rc) return rc;
+        GN_HIP(hipMemcpyAsync(h->plist_buf.p, h->refit.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
+        rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov, 0, 0, (const int*)h->plist_buf.p,
+                                  (long long)nl);
         if (rc) return rc;
     }
     mark(1);
@@ -1272,17 +1309,9 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
                 rc = extreme_shifts(h, one, &sJ, &sA);
                 if (rc) return rc;
                 if (!sJ && !sA) continue;
-                const size_t j = h->rescue_prob.size();
-                if (j >= 64) { h->err = "more than 64 problems of the batch need rescaling (magnitudes beyond 2^+-400): solve them separately"; return -18; }
-                if (j >= h->rescue.size()) {
-                    enlsip_gn_handle r = nullptr;
-                    rc = create_helper(h, &r, nullptr);
-                    if (rc) { h->err = "could not create a handle for a rescaled problem"; return rc; }
-                    r->is_rescue = true;
-                    r->pipeline = false;
-                    h->rescue.push_back(r);
-                }
-                enlsip_gn_handle r = h->rescue[j];
+                enlsip_gn_handle r = nullptr;
+                rc = next_rescue_handle(h, &r);
+                if (rc) return rc;
                 const unsigned long long route_here = gn_route_acc;
                 rc = solve_dev(r, one, eps_rank, dimA_ov, dimJ2_ov);
                 gn_route_acc = route_here | r->route;
@@ -1311,6 +1340,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
         rc = collect_stage_ms(h);
         if (rc) return rc;
     }
+    h->refit.clear();
     h->factors_valid = true;
     h->route = gn_route_acc;
     return 0;
@@ -1438,6 +1468,7 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
         if (e) (void)hipEventDestroy(e);
     if (h->h_lagflag) (void)hipHostFree(h->h_lagflag);
     if (h->cws.p) (void)hipFree(h->cws.p);
+    if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);
     if (h->xbuf.p) (void)hipFree(h->xbuf.p);
     tsqr_drop_comm(h);
@@ -1615,51 +1646,75 @@ int enlsip_gn_get_update_totals(enlsip_gn_handle h, float* far_ms, float* other_
     return 0;
 }
 
+// Where a batch is cut into two pipelined halves (see gn_context.hpp): problems [split, batch) run on the child handle; 0 = no split.
+// one-tile problems of the wave-per-problem pipeline (n <= 64, m <= 512: C3, C5) are a handful of short, uniform launches with
+// nothing latency-bound to hide behind them: the split costs C3 4 % (1.276 -> 1.325 M solves/s without it), C5 nothing
+static long long pipeline_split_of(enlsip_gn_handle h, long long batch, long long m, long long n) {
+    const bool small_uniform = (n <= 64 && m <= 512) && !h->pipeline_forced;
+    return (h->pipeline && !h->profiling && batch >= h->pipeline_min && !small_uniform) ? (batch + 1) / 2 : 0;
+}
+
+// part(handle, first problem, count) for the two halves of a batch split at b0, on two streams: the child's stream is ordered after
+// everything the caller has enqueued on this handle's stream, the second half is driven by a host thread, and both halves are
+// complete when this returns.  Records the split for the accessors.
+static int on_both_halves(enlsip_gn_handle h, long long batch, long long b0,
+                          const std::function<int(enlsip_gn_handle, long long, long long)>& part) {
+    GN_HIP(hipSetDevice(h->device));
+    if (!h->child) {
+        int rc = create_helper(h, &h->child, nullptr);
+        if (rc) { h->err = "could not create the second pipeline handle"; return rc; }
+        h->child->pipeline = false;
+    }
+    if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    GN_HIP(hipEventRecord(h->ev_fork, h->stream));
+    GN_HIP(hipStreamWaitEvent(h->child->stream, h->ev_fork, 0));
+    const long long b1 = batch - b0;
+    enlsip_gn_handle c = h->child;
+    int rc1 = 0;
+    std::thread worker([&] {
+        (void)hipSetDevice(c->device);
+        try {
+            rc1 = part(c, b0, b1);
+        } catch (...) {
+            c->err = "exception in the second pipeline half (out of host memory?)";
+            rc1 = 997;
+        }
+    });
+    int rc0;
+    try {
+        rc0 = part(h, 0LL, b0);
+    } catch (...) {
+        worker.join();
+        throw;
+    }
+    worker.join();
+    if (rc0) return rc0;
+    if (rc1) { h->err = c->err; return rc1; }
+    h->split = b0;
+    h->route |= c->route | (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
+    return 0;
+}
+
 // One launch set over at most GN_MAX_LAUNCH_BATCH problems: either two pipelined halves on two streams or one solve_dev.
+// With a resident constraint stage (reuse_once) the halves are those the stage was placed on: enlsip_gn_factor_constraints_batched
+// recorded its split, and the solve must come to the same one.
 static int solve_launchable(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
     h->split = 0;
     const long long batch = v.batch, m = v.m, n = v.n;
-    // one-tile problems of the wave-per-problem pipeline (n <= 64, m <= 512: C3, C5) are a handful of short, uniform launches with
-    // nothing latency-bound to hide behind them: the split costs C3 4 % (1.276 -> 1.325 M solves/s without it), C5 nothing
-    const bool small_uniform = (n <= 64 && m <= 512) && !h->pipeline_forced;
-    const bool plain = (dimA_ov < 0 && dimJ2_ov < 0 && !h->reuse_once);
-    if (plain && h->pipeline && !h->profiling && batch >= h->pipeline_min && !small_uniform) {
-        // two halves on two streams (see gn_context.hpp); the child's stream is ordered after everything the caller
-        // has enqueued on this handle's stream, and both halves are complete when this call returns
-        GN_HIP(hipSetDevice(h->device));
-        if (!h->child) {
-            int rc = create_helper(h, &h->child, nullptr);
-            if (rc) { h->err = "could not create the second pipeline handle"; return rc; }
-            h->child->pipeline = false;
-        }
-        if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-        GN_HIP(hipEventRecord(h->ev_fork, h->stream));
-        GN_HIP(hipStreamWaitEvent(h->child->stream, h->ev_fork, 0));
-        const long long b0 = (batch + 1) / 2, b1 = batch - b0;
-        enlsip_gn_handle c = h->child;
-        int rc1 = 0;
-        std::thread worker([&] {
-            (void)hipSetDevice(c->device);
-            try {
-                rc1 = solve_dev(c, v.slice(b0, b1), eps_rank, -1, -1);
-            } catch (...) {
-                c->err = "exception in the second pipeline half (out of host memory?)";
-                rc1 = 997;
-            }
+    const bool factored = h->reuse_once;
+    const bool plain = (dimA_ov < 0 && dimJ2_ov < 0);
+    const long long b0 = plain ? pipeline_split_of(h, batch, m, n) : 0;
+    if (factored && b0 != (h->fb.valid ? h->fb.split : 0)) {
+        h->reuse_once = false;
+        h->err = "the batch would be split over the pipeline halves differently from the constraint stage that is resident "
+                 "(profiling or the pipeline setting changed in between?): call enlsip_gn_factor_constraints_batched again";
+        return -1;
+    }
+    if (b0 > 0) {
+        if (factored) h->child->reuse_once = true;
+        return on_both_halves(h, batch, b0, [&](enlsip_gn_handle hh, long long k0, long long cnt) {
+            return solve_dev(hh, v.slice(k0, cnt), eps_rank, -1, -1);
         });
-        int rc0;
-        try {
-            rc0 = solve_dev(h, v.slice(0, b0), eps_rank, -1, -1);
-        } catch (...) {
-            worker.join();
-            throw;
-        }
-        worker.join();
-        if (rc0) return rc0;
-        if (rc1) { h->err = c->err; return rc1; }
-        h->split = b0;
-        h->route |= c->route | (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
-        return 0;
     }
     return solve_dev(h, v, eps_rank, dimA_ov, dimJ2_ov);
 }
@@ -1700,9 +1755,14 @@ int enlsip_gn_solve_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
     GN_CATCH(h)
 }
 
+static int solve_factored_core(enlsip_gn_handle h, const BatchOperands& v, const int64_t* refactor, double eps_rank, bool host_form);
+
 // hv: the caller's host arrays (hinfo = the info records): staged packed (ld = m / n), solved, outputs copied back
+// factored: the constraint stage is resident and A', cx sit in their staging slots (enlsip_gn_solve_factored); batched_factored:
+// that of a whole batch (enlsip_gn_solve_factored_batched, which has checked the state), where the problems with a refactor flag
+// bring new A', cx into their slots
 static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_rank, long long dimA_ov, long long dimJ2_ov,
-                      bool factored = false) {
+                      bool factored = false, bool batched_factored = false, const int64_t* refactor = nullptr) {
     if (!h) return -1;
     GN_TRY
     const long long batch = hv.batch, m = hv.m, n = hv.n, t = hv.t;
@@ -1711,13 +1771,13 @@ static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_ra
     if (!hv.J) { h->err = "J is NULL"; return -6; }
     if (hv.ldj < m) { h->err = "ldj < m"; return -7; }
     if (!hv.rx) { h->err = "rx is NULL"; return -9; }
-    if (factored) {
+    if (factored && !batched_factored) {
         const Plan& P = h->plan;
         if (!(h->factors_valid && h->constraints_only && h->have_plan && P.batch == 1 && P.m == m && P.n == n && P.t == t)) {
             h->err = "enlsip_gn_solve_factored needs enlsip_gn_factor_constraints with the same m, n, t right before";
             return -1;
         }
-    } else {
+    } else if (!factored) {
         if (t > 0 && (!hv.At || !hv.cx)) { h->err = "At / cx is NULL with t > 0"; return -10; }
         if (t > 0 && hv.ldat < n) { h->err = "ldat < n"; return -11; }
     }
@@ -1751,14 +1811,20 @@ static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_ra
     for (int64_t k = 0; k < batch; ++k) {
         GN_HIP(hipMemcpy2DAsync(dJ + (size_t)k * m * n, (size_t)m * 8, hv.J + (size_t)k * hv.strideJ, (size_t)hv.ldj * 8,
                                 (size_t)m * 8, (size_t)n, hipMemcpyHostToDevice, s));
-        if (t > 0 && !factored)
+        if (t > 0 && (!factored || (refactor && refactor[k]))) {
             GN_HIP(hipMemcpy2DAsync(dAt + (size_t)k * n * t, (size_t)n * 8, hv.At + (size_t)k * hv.strideAt,
                                     (size_t)hv.ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
+            if (factored) GN_HIP(hipMemcpyAsync(dcx + (size_t)k * t, hv.cx + (size_t)k * t, (size_t)t * 8, hipMemcpyHostToDevice, s));
+        }
     }
     GN_HIP(hipMemcpyAsync(drx, hv.rx, (size_t)batch * m * 8, hipMemcpyHostToDevice, s));
     if (t > 0 && !factored) GN_HIP(hipMemcpyAsync(dcx, hv.cx, (size_t)batch * t * 8, hipMemcpyHostToDevice, s));
-    h->reuse_once = factored;      // A', cx (same staging slots) and the constraint factors are resident
-    rc = solve_chunked(h, dv, eps_rank, dimA_ov, dimJ2_ov);
+    if (batched_factored) {
+        rc = solve_factored_core(h, dv, refactor, eps_rank, true);
+    } else {
+        h->reuse_once = factored;      // A', cx (same staging slots) and the constraint factors are resident
+        rc = solve_chunked(h, dv, eps_rank, dimA_ov, dimJ2_ov);
+    }
     if (rc) return rc;
     if (hv.p) GN_HIP(hipMemcpyAsync(hv.p, dp, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
     if (hv.b && t > 0) GN_HIP(hipMemcpyAsync(hv.b, db, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
@@ -1771,31 +1837,20 @@ static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_ra
     GN_CATCH(h)
 }
 
-int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* At, int64_t ldat,
-                                 const double* cx, double eps_rank, enlsip_gn_info* info) {
-    if (!h) return -1;
-    int rc = check_limits(h, 1, m, n, t);
-    if (rc) return rc;
-    if (t > 0 && (!At || !cx)) return -5;
-    if (t > 0 && ldat < n) return -6;
+// the constraint stage of ONE problem from device buffers (enlsip_gn_factor_constraints after its staging; a problem of
+// enlsip_gn_factor_constraints_batched whose magnitudes need the rescaling, on its rescue handle)
+static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long long t, const double* dAt, long long ldat, const double* dcx,
+                          double eps_rank, enlsip_gn_info* info) {
     GN_HIP(hipSetDevice(h->device));
     h->split = 0;
     h->chunk0 = 0;
-    rc = make_plan(h, 1, m, n, t);
+    h->fb.valid = false;
+    h->refit.clear();
+    int rc = make_plan(h, 1, m, n, t);
     if (rc) return rc;
-    // same staging layout as solve_host, so that a following solve of the same shape reuses the buffers
-    const size_t inJ = (size_t)m * n, inAt = (size_t)n * t;
-    rc = grow(h, h->in_stage, (inJ + (size_t)m + inAt + (size_t)t) * 8 + 1024);
-    if (rc) return rc;
-    double* dAt = (double*)h->in_stage.p + inJ + (size_t)m;
-    double* dcx = dAt + inAt;
     hipStream_t s = h->stream;
-    if (t > 0) {
-        GN_HIP(hipMemcpy2DAsync(dAt, (size_t)n * 8, At, (size_t)ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
-        GN_HIP(hipMemcpyAsync(dcx, cx, (size_t)t * 8, hipMemcpyHostToDevice, s));
-    }
     BatchOperands v{1, m, n, t};     // no J, rx: the constraint side only
-    v.At = dAt; v.ldat = n; v.strideAt = n * t; v.cx = dcx;
+    v.At = dAt; v.ldat = ldat; v.strideAt = ldat * t; v.cx = dcx;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
     h->held.clear();
@@ -1803,7 +1858,7 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
     h->sc_eJ = 0; h->sc_eA = 0;
     h->rescue_prob.clear();
     h->h_tk.clear();
-    rc = run_constraint_stage(h, 1, m, n, t, dAt, n, (long long)n * t, dcx, eps_rank, -1);
+    rc = run_constraint_stage(h, 1, m, n, t, dAt, ldat, ldat * t, dcx, eps_rank, -1);
     if (rc) return rc;
     if (h->rescale_enabled && t > 0)
         hipLaunchKernelGGL(k_extreme_flags, dim3(1), dim3(256), 0, s, h->state, (const double*)nullptr, 0LL, (const double*)h->FA, h->plan.sFA,
@@ -1819,7 +1874,7 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
             rc = scaled_copies(h, v, 0, sA);
             if (rc) return rc;
             h->sc_eA = sA;
-            rc = run_constraint_stage(h, 1, m, n, t, dAt, n, (long long)n * t, dcx, eps_rank, -1);
+            rc = run_constraint_stage(h, 1, m, n, t, dAt, ldat, ldat * t, dcx, eps_rank, -1);
             if (rc) return rc;
             GN_HIP(hipMemcpyAsync(h->h_state, h->state, sizeof(ProbState), hipMemcpyDeviceToHost, s));
             GN_HIP(hipStreamSynchronize(s));
@@ -1836,6 +1891,28 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
         info->rankJ2 = info->dimJ2 = 0;       // nothing about J is resident
     }
     return 0;
+}
+
+int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* At, int64_t ldat,
+                                 const double* cx, double eps_rank, enlsip_gn_info* info) {
+    if (!h) return -1;
+    int rc = check_limits(h, 1, m, n, t);
+    if (rc) return rc;
+    if (t > 0 && (!At || !cx)) return -5;
+    if (t > 0 && ldat < n) return -6;
+    GN_HIP(hipSetDevice(h->device));
+    // same staging layout as solve_host, so that a following solve of the same shape reuses the buffers
+    const size_t inJ = (size_t)m * n, inAt = (size_t)n * t;
+    rc = grow(h, h->in_stage, (inJ + (size_t)m + inAt + (size_t)t) * 8 + 1024);
+    if (rc) return rc;
+    double* dAt = (double*)h->in_stage.p + inJ + (size_t)m;
+    double* dcx = dAt + inAt;
+    hipStream_t s = h->stream;
+    if (t > 0) {
+        GN_HIP(hipMemcpy2DAsync(dAt, (size_t)n * 8, At, (size_t)ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
+        GN_HIP(hipMemcpyAsync(dcx, cx, (size_t)t * 8, hipMemcpyHostToDevice, s));
+    }
+    return factor_one_dev(h, m, n, t, dAt, n, dcx, eps_rank, info);
 }
 
 int enlsip_gn_solve_factored(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* J, int64_t ldj,
@@ -1859,19 +1936,23 @@ int enlsip_gn_solve_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
 // Argument errors are LAPACK-style (position in the argument list), all checked before anything is launched.
 static int check_ragged(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t, const double* J,
                         int64_t ldj, const double* rx, const double* At, int64_t ldat, int64_t strideAt, const double* cx,
-                        std::vector<int>& tk) {
+                        std::vector<int>& tk, bool with_J = true, bool with_A = true, bool t_optional = false) {
     int rc = check_limits(h, batch, m, n, t_max);
     if (rc) return rc;
-    if (!t) { h->err = "t is NULL"; return -6; }
-    if (!J) { h->err = "J is NULL"; return -7; }
-    if (ldj < m) { h->err = "ldj < m"; return -8; }
-    if (!rx) { h->err = "rx is NULL"; return -10; }
-    if (t_max > 0 && !At) { h->err = "At is NULL with t_max > 0"; return -11; }
-    if (t_max > 0 && ldat < n) { h->err = "ldat < n"; return -12; }
-    if (t_max > 0 && strideAt < ldat * t_max) { h->err = "strideAt < ldat * t_max"; return -13; }
-    if (t_max > 0 && !cx) { h->err = "cx is NULL with t_max > 0"; return -14; }
-    tk.resize((size_t)batch);
-    for (int64_t k = 0; k < batch; ++k) {
+    if (!t && !t_optional) { h->err = "t is NULL"; return -6; }
+    if (with_J) {
+        if (!J) { h->err = "J is NULL"; return -7; }
+        if (ldj < m) { h->err = "ldj < m"; return -8; }
+        if (!rx) { h->err = "rx is NULL"; return -10; }
+    }
+    if (with_A) {
+        if (t_max > 0 && !At) { h->err = "At is NULL with t_max > 0"; return -11; }
+        if (t_max > 0 && ldat < n) { h->err = "ldat < n"; return -12; }
+        if (t_max > 0 && strideAt < ldat * t_max) { h->err = "strideAt < ldat * t_max"; return -13; }
+        if (t_max > 0 && !cx) { h->err = "cx is NULL with t_max > 0"; return -14; }
+    }
+    tk.assign((size_t)batch, (int)t_max);
+    for (int64_t k = 0; t && k < batch; ++k) {
         if (t[k] < 0 || t[k] > t_max) {
             h->err = "t[" + std::to_string(k) + "] = " + std::to_string(t[k]) + " is outside 0..t_max";
             return -6;
@@ -1907,6 +1988,272 @@ int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_
     return solve_chunked(h, {batch, m, n, t_max, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, dp, db, dd, dinfo,
                              (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()}, eps_rank, -1, -1);
     GN_CATCH(h)
+}
+
+// ---- batched constraint stage and the solve that goes on with it (update_working_set, src/enlsip_functions.jl:700-704 before the
+// deletion decision, :725 / :771 after it), see include/enlsip_gn.h -------------------------------------------------------------
+
+// The constraint stage of the problems of v (device buffers, v.tk on the host) on ONE handle: the parent or a pipeline child.
+static int factor_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank) {
+    const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
+    GN_HIP(hipSetDevice(h->device));
+    h->split = 0;
+    h->chunk0 = 0;
+    gn_route_acc = 0;
+    h->reuse_once = false;
+    h->upper_once = false;
+    h->refit.clear();
+    h->cstage_problems = 0;
+    int rc = make_plan(h, batch, m, n, t);
+    if (rc) return rc;
+    const Plan& P = h->plan;
+    h->eps_rank = eps_rank;
+    h->factors_valid = false;
+    h->held.clear();
+    h->last = v.inputs();           // J, rx absent: the consumers that need them say so
+    h->sc_eJ = 0; h->sc_eA = 0;
+    h->rescue_prob.clear();
+    hipStream_t s = h->stream;
+    h->h_tk.assign(v.tk, v.tk + batch);
+    rc = grow(h, h->tkbuf, (size_t)batch * sizeof(int));
+    if (rc) return rc;
+    GN_HIP(hipMemcpyAsync(h->tkbuf.p, h->h_tk.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s));
+    rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, -1);
+    if (rc) return rc;
+    const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
+    if (h->rescale_enabled && t > 0)
+        hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)nullptr, 0LL,
+                           (const double*)h->FA, P.sFA, P.kA, 0, (int)batch, (const int*)h->tkbuf.p);
+    GN_HIP(hipGetLastError());
+    GN_HIP(hipMemcpyAsync(h->h_state, h->state, (size_t)batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipStreamSynchronize(s));
+    // A', cx beyond the range of plain sums of squares (gn_rescale.hpp): the problem's stage on a one-problem handle of its own,
+    // which rescales; the accessors and the first estimate are routed to it
+    bool flagged = false;
+    for (long long k = 0; k < batch; ++k) {
+        if (!(h->h_state[k].status & fl)) continue;
+        flagged = true;
+        int sJ = 0, sA = 0;
+        BatchOperands one = v.slice(k, 1);
+        one.t = v.tk[k];
+        one.tk = nullptr;
+        rc = extreme_shifts(h, one, &sJ, &sA);
+        if (rc) return rc;
+        if (!sA) continue;
+        enlsip_gn_handle r = nullptr;
+        rc = next_rescue_handle(h, &r);
+        if (rc) return rc;
+        rc = factor_one_dev(r, m, n, one.t, one.At, one.ldat, one.cx, eps_rank, nullptr);
+        if (rc) { h->err = r->err; return rc; }
+        gn_route_acc |= r->route & (1ull << ENLSIP_GN_ROUTE_RESCALED);
+        GN_HIP(hipSetDevice(h->device));
+        h->h_state[k] = r->h_state[0];
+        h->rescue_prob.push_back(k);
+    }
+    if (flagged) {
+        for (long long k = 0; k < batch; ++k) h->h_state[k].status &= ~fl;
+        hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)batch);
+        GN_HIP(hipGetLastError());
+    }
+    if (v.hinfo || v.dinfo) {
+        std::vector<enlsip_gn_info> tmp((size_t)batch);
+        for (long long k = 0; k < batch; ++k) {
+            tmp[k] = info_of(h->h_state[k]);
+            tmp[k].rankJ2 = tmp[k].dimJ2 = 0;      // nothing about J is resident
+            if (v.hinfo) v.hinfo[k] = tmp[k];
+        }
+        if (v.dinfo) {
+            GN_HIP(hipMemcpyAsync(v.dinfo, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
+            GN_HIP(hipStreamSynchronize(s));
+        }
+    }
+    h->factors_valid = true;
+    h->constraints_only = true;
+    h->route = gn_route_acc;
+    return 0;
+}
+
+// Both forms of enlsip_gn_factor_constraints_batched after their checks (and the host form's staging): every problem's stage on the
+// handle the following solve will run it on, and the record that lets that solve recognise it.
+static int factor_batched_core(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, bool host_form) {
+    h->fb.valid = false;
+    const long long batch = v.batch;
+    const long long b0 = pipeline_split_of(h, batch, v.m, v.n);
+    int rc = b0 > 0 ? on_both_halves(h, batch, b0, [&](enlsip_gn_handle hh, long long k0, long long cnt) {
+                          return factor_dev(hh, v.slice(k0, cnt), eps_rank);
+                      })
+                    : factor_dev(h, v, eps_rank);
+    if (rc) return rc;
+    auto& F = h->fb;
+    F.host = host_form;
+    F.batch = batch; F.m = v.m; F.n = v.n; F.t = v.t; F.split = b0;
+    F.At = v.At; F.ldat = v.ldat; F.strideAt = v.strideAt; F.cx = v.cx;
+    F.tk.assign(v.tk, v.tk + batch);
+    F.valid = true;
+    h->constraint_refactored = h->cstage_problems + (b0 > 0 ? h->child->cstage_problems : 0);
+    return 0;
+}
+
+// Is the resident constraint stage the one an enlsip_gn_solve_factored_batched call with these arguments goes on with?  (The host form
+// asks before it stages anything over the resident inputs.)
+static int check_factored_call(enlsip_gn_handle h, const BatchOperands& v, const int64_t* refactor, bool host_form) {
+    const long long batch = v.batch;
+    const auto& F = h->fb;
+    auto resident = [&](enlsip_gn_handle hh, long long cnt) {
+        return hh && hh->factors_valid && hh->constraints_only && hh->have_plan && hh->plan.batch == cnt && hh->plan.m == v.m &&
+               hh->plan.n == v.n && hh->plan.t == v.t;
+    };
+    bool ok = F.valid && F.host == host_form && F.batch == batch && F.m == v.m && F.n == v.n && F.t == v.t;
+    if (ok) ok = F.split > 0 ? (resident(h, F.split) && resident(h->child, batch - F.split)) : resident(h, batch);
+    if (!ok) {
+        h->err = "enlsip_gn_solve_factored_batched needs enlsip_gn_factor_constraints_batched (same form, host or device) with the same "
+                 "batch, m, n, t_max right before";
+        return -1;
+    }
+    for (long long k = 0; k < batch; ++k)
+        if (!(refactor && refactor[k]) && v.tk[k] != F.tk[(size_t)k]) {
+            h->err = "t[" + std::to_string(k) + "] = " + std::to_string(v.tk[k]) + " but problem " + std::to_string(k) +
+                     " was factored with " + std::to_string(F.tk[(size_t)k]) + " constraints and has no refactor flag";
+            return -6;
+        }
+    return 0;
+}
+
+// Both forms of enlsip_gn_solve_factored_batched (v: device buffers) after check_factored_call: which problems get their constraint
+// stage again, and the solve over the same halves.
+static int solve_factored_core(enlsip_gn_handle h, const BatchOperands& v, const int64_t* refactor, double eps_rank, bool host_form) {
+    const long long batch = v.batch;
+    auto& F = h->fb;
+    if (!host_form && v.t > 0 && (v.At != F.At || v.ldat != F.ldat || v.strideAt != F.strideAt || v.cx != F.cx)) {
+        h->err = "dAt, ldat, strideAt, dcx must be the buffers of the enlsip_gn_factor_constraints_batched_dev call (the slots of the "
+                 "problems with a refactor flag rewritten in place)";
+        return -11;
+    }
+    const long long b0 = F.split > 0 ? F.split : batch;
+    h->refit.clear();
+    if (F.split > 0) h->child->refit.clear();
+    for (long long k = 0; refactor && k < batch; ++k)
+        if (refactor[k]) (k < b0 ? h : h->child)->refit.push_back((int)(k < b0 ? k : k - b0));
+    h->chunk0 = 0;
+    h->reuse_once = true;
+    const int rc = solve_launchable(h, v, eps_rank, -1, -1);
+    h->reuse_once = false;
+    if (F.split > 0) h->child->reuse_once = false;
+    F.valid = false;
+    if (rc) return rc;
+    h->constraint_refactored = h->cstage_problems + (h->split > 0 ? h->child->cstage_problems : 0);
+    return 0;
+}
+
+static int check_launch_batch(enlsip_gn_handle h, int64_t batch) {
+    if (batch > GN_MAX_LAUNCH_BATCH) {
+        h->err = "batch above the launch limit (" + std::to_string(GN_MAX_LAUNCH_BATCH) + "): only the last chunk's factors would "
+                 "stay resident, so the constraint stage cannot be kept for a following solve";
+        return -2;
+    }
+    return 0;
+}
+
+int enlsip_gn_factor_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                             const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx, double eps_rank,
+                                             enlsip_gn_info* dinfo) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    int rc = check_ragged(h, batch, m, n, t_max, t, nullptr, 0, nullptr, dAt, ldat, strideAt, dcx, tk, false, true, true);
+    if (rc) return rc;
+    rc = check_launch_batch(h, batch);
+    if (rc) return rc;
+    BatchOperands v{batch, m, n, t_max};
+    v.At = dAt; v.ldat = ldat; v.strideAt = strideAt; v.cx = dcx; v.dinfo = dinfo; v.tk = tk.data();
+    return factor_batched_core(h, v, eps_rank, false);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_factor_constraints_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                         const double* At, int64_t ldat, int64_t strideAt, const double* cx, double eps_rank,
+                                         enlsip_gn_info* info) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    int rc = check_ragged(h, batch, m, n, t_max, t, nullptr, 0, nullptr, At, ldat, strideAt, cx, tk, false, true, true);
+    if (rc) return rc;
+    rc = check_launch_batch(h, batch);
+    if (rc) return rc;
+    GN_HIP(hipSetDevice(h->device));
+    // the staging layout of solve_host for this batch, whole: the solve that follows finds A', cx in their slots (and must not grow it)
+    const size_t inJ = (size_t)batch * m * n, inAt = (size_t)batch * n * t_max;
+    rc = grow(h, h->in_stage, (inJ + (size_t)batch * m + inAt + (size_t)batch * t_max) * 8 + 1024);
+    if (rc) return rc;
+    double* dAt = (double*)h->in_stage.p + inJ + (size_t)batch * m;
+    double* dcx = dAt + inAt;
+    hipStream_t s = h->stream;
+    if (t_max > 0) {
+        for (int64_t k = 0; k < batch; ++k)
+            GN_HIP(hipMemcpy2DAsync(dAt + (size_t)k * n * t_max, (size_t)n * 8, At + (size_t)k * strideAt, (size_t)ldat * 8, (size_t)n * 8,
+                                    (size_t)t_max, hipMemcpyHostToDevice, s));
+        GN_HIP(hipMemcpyAsync(dcx, cx, (size_t)batch * t_max * 8, hipMemcpyHostToDevice, s));
+    }
+    BatchOperands v{batch, m, n, t_max};
+    v.At = dAt; v.ldat = n; v.strideAt = n * t_max; v.cx = dcx; v.hinfo = info; v.tk = tk.data();
+    return factor_batched_core(h, v, eps_rank, true);
+    GN_CATCH(h)
+}
+
+// the refactor flags decide whether A', cx are looked at at all
+static bool any_flag(const int64_t* refactor, int64_t batch) {
+    for (int64_t k = 0; refactor && k < batch; ++k)
+        if (refactor[k]) return true;
+    return false;
+}
+
+int enlsip_gn_solve_factored_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                     const int64_t* refactor, const double* J, int64_t ldj, int64_t strideJ, const double* rx,
+                                     const double* At, int64_t ldat, int64_t strideAt, const double* cx, double eps_rank, double* p,
+                                     double* b, double* d, enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    int rc = check_ragged(h, batch, m, n, t_max, t, J, ldj, rx, At, ldat, strideAt, cx, tk, true, any_flag(refactor, batch), true);
+    if (rc) return rc;
+    rc = check_launch_batch(h, batch);
+    if (rc) return rc;
+    BatchOperands shape{batch, m, n, t_max};
+    shape.tk = tk.data();
+    rc = check_factored_call(h, shape, refactor, true);
+    if (rc) return rc;
+    return solve_host(h, {batch, m, n, t_max, J, ldj, strideJ, rx, At, ldat, strideAt, cx, p, b, d, nullptr, (long long*)jpvtA,
+                          (long long*)jpvtL, (long long*)jpvtJ2, info, tk.data()}, eps_rank, -1, -1, true, true, refactor);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_solve_factored_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                         const int64_t* refactor, const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
+                                         const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx, double eps_rank,
+                                         double* dp, double* db, double* dd, enlsip_gn_info* dinfo, int64_t* djpvtA, int64_t* djpvtL,
+                                         int64_t* djpvtJ2) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    int rc = check_ragged(h, batch, m, n, t_max, t, dJ, ldj, drx, dAt, ldat, strideAt, dcx, tk, true, any_flag(refactor, batch), true);
+    if (rc) return rc;
+    rc = check_launch_batch(h, batch);
+    if (rc) return rc;
+    BatchOperands shape{batch, m, n, t_max};
+    shape.tk = tk.data();
+    rc = check_factored_call(h, shape, refactor, false);
+    if (rc) return rc;
+    return solve_factored_core(h, {batch, m, n, t_max, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, dp, db, dd, dinfo,
+                                   (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()},
+                               refactor, eps_rank, false);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_get_constraint_refactored(enlsip_gn_handle h, int64_t* count) {
+    if (!h) return -1;
+    if (!count) return -2;
+    *count = (int64_t)h->constraint_refactored;
+    return 0;
 }
 
 int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* J, int64_t ldj,

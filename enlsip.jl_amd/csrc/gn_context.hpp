@@ -160,6 +160,23 @@ struct enlsip_gn_context {
     // solve.  The device copy is what the RAGGED forms of the constraint kernels read; the host copy answers the accessors.
     std::vector<int> h_tk;
     gn::DevBuf tkbuf;
+    // Batched constraint stage (enlsip_gn_factor_constraints_batched*) and the solve that goes on with it
+    // (enlsip_gn_solve_factored_batched*).  On the handle the caller holds: what the constraint call was made with, so that the solve
+    // can tell whether it follows it — shape, pipeline split, each problem's t, the input buffers (device form: the caller's; host
+    // form: the staging area).  On every handle that runs a part (parent, pipeline child): the problems of its part whose
+    // constraint stage the next solve_dev runs again (indices in its part; device copy in plist_buf), and the number of problems
+    // the constraint kernels of its last call were launched over.
+    struct {
+        bool valid = false, host = false;
+        long long batch = 0, m = 0, n = 0, t = 0, split = 0;
+        const double* At = nullptr; long long ldat = 0, strideAt = 0;
+        const double* cx = nullptr;
+        std::vector<int> tk;
+    } fb;
+    std::vector<int> refit;
+    gn::DevBuf plist_buf;
+    long long cstage_problems = 0;
+    long long constraint_refactored = 0;   // ... summed over the handles (enlsip_gn_get_constraint_refactored)
     unsigned long long route = 0;       // ENLSIP_GN_ROUTE_* bits of the last solve (enlsip_gn_get_route)
     long long chunk0 = 0;               // first problem (index in the caller's batch) of the resident chunk: batches above the launch limit run in chunks
     long long tsqr_n2 = -1;             // n2 of the last tsqr_local on this handle

@@ -42,6 +42,10 @@ struct ProbState {
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 
+// The problem a workgroup of a batched constraint kernel works on: entry `idx` of a device list of problem indices (a launch over
+// a SUBSET of the resident batch, grid = the list's length), or idx + prob0 without one.
+__device__ __forceinline__ int listed_prob(const int* __restrict__ plist, int idx, int prob0) { return plist ? plist[idx] : idx + prob0; }
+
 // Orders memory traffic between the LANES OF ONE WAVE: loads that follow may read what other lanes of the wave stored
 // before.  Without it the compiler, which reasons per lane, may hoist a load above another lane's (conditional) store of
 // the same address and forward the stored value only inside the storing lane.  Costs a waitcnt, no barrier instruction.

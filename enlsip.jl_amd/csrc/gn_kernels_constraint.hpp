@@ -22,6 +22,7 @@ struct ConstraintArgs {
     int dimA_override;   // -1 = rankA
     int code_override;   // 0 = derive from rankA; +1 / -1 force (resolve path)
     int prob0;           // problem index offset
+    const int* plist;    // device list of problem indices, one per workgroup (NULL: workgroup i = problem i + prob0)
     int fa_done;         // 1: F_A, tau_A, jpvt_A and the block T factor were produced by k_geqp3_reg
     int nv, blkd, gld, matd;   // LDS carve in doubles (constraint_carve)
     // many constraints (run_constraint_dist): both factorisations were produced by the distributed pivoted QR
@@ -76,7 +77,7 @@ __device__ __forceinline__ void constraint_body(const ConstraintArgs& a, const i
     double* mat = gl + a.gld;
     int* sh_i = reinterpret_cast<int*>(mat + a.matd);
 
-    const int prob = blockIdx.x + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.x, a.prob0);
     const int n = a.n;
     const int t = RAGGED ? tk[prob] : a.t;
     const int kA = RAGGED ? (n < t ? n : t) : a.kA;

@@ -7,11 +7,12 @@
 
 namespace gn {
 
+// plist (every kernel of this file with a problem per grid row): device list of problem indices, NULL = row y is problem y
 // dst[r + c * ldd] = src[r + c * lds], r < rows, c < cols, per problem
 __global__ __launch_bounds__(256) void k_copy_cols(double* __restrict__ dst, long long ldd, long long sD, const double* __restrict__ src,
-                                                   long long lds, long long sS, int rows, int cols) {
+                                                   long long lds, long long sS, int rows, int cols, const int* __restrict__ plist) {
     const int c = blockIdx.x;
-    const int prob = blockIdx.y;
+    const int prob = listed_prob(plist, blockIdx.y, 0);
     if (c >= cols) return;
     double* d = dst + prob * sD + (size_t)c * ldd;
     const double* s = src + prob * sS + (size_t)c * lds;
@@ -20,8 +21,9 @@ __global__ __launch_bounds__(256) void k_copy_cols(double* __restrict__ dst, lon
 
 // b_buff[i] = -cx[F_A.p[i]]   (src/enlsip_functions.jl:131 / :141)
 __global__ __launch_bounds__(256) void k_bbuff(double* __restrict__ out, long long sOut, const double* __restrict__ cx, long long sCx,
-                                               const long long* __restrict__ jpvt, long long sJ, int t) {
-    const int prob = blockIdx.y;
+                                               const long long* __restrict__ jpvt, long long sJ, int t,
+                                               const int* __restrict__ plist) {
+    const int prob = listed_prob(plist, blockIdx.y, 0);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < t) out[prob * sOut + i] = -cx[prob * sCx + jpvt[prob * sJ + i] - 1];
 }
@@ -43,9 +45,10 @@ __global__ __launch_bounds__(256) void k_fake_state(ProbState* st, int batch, in
 // mode 2 (F_L11.Q' b_buff): column kA of src (the carried column sits right of the problem's own kA columns), tk rows
 __global__ __launch_bounds__(256) void k_copy_cols_ragged(double* __restrict__ dst, long long ldd, long long sD,
                                                           const double* __restrict__ src, long long lds, long long sS, int rows,
-                                                          int cols_max, int n, const int* __restrict__ tk, int mode) {
+                                                          int cols_max, int n, const int* __restrict__ tk, int mode,
+                                                          const int* __restrict__ plist) {
     const int c = blockIdx.x;
-    const int prob = blockIdx.y;
+    const int prob = listed_prob(plist, blockIdx.y, 0);
     const int t = tk[prob], kA = n < t ? n : t;
     if (mode == 0) {
         if (c >= cols_max) return;
@@ -68,8 +71,8 @@ __global__ __launch_bounds__(256) void k_copy_cols_ragged(double* __restrict__ d
 // b_buff[i] = -cx[F_A.p[i]] for i < tk, 0 up to t (the padded rows of the F_L11 factorisation must be zero)
 __global__ __launch_bounds__(256) void k_bbuff_ragged(double* __restrict__ out, long long sOut, const double* __restrict__ cx,
                                                       long long sCx, const long long* __restrict__ jpvt, long long sJ, int t,
-                                                      const int* __restrict__ tk) {
-    const int prob = blockIdx.y;
+                                                      const int* __restrict__ tk, const int* __restrict__ plist) {
+    const int prob = listed_prob(plist, blockIdx.y, 0);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < t) out[prob * sOut + i] = (i < tk[prob]) ? -cx[prob * sCx + jpvt[prob * sJ + i] - 1] : 0.0;
 }

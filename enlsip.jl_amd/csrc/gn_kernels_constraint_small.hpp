@@ -27,7 +27,8 @@ template <int NR, bool RAGGED>
 __device__ __forceinline__ void constraint_small_body(const ConstraintArgs& a, const int* tk) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int n = a.n;
-    const int t = RAGGED ? tk[blockIdx.x + a.prob0] : a.t;
+    const int prob = listed_prob(a.plist, blockIdx.x, a.prob0);
+    const int t = RAGGED ? tk[prob] : a.t;
     const int kA = RAGGED ? (n < t ? n : t) : a.kA;
     const int kd = kA > 0 ? kA : 1;
     double* tmp = smem;
@@ -36,7 +37,6 @@ __device__ __forceinline__ void constraint_small_body(const ConstraintArgs& a, c
     double* gcol = dg + 64;
     double* tail = gcol + 64;
     double* Tl = tail + 64;
-    const int prob = blockIdx.x + a.prob0;
     const double* At = a.At + prob * a.strideAt;
     const double* cx = a.cx + prob * a.stride_cx;
     double* FA = a.FA + prob * a.sFA;

@@ -19,6 +19,7 @@ struct Geqp3RegArgs {
     long long* jpvt;  long long sJ;
     double* T;        long long sT;      // 64 x 64 block T factor (column-major, zero padded); may be null
     int prob0;
+    const int* plist;          // device list of problem indices, one per workgroup (NULL: workgroup i = problem i + prob0)
 };
 
 // RAGGED: the problem's own column count tk[prob]; the padding of F, tau and jpvt up to a.cols is left to the k_constraint
@@ -31,7 +32,7 @@ __device__ __forceinline__ void geqp3_reg_body(const Geqp3RegArgs& a, const int*
     __shared__ int cpos[2][64], colat[64], tslot[64];
     __shared__ double gram[64 * 65];
     __shared__ double tau_s[2], beta_s[2];
-    const int prob = blockIdx.x + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.x, a.prob0);
     const int rows = a.rows;
     const int cols = RAGGED ? tk[prob] : a.cols;
     const int tid = threadIdx.x, ln = lane_id();

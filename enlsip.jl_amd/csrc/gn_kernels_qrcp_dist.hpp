@@ -52,6 +52,7 @@ struct QdArgs {
     const double* Ain; long long ldain, sAin;
     const double* rin; long long sRin;
     double* Lout;      long long sLout;
+    const int* plist;  // device list of problem indices, one per grid row y (NULL: row y = problem y + prob0)
     int hyb;           // k_qd_assemble after a hybrid stage (run_qrcp_block with a launch-per-step head of `hyb` steps, hyb even): a
                        // problem that finished inside the head keeps its maps in the parity of its step count, the others in 0
 };
@@ -70,7 +71,7 @@ template <int RPL>
 __global__ __launch_bounds__(256) void k_qd_init(QdArgs a) {
     __shared__ double cval[QD_CPW];
     __shared__ int cpos[QD_CPW];
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const ProbState st = a.state[prob];
     if (a.n2cap > 0 && st.n2 > a.n2cap) return;
     const int n2 = st.n2, ctot = n2 + 1;
@@ -166,7 +167,7 @@ template <int RPL>
 __global__ __launch_bounds__(256) void k_qd_step(QdArgs a) {
     __shared__ double cval[QD_CPW];
     __shared__ int cpos[QD_CPW];
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const ProbState st = a.state[prob];
     if (a.n2cap > 0 && st.n2 > a.n2cap) return;
     const int n2 = st.n2, ctot = n2 + 1;
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(256) void k_qd_step(QdArgs a) {
 
 // gather the LAPACK-style compact factors in pivoted order + jpvt
 __global__ __launch_bounds__(256) void k_qd_assemble(QdArgs a) {
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const ProbState st = a.state[prob];
     if (a.n2cap > 0 && st.n2 > a.n2cap) return;
     const int n2 = st.n2, ctot = n2 + 1;

@@ -409,6 +409,61 @@ function gn_search_direction_batched_hip(h::Handle, Js::Array{Float64,3}, rxs::M
     return P, infos
 end
 
+# ---- the batched constraint stage and the solve that goes on with it (src/enlsip_functions.jl:700-704, then :725 / :771) ----------
+
+# n×t_max×B / t_max×B padded copies of every problem's C.A' and cx (slice k: its first t_k columns / entries)
+function pack_working_sets(n::Integer, t_max::Integer, As::Vector{Matrix{Float64}}, cxs::Vector{Vector{Float64}})
+    B = length(As)
+    t = Int64[size(A, 1) for A in As]
+    all(tk -> tk <= t_max, t) || error("a working set has more than t_max = $t_max constraints")
+    Ats = zeros(Float64, n, max(t_max, 1), B)
+    cxp = zeros(Float64, max(t_max, 1), B)
+    for k in 1:B
+        t[k] > 0 || continue
+        Ats[:, 1:t[k], k] = permutedims(As[k], (2, 1))
+        cxp[1:t[k], k] = cxs[k]
+    end
+    return t, Ats, cxp
+end
+
+"""    factor_constraints_batched_hip(h, m, n, t_max, As, cxs, ε_rank) -> infos
+
+`F_A = qr(C.A', ColumnNorm())` (src/enlsip_functions.jl:700), rankA and `F_L11` (:768-769) of every problem of a batch, nothing about
+J: what a batched update_working_set needs before the deletion test (:704, `first_lagrange_batched_hip` with `grad_fx`).  `t_max` is
+the padding both calls of the pair share; `m` the row count of the solve that follows."""
+function factor_constraints_batched_hip(h::Handle, m::Integer, n::Integer, t_max::Integer, As::Vector{Matrix{Float64}},
+                                        cxs::Vector{Vector{Float64}}, ε_rank::Float64)
+    B = length(As)
+    t, Ats, cxp = pack_working_sets(n, t_max, As, cxs)
+    infos = fill(Info(0, 0, 0, 0, 0, 0), B)
+    GC.@preserve t Ats cxp infos check(h, ccall((:enlsip_gn_factor_constraints_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64, Ptr{Info}),
+        h.ptr, B, m, n, t_max, t, Ats, max(n, 1), n * max(t_max, 1), cxp, ε_rank, infos))
+    return infos
+end
+
+"""    gn_search_direction_factored_batched_hip(h, Js, rxs, t_max, As, cxs, refactor, ε_rank) -> (P, infos)
+
+The Jacobian side right after `factor_constraints_batched_hip` (same `t_max`): problems with `refactor[k]` false keep their
+constraint stage (`As[k]` must have the row count it was factored with and is not read), the others get theirs again from `As[k]`,
+`cxs[k]` first.  Results per problem as `gn_search_direction_batched_hip` on the final working sets."""
+function gn_search_direction_factored_batched_hip(h::Handle, Js::Array{Float64,3}, rxs::Matrix{Float64}, t_max::Integer,
+                                                  As::Vector{Matrix{Float64}}, cxs::Vector{Vector{Float64}},
+                                                  refactor::AbstractVector{Bool}, ε_rank::Float64)
+    m, n, B = size(Js)
+    kA = min(n, t_max)
+    t, Ats, cxp = pack_working_sets(n, t_max, As, cxs)
+    flags = Int64[r ? 1 : 0 for r in refactor]
+    P = zeros(Float64, n, B); b = zeros(Float64, max(t_max, 1), B); d = zeros(Float64, m, B)
+    jA = zeros(Int64, max(t_max, 1), B); jL = zeros(Int64, max(kA, 1), B); jJ = zeros(Int64, n, B)
+    infos = fill(Info(0, 0, 0, 0, 0, 0), B)
+    GC.@preserve Js rxs t flags Ats cxp P b d jA jL jJ infos check(h, ccall((:enlsip_gn_solve_factored_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64,
+         Int64, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Info}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        h.ptr, B, m, n, t_max, t, flags, Js, m, m * n, rxs, Ats, max(n, 1), n * max(t_max, 1), cxp, ε_rank, P, b, d, infos, jA, jL, jJ))
+    return P, infos
+end
+
 # ---- the consumers of a batched solve over a range of its problems (one call, a fixed number of launches) ----------------------
 #
 # A batched outer iteration: solve (ragged), first estimate over the batch, the host deletion test of update_working_set

@@ -273,6 +273,110 @@ class GNSolver:
             self._h, batch, m, n, t_max, t.ctypes.data_as(C.c_void_p), v(dJ), ldj, strideJ, v(drx), v(dAt), ldat, strideAt,
             v(dcx), eps_rank, v(dp), v(db), v(dd), v(dinfo), v(djA), v(djL), v(djJ)))
 
+    # ---- batched constraint stage and the solve that goes on with it (src/enlsip_functions.jl:700-704, then :725 / :771) ----------
+    @staticmethod
+    def _ragged_A(At, cx, t, n: Optional[int] = None):
+        """Checked (At (batch, t_max, n) float64 C-order, cx (batch, t_max), t int64 (batch,)) of the padded ragged layout."""
+        At = np.asarray(At, dtype=np.float64)
+        if At.ndim != 3:
+            raise ValueError("At must be (batch, t_max, n) (pack_ragged builds it)")
+        batch, t_max, nn = At.shape
+        if n is not None and nn != n:
+            raise ValueError(f"At has {nn} columns per constraint, J has n = {n}")
+        cx = np.asarray(cx, dtype=np.float64)
+        if cx.shape != (batch, t_max):
+            raise ValueError(f"cx must be ({batch}, {t_max}), got {cx.shape}")
+        t = np.full(batch, t_max, dtype=np.int64) if t is None else np.ascontiguousarray(t, dtype=np.int64)
+        if t.shape != (batch,):
+            raise ValueError(f"t must have {batch} entries")
+        if np.any(t < 0) or np.any(t > t_max):
+            raise ValueError(f"every t[k] must lie in 0..t_max = {t_max}")
+        return np.ascontiguousarray(At), np.ascontiguousarray(cx), t
+
+    @staticmethod
+    def _refactor_mask(refactor, batch: int):
+        if refactor is None:
+            return None
+        r = np.ascontiguousarray(np.asarray(refactor).astype(np.int64))
+        if r.shape != (batch,):
+            raise ValueError(f"refactor must have {batch} entries")
+        return r
+
+    def factor_constraints_batched(self, m: int, At: np.ndarray, cx: np.ndarray, t=None, eps_rank: float = SQRT_EPS):
+        """Constraint stage of a whole ragged batch, nothing about J: At (batch, t_max, n), cx (batch, t_max), t (batch,) or None
+        (all t_max), m: rows of the solve that follows.  Leaves F_A, F_L11 of every problem resident (first_lagrange_batched with
+        grad_fx, the F_A / F_L11 accessors).  Returns [(rankA, code, dimA), ...]."""
+        At, cx, t = self._ragged_A(At, cx, t)
+        batch, t_max, n = At.shape
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        info = (L.Info * batch)()
+        self._chk(self._lib.enlsip_gn_factor_constraints_batched(
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(At) if t_max else None, max(n, 1), n * t_max,
+            _fptr(cx) if t_max else None, eps_rank, C.cast(info, C.c_void_p)))
+        return [(int(i.rankA), int(i.code), int(i.dimA)) for i in info]
+
+    def factor_constraints_batched_dev(self, batch, m, n, t_max, t, dAt, ldat, strideAt, dcx, eps_rank=SQRT_EPS, dinfo=0):
+        """Device pointers; t stays a host array of batch entries (None: all t_max)."""
+        v = lambda x: C.c_void_p(x) if x else None
+        if t is not None:
+            t = np.ascontiguousarray(t, dtype=np.int64)
+            if t.shape != (batch,):
+                raise ValueError(f"t must have {batch} entries")
+        self._chk(self._lib.enlsip_gn_factor_constraints_batched_dev(
+            self._h, batch, m, n, t_max, _fptr(t), v(dAt), ldat, strideAt, v(dcx), eps_rank, v(dinfo)))
+
+    def solve_factored_batched(self, J: np.ndarray, rx: np.ndarray, At: np.ndarray, cx: np.ndarray, t=None, refactor=None,
+                               eps_rank: float = SQRT_EPS):
+        """The Jacobian side right after factor_constraints_batched: arguments and results as solve_batched_ragged, plus
+        refactor (batch,) flags or None.  A problem without a flag keeps its constraint stage (its t[k] must be the factored
+        one, its At / cx rows are not read); a flagged problem gets its stage again from its At / cx rows and t[k]."""
+        J = np.asarray(J, dtype=np.float64)
+        if J.ndim != 3:
+            raise ValueError("J must be (batch, n, m)")
+        batch, n, m = J.shape
+        At, cx, t = self._ragged_A(At, cx, t, n)
+        if At.shape[0] != batch:
+            raise ValueError(f"At holds {At.shape[0]} problems, J {batch}")
+        rx = np.ascontiguousarray(rx, dtype=np.float64)
+        if rx.shape != (batch, m):
+            raise ValueError(f"rx must be ({batch}, {m})")
+        r = self._refactor_mask(refactor, batch)
+        t_max = At.shape[1]
+        kA = min(n, t_max)
+        J = np.ascontiguousarray(J)
+        p, b, d = np.zeros((batch, n)), np.zeros((batch, t_max)), np.zeros((batch, m))
+        jA = np.zeros((batch, t_max), np.int64)
+        jL = np.zeros((batch, kA), np.int64)
+        jJ = np.zeros((batch, n), np.int64)
+        info = (L.Info * batch)()
+        self._chk(self._lib.enlsip_gn_solve_factored_batched(
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(r), _fptr(J), m, m * n, _fptr(rx),
+            _fptr(At) if t_max else None, max(n, 1), n * t_max, _fptr(cx) if t_max else None, eps_rank,
+            _fptr(p), _fptr(b), _fptr(d), C.cast(info, C.c_void_p), _fptr(jA), _fptr(jL), _fptr(jJ)))
+        infos = [(int(i.rankA), int(i.rankJ2), int(i.code), int(i.dimA), int(i.dimJ2), int(i.status)) for i in info]
+        return p, b, d, infos, jA, jL, jJ
+
+    def solve_factored_batched_dev(self, batch, m, n, t_max, t, refactor, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx,
+                                   eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):
+        """Device pointers as solve_batched_ragged_dev; t and refactor stay host arrays.  dAt, ldat, strideAt, dcx are those of
+        factor_constraints_batched_dev, the flagged problems' slots rewritten in place."""
+        v = lambda x: C.c_void_p(x) if x else None
+        if t is not None:
+            t = np.ascontiguousarray(t, dtype=np.int64)
+            if t.shape != (batch,):
+                raise ValueError(f"t must have {batch} entries")
+        r = self._refactor_mask(refactor, batch)
+        self._chk(self._lib.enlsip_gn_solve_factored_batched_dev(
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(r), v(dJ), ldj, strideJ, v(drx), v(dAt), ldat, strideAt, v(dcx),
+            eps_rank, v(dp), v(db), v(dd), v(dinfo), v(djA), v(djL), v(djJ)))
+
+    def constraint_refactored(self) -> int:
+        """Problems the constraint kernels of the last factor_constraints_batched / solve_factored_batched were launched over."""
+        c = C.c_int64(0)
+        self._chk(self._lib.enlsip_gn_get_constraint_refactored(self._h, C.byref(c)))
+        return int(c.value)
+
     # ---- batch, device buffers (raw pointers, e.g. torch tensor .data_ptr()) ------------------
     def solve_batched_dev(self, batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx,
                           eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):

@@ -237,3 +237,118 @@ def update_working_set(solver: GNSolver, W: WorkingSet, rx, A, C: Constraint, gr
         rankA, lam = _second_order(rankA, lam)
     it.lam = lam
     return _views()
+
+
+# ---- update_working_set for a batch (src/enlsip_functions.jl:686-795 per problem) -----------------------
+def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p_gns, its, eps_rank: float):
+    """``update_working_set`` for B problems of one shape (m, n) with the batched calls: the constraint stage of the whole batch
+    (:700), the first estimate (:704), the host deletion test, then the Jacobian side on the working sets that survived (:725 /
+    :771), with the constraint stage run again only for the problems whose set changed.  ``A`` is the full (l x n) constraint
+    Jacobian of every problem (a list, or one matrix shared by all).  Leaves in ``Ws[k]``, ``Cs[k]``, ``its[k]``, ``p_gns[k]``
+    what ``update_working_set`` leaves for problem k and returns the (F_A, F_L11, F_J2) views per problem; the whole batch is
+    resident afterwards.  A later change of some working set (the undo of :728-743, a second-order deletion :745 / :773) takes the
+    pair of calls again on the final sets; the Jacobian side of the unchanged problems is then recomputed with the same result."""
+    B = len(Ws)
+    m, n = Js[0].shape
+    As_full = A if isinstance(A, (list, tuple)) else [A] * B
+    J = np.stack([np.asfortranarray(Jk, dtype=np.float64).T for Jk in Js])        # (B, n, m): problem k column-major
+    rx = np.stack([np.asarray(r, dtype=np.float64) for r in rxs])
+    G = np.stack([np.asarray(g, dtype=np.float64) for g in grad_fxs])
+
+    def packed():
+        Ak = [np.asarray(C.A, dtype=np.float64).reshape(-1, n) for C in Cs]
+        return GNSolver.pack_ragged(Ak, [C.cx for C in Cs], n=n)
+
+    def scales(t_max):
+        if not any(C.scaling for C in Cs):
+            return None
+        ds = np.ones((B, max(t_max, 1)))
+        for k, C in enumerate(Cs):
+            if C.scaling:
+                ds[k, :Ws[k].t] = C.diag_scale
+        return ds[:, :t_max] if t_max else None
+
+    def take(out, ks):
+        p, b, d, infos = out[:4]
+        for k in ks:
+            p_gns[k][:] = p[k]
+            its[k].rankA, its[k].rankJ2 = infos[k][0], infos[k][1]
+            its[k].dimA, its[k].dimJ2 = infos[k][0], infos[k][1]
+            its[k].b_gn, its[k].d_gn = b[k, :Ws[k].t].copy(), d[k].copy()
+
+    def solve_again(ks):
+        """the pair of calls on the current working sets; results taken for the problems ks"""
+        At, cx, t = packed()
+        solver.factor_constraints_batched(m, At, cx, t, eps_rank)
+        take(solver.solve_factored_batched(J, rx, At, cx, t, None, eps_rank), ks)
+        return At.shape[1]
+
+    At, cx, t = packed()
+    t_max = At.shape[1]
+    solver.factor_constraints_batched(m, At, cx, t, eps_rank)                               # :700
+    lam_b, gres, _, _ = solver.first_lagrange_batched(t_max, 0, B, G, scales(t_max), eps_rank)   # :704
+    lams, removed = [], {}
+    for k in range(B):
+        W, C, it = Ws[k], Cs[k], its[k]
+        lam = lam_b[k, :W.t].copy()
+        it.grad_res = float(gres[k])
+        s = check_constraint_deletion(W.q, C.A, lam, C.scaling, C.diag_scale, it.grad_res)
+        if s != 0:                                                                          # :706-723
+            removed[k] = (s, C.cx[s - 1], C.A[s - 1, :].copy(), lam[s - 1], C.diag_scale[s - 1], int(W.active[s - 1]))
+            lam = np.delete(lam, s - 1)
+            C.cx = np.delete(C.cx, s - 1)
+            C.diag_scale = np.delete(C.diag_scale, s - 1)
+            W.remove_constraint(s)
+            it.delete = True
+            it.index_del = removed[k][5]
+            C.A = np.delete(C.A, s - 1, axis=0)
+        lams.append(lam)
+    flags = np.array([1 if k in removed else 0 for k in range(B)], dtype=np.int64)
+    At, cx, t = packed()
+    if At.shape[1] != t_max:        # every longest working set lost a row: the padded layout of the factor call stays
+        pad = t_max - At.shape[1]
+        At = np.concatenate([At, np.zeros((B, pad, n))], axis=1)
+        cx = np.concatenate([cx, np.zeros((B, pad))], axis=1)
+    take(solver.solve_factored_batched(J, rx, At, cx, t, flags, eps_rank), range(B))        # :725 / :771
+    undone = []
+    for k, (s, cx_s, A_s, lam_s, ds_s, index_s) in removed.items():                         # :728-743
+        W, C, it = Ws[k], Cs[k], its[k]
+        As_p = 0.0 if it.rankA <= W.t else float(A_s @ p_gns[k])                            # quirk Q1
+        if (As_p >= -cx_s) and (As_p > 0):
+            continue
+        C.cx = np.insert(C.cx, s - 1, cx_s)
+        lams[k] = np.insert(lams[k], s - 1, lam_s)
+        C.diag_scale = np.insert(C.diag_scale, s - 1, ds_s)
+        W.add_constraint(int(np.where(W.inactive == index_s)[0][0]) + 1)
+        it.index_del = 0
+        it.delete = False
+        rows = As_full[k][W.active[: W.t] - 1, :]
+        C.A = rows * C.diag_scale[:, None] if C.scaling else rows.copy()
+        undone.append(k)
+    if undone:
+        t_max = solve_again(undone)
+    # second-order estimate where :745 / :773 ask for it: the problems that kept their set or got it back
+    cand = [k for k in range(B) if (k not in removed or k in undone)
+            and not (Ws[k].t != its[k].rankA or its[k].rankJ2 != min(m, n - its[k].rankA))]
+    if cand:
+        lam2, _, _ = solver.second_lagrange_batched(t_max, np.stack(p_gns), 0, scales(t_max))
+        dropped = []
+        for k in cand:
+            W, C, it = Ws[k], Cs[k], its[k]
+            lam = lam2[k, :W.t].copy()
+            s2 = check_constraint_deletion(W.q, C.A, lam, C.scaling, C.diag_scale, 0.0)
+            if s2 != 0:
+                it.index_del = int(W.active[s2 - 1])
+                lam = np.delete(lam, s2 - 1)
+                C.diag_scale = np.delete(C.diag_scale, s2 - 1)
+                C.cx = np.delete(C.cx, s2 - 1)
+                W.remove_constraint(s2)
+                it.delete = True
+                C.A = np.delete(C.A, s2 - 1, axis=0)
+                dropped.append(k)
+            lams[k] = lam
+        if dropped:
+            solve_again(dropped)
+    for k in range(B):
+        its[k].lam = lams[k]
+    return [(solver.factor(FACTOR_A, k), solver.factor(FACTOR_L11, k), solver.factor(FACTOR_J2, k)) for k in range(B)]

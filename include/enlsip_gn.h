@@ -193,6 +193,61 @@ int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_
                                        double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
                                        int64_t* djpvtA, int64_t* djpvtL, int64_t* djpvtJ2);
 
+/*
+ * The constraint stage of a whole ragged batch, nothing about J: F_A = qr(C.A', ColumnNorm()) (src/enlsip_functions.jl:700), rankA
+ * (:768, :17-31), F_L11 (:769), b, p1 and the block T of Q1 of every problem, left resident — what a batched update_working_set
+ * needs BEFORE it decides which constraint each problem drops (:700-704).  Packing, strides, padding and error numbering are those
+ * of enlsip_gn_solve_batched_ragged without its J, rx arguments' checks; t is a HOST array in both forms, NULL = every problem has
+ * t_max constraints.  m is the row count of the solve that follows.  Afterwards the handle holds only F_A / F_L11 for all `batch`
+ * problems: info[k] carries rankA, code, dimA (J fields zero); the FACTOR_A / FACTOR_L11 accessors, apply_q / apply_qt and
+ * enlsip_gn_get_diagR_batched answer per problem with its own t[k]; enlsip_gn_first_lagrange_batched* answers over any range when
+ * grad_fx is given (pipelined halves included); everything that needs J reports "only F_A / F_L11 are resident".  A problem whose
+ * A', cx lie beyond the plain magnitude range is factored on a one-problem handle of its own (the magnitude contract above).
+ * A batch above the launch limit (32768) returns -2: only its last chunk would stay resident.
+ */
+int enlsip_gn_factor_constraints_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                         const double* At, int64_t ldat, int64_t strideAt, const double* cx,
+                                         double eps_rank, enlsip_gn_info* info);
+/* Same, DEVICE buffers (t stays a HOST array; dinfo DEVICE or NULL). */
+int enlsip_gn_factor_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                             const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
+                                             double eps_rank, enlsip_gn_info* dinfo);
+
+/*
+ * The Jacobian side on that resident constraint stage (src/enlsip_functions.jl:725 / :771: gn_search_direction on the working set
+ * that survived the deletion test).  Needs enlsip_gn_factor_constraints_batched (same form, host or device) with the same batch, m,
+ * n, t_max right before: -1 otherwise.  refactor is a HOST array of `batch` flags, NULL = none.  A problem with refactor[k] == 0
+ * keeps its constraint stage and must come with the t[k] it was factored with (-6 names k); its At / cx slots are not read.  A
+ * problem with refactor[k] != 0 (its working set changed) may have any t[k] in 0..t_max and gets its constraint stage again from
+ * its At / cx slots first; the constraint kernels are launched over exactly those problems and write no slot of another one.
+ * Host form: only the flagged problems' At / cx are staged.  Device form: dAt, ldat, strideAt, dcx must be the buffers of the
+ * factor call, the flagged problems' slots rewritten in place (-11 otherwise).  Either way the resident inputs afterwards are the
+ * final working sets.  Per problem the outputs, the resident factors and every later consumer are those of
+ * enlsip_gn_solve_batched_ragged on the final (J, rx, At, cx, t), bit for bit (same kernels, same inputs), the second attempt after
+ * a rank-deficient A' (which restarts from J*Q1) and the magnitude contract included.  The pipelined halves are those the constraint
+ * stage was placed on; if the library would now split the batch differently (profiling toggled in between) the call returns -1.
+ * A batch above the launch limit returns -2.
+ */
+int enlsip_gn_solve_factored_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                     const int64_t* refactor,
+                                     const double* J, int64_t ldj, int64_t strideJ, const double* rx,
+                                     const double* At, int64_t ldat, int64_t strideAt, const double* cx,
+                                     double eps_rank,
+                                     double* p, double* b, double* d, enlsip_gn_info* info,
+                                     int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2);
+/* Same, DEVICE buffers in and out (t and refactor stay HOST arrays), as enlsip_gn_solve_batched_ragged_dev. */
+int enlsip_gn_solve_factored_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                         const int64_t* refactor,
+                                         const double* dJ, int64_t ldj, int64_t strideJ, const double* drx,
+                                         const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
+                                         double eps_rank,
+                                         double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
+                                         int64_t* djpvtA, int64_t* djpvtL, int64_t* djpvtJ2);
+/* Problems the constraint kernels of the last enlsip_gn_factor_constraints_batched* / enlsip_gn_solve_factored_batched* call on h were
+ * launched over (on the handle and its pipeline half): batch after the former, the number of refactor flags after the latter (0 with
+ * refactor == NULL: no constraint kernel is launched).  This, not the results, tells the call from a full re-solve. */
+int enlsip_gn_get_constraint_refactored(enlsip_gn_handle h, int64_t* count);
+
 /* ---- accessors on the resident factors of problem `prob` of the last solve (host buffers) ---- */
 
 /* rows/cols of F.R for `which`: A: min(n,t) x t; L11: min(t,kA) x kA; J2: min(m,n2) x n2 */
