@@ -1654,9 +1654,17 @@ static long long pipeline_split_of(enlsip_gn_handle h, long long batch, long lon
     return (h->pipeline && !h->profiling && batch >= h->pipeline_min && !small_uniform) ? (batch + 1) / 2 : 0;
 }
 
+// Orders `stream` (a pipeline child's) after everything the caller has enqueued on this handle's stream.
+static int fork_after(enlsip_gn_handle h, hipStream_t stream) {
+    if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
+    GN_HIP(hipEventRecord(h->ev_fork, h->stream));
+    GN_HIP(hipStreamWaitEvent(stream, h->ev_fork, 0));
+    return 0;
+}
+
 // part(handle, first problem, count) for the two halves of a batch split at b0, on two streams: the child's stream is ordered after
-// everything the caller has enqueued on this handle's stream, the second half is driven by a host thread, and both halves are
-// complete when this returns.  Records the split for the accessors.
+// everything the caller has enqueued on this handle's stream (fork_after), the second half is driven by a host thread, and both
+// halves are complete when this returns.  Records the split for the accessors.
 static int on_both_halves(enlsip_gn_handle h, long long batch, long long b0,
                           const std::function<int(enlsip_gn_handle, long long, long long)>& part) {
     GN_HIP(hipSetDevice(h->device));
@@ -1665,9 +1673,8 @@ static int on_both_halves(enlsip_gn_handle h, long long batch, long long b0,
         if (rc) { h->err = "could not create the second pipeline handle"; return rc; }
         h->child->pipeline = false;
     }
-    if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-    GN_HIP(hipEventRecord(h->ev_fork, h->stream));
-    GN_HIP(hipStreamWaitEvent(h->child->stream, h->ev_fork, 0));
+    int rc = fork_after(h, h->child->stream);
+    if (rc) return rc;
     const long long b1 = batch - b0;
     enlsip_gn_handle c = h->child;
     int rc1 = 0;

@@ -1,5 +1,8 @@
-// Accessors on the resident factors (QRPivoted .R / .p / .Q' / .Q, J*F_A.Q) and the re-solve
-// entry.  Included at the end of enlsip_gn.hip.
+// Accessors on the resident factors (QRPivoted .R / .p / .Q' / .Q, J*F_A.Q) and the re-solve entry, and what the batched calls
+// over a range of the resident batch share: resident_range, for_each_segment, needs_jacobian_side, stage_in / stage_out.  Included at
+// the end of enlsip_gn.hip.
+
+#define GN_ERR_CONSTRAINTS_ONLY "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"
 
 namespace {
 
@@ -62,6 +65,80 @@ int need_factors(enlsip_gn_handle& h, int64_t& prob) {
     return 0;
 }
 
+struct AloneAt { enlsip_gn_handle hh = nullptr; long long k = 0; };      // where a slot answered on its own lives
+
+// The range prob0 .. prob0+count-1 of the caller's batch as a batched call sees it.
+struct ResidentRange {
+    std::vector<ResidentSeg> seg;       // the half-segments, slot order: they get the batched launches
+    std::vector<long long> slots;       // the slots answered on their own, by the per-problem entry point
+    std::vector<AloneAt> alone;         // empty, or count entries: where each such slot lives (hh null: not on its own)
+    const Plan& plan() const { return seg[0].hh->plan; }      // of the half that holds prob0
+};
+int resident_range(enlsip_gn_handle h, int64_t prob0, int64_t count, ResidentRange& r) {
+    return map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
+        if (!sg.alone) { r.seg.push_back(sg); return; }
+        if (r.alone.empty()) r.alone.resize((size_t)count);
+        for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) {
+            r.slots.push_back(j);
+            r.alone[(size_t)j] = {sg.hh, sg.k0 + (j - sg.j0)};
+        }
+    });
+}
+
+// launch(sg) for every half-segment of the range, enqueued on its own handle's stream.  A segment on another handle than h (the
+// second pipeline half) is ordered after what the caller enqueued on h's stream, and its error text is reported on h.
+template <class Launch>
+int for_each_segment(enlsip_gn_handle h, const ResidentRange& r, Launch&& launch) {
+    for (const ResidentSeg& sg : r.seg) {
+        int rc = sg.hh != h ? fork_after(h, sg.hh->stream) : 0;
+        if (rc) return rc;
+        rc = launch(sg);
+        if (rc && sg.hh != h) h->err = sg.hh->err;
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// what a handle of the range must hold for the calls that work on the Jacobian side (re-solve, Newton direction, diag of F_J2)
+int needs_jacobian_side(enlsip_gn_handle h, enlsip_gn_handle hh) {
+    if (hh->constraints_only) { h->err = GN_ERR_CONSTRAINTS_ONLY; return -1; }
+    if (!hh->last.rx || (hh->plan.t > 0 && !hh->last.cx)) { h->err = "rx / cx of the last solve are not available"; return -1; }
+    return 0;
+}
+
+// One array of a host-buffer form, staged through a device buffer of the call's own.  A NULL array stays NULL on the device; one of
+// zero bytes (t_max = 0) does not.
+struct Staged { void* host; size_t bytes; bool in, out; void* dev; };
+
+// Carves the arrays in order from buf (64 bytes of slack) and copies in those marked `in`: a call's outputs too, so that the
+// slots it leaves alone come back as they were.
+int stage_in(enlsip_gn_handle h, DevBuf& buf, Staged* a, int na) {
+    GN_HIP(hipSetDevice(h->device));
+    size_t tot = 64;
+    for (int i = 0; i < na; ++i) tot += a[i].host ? (size_t)rup((long long)a[i].bytes, 8) : 0;
+    int rc = grow(h, buf, tot);
+    if (rc) return rc;
+    char* at = (char*)buf.p;
+    for (int i = 0; i < na; ++i) {
+        if (!a[i].host) continue;
+        a[i].dev = at;
+        at += rup((long long)a[i].bytes, 8);
+        if (a[i].in && a[i].bytes) GN_HIP(hipMemcpyAsync(a[i].dev, a[i].host, a[i].bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    return 0;
+}
+
+// copies back those marked `out` and synchronises
+int stage_out(enlsip_gn_handle h, const Staged* a, int na) {
+    for (int i = 0; i < na; ++i)
+        if (a[i].dev && a[i].out && a[i].bytes) GN_HIP(hipMemcpyAsync(a[i].host, a[i].dev, a[i].bytes, hipMemcpyDeviceToHost, h->stream));
+    GN_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// the NULL checks of the getters of what a batched call recorded on the handle
+#define GN_GETTER_CHECK(h, out) if (!(h)) return -1; if (!(out)) { (h)->err = #out " is NULL"; return -2; }
+
 // the constraint count of problem `prob` of the resident batch: its own t after a ragged solve, the batch's t otherwise
 int prob_t(enlsip_gn_handle h, int64_t prob) {
     return h->h_tk.empty() ? (int)h->plan.t : h->h_tk[(size_t)prob];
@@ -87,7 +164,7 @@ int view(enlsip_gn_handle h, int which, int64_t prob, FactorView& v) {
                  h->tauL + prob * P.sTauL, h->jpvtL + prob * P.sJL};
             return 0;
         case ENLSIP_GN_FACTOR_J2:
-            if (h->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+            if (h->constraints_only) { h->err = GN_ERR_CONSTRAINTS_ONLY; return -1; }
             v = {h->Rt + prob * P.sRt, P.ldr, st.kp, st.n2, st.kp, h->tauJ + prob * P.sTauJ, h->jpvtJ + prob * P.sJJ};
             return 0;
         default:
@@ -239,7 +316,7 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
     int rc = need_factors(h, prob);
     if (rc) return rc;
     if (code != 1 && code != -1) { h->err = "code must be 1 or -1"; return -5; }
-    if (h->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+    if (h->constraints_only) { h->err = GN_ERR_CONSTRAINTS_ONLY; return -1; }
     const Plan& P = h->plan;
     const ProbState st0 = h->h_state[prob];
     const int tk = prob_t(h, prob);       // the problem's own t (ragged batch); the stage below runs with the batch's t_max

@@ -1,5 +1,6 @@
 // Batched consumers of a solve: gradient, J p / A p and the two multiplier estimates over a contiguous range of the resident batch
-// (kernels: gn_kernels_lagrange_batched.hpp).  Included at the end of enlsip_gn.hip, after gn_lagrange.inc.
+// (kernels: gn_kernels_lagrange_batched.hpp).  The range and the driver of its half-segments are the shared ones of
+// gn_accessors.inc (resident_range, for_each_segment).  Included at the end of enlsip_gn.hip, after gn_lagrange.inc.
 
 namespace {
 
@@ -28,7 +29,7 @@ int consumer_needs(enlsip_gn_handle h, enlsip_gn_handle hh, int kind, const Cons
             return 0;
         case CONS_FIRST:
             if (hh->constraints_only && !io.in) {
-                h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
+                h->err = GN_ERR_CONSTRAINTS_ONLY ": pass grad_fx; no second estimate";
                 return -1;
             }
             if (hh->plan.t > 0 && !hh->last.cx) { h->err = "cx of the last solve is not available"; return -1; }
@@ -36,7 +37,7 @@ int consumer_needs(enlsip_gn_handle h, enlsip_gn_handle hh, int kind, const Cons
             return 0;
         default:
             if (hh->constraints_only) {
-                h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints): pass grad_fx; no second estimate";
+                h->err = GN_ERR_CONSTRAINTS_ONLY ": pass grad_fx; no second estimate";
                 return -1;
             }
             if (!hh->last.J || !hh->last.rx) { h->err = no_j; return -1; }
@@ -130,9 +131,9 @@ int per_problem_status(int rc, int& st) {
 
 // Problems of the range that live on a rescue handle (or on a handle whose one problem was rescaled in place) are answered by the
 // per-problem entry point; their slots are overwritten with its results.  Returns the status OR of the whole range in *flagged.
-int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const std::vector<ResidentSeg>& seg,
-                         const ConsumerIO& io, const std::vector<long long>& slots, bool& flagged) {
-    const Plan& P = seg[0].hh->plan;
+int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const ResidentRange& r, const ConsumerIO& io,
+                         bool& flagged) {
+    const Plan& P = r.plan();
     const long long m = P.m, n = P.n, tmax = P.t;
     hipStream_t s = h->stream;
     std::vector<double> in((size_t)n), dg((size_t)std::max(tmax, 1LL)), o0((size_t)std::max({m, n, tmax, 1LL})),
@@ -141,12 +142,12 @@ int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t co
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
     if (est) {      // statuses of the batched launch: the rescued slots' entries are replaced below
         st_all.assign((size_t)count, 0);
-        for (const ResidentSeg& sg : seg) {
+        for (const ResidentSeg& sg : r.seg) {
             const int* src = io.status ? io.status + sg.j0 : (const int*)((char*)sg.hh->lagb_scr.p + 256);
             GN_HIP(hipMemcpy(st_all.data() + sg.j0, src, (size_t)sg.cnt * sizeof(int), hipMemcpyDeviceToHost));
         }
     }
-    for (long long j : slots) {
+    for (long long j : r.slots) {
         const int64_t gp = prob0 + j;
         if (io.in) GN_HIP(hipMemcpy(in.data(), io.in + j * n, (size_t)n * 8, hipMemcpyDeviceToHost));
         if (io.diag && tmax > 0) GN_HIP(hipMemcpy(dg.data(), io.diag + j * tmax, (size_t)tmax * 8, hipMemcpyDeviceToHost));
@@ -192,14 +193,10 @@ int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t co
 int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const ConsumerIO& io) {
     if (!h) return -1;
     // the halves that hold the range get the batched launches; the slots answered on their own, the per-problem entry point
-    std::vector<ResidentSeg> seg;
-    std::vector<long long> slots;
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
-        if (!sg.alone) seg.push_back(sg);
-        else for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) slots.push_back(j);
-    });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
-    const Plan& P = seg[0].hh->plan;
+    const Plan& P = r.plan();
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
     switch (kind) {
         case CONS_GRADIENT: if (!io.out0) { h->err = "dgrad is NULL"; return -4; } break;
@@ -212,32 +209,22 @@ int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, con
             if (!io.in) { h->err = "dp_gn is NULL"; return -4; }
             if (!io.out0 && P.t > 0) { h->err = "dlambda is NULL"; return -4; }
     }
-    for (const ResidentSeg& sg : seg) {
+    for (const ResidentSeg& sg : r.seg) {
         rc = consumer_needs(h, sg.hh, kind, io);
         if (rc) return rc;
     }
     GN_HIP(hipSetDevice(h->device));
     const bool small = h->lagrange_small && P.n <= 64 && P.t <= 64;
     if (est) h->consumer_form = small ? 1 : 0;
-    for (const ResidentSeg& sg : seg) {
-        if (sg.hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
-            if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            GN_HIP(hipEventRecord(h->ev_fork, h->stream));
-            GN_HIP(hipStreamWaitEvent(sg.hh->stream, h->ev_fork, 0));
-        }
-        rc = consumer_launch(sg.hh, kind, sg, io, small);
-        if (rc) {
-            if (sg.hh != h) h->err = sg.hh->err;
-            return rc;
-        }
-    }
+    rc = for_each_segment(h, r, [&](const ResidentSeg& sg) { return consumer_launch(sg.hh, kind, sg, io, small); });
+    if (rc) return rc;
     bool flagged = false;
-    for (const ResidentSeg& sg : seg) {
+    for (const ResidentSeg& sg : r.seg) {
         GN_HIP(hipStreamSynchronize(sg.hh->stream));
         if (est) flagged = flagged || *sg.hh->h_lagflag != 0;
     }
-    if (!slots.empty()) {
-        rc = consumer_per_problem(h, kind, prob0, count, seg, io, slots, flagged);
+    if (!r.slots.empty()) {
+        rc = consumer_per_problem(h, kind, prob0, count, r, io, flagged);
         if (rc) return rc;
     }
     return flagged ? 1 : 0;
@@ -248,38 +235,25 @@ int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, con
 int consumer_host(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, const double* in, const double* diag, double eps_rank,
                   double* out0, double* out1, int* status) {
     if (!h) return -1;
-    enlsip_gn_handle first = nullptr;       // the half that holds prob0
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) { if (!first) first = sg.hh; });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
-    const Plan& P = first->plan;
+    const Plan& P = r.plan();
     const long long m = P.m, n = P.n, tmax = P.t;
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
-    const size_t c = (size_t)count;
-    const size_t n_in = in ? c * n : 0, n_dg = (diag && est) ? c * tmax : 0;
-    const size_t n_o0 = !out0 ? 0 : kind == CONS_GRADIENT ? c * n : kind == CONS_JTIMES ? c * m : c * tmax;
-    const size_t n_o1 = !out1 ? 0 : kind == CONS_JTIMES ? c * tmax : kind == CONS_FIRST ? c : 0;
-    const size_t n_st = (status && est) ? c : 0;
-    GN_HIP(hipSetDevice(h->device));
-    rc = grow(h, h->lagb_io, (n_in + n_dg + n_o0 + n_o1 + n_st + 8) * 8);
-    if (rc) return rc;
-    double* d_in = (double*)h->lagb_io.p;
-    double* d_dg = d_in + n_in;
-    double* d_o0 = d_dg + n_dg;
-    double* d_o1 = d_o0 + n_o0;
-    int* d_st = (int*)(d_o1 + n_o1);
-    hipStream_t s = h->stream;
-    if (n_in) GN_HIP(hipMemcpyAsync(d_in, in, n_in * 8, hipMemcpyHostToDevice, s));
-    if (n_dg) GN_HIP(hipMemcpyAsync(d_dg, diag, n_dg * 8, hipMemcpyHostToDevice, s));
+    const size_t c = (size_t)count, dbl = c * 8;
+    const size_t b_o0 = dbl * (kind == CONS_GRADIENT ? n : kind == CONS_JTIMES ? m : tmax), b_o1 = dbl * (kind == CONS_JTIMES ? tmax : 1);
     // a NULL pointer keeps its meaning; an output of zero entries (t_max = 0) still passes the NULL checks
-    const ConsumerIO io{in ? d_in : nullptr, (diag && est) ? d_dg : nullptr, eps_rank, out0 ? d_o0 : nullptr,
-                        (out1 && (kind == CONS_JTIMES || kind == CONS_FIRST)) ? d_o1 : nullptr, n_st ? d_st : nullptr};
+    Staged a[5] = {{(void*)in, dbl * n, true, false}, {est ? (void*)diag : nullptr, dbl * tmax, true, false}, {out0, b_o0, false, true},
+                   {(kind == CONS_JTIMES || kind == CONS_FIRST) ? out1 : nullptr, b_o1, false, true},
+                   {est ? status : nullptr, c * sizeof(int), false, true}};
+    rc = stage_in(h, h->lagb_io, a, 5);
+    if (rc) return rc;
+    const ConsumerIO io{(double*)a[0].dev, (double*)a[1].dev, eps_rank, (double*)a[2].dev, (double*)a[3].dev, (int*)a[4].dev};
     rc = consumer_dev(h, kind, prob0, count, io);
     if (rc < 0) return rc;
-    if (n_o0) GN_HIP(hipMemcpyAsync(out0, d_o0, n_o0 * 8, hipMemcpyDeviceToHost, s));
-    if (n_o1) GN_HIP(hipMemcpyAsync(out1, d_o1, n_o1 * 8, hipMemcpyDeviceToHost, s));
-    if (n_st) GN_HIP(hipMemcpyAsync(status, d_st, n_st * sizeof(int), hipMemcpyDeviceToHost, s));
-    GN_HIP(hipStreamSynchronize(s));
-    return rc;
+    const int rc2 = stage_out(h, a, 5);
+    return rc2 ? rc2 : rc;
 }
 
 }  // namespace
@@ -353,8 +327,7 @@ int enlsip_gn_second_lagrange_batched(enlsip_gn_handle h, int64_t prob0, int64_t
 }
 
 int enlsip_gn_get_consumer_form(enlsip_gn_handle h, int* form) {
-    if (!h) return -1;
-    if (!form) { h->err = "form is NULL"; return -2; }
+    GN_GETTER_CHECK(h, form)
     *form = h->consumer_form;
     return 0;
 }

@@ -7,7 +7,7 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
     int rc = need_factors(h, prob);
     if (rc) return rc;
     GN_TRY
-    if (h->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+    if (h->constraints_only) { h->err = GN_ERR_CONSTRAINTS_ONLY; return -1; }
     if (!Gamma) { h->err = "Gamma is NULL"; return -3; }
     if (!p) { h->err = "p is NULL"; return -5; }
     if (!h->last.J || !h->last.rx) { h->err = "J / rx of the last solve are not available"; return -1; }

@@ -1,7 +1,8 @@
 // Batched Newton direction over a contiguous range of the resident batch (kernels: gn_kernels_newton_batched.hpp): what
 // newton_search_direction does per problem at src/enlsip_functions.jl:371-421 after its Hessian sums, in a number of launches and
-// synchronisations that does not depend on the size of the range.  Routing as the batched re-solve (gn_resolve_batched.inc).
-// Included at the end of enlsip_gn.hip, after gn_newton.inc.
+// synchronisations that does not depend on the size of the range.  The range and the driver of its half-segments are the shared
+// ones of gn_accessors.inc (resident_range, for_each_segment); the b / p1 / d stages are the batched re-solve's (resolve_stages,
+// gn_resolve_batched.inc).  Included at the end of enlsip_gn.hip, after gn_newton.inc.
 
 namespace {
 
@@ -44,14 +45,13 @@ int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, co
     // requests: the re-solve's record with the default dimensions for the slots that take the step
     pack.assign((size_t)cnt * 5 + 1, 0);
     ResolveDims* hd = (ResolveDims*)pack.data();
-    int kpmax = -1;
     for (long long jj = 0; jj < cnt; ++jj) {
         pack[(size_t)cnt * 4 + jj] = req[jj];
         if (req[jj] != NW_TAKE) continue;
         const ProbState& st = hh->h_state[k0 + jj];
         hd[jj] = {st.rankA, RESOLVE_HOLD, st.rankA == prob_t(hh, k0 + jj) ? 1 : -1, 0};
-        kpmax = std::max(kpmax, st.kp);
     }
+    const int kpmax = resolve_kpmax(hh, k0, cnt, hd);
     GN_HIP(hipMemcpyAsync(ddims, pack.data(), pack.size() * sizeof(int), hipMemcpyHostToDevice, s));
     GN_HIP(hipMemcpyAsync(dst, hh->state + k0, (size_t)cnt * sizeof(ProbState), hipMemcpyDeviceToDevice, s));
     const unsigned cn = (unsigned)cnt;
@@ -62,27 +62,14 @@ int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, co
         GN_HIP(hipEventRecord(hh->nwb_ev[0], s));
     }
     hh->nwb_timed = timed;
-    if (kpmax >= 0) {
-        // b, p1 (resident, as the per-problem entry point leaves them) and d = F_J2.Q' d_temp (the call's own vec); the state
-        // records the head stage writes are the copy's, so the resident ones stay what they were (the per-problem call restores them)
-        ResolveBatchArgs a = resolve_args(hh, k0, cnt);
-        a.dims = ddims;
-        a.state = dst;
-        a.vec = dvec;
-        const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
-        if (small && P.t <= 64) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, s, a);
-        else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, s, a);
-        hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
-        const int npan = (kpmax + PB - 1) / PB;
-        for (int k = 0; k < npan; ++k)
-            for (const LevelPlan& L : P.panels[k].levels) {
-                CaqrArgs ca = caqr_args(hh, k, L);
-                ca.ext_cols = 1; ca.C = dvec - k0 * P.sVec; ca.sC = P.sVec; ca.prob0 = (int)k0;
-                if (P.F == 16) hipLaunchKernelGGL(k_caqr_vec_batched<4>, dim3(L.groups, cn), dim3(256), 0, s, ca, (const ResolveDims*)ddims);
-                else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, (const ResolveDims*)ddims);
-            }
-        if (kpmax > 0) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
-    }
+    // b, p1 (resident, as the per-problem entry point leaves them) and d = F_J2.Q' d_temp (the call's own vec); the state
+    // records the head stage writes are the copy's, so the resident ones stay what they were (the per-problem call restores them)
+    ResolveBatchArgs ra = resolve_args(hh, k0, cnt);
+    ra.dims = ddims;
+    ra.state = dst;
+    ra.vec = dvec;
+    rc = resolve_stages(hh, ra, k0, cnt, kpmax, resolve_small(P), false, nullptr);
+    if (rc) return rc;
     if (timed) GN_HIP(hipEventRecord(hh->nwb_ev[1], s));
     NewtonBatchArgs a{};
     a.n = n; a.t = (int)P.t; a.kA = P.kA; a.ldr = P.ldr;
@@ -118,35 +105,26 @@ int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, co
 
 int newton_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const NewtonIO& io, const int64_t* take) {
     if (!h) return -1;
-    std::vector<ResidentSeg> seg;
-    std::vector<long long> slots;
-    std::vector<AloneAt> alone;
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
-        if (!sg.alone) { seg.push_back(sg); return; }
-        if (alone.empty()) alone.resize((size_t)count);
-        for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) {
-            slots.push_back(j);
-            alone[(size_t)j] = {sg.hh, sg.k0 + (j - sg.j0)};
-        }
-    });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
-    for (const ResidentSeg& sg : seg) {
-        if (sg.hh->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
-        if (!sg.hh->last.rx || (sg.hh->plan.t > 0 && !sg.hh->last.cx)) { h->err = "rx / cx of the last solve are not available"; return -1; }
+    for (const ResidentSeg& sg : r.seg) {
+        rc = needs_jacobian_side(h, sg.hh);
+        if (rc) return rc;
     }
-    const Plan& P = seg[0].hh->plan;
+    const Plan& P = r.plan();
     if (!io.Gamma) { h->err = "Gamma is NULL"; return -4; }
     if (!io.p) { h->err = "p is NULL"; return -4; }
     if (io.ldg < P.n) { h->err = "ldg < n"; return -5; }
     if (io.strideG < io.ldg * P.n) { h->err = "strideG < ldg * n"; return -5; }
-    for (const ResidentSeg& sg : seg)
+    for (const ResidentSeg& sg : r.seg)
         if (P.t > 0 && sg.hh->cdist.valid) { h->err = "newton direction after the distributed constraint stage is not supported"; return -7; }
     // per-problem validation (enlsip_gn_newton_direction's) on the host mirror of the state records
     std::vector<int> req((size_t)count, NW_SKIP);
-    for (const ResidentSeg& sg : seg)
+    for (const ResidentSeg& sg : r.seg)
         for (long long jj = 0; jj < sg.cnt; ++jj) {
             const long long j = sg.j0 + jj, k = sg.k0 + jj;
-            if (!alone.empty() && alone[(size_t)j].hh) continue;       // answered on its own below
+            if (!r.alone.empty() && r.alone[(size_t)j].hh) continue;       // answered on its own below
             if (take && take[j] == 0) continue;
             const int tk = prob_t(sg.hh, k);
             req[(size_t)j] = (tk != sg.hh->h_state[k].rankA && tk < P.n) ? NW_RANKDEF : NW_TAKE;
@@ -154,24 +132,14 @@ int newton_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const NewtonIO&
     GN_HIP(hipSetDevice(h->device));
     const bool small = P.n <= 64;
     h->newton_form = small ? 1 : 0;
-    std::vector<std::vector<int>> packs(seg.size());      // alive until the streams are synchronised
-    for (size_t i = 0; i < seg.size(); ++i) {
-        const ResidentSeg& sg = seg[i];
-        if (sg.hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
-            if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            GN_HIP(hipEventRecord(h->ev_fork, h->stream));
-            GN_HIP(hipStreamWaitEvent(sg.hh->stream, h->ev_fork, 0));
-        }
-        rc = newton_launch(sg.hh, sg, req.data() + sg.j0, io, small, h->profiling, packs[i]);
-        if (rc) {
-            if (sg.hh != h) h->err = sg.hh->err;
-            return rc;
-        }
-    }
+    std::vector<std::vector<int>> packs(r.seg.size());      // one per segment, alive until the streams are synchronised
+    rc = for_each_segment(h, r, [&](const ResidentSeg& sg) {
+        return newton_launch(sg.hh, sg, req.data() + sg.j0, io, small, h->profiling, packs[(size_t)(&sg - r.seg.data())]);
+    });
+    if (rc) return rc;
     bool flagged = false;
     for (float& ms : h->newton_ms) ms = 0.f;
-    for (size_t i = 0; i < seg.size(); ++i) {
-        const ResidentSeg& sg = seg[i];
+    for (const ResidentSeg& sg : r.seg) {
         GN_HIP(hipStreamSynchronize(sg.hh->stream));
         flagged = flagged || *sg.hh->h_nwflag != 0;
         if (sg.hh->nwb_timed)
@@ -185,9 +153,9 @@ int newton_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const NewtonIO&
             if (req[(size_t)(sg.j0 + jj)] == NW_TAKE && sg.hh->held.size() > (size_t)(sg.k0 + jj)) sg.hh->held[(size_t)(sg.k0 + jj)] = {};
     }
     // problems answered on their own (rescue handles): enlsip_gn_newton_direction
-    if (!slots.empty()) {
+    if (!r.slots.empty()) {
         std::vector<double> hG((size_t)P.n * P.n), hp((size_t)P.n);
-        for (long long j : slots) {
+        for (long long j : r.slots) {
             if (take && take[j] == 0) continue;
             GN_HIP(hipMemcpy2D(hG.data(), (size_t)P.n * 8, io.Gamma + j * io.strideG, (size_t)io.ldg * 8, (size_t)P.n * 8, (size_t)P.n,
                                hipMemcpyDeviceToHost));
@@ -221,11 +189,11 @@ int enlsip_gn_newton_direction_batched(enlsip_gn_handle h, int64_t prob0, int64_
                                        int64_t strideG, const int64_t* take, double* p, int* status) {
     if (!h) return -1;
     GN_TRY
-    enlsip_gn_handle first = nullptr;
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) { if (!first) first = sg.hh; });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
-    const Plan& P = first->plan;
-    if (first->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
+    const Plan& P = r.plan();
+    if (r.seg[0].hh->constraints_only) { h->err = GN_ERR_CONSTRAINTS_ONLY; return -1; }
     if (!Gamma) { h->err = "Gamma is NULL"; return -4; }
     if (!p) { h->err = "p is NULL"; return -4; }
     if (ldg < P.n) { h->err = "ldg < n"; return -5; }
@@ -233,36 +201,25 @@ int enlsip_gn_newton_direction_batched(enlsip_gn_handle h, int64_t prob0, int64_
     const size_t c = (size_t)count;
     // staged through a buffer of its own, one copy each way; the caller's p and status go in first so that the slots the call
     // leaves alone come back as they were
-    const size_t n_g = (c - 1) * (size_t)strideG + (size_t)ldg * P.n, n_p = c * P.n, n_s = status ? c : 0;
-    GN_HIP(hipSetDevice(h->device));
-    rc = grow(h, h->nwb_io, (n_g + n_p + n_s + 8) * 8);
+    Staged a[3] = {{(void*)Gamma, ((c - 1) * (size_t)strideG + (size_t)ldg * P.n) * 8, true, false}, {p, c * P.n * 8, true, true},
+                   {status, c * sizeof(int), true, true}};
+    rc = stage_in(h, h->nwb_io, a, 3);
     if (rc) return rc;
-    double* d_g = (double*)h->nwb_io.p;
-    double* d_p = d_g + n_g;
-    int* d_s = (int*)(d_p + n_p);
-    hipStream_t s = h->stream;
-    GN_HIP(hipMemcpyAsync(d_g, Gamma, n_g * 8, hipMemcpyHostToDevice, s));
-    GN_HIP(hipMemcpyAsync(d_p, p, n_p * 8, hipMemcpyHostToDevice, s));
-    if (n_s) GN_HIP(hipMemcpyAsync(d_s, status, n_s * sizeof(int), hipMemcpyHostToDevice, s));
-    rc = newton_dev(h, prob0, count, {d_g, ldg, strideG, d_p, n_s ? d_s : nullptr}, take);
+    rc = newton_dev(h, prob0, count, {(double*)a[0].dev, ldg, strideG, (double*)a[1].dev, (int*)a[2].dev}, take);
     if (rc < 0 || rc > 1) return rc;
-    GN_HIP(hipMemcpyAsync(p, d_p, n_p * 8, hipMemcpyDeviceToHost, s));
-    if (n_s) GN_HIP(hipMemcpyAsync(status, d_s, n_s * sizeof(int), hipMemcpyDeviceToHost, s));
-    GN_HIP(hipStreamSynchronize(s));
-    return rc;
+    const int rc2 = stage_out(h, a, 3);
+    return rc2 ? rc2 : rc;
     GN_CATCH(h)
 }
 
 int enlsip_gn_get_newton_form(enlsip_gn_handle h, int* form) {
-    if (!h) return -1;
-    if (!form) { h->err = "form is NULL"; return -2; }
+    GN_GETTER_CHECK(h, form)
     *form = h->newton_form;
     return 0;
 }
 
 int enlsip_gn_get_newton_stage_ms(enlsip_gn_handle h, float* ms) {
-    if (!h) return -1;
-    if (!ms) { h->err = "ms is NULL"; return -2; }
+    GN_GETTER_CHECK(h, ms)
     for (int e = 0; e < 4; ++e) ms[e] = h->newton_ms[e];
     return 0;
 }

@@ -1,8 +1,9 @@
 // Batched subspace re-solve over a contiguous range of the resident batch (kernels: gn_kernels_resolve_batched.hpp): what
 // search_direction_analys does per problem at src/enlsip_functions.jl:1249-1253 — b = F_L11.Q' (-cx[F_A.p]), the d of
 // choose_subspace_dimensions (:1118-1176, :1156-1163) and sub_search_direction (:116-153) — in a number of launches and
-// synchronisations that does not depend on the size of the range.  Routing as the batched consumers (gn_lagrange_batched.inc).
-// Included at the end of enlsip_gn.hip.
+// synchronisations that does not depend on the size of the range.  The range and the driver of its half-segments are the shared
+// ones of gn_accessors.inc (resident_range, for_each_segment); the b / p1 / d stages are enqueued by resolve_stages, here, for the
+// batched Newton direction too.  Included at the end of enlsip_gn.hip.
 
 namespace {
 
@@ -36,6 +37,51 @@ ResolveBatchArgs resolve_args(enlsip_gn_handle hh, long long k0, long long cnt) 
     return a;
 }
 
+bool resolve_small(const Plan& P) { return P.n <= 64 && P.t <= 64; }      // head and tail in their one-wave form
+
+// the largest kp among the requests (host) that run the stages before the tail (not skipped, flagged or held); -1: none does
+int resolve_kpmax(enlsip_gn_handle hh, long long k0, long long cnt, const ResolveDims* dims) {
+    int kpmax = -1;
+    for (long long jj = 0; jj < cnt; ++jj) {
+        const ResolveDims& d = dims[jj];
+        if (d.code == 0 || d.status != 0 || d.dimA == RESOLVE_HOLD) continue;
+        kpmax = std::max(kpmax, hh->h_state[k0 + jj].kp);
+    }
+    return kpmax;
+}
+
+// Enqueues on hh's stream the stages before the tail for problems k0 .. k0+cnt-1 of hh: b and p1 (head), d_temp, and
+// d = F_J2.Q' d_temp as Q0' (one launch per (panel, level) of the CAQR plan) then Qt', into a.vec.  a.dims: the requests on the
+// device; kpmax: theirs.  b_only: b and p1 are all there is to compute.  q0_ev: null, or two events recorded around the Q0' launches.
+int resolve_stages(enlsip_gn_handle hh, const ResolveBatchArgs& a, long long k0, long long cnt, int kpmax, bool small, bool b_only,
+                   hipEvent_t* q0_ev) {
+    enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
+    if (kpmax < 0) return 0;
+    const Plan& P = hh->plan;
+    hipStream_t s = hh->stream;
+    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
+    const unsigned cn = (unsigned)cnt;
+    if (small) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, s, a);
+    else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, s, a);
+    if (!b_only) hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
+    const int npan = b_only ? 0 : (kpmax + PB - 1) / PB;
+    if (q0_ev) {
+        for (int e = 0; e < 2; ++e)
+            if (!q0_ev[e]) GN_HIP(hipEventCreate(&q0_ev[e]));
+        GN_HIP(hipEventRecord(q0_ev[0], s));
+    }
+    for (int k = 0; k < npan; ++k)
+        for (const LevelPlan& L : P.panels[k].levels) {
+            CaqrArgs ca = caqr_args(hh, k, L);
+            ca.ext_cols = 1; ca.C = a.vec - k0 * P.sVec; ca.sC = P.sVec; ca.prob0 = (int)k0;      // C: indexed from hh's problem 0
+            if (P.F == 16) hipLaunchKernelGGL(k_caqr_vec_batched<4>, dim3(L.groups, cn), dim3(256), 0, s, ca, a.dims);
+            else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, a.dims);
+        }
+    if (q0_ev) GN_HIP(hipEventRecord(q0_ev[1], s));
+    if (kpmax > 0 && !b_only) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
+    return 0;
+}
+
 // Enqueues the re-solve of one segment on its handle's stream: one copy of the requests, then 4 launches plus one per
 // (panel, level) of the CAQR plan, whatever the segment's size.  dims: the requests of the segment's slots (host).
 int resolve_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDims* dims, const ResolveIO& io, bool small, bool b_only, bool prof) {
@@ -54,39 +100,14 @@ int resolve_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDims
     a.d_out = io.d ? io.d + j0 * P.m : nullptr;
     a.info_out = io.info ? io.info + j0 : nullptr;
     a.status_out = io.status ? io.status + j0 : nullptr;
-    // the stages before the tail run for the slots that do not start from a held result
-    int kpmax = -1;
-    for (long long jj = 0; jj < cnt; ++jj) {
-        const ResolveDims& d = dims[jj];
-        if (d.code == 0 || d.status != 0 || d.dimA == RESOLVE_HOLD) continue;
-        kpmax = std::max(kpmax, hh->h_state[k0 + jj].kp);
-    }
+    // the stages before the tail run for the slots that do not start from a held result; b_only: every request of the call stops at
+    // HOLD and no d is asked for.  Profiling on: HIP events around the Q0' launches, if there are any (enlsip_gn_get_resolve_q0_ms)
+    const int kpmax = resolve_kpmax(hh, k0, cnt, dims);
+    hh->rsb_timed = prof && !b_only && kpmax > 0;
+    rc = resolve_stages(hh, a, k0, cnt, kpmax, small, b_only, hh->rsb_timed ? hh->rsb_ev : nullptr);
+    if (rc) return rc;
     const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
     const unsigned cn = (unsigned)cnt;
-    hh->rsb_timed = false;
-    if (kpmax >= 0) {
-        if (small) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, s, a);
-        else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, s, a);
-        // b_only (every request of the call stops at HOLD and no d is asked for): b and p1 are all there is to compute
-        if (!b_only) hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
-        const int npan = b_only ? 0 : (kpmax + PB - 1) / PB;
-        const bool timed = prof && npan > 0;       // HIP events around the Q0' launches (enlsip_gn_get_resolve_q0_ms)
-        if (timed) {
-            for (hipEvent_t& e : hh->rsb_ev)
-                if (!e) GN_HIP(hipEventCreate(&e));
-            GN_HIP(hipEventRecord(hh->rsb_ev[0], s));
-        }
-        hh->rsb_timed = timed;
-        for (int k = 0; k < npan; ++k)
-            for (const LevelPlan& L : P.panels[k].levels) {
-                CaqrArgs ca = caqr_args(hh, k, L);
-                ca.ext_cols = 1; ca.C = hh->vec; ca.sC = P.sVec; ca.prob0 = (int)k0;
-                if (P.F == 16) hipLaunchKernelGGL(k_caqr_vec_batched<4>, dim3(L.groups, cn), dim3(256), 0, s, ca, (const ResolveDims*)ddims);
-                else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, (const ResolveDims*)ddims);
-            }
-        if (timed) GN_HIP(hipEventRecord(hh->rsb_ev[1], s));
-        if (kpmax > 0 && !b_only) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
-    }
     if (small) hipLaunchKernelGGL((k_resolve_tail<1, 64>), dim3(cn), dim3(64), lds, s, a);
     else if (P.n <= 512) hipLaunchKernelGGL((k_resolve_tail<8, 256>), dim3(cn), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((k_resolve_tail<0, 256>), dim3(cn), dim3(256), lds, s, a);
@@ -95,39 +116,27 @@ int resolve_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDims
     return 0;
 }
 
-// where a slot answered on its own lives
-struct AloneAt { enlsip_gn_handle hh = nullptr; long long k = 0; };
-
 int resolve_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* dimA, const int64_t* dimJ2, const int64_t* code,
                 const ResolveIO& io) {
     if (!h) return -1;
-    std::vector<ResidentSeg> seg;
-    std::vector<long long> slots;
-    std::vector<AloneAt> alone;
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
-        if (!sg.alone) { seg.push_back(sg); return; }
-        if (alone.empty()) alone.resize((size_t)count);
-        for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) {
-            slots.push_back(j);
-            alone[(size_t)j] = {sg.hh, sg.k0 + (j - sg.j0)};
-        }
-    });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
     if (!dimA || !dimJ2 || !code) { h->err = "dimA, dimJ2 and code are host arrays of count entries"; return -4; }
-    for (const ResidentSeg& sg : seg) {
-        if (sg.hh->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
-        if (!sg.hh->last.rx || (sg.hh->plan.t > 0 && !sg.hh->last.cx)) { h->err = "rx / cx of the last solve are not available"; return -1; }
+    for (const ResidentSeg& sg : r.seg) {
+        rc = needs_jacobian_side(h, sg.hh);
+        if (rc) return rc;
     }
-    const Plan& P = seg[0].hh->plan;
+    const Plan& P = r.plan();
     // per-problem validation (enlsip_gn_resolve's) on the host mirror of the state records
     std::vector<ResolveDims> dims((size_t)count, ResolveDims{0, 0, 0, 0});
     bool flagged = false;
-    for (const ResidentSeg& sg : seg) {
+    for (const ResidentSeg& sg : r.seg) {
         enlsip_gn_handle hh = sg.hh;
         if (hh->held.size() < (size_t)hh->plan.batch) hh->held.resize((size_t)hh->plan.batch);
         for (long long jj = 0; jj < sg.cnt; ++jj) {
             const long long j = sg.j0 + jj, k = sg.k0 + jj;
-            if (!alone.empty() && alone[(size_t)j].hh) continue;       // left at code 0 here
+            if (!r.alone.empty() && r.alone[(size_t)j].hh) continue;       // left at code 0 here
             if (code[j] == 0) continue;
             const ProbState& st = hh->h_state[k];
             const int tk = prob_t(hh, k);
@@ -145,26 +154,18 @@ int resolve_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t*
         }
     }
     GN_HIP(hipSetDevice(h->device));
-    const bool small = P.n <= 64 && P.t <= 64;
+    const bool small = resolve_small(P);
     h->resolve_form = small ? 1 : 0;
     // the first call of the reference's flow asks for b alone (:1251): no d pointer and every request held — F_J2.Q' is not applied
     bool b_only = io.d == nullptr;
     for (const ResolveDims& d : dims)
         if (d.code != 0 && d.status == 0 && d.dimJ2 != RESOLVE_HOLD) b_only = false;
-    for (const ResidentSeg& sg : seg) {
-        if (sg.hh != h) {      // the second half: ordered after what the caller enqueued on this handle's stream
-            if (!h->ev_fork) GN_HIP(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            GN_HIP(hipEventRecord(h->ev_fork, h->stream));
-            GN_HIP(hipStreamWaitEvent(sg.hh->stream, h->ev_fork, 0));
-        }
-        rc = resolve_launch(sg.hh, sg, dims.data() + sg.j0, io, small, b_only, h->profiling);
-        if (rc) {
-            if (sg.hh != h) h->err = sg.hh->err;
-            return rc;
-        }
-    }
+    rc = for_each_segment(h, r, [&](const ResidentSeg& sg) {
+        return resolve_launch(sg.hh, sg, dims.data() + sg.j0, io, small, b_only, h->profiling);
+    });
+    if (rc) return rc;
     h->resolve_q0_ms = 0.f;
-    for (const ResidentSeg& sg : seg) {
+    for (const ResidentSeg& sg : r.seg) {
         GN_HIP(hipStreamSynchronize(sg.hh->stream));
         if (sg.hh->rsb_timed) {       // the halves fill the device one after the other: their Q0' times add up
             float ms = 0.f;
@@ -181,11 +182,11 @@ int resolve_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t*
     }
     // problems answered on their own (rescue handles): enlsip_gn_resolve; a held call is the re-solve with dimJ2 = 0, whose b and d
     // are the held ones, and dimA = HOLD repeats the held dimA
-    if (!slots.empty()) {
+    if (!r.slots.empty()) {
         std::vector<double> hp((size_t)P.n), hb((size_t)std::max<long long>(P.t, 1)), hd_((size_t)P.m);
-        for (long long j : slots) {
+        for (long long j : r.slots) {
             if (code[j] == 0) continue;
-            const AloneAt at = alone[(size_t)j];
+            const AloneAt at = r.alone[(size_t)j];
             if (at.hh->held.size() <= (size_t)at.k) at.hh->held.resize((size_t)at.k + 1);
             const auto was = at.hh->held[(size_t)at.k];
             long long dA = dimA[j], dJ = dimJ2[j], c = code[j];
@@ -237,63 +238,43 @@ int enlsip_gn_resolve_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, 
                               const int64_t* code, double* p, double* b, double* d, enlsip_gn_info* info, int* status) {
     if (!h) return -1;
     GN_TRY
-    enlsip_gn_handle first = nullptr;
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) { if (!first) first = sg.hh; });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
-    const Plan& P = first->plan;
+    const Plan& P = r.plan();
     const size_t c = (size_t)count;
     // staged through a buffer of its own; the caller's arrays go in first so that the slots the call leaves alone come back as they were
-    const size_t n_p = p ? c * P.n : 0, n_b = b ? c * P.t : 0, n_d = d ? c * P.m : 0;
-    const size_t n_i = info ? c * sizeof(enlsip_gn_info) / 8 : 0, n_s = status ? c : 0;
-    GN_HIP(hipSetDevice(h->device));
-    rc = grow(h, h->rsb_io, (n_p + n_b + n_d + n_i + n_s + 8) * 8);
+    Staged a[5] = {{p, c * P.n * 8, true, true}, {b, c * P.t * 8, true, true}, {d, c * P.m * 8, true, true},
+                   {info, c * sizeof(enlsip_gn_info), true, true}, {status, c * sizeof(int), true, true}};
+    rc = stage_in(h, h->rsb_io, a, 5);
     if (rc) return rc;
-    double* d_p = (double*)h->rsb_io.p;
-    double* d_b = d_p + n_p;
-    double* d_d = d_b + n_b;
-    enlsip_gn_info* d_i = (enlsip_gn_info*)(d_d + n_d);
-    int* d_s = (int*)((double*)d_i + n_i);
-    hipStream_t s = h->stream;
-    if (n_p) GN_HIP(hipMemcpyAsync(d_p, p, n_p * 8, hipMemcpyHostToDevice, s));
-    if (n_b) GN_HIP(hipMemcpyAsync(d_b, b, n_b * 8, hipMemcpyHostToDevice, s));
-    if (n_d) GN_HIP(hipMemcpyAsync(d_d, d, n_d * 8, hipMemcpyHostToDevice, s));
-    if (n_i) GN_HIP(hipMemcpyAsync(d_i, info, n_i * 8, hipMemcpyHostToDevice, s));
-    if (n_s) GN_HIP(hipMemcpyAsync(d_s, status, n_s * sizeof(int), hipMemcpyHostToDevice, s));
     rc = resolve_dev(h, prob0, count, dimA, dimJ2, code,
-                     {n_p ? d_p : nullptr, n_b ? d_b : nullptr, n_d ? d_d : nullptr, n_i ? d_i : nullptr, n_s ? d_s : nullptr});
+                     {(double*)a[0].dev, (double*)a[1].dev, (double*)a[2].dev, (enlsip_gn_info*)a[3].dev, (int*)a[4].dev});
     if (rc < 0 || rc > 1) return rc;
-    if (n_p) GN_HIP(hipMemcpyAsync(p, d_p, n_p * 8, hipMemcpyDeviceToHost, s));
-    if (n_b) GN_HIP(hipMemcpyAsync(b, d_b, n_b * 8, hipMemcpyDeviceToHost, s));
-    if (n_d) GN_HIP(hipMemcpyAsync(d, d_d, n_d * 8, hipMemcpyDeviceToHost, s));
-    if (n_i) GN_HIP(hipMemcpyAsync(info, d_i, n_i * 8, hipMemcpyDeviceToHost, s));
-    if (n_s) GN_HIP(hipMemcpyAsync(status, d_s, n_s * sizeof(int), hipMemcpyDeviceToHost, s));
-    GN_HIP(hipStreamSynchronize(s));
-    return rc;
+    const int rc2 = stage_out(h, a, 5);
+    return rc2 ? rc2 : rc;
     GN_CATCH(h)
 }
 
 int enlsip_gn_get_diagR_batched(enlsip_gn_handle h, int which, int64_t prob0, int64_t count, double* diag, int64_t stride) {
     if (!h) return -1;
     GN_TRY
-    std::vector<ResidentSeg> seg;
-    std::vector<long long> slots;
-    int rc = map_resident(h, prob0, count, false, [&](const ResidentSeg& sg) {
-        if (!sg.alone) seg.push_back(sg);
-        else for (long long j = sg.j0; j < sg.j0 + sg.cnt; ++j) slots.push_back(j);
-    });
+    ResidentRange r;
+    int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
     if (which != ENLSIP_GN_FACTOR_A && which != ENLSIP_GN_FACTOR_L11 && which != ENLSIP_GN_FACTOR_J2) { h->err = "bad factor selector"; return -2; }
     if (!diag) { h->err = "diag is NULL"; return -5; }
-    const Plan& P = seg[0].hh->plan;
+    const Plan& P = r.plan();
     long long need = which == ENLSIP_GN_FACTOR_J2 ? 0 : std::min(P.n, P.t);
-    for (const ResidentSeg& sg : seg) {
-        if (which == ENLSIP_GN_FACTOR_J2 && sg.hh->constraints_only) { h->err = "only F_A / F_L11 are resident (enlsip_gn_factor_constraints)"; return -1; }
-        if (which == ENLSIP_GN_FACTOR_J2)
+    if (which == ENLSIP_GN_FACTOR_J2)
+        for (const ResidentSeg& sg : r.seg) {
+            rc = needs_jacobian_side(h, sg.hh);
+            if (rc) return rc;
             for (long long k = sg.k0; k < sg.k0 + sg.cnt; ++k) need = std::max<long long>(need, sg.hh->h_state[k].kp);
-    }
+        }
     if (stride < need || stride < 1) { h->err = "stride is smaller than the longest diagonal of the range"; return -6; }
     GN_HIP(hipSetDevice(h->device));
-    for (const ResidentSeg& sg : seg) {
+    for (const ResidentSeg& sg : r.seg) {
         enlsip_gn_handle hh = sg.hh;
         rc = grow(hh, hh->rsb_io, (size_t)sg.cnt * stride * 8);
         if (rc) { h->err = hh->err; return rc; }
@@ -302,8 +283,8 @@ int enlsip_gn_get_diagR_batched(enlsip_gn_handle h, int which, int64_t prob0, in
         GN_HIP(hipGetLastError());
         GN_HIP(hipMemcpyAsync(diag + sg.j0 * stride, hh->rsb_io.p, (size_t)sg.cnt * stride * 8, hipMemcpyDeviceToHost, hh->stream));
     }
-    for (const ResidentSeg& sg : seg) GN_HIP(hipStreamSynchronize(sg.hh->stream));
-    for (long long j : slots) {      // answered on their own
+    for (const ResidentSeg& sg : r.seg) GN_HIP(hipStreamSynchronize(sg.hh->stream));
+    for (long long j : r.slots) {      // answered on their own
         std::fill(diag + j * stride, diag + (j + 1) * stride, 0.0);
         int64_t r = 0, c = 0;
         rc = enlsip_gn_factor_shape(h, which, prob0 + j, &r, &c);
@@ -317,15 +298,13 @@ int enlsip_gn_get_diagR_batched(enlsip_gn_handle h, int which, int64_t prob0, in
 }
 
 int enlsip_gn_get_resolve_q0_ms(enlsip_gn_handle h, float* ms) {
-    if (!h) return -1;
-    if (!ms) { h->err = "ms is NULL"; return -2; }
+    GN_GETTER_CHECK(h, ms)
     *ms = h->resolve_q0_ms;
     return 0;
 }
 
 int enlsip_gn_get_resolve_form(enlsip_gn_handle h, int* form) {
-    if (!h) return -1;
-    if (!form) { h->err = "form is NULL"; return -2; }
+    GN_GETTER_CHECK(h, form)
     *form = h->resolve_form;
     return 0;
 }

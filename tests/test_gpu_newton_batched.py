@@ -367,3 +367,37 @@ def test_dev_form_equals_host_form(shape, monkeypatch):
                 assert np.all(pdev[g + j].view(np.int64) == SENT) and sdev[g + j] == -77
     finally:
         s.close()
+
+
+def test_profiling_changes_no_result(monkeypatch):
+    """set_profiling(True) after the solve keeps the resident split: the same call over a range straddling the pipelined halves
+    gives the same bits and return code with the HIP events around the stages of both halves, and their times are reported"""
+    case = next(g for g in GRID if g[0] == "pipelined")
+    name, m, n, t_max, members, B, env, ranges = case
+    probs = [synth.make_problem(13000 + k, m, n, t_max) for k in range(B)]
+    s = make_solver(monkeypatch, **env)
+    try:
+        solve(s, probs, t_max, False)
+        split = s.pipeline_split()
+        assert 0 < split < B
+        p0, cnt = split - 7, 21
+        gam = []
+        for k in range(p0, p0 + cnt):
+            ref = go.gn_subproblem(*probs[k])
+            gam.append(nr.make_gammas(13000 + 7 * k, probs[k][0], probs[k][2], ref)[k % 5 == 0])     # every fifth one indefinite
+        G = np.stack(gam)
+        take = np.array([j != 3 for j in range(cnt)], dtype=np.int64)
+        p_off, st_off, rc_off = s.newton_direction_batched(G, p0, cnt, take=take)
+        assert rc_off == 1 and sorted(set(st_off)) == [-1, 0, 1]
+        s.set_profiling(True)
+        try:
+            p_on, st_on, rc_on = s.newton_direction_batched(G, p0, cnt, take=take)
+            ms = s.newton_stage_ms()
+        finally:
+            s.set_profiling(False)
+        assert s.pipeline_split() == split
+        assert rc_on == rc_off
+        assert np.array_equal(p_on, p_off, equal_nan=True) and np.array_equal(st_on, st_off)
+        assert len(ms) == 4 and all(np.isfinite(x) and x >= 0 for x in ms) and sum(ms) > 0, ms
+    finally:
+        s.close()

@@ -529,3 +529,40 @@ def test_dev_form_writes_only_its_slots(shape, monkeypatch):
                     assert np.array_equal(v[j].ravel(), np.atleast_1d(host[key][j - g]).ravel()), (key, j)
     finally:
         s.close()
+
+
+def test_profiling_changes_no_result(monkeypatch):
+    """set_profiling(True) after the solve keeps the resident split: the same call over a range straddling the pipelined halves
+    gives the same bits and return code with the HIP events around the Q0' launches of both halves, and their time is reported"""
+    B, m, n, t = 160, 512, 64, 8
+    J = synth.normal_stream(10100, 0, B * m * n).reshape(B, n, m)
+    rx = synth.normal_stream(10100, 1, B * m).reshape(B, m)
+    At = synth.normal_stream(10100, 2, B * t * n).reshape(B, t, n)
+    cx = synth.normal_stream(10100, 3, B * t).reshape(B, t)
+    s = make_solver(monkeypatch, ENLSIP_GN_PIPELINE="1")
+    try:
+        infos = s.solve_batched(J, rx, At, cx)[3]
+        split = s.pipeline_split()
+        assert 0 < split < B
+        p0, cnt = split - 9, 21
+        # truncated and full dimensions, a code 0 hole and one request that is refused (dimJ2 beyond kp)
+        dA = np.array([infos[p0 + j][0] - (j % 3) for j in range(cnt)], dtype=np.int64)
+        dJ = np.array([infos[p0 + j][1] - 5 * (j % 4) for j in range(cnt)], dtype=np.int64)
+        cd = np.array([0 if j == 4 else -1 for j in range(cnt)], dtype=np.int64)
+        dJ[13] = n + 1
+        off, rc_off = s.resolve_batched(m, n, t, dA, dJ, cd, p0, cnt)
+        assert rc_off == 1 and off["status"][13] != 0 and np.count_nonzero(off["status"] > 0) == 1
+        s.set_profiling(True)
+        try:
+            on, rc_on = s.resolve_batched(m, n, t, dA, dJ, cd, p0, cnt)
+            q0_ms = s.resolve_q0_ms()
+        finally:
+            s.set_profiling(False)
+        assert s.pipeline_split() == split
+        assert rc_on == rc_off
+        assert set(on) == set(off)
+        for key in off:
+            assert np.array_equal(on[key], off[key], equal_nan=on[key].dtype.kind == "f"), key
+        assert np.isfinite(q0_ms) and q0_ms > 0, q0_ms
+    finally:
+        s.close()
