@@ -305,7 +305,7 @@ static JQ1Args jq1_args(enlsip_gn_handle h, const double* J, long long ldj, long
     qa.J = J; qa.ldj = ldj; qa.strideJ = strideJ; qa.rx = rx; qa.stride_rx = P.m;
     qa.FA = h->FA; qa.sFA = P.sFA; qa.TA = h->TA; qa.sTA = P.sTA; qa.p1 = h->p1; qa.sP1 = P.sP1;
     qa.W = h->W; qa.sW = P.sW; qa.state = h->state;
-    qa.prob0 = 0;
+    qa.prob0 = 0; qa.plist = h->run_plist;
     // V T' of the fast path lives in the (still unused) working matrix of the pivoted QR
     qa.VT = (P.sM >= P.n * KBLK) ? h->qdM : nullptr; qa.sVT = P.sM;
     return qa;
@@ -316,6 +316,11 @@ static void launch_jq1_any(enlsip_gn_handle h, const JQ1Args& qa, int batch, hip
     else if (!launch_jq1_v2(qa, batch, s)) launch_jq1_mfma(qa, batch, s);   // regular shapes / general shapes
 }
 
+// Problems the Jacobian-side launches of the running solve_dev cover: the whole part, or the listed problems of a changed-problems
+// solve.  Only the GRIDS are sized by it: every kernel-form predicate keeps reading the part's whole problem count (plan.batch), so
+// that a listed problem runs through the kernels a solve of the whole part would give it.
+static long long launch_count(enlsip_gn_handle h) { return h->run_plist ? h->run_nlist : h->plan.batch; }
+
 static CaqrArgs caqr_args(enlsip_gn_handle h, int k, const LevelPlan& L) {
     const Plan& P = h->plan;
     CaqrArgs a{};
@@ -324,12 +329,13 @@ static CaqrArgs caqr_args(enlsip_gn_handle h, int k, const LevelPlan& L) {
     a.W = h->W; a.sW = P.sW; a.Tbuf = h->Tbuf; a.sT = P.sT; a.state = h->state;
     a.ext_cols = 0; a.C = nullptr; a.sC = 0; a.reverse = 0;
     a.mode = L.mode; a.base = L.base; a.skip = L.skip; a.win = 0; a.pair = 0; a.tOff2 = 0;
+    a.plist = h->run_plist;
     return a;
 }
 
 static void launch_factor(enlsip_gn_handle h, const CaqrArgs& a, int groups, hipStream_t st = nullptr) {
     if (!st) st = h->stream;
-    dim3 grid(groups, (unsigned)h->plan.batch);
+    dim3 grid(groups, (unsigned)launch_count(h));
     // one-tile problems of at most 256 rows: 4 waves x 8 columns issue ~20 % fewer instructions per step than 8 x 4
     // (measured on C5: panel stage 0.63 -> 0.57 ms); everywhere else the 8-wave form wins (a 16-wave form: 8.1 -> 11.2 ms)
     if (h->plan.m > 256) {
@@ -398,7 +404,7 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     const Plan& P = h->plan;
     const int kp_launch = (int)std::min<long long>(P.m, n2_launch);
     const int npan = (kp_launch + PB - 1) / PB;
-    const int nprob = (int)P.batch;
+    const int nprob = (int)launch_count(h);       // grids only; P.batch below decides the forms
     const bool use_mfma = !(h->flags & ENLSIP_GN_UPDATE_REFLECTORS);
     GN_ROUTE(P.RPL == 8 ? ENLSIP_GN_ROUTE_SWEEP_TILE512 : ENLSIP_GN_ROUTE_SWEEP_TILE256);
     if (!use_mfma) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_REFLECTORS);
@@ -634,7 +640,7 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
 static QdArgs qd_args_r0(enlsip_gn_handle h, int n2_launch) {
     const Plan& P = h->plan;
     QdArgs a{};
-    a.n = (int)P.n; a.ldw = P.ldw; a.ldr = P.ldr; a.step = 0; a.prob0 = 0;
+    a.n = (int)P.n; a.ldw = P.ldw; a.ldr = P.ldr; a.step = 0; a.prob0 = 0; a.plist = h->run_plist;
     a.W = h->W; a.sW = P.sW; a.M = h->qdM; a.sM = P.sM; a.Vb = h->qdVb; a.sVb = P.sVb; a.Rt = h->Rt; a.sRt = P.sRt;
     a.tau = h->tauJ; a.sTau = P.sTauJ; a.diag = h->qdDiag; a.sDiag = P.sDiag;
     a.vn1 = h->qdVn1; a.vn2 = h->qdVn2; a.sVn = P.sVn;
@@ -664,7 +670,7 @@ static int run_qrcp_dist(enlsip_gn_handle h, int n2_launch) {
     const int kp_launch = (int)std::min<long long>(P.m, n2_launch);
     QdArgs a = qd_args_r0(h, n2_launch);
     GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_STEPS);
-    const dim3 grid = qd_grid(n2_launch, P.batch);
+    const dim3 grid = qd_grid(n2_launch, launch_count(h));
     launch_qd_steps(grid, kp_launch > 512, h->stream, a, kp_launch);
     hipLaunchKernelGGL(k_qd_assemble, grid, dim3(256), 0, h->stream, a);
     GN_HIP(hipGetLastError());
@@ -689,7 +695,12 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
     a.info = (SbInfo*)h->sbInfo; a.inblk = h->sbInblk; a.sIn = P.sQI; a.blkid = 0;
     a.Tsb = h->sbT; a.sTsb = PB * PB; a.act = h->sbAct; a.sAct = P.sQI + 32;
     a.dbg = nullptr;
-    const dim3 grid = qd_grid(n2_launch, P.batch);
+    // a changed-problems solve: grids over the listed problems, the end-of-stage check over them too (the block records of the
+    // others are whatever their own solve left); it neither uses nor renews the form hints, which belong to whole-part stages
+    const bool listed = h->run_plist != nullptr;
+    const long long nl = launch_count(h);
+    auto prob_at = [&](long long i) -> long long { return listed ? h->refit[(size_t)i] : i; };
+    const dim3 grid = qd_grid(n2_launch, nl);
     hipStream_t s = h->stream;
     // Row-count statistics per block id (see SbArgs::rows_stat).  Every block is launched in up to three forms of the select /
     // factor kernel and a problem runs in the one that fits its current row count; in a batch of similar problems two of the
@@ -704,20 +715,25 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
         GN_HIP(hipMemsetAsync(h->sb_stat.p, 0, 2 * SB_STAT_BLKS * sizeof(int), s));
         a.rows_stat = (int*)h->sb_stat.p;
     }
-    bool hints = h->sb_form_hints && h->sb_rows_kp == kp_launch && h->sb_rows_batch == P.batch && !h->sb_rows_max.empty();
+    bool hints = !listed && h->sb_form_hints && h->sb_rows_kp == kp_launch && h->sb_rows_batch == P.batch && !h->sb_rows_max.empty();
     const bool hinted = hints;
     bool fell_back = false;
     launch_qd_steps(grid, jhead > 0, s, q, jhead);     // the head, if any: more than 512 rows
     q.step = -1;
     q.hyb = jhead;
-    hipLaunchKernelGGL(k_sb_reset, dim3(((unsigned)P.n + 255) / 256, (unsigned)P.batch), dim3(256), 0, s, a, (int)P.n, jhead);
+    hipLaunchKernelGGL(k_sb_reset, dim3(((unsigned)P.n + 255) / 256, (unsigned)nl), dim3(256), 0, s, a, (int)P.n, jhead);
     const int kp_blk = kp_launch - jhead;           // steps (= rows) left to the blocks
-    dim3 ugrid((n2_launch + 1 + SB_UCW - 1) / SB_UCW, (unsigned)P.batch);
+    dim3 ugrid((n2_launch + 1 + SB_UCW - 1) / SB_UCW, (unsigned)nl);
     int it = 0;
     // blocks of <= 32 steps; the first chunk is sized from the previous solve on this handle (one host check per
     // solve in steady state), later chunks are small
-    int chunk = std::min(kp_blk, h->sb_hint > 0 ? h->sb_hint : kp_blk / 16 + 4);
+    int chunk = std::min(kp_blk, (h->sb_hint > 0 && !listed) ? h->sb_hint : kp_blk / 16 + 4);
     SbInfo* hinfo = (SbInfo*)h->h_sbinfo;
+    // the state records read back at the end of a chunk: into the handle's mirror, but for a changed-problems solve, whose mirror
+    // keeps the records of the problems it leaves alone (a rescued one's is its rescue handle's, not the device's)
+    std::vector<ProbState> own_states;
+    if (listed) own_states.resize((size_t)P.batch);
+    ProbState* hstate = listed ? own_states.data() : h->h_state;
     // rows_bound: an upper bound of kp - j0 over the problems.  A block in which EVERY form the bound asks for was launched
     // serves every unfinished problem, and a served problem makes at least one step: the bound then falls by one.  A block
     // in which the hints suppressed one of those forms may have left a problem unserved: the bound stays, and the read-back
@@ -734,7 +750,11 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
             // candidates in the registers of one workgroup (kp <= 512), block reflector applied to the still-active columns.
             // Up to three forms per block, each problem runs in the one that fits its current row count kp - j0
             // (gn_kernels_qrcp_block_reg.hpp): the large forms are no longer launched once the bound fits a smaller one.
-            const dim3 fg((unsigned)P.batch);
+            const dim3 fg((unsigned)nl);
+            // a form of the select / factor kernel: its whole-part instantiation, or the one that reads the problem list
+            auto factor_form = [&](void (*whole)(SbArgs), void (*by_list)(SbArgs)) {
+                hipLaunchKernelGGL(listed ? by_list : whole, fg, dim3(512), 0, s, a);
+            };
             const bool big0 = rows_bound > 256, med0 = rows_bound > 128;
             bool big = big0, med = med0, small = true;
             if (hints && it < (int)h->sb_rows_max.size() && h->sb_rows_max[it] > 0) {
@@ -746,29 +766,31 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
             }
             if (big) {
                 GN_ROUTE(kp_blk <= 448 ? ENLSIP_GN_ROUTE_PIVOT_BLOCKS_448 : ENLSIP_GN_ROUTE_PIVOT_BLOCKS_512);
-                if (kp_blk <= 448) hipLaunchKernelGGL((k_sb_factor_reg<7, 8, 4>), fg, dim3(512), 0, s, a);
-                else hipLaunchKernelGGL((k_sb_factor_reg<8, 8, 4>), fg, dim3(512), 0, s, a);
+                if (kp_blk <= 448) factor_form(k_sb_factor_reg<7, 8, 4>, k_sb_factor_reg<7, 8, 4, true>);
+                else factor_form(k_sb_factor_reg<8, 8, 4>, k_sb_factor_reg<8, 8, 4, true>);
             }
-            if (med) { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_BLOCKS_256); hipLaunchKernelGGL((k_sb_factor_reg<4, 8, 2>), fg, dim3(512), 0, s, a); }
-            if (small) { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_BLOCKS_128); hipLaunchKernelGGL((k_sb_factor_reg<2, 8, 0>), fg, dim3(512), 0, s, a); }
+            if (med) { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_BLOCKS_256); factor_form(k_sb_factor_reg<4, 8, 2>, k_sb_factor_reg<4, 8, 2, true>); }
+            if (small) { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_BLOCKS_128); factor_form(k_sb_factor_reg<2, 8, 0>, k_sb_factor_reg<2, 8, 0, true>); }
             hipLaunchKernelGGL(k_sb_update_blk, ugrid, dim3(256), 0, s, a);
             if (big == big0 && med == med0 && small) --rows_bound;
         }
         GN_HIP(hipGetLastError());
         GN_HIP(hipMemcpyAsync(hinfo, h->sbInfo, (size_t)P.batch * sizeof(SbInfo), hipMemcpyDeviceToHost, s));
-        GN_HIP(hipMemcpyAsync(h->h_state, h->state, (size_t)P.batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
+        GN_HIP(hipMemcpyAsync(hstate, h->state, (size_t)P.batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
         GN_HIP(hipMemcpyAsync(h->h_sb_stat, h->sb_stat.p, 2 * SB_STAT_BLKS * sizeof(int), hipMemcpyDeviceToHost, s));
         GN_HIP(hipStreamSynchronize(s));
         done = true;
         int rows_left = 0;                       // exact maximum of kp - j0 over the unfinished problems
-        for (long long k = 0; k < P.batch; ++k) {
-            if (h->h_state[k].n2 > n2_launch) continue;            // wider problems are skipped here
-            const int left = h->h_state[k].kp - hinfo[k].j0;
+        for (long long i = 0; i < nl; ++i) {
+            const long long k = prob_at(i);
+            if (hstate[k].n2 > n2_launch) continue;                // wider problems are skipped here
+            const int left = hstate[k].kp - hinfo[k].j0;
             if (left > 0) {
                 done = false;
                 rows_left = std::max(rows_left, left);
             }
         }
+        if (done && listed) break;
         if (done) {
             int used = 0;
             for (long long k = 0; k < P.batch; ++k) used = std::max(used, hinfo[k].blk + 1);
@@ -1125,12 +1147,24 @@ static int next_rescue_handle(enlsip_gn_handle h, enlsip_gn_handle* out) {
 
 static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
     const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
-    h->split = 0;   // routing of accessors to the pipeline child is (re)established by the batched entry point
-    h->chunk0 = 0;  // ... and to the resident chunk by solve_chunked
+    if (!h->changed_once) {
+        h->split = 0;   // routing of accessors to the pipeline child is (re)established by the batched entry point
+        h->chunk0 = 0;  // ... and to the resident chunk by solve_chunked
+    }
     gn_route_acc = 0;
-    const bool reuse = h->reuse_once;
+    // a changed-problems solve (enlsip_gn_solve_changed_batched, which has checked the resident state): the problems of h->refit
+    // only, constraint stage and Jacobian side, into their own slots of the resident batch; nothing else of it is touched
+    const bool listed = h->changed_once;
+    h->changed_once = false;
+    const bool reuse = h->reuse_once || listed;
     h->reuse_once = false;
     if (!reuse) h->refit.clear();
+    struct ListGuard {      // no launch after this solve is sized by its list
+        enlsip_gn_handle h;
+        ~ListGuard() { h->run_plist = nullptr; h->run_nlist = 0; }
+    } list_guard{h};
+    const long long nlaunch = listed ? (long long)h->refit.size() : batch;       // problems every launch of this solve covers
+    auto prob_at = [&](long long i) -> long long { return listed ? h->refit[(size_t)i] : i; };
     const bool upper_in = h->upper_once && t == 0 && m <= n;      // J is upper triangular (and unconstrained): it IS its own R0, Q0 = I
     h->upper_once = false;
     int rc = check_limits(h, batch, m, n, t);
@@ -1142,13 +1176,41 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     if (rc) return rc;
     const Plan& P = h->plan;
     h->eps_rank = eps_rank;
-    h->factors_valid = false;
-    h->held.clear();
-    h->last = v.inputs();
-    h->sc_eJ = 0;
-    if (!reuse) h->sc_eA = 0;       // (a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it)
-    h->rescue_prob.clear();
+    if (listed) {
+        // a held re-solve of a listed problem is dropped; a listed problem that lived on a rescue handle gives it back (the handle
+        // moves behind the ones in use)
+        for (int k : h->refit) {
+            if ((size_t)k < h->held.size()) h->held[(size_t)k] = {};
+            for (size_t j = 0; j < h->rescue_prob.size(); ++j)
+                if (h->rescue_prob[j] == k) {
+                    enlsip_gn_handle r = h->rescue[j];
+                    h->rescue.erase(h->rescue.begin() + (long)j);
+                    h->rescue.push_back(r);
+                    h->rescue_prob.erase(h->rescue_prob.begin() + (long)j);
+                    break;
+                }
+        }
+    } else {
+        h->factors_valid = false;
+        h->held.clear();
+        h->last = v.inputs();
+        h->sc_eJ = 0;
+        if (!reuse) h->sc_eA = 0;       // (a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it)
+        h->rescue_prob.clear();
+    }
     hipStream_t s = h->stream;
+    // The state records of the part from the device into the host mirror.  A changed-problems solve never writes the mirror's
+    // records of the problems it leaves alone (a rescued problem's holds its rescue handle's record, not the device's): it reads
+    // back into a buffer of its own and takes the listed records from there.
+    std::vector<ProbState> fresh;
+    auto fetch_states = [&]() -> int {
+        if (listed) fresh.resize((size_t)batch);
+        GN_HIP(hipMemcpyAsync(listed ? fresh.data() : h->h_state, h->state, (size_t)batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
+        GN_HIP(hipStreamSynchronize(s));
+        if (listed)
+            for (int k : h->refit) h->h_state[k] = fresh[(size_t)k];
+        return 0;
+    };
     // ragged batch: every problem's own t, kept on the host for the accessors and copied to the device for the constraint kernels
     int t_min = (int)t;
     if (v.tk) {
@@ -1178,6 +1240,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     // 1. constraint stage
     GN_TRACE(h, "solve m=%lld n=%lld t=%lld batch=%lld: constraint stage%s", m, n, t, batch, reuse ? " (resident)" : "");
     h->cstage_problems = 0;
+    h->jstage_problems = 0;
     if (!reuse) {       // enlsip_gn_solve_factored: F_A, F_L11, b, p1, T and the state record are those of enlsip_gn_factor_constraints
         h->fb.valid = false;
         rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov);
@@ -1190,6 +1253,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
         rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov, 0, 0, (const int*)h->plist_buf.p,
                                   (long long)nl);
         if (rc) return rc;
+        if (listed) { h->run_plist = (const int*)h->plist_buf.p; h->run_nlist = (long long)nl; }
     }
     mark(1);
     GN_TRACE(h, "constraint stage done");
@@ -1198,6 +1262,15 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     auto attempts = [&](const double* dJ, long long ldj, long long strideJ, const double* drx, int abs_shift) -> int {
     // speculate rankA = min(n, t) (ragged: the smallest min(n, t_k), so that only a rank-deficient A' widens J2); verified after the solve
     int n2_launch = (int)(n - std::min<long long>(n, t_min));
+    // a changed-problems solve launches with the width a solve of the whole part on the final sets ends with: no narrower than the
+    // widest J2 among the problems it leaves alone (one of them had a rank-deficient A')
+    if (listed) {
+        std::vector<char> in_list((size_t)batch, 0);
+        for (int k : h->refit) in_list[(size_t)k] = 1;
+        for (long long k = 0; k < batch; ++k)
+            if (!in_list[(size_t)k]) n2_launch = std::max(n2_launch, h->h_state[k].n2);
+    }
+    h->jstage_problems = nlaunch;
     for (int attempt = 0; attempt < 2; ++attempt) {
         // 2. JQ1 = J*Q1, d_temp
         const JQ1Args qa = jq1_args(h, dJ, ldj, strideJ, drx);
@@ -1207,9 +1280,9 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
         if (fused) {
             CaqrArgs ca = caqr_args(h, 0, P.panels[0].levels[0]);
             ca.npass = 1;
-            launch_jq1_factor_small(qa, ca, (int)batch, s);
+            launch_jq1_factor_small(qa, ca, (int)nlaunch, s);
             GN_HIP(hipGetLastError());
-        } else launch_jq1_any(h, qa, (int)batch, s);
+        } else launch_jq1_any(h, qa, (int)nlaunch, s);
         mark(2);
         GN_TRACE(h, "attempt %d n2_launch=%d: J*Q1 done%s", attempt, n2_launch, fused ? " (fused with the panel factorisation)" : "");
         // 3. CAQR of [J2 | d]
@@ -1232,7 +1305,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
         fa.jA_out = v.jpvtA; fa.sJAo = t; fa.jpvtA = h->jpvtA; fa.sJA = P.sJA;
         fa.jL_out = v.jpvtL; fa.sJLo = P.kA; fa.jpvtL = h->jpvtL; fa.sJL = P.sJL;
         fa.jJ_out = v.jpvtJ2; fa.sJJo = n;
-        fa.state = h->state;
+        fa.state = h->state; fa.plist = h->run_plist;
         fa.n2cap = n2_launch;
         {
             const int kp_launch = (int)std::min<long long>(m, n2_launch);
@@ -1245,22 +1318,21 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
             }
         }
         GN_TRACE(h, "pivoted QR of R0 done (refactor %d)", fa.refactor);
-        if (!launch_pivot_small((int)std::min<long long>(m, n2_launch), n2_launch, (int)batch, s, fa))
-            launch_pivot((int)std::min<long long>(m, n), (int)batch, s, fa);
+        if (!launch_pivot_small((int)std::min<long long>(m, n2_launch), n2_launch, (int)batch, s, fa, (int)nlaunch))
+            launch_pivot((int)std::min<long long>(m, n), (int)nlaunch, s, fa);
         mark(4);
         GN_TRACE(h, "final kernel done");
         // nominate problems whose largest column norm overflowed or sits at the bottom of the exponent range (gn_rescale.hpp)
         if (h->rescale_enabled && !h->h_tk.empty())
-            hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt,
-                               P.sRt, (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)batch, (const int*)h->tkbuf.p);
+            hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt,
+                               P.sRt, (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)nlaunch, (const int*)h->tkbuf.p, h->run_plist);
         else if (h->rescale_enabled)
-            hipLaunchKernelGGL(k_extreme_flags, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt, P.sRt,
-                               (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)batch);
+            hipLaunchKernelGGL(k_extreme_flags, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt, P.sRt,
+                               (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)nlaunch, h->run_plist);
         GN_HIP(hipGetLastError());
-        GN_HIP(hipMemcpyAsync(h->h_state, h->state, (size_t)batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
-        GN_HIP(hipStreamSynchronize(s));
+        if (int rcf = fetch_states()) return rcf;
         int n2max = 0;
-        for (long long k = 0; k < batch; ++k) n2max = std::max(n2max, h->h_state[k].n2);
+        for (long long i = 0; i < nlaunch; ++i) n2max = std::max(n2max, h->h_state[prob_at(i)].n2);
         if (n2max <= n2_launch) break;
         n2_launch = n2max;  // some A was rank deficient: J2 is wider than speculated, redo from J*Q1
     }
@@ -1272,7 +1344,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     {
         const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
         bool flagged = false;
-        for (long long k = 0; k < batch; ++k) flagged = flagged || (h->h_state[k].status & fl);
+        for (long long i = 0; i < nlaunch; ++i) flagged = flagged || (h->h_state[prob_at(i)].status & fl);
         if (flagged && batch == 1 && !v.tk) {
             int sJ = 0, sA = 0;
             BatchOperands looked = v;
@@ -1300,7 +1372,8 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
         } else if (flagged) {
             // a batch (or a ragged batch of one, whose problem is solved with its own t there): every nominated problem whose inputs are beyond the band goes to a one-problem handle of its own (which
             // rescales in place as above); its outputs land in the caller's slots, the accessors are routed to it
-            for (long long k = 0; k < batch; ++k) {
+            for (long long i = 0; i < nlaunch; ++i) {
+                const long long k = prob_at(i);
                 if (!(h->h_state[k].status & fl)) continue;
                 int sJ = 0, sA = 0;
                 BatchOperands one = v.slice(k, 1);      // offsets with the batch's strides (t_max) ...
@@ -1322,14 +1395,25 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
             }
         }
         if (flagged) {       // the nomination bits are host-internal
-            for (long long k = 0; k < batch; ++k) h->h_state[k].status &= ~fl;
-            hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)batch);
+            for (long long i = 0; i < nlaunch; ++i) h->h_state[prob_at(i)].status &= ~fl;
+            hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)nlaunch,
+                               h->run_plist);
             GN_HIP(hipGetLastError());
         }
     }
     if (v.hinfo)
-        for (long long k = 0; k < batch; ++k) v.hinfo[k] = info_of(h->h_state[k]);
-    if (v.dinfo) {
+        for (long long i = 0; i < nlaunch; ++i) v.hinfo[prob_at(i)] = info_of(h->h_state[prob_at(i)]);
+    if (v.dinfo && listed) {        // the listed problems' records only: one upload in list order, scattered by one launch
+        std::vector<enlsip_gn_info> tmp((size_t)nlaunch);
+        for (long long i = 0; i < nlaunch; ++i) tmp[(size_t)i] = info_of(h->h_state[prob_at(i)]);
+        rc = grow(h, h->info_stage, tmp.size() * sizeof(enlsip_gn_info));
+        if (rc) return rc;
+        GN_HIP(hipMemcpyAsync(h->info_stage.p, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_scatter_info, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, v.dinfo,
+                           (const enlsip_gn_info*)h->info_stage.p, h->run_plist, (int)nlaunch);
+        GN_HIP(hipGetLastError());
+        GN_HIP(hipStreamSynchronize(s));
+    } else if (v.dinfo) {
         // info records are produced on the host from the state mirror and copied to the device buffer
         std::vector<enlsip_gn_info> tmp((size_t)batch);
         for (long long k = 0; k < batch; ++k) tmp[k] = info_of(h->h_state[k]);
@@ -1469,6 +1553,7 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->h_lagflag) (void)hipHostFree(h->h_lagflag);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);
+    if (h->info_stage.p) (void)hipFree(h->info_stage.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);
     if (h->xbuf.p) (void)hipFree(h->xbuf.p);
     tsqr_drop_comm(h);
@@ -1869,7 +1954,7 @@ static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long lon
     if (rc) return rc;
     if (h->rescale_enabled && t > 0)
         hipLaunchKernelGGL(k_extreme_flags, dim3(1), dim3(256), 0, s, h->state, (const double*)nullptr, 0LL, (const double*)h->FA, h->plan.sFA,
-                           h->plan.kA, 0, 1);
+                           h->plan.kA, 0, 1, (const int*)nullptr);
     GN_HIP(hipMemcpyAsync(h->h_state, h->state, sizeof(ProbState), hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
     if (h->h_state[0].status & (GN_FLAG_NONFINITE | GN_FLAG_TINY)) {
@@ -1888,7 +1973,7 @@ static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long lon
             h->route |= (1ull << ENLSIP_GN_ROUTE_RESCALED);
         }
         h->h_state[0].status &= ~(GN_FLAG_NONFINITE | GN_FLAG_TINY);
-        hipLaunchKernelGGL(k_clear_status_bits, dim3(1), dim3(256), 0, s, h->state, GN_FLAG_NONFINITE | GN_FLAG_TINY, 1);
+        hipLaunchKernelGGL(k_clear_status_bits, dim3(1), dim3(256), 0, s, h->state, GN_FLAG_NONFINITE | GN_FLAG_TINY, 1, (const int*)nullptr);
         GN_HIP(hipGetLastError());
     }
     h->factors_valid = true;
@@ -2011,6 +2096,7 @@ static int factor_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_ran
     h->upper_once = false;
     h->refit.clear();
     h->cstage_problems = 0;
+    h->jstage_problems = 0;
     int rc = make_plan(h, batch, m, n, t);
     if (rc) return rc;
     const Plan& P = h->plan;
@@ -2030,7 +2116,7 @@ static int factor_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_ran
     const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
     if (h->rescale_enabled && t > 0)
         hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)nullptr, 0LL,
-                           (const double*)h->FA, P.sFA, P.kA, 0, (int)batch, (const int*)h->tkbuf.p);
+                           (const double*)h->FA, P.sFA, P.kA, 0, (int)batch, (const int*)h->tkbuf.p, (const int*)nullptr);
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpyAsync(h->h_state, h->state, (size_t)batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
@@ -2059,7 +2145,8 @@ static int factor_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_ran
     }
     if (flagged) {
         for (long long k = 0; k < batch; ++k) h->h_state[k].status &= ~fl;
-        hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)batch);
+        hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)batch,
+                           (const int*)nullptr);
         GN_HIP(hipGetLastError());
     }
     if (v.hinfo || v.dinfo) {
@@ -2254,6 +2341,204 @@ int enlsip_gn_solve_factored_batched_dev(enlsip_gn_handle h, int64_t batch, int6
                                    (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()},
                                refactor, eps_rank, false);
     GN_CATCH(h)
+}
+
+// ---- changed-problems solve: update_working_set (src/enlsip_functions.jl:686-795) solves the subproblem again after the undo of a
+// deletion (:728-743) and after a second-order deletion (:745-762 / :773-790), each time for the problems whose working set changed
+// only; the direction itself is gn_search_direction's (:725 / :771).  See include/enlsip_gn.h. ---------------------------------------
+
+// What the resident batch must be for enlsip_gn_solve_changed_batched*: a fully solved ragged batch of this shape, split as it would
+// be split now.  Nothing is staged or launched before this has passed.
+static int check_changed_call(enlsip_gn_handle h, long long batch, long long m, long long n, long long t_max, const std::vector<int>& tk,
+                              const int64_t* changed) {
+    const enlsip_gn_handle c = h->split > 0 ? h->child : nullptr;
+    auto solved = [&](enlsip_gn_handle hh) { return hh && hh->factors_valid && hh->have_plan; };
+    if (!solved(h) || (c && !solved(c))) {
+        h->err = "enlsip_gn_solve_changed_batched needs a fully solved batch resident on the handle (nothing is, or the last solve was "
+                 "a TSQR solve, which leaves no whole problem resident)";
+        return -1;
+    }
+    if (h->constraints_only || (c && c->constraints_only)) { h->err = "enlsip_gn_solve_changed_batched: only F_A / F_L11 are resident (enlsip_gn_factor_constraints*): solve first";
+        return -1;
+    }
+    if (h->h_tk.empty() || (c && c->h_tk.empty())) {
+        h->err = "enlsip_gn_solve_changed_batched: the resident batch is a uniform one (enlsip_gn_solve_batched): it has no per-problem t";
+        return -1;
+    }
+    const long long total = h->plan.batch + (c ? c->plan.batch : 0);
+    if (h->chunk0 != 0 || total != batch || h->plan.m != m || h->plan.n != n || h->plan.t != t_max) {
+        h->err = "enlsip_gn_solve_changed_batched: batch, m, n, t_max must be those of the resident solve";
+        return -1;
+    }
+    if (pipeline_split_of(h, batch, m, n) != h->split) {
+        h->err = "enlsip_gn_solve_changed_batched: the batch would now be split over the pipeline halves differently from the resident "
+                 "solve (profiling or the pipeline setting changed in between?)";
+        return -1;
+    }
+    for (long long k = 0; k < batch; ++k) {
+        const int have = (c && k >= h->split) ? c->h_tk[(size_t)(k - h->split)] : h->h_tk[(size_t)k];
+        if (!changed[k] && tk[(size_t)k] != have) {
+            h->err = "t[" + std::to_string(k) + "] = " + std::to_string(tk[(size_t)k]) + " but problem " + std::to_string(k) +
+                     " is resident with " + std::to_string(have) + " constraints and has no changed flag";
+            return -6;
+        }
+    }
+    return 0;
+}
+
+// Both forms after their checks (and the host form's staging).  v: device buffers; J, rx the resident ones.
+static int solve_changed_core(enlsip_gn_handle h, const BatchOperands& v, const int64_t* changed, double eps_rank) {
+    const long long batch = v.batch;
+    const long long split = h->split;
+    const enlsip_gn_handle c = split > 0 ? h->child : nullptr;
+    const long long b0 = c ? split : batch;
+    h->refit.clear();
+    if (c) c->refit.clear();
+    for (long long k = 0; k < batch; ++k)
+        if (changed[k]) (k < b0 ? h : c)->refit.push_back((int)(k < b0 ? k : k - b0));
+    h->fb.valid = false;
+    const bool part0 = !h->refit.empty(), part1 = c && !c->refit.empty();
+    if (!part0) h->cstage_problems = h->jstage_problems = 0;
+    if (c && !part1) c->cstage_problems = c->jstage_problems = 0;
+    int rc = 0;
+    if (part0 && part1) {
+        h->changed_once = c->changed_once = true;
+        rc = on_both_halves(h, batch, b0, [&](enlsip_gn_handle hh, long long k0, long long cnt) {
+            return solve_dev(hh, v.slice(k0, cnt), eps_rank, -1, -1);
+        });
+        h->changed_once = c->changed_once = false;
+    } else if (part0) {
+        h->changed_once = true;
+        rc = solve_dev(h, v.slice(0, b0), eps_rank, -1, -1);
+        if (!rc && c) h->route |= (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
+    } else if (part1) {
+        GN_HIP(hipSetDevice(h->device));
+        rc = fork_after(h, c->stream);
+        if (rc) return rc;
+        c->changed_once = true;
+        rc = solve_dev(c, v.slice(b0, batch - b0), eps_rank, -1, -1);
+        if (rc) h->err = c->err;
+        else h->route = c->route | (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
+        GN_HIP(hipSetDevice(h->device));
+    }
+    h->split = split;
+    if (rc) return rc;
+    h->constraint_refactored = h->cstage_problems + (c ? c->cstage_problems : 0);
+    return 0;
+}
+
+// argument checks shared by the two forms; tk: the checked t
+static int check_changed_args(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t, const int64_t* changed,
+                              const double* At, int64_t ldat, int64_t strideAt, const double* cx, std::vector<int>& tk, bool* any) {
+    int rc = check_ragged(h, batch, m, n, t_max, t, nullptr, 0, nullptr, nullptr, 0, 0, nullptr, tk, false, false, false);
+    if (rc) return rc;
+    rc = check_launch_batch(h, batch);
+    if (rc) return rc;
+    if (!changed) { h->err = "changed is NULL"; return -7; }
+    rc = check_changed_call(h, batch, m, n, t_max, tk, changed);
+    if (rc) return rc;
+    bool flagged = false, constrained = false;
+    for (int64_t k = 0; k < batch; ++k)
+        if (changed[k]) { flagged = true; constrained = constrained || t[k] > 0; }
+    *any = flagged;
+    if (constrained) {
+        if (!At) { h->err = "At is NULL while a changed problem has t[k] > 0"; return -8; }
+        if (ldat < n) { h->err = "ldat < n"; return -9; }
+        if (strideAt < ldat * t_max) { h->err = "strideAt < ldat * t_max"; return -10; }
+        if (!cx) { h->err = "cx is NULL while a changed problem has t[k] > 0"; return -11; }
+    }
+    return 0;
+}
+
+// a call without a flag: nothing launched, nothing written
+static int nothing_changed(enlsip_gn_handle h) {
+    h->cstage_problems = h->jstage_problems = 0;
+    if (h->split > 0) h->child->cstage_problems = h->child->jstage_problems = 0;
+    h->constraint_refactored = 0;
+    return 0;
+}
+
+int enlsip_gn_solve_changed_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                        const int64_t* changed, const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
+                                        double eps_rank, double* dp, double* db, double* dd, enlsip_gn_info* dinfo, int64_t* djpvtA,
+                                        int64_t* djpvtL, int64_t* djpvtJ2) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    bool any = false;
+    int rc = check_changed_args(h, batch, m, n, t_max, t, changed, dAt, ldat, strideAt, dcx, tk, &any);
+    if (rc) return rc;
+    const BatchOperands& L = h->last;
+    if (t_max > 0 && (dAt != L.At || ldat != L.ldat || strideAt != L.strideAt || dcx != L.cx)) {
+        h->err = "dAt, ldat, strideAt, dcx must be the buffers the resident solve was made with (the slots of the changed problems "
+                 "rewritten in place)";
+        return -8;
+    }
+    if (!any) return nothing_changed(h);
+    return solve_changed_core(h, {batch, m, n, t_max, L.J, L.ldj, L.strideJ, L.rx, L.At, L.ldat, L.strideAt, L.cx, dp, db, dd, dinfo,
+                                  (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()}, changed, eps_rank);
+    GN_CATCH(h)
+}
+
+int enlsip_gn_solve_changed_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                    const int64_t* changed, const double* At, int64_t ldat, int64_t strideAt, const double* cx,
+                                    double eps_rank, double* p, double* b, double* d, enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL,
+                                    int64_t* jpvtJ2) {
+    if (!h) return -1;
+    GN_TRY
+    std::vector<int> tk;
+    bool any = false;
+    int rc = check_changed_args(h, batch, m, n, t_max, t, changed, At, ldat, strideAt, cx, tk, &any);
+    if (rc) return rc;
+    const BatchOperands L = h->last;
+    if (!h->in_stage.p || L.J != (const double*)h->in_stage.p) {
+        h->err = "enlsip_gn_solve_changed_batched: the resident solve was made from device buffers: use enlsip_gn_solve_changed_batched_dev";
+        return -1;
+    }
+    if (!any) return nothing_changed(h);
+    GN_HIP(hipSetDevice(h->device));
+    const int kA = (int)std::min(n, t_max);
+    // outputs packed as solve_host packs them (the resident solve reads nothing of this buffer)
+    rc = grow(h, h->out_stage, ((size_t)batch * (n + t_max + m) + (size_t)batch * (t_max + kA + n)) * 8 + 1024);
+    if (rc) return rc;
+    double* dp = (double*)h->out_stage.p;
+    double* db = dp + (size_t)batch * n;
+    double* dd = db + (size_t)batch * t_max;
+    long long* djA = (long long*)(dd + (size_t)batch * m);
+    long long* djL = djA + (size_t)batch * t_max;
+    long long* djJ = djL + (size_t)batch * kA;
+    hipStream_t s = h->stream;
+    // the changed problems' A', cx into the slots of the staging area the resident solve reads
+    double* sAt = const_cast<double*>(L.At);
+    double* scx = const_cast<double*>(L.cx);
+    for (int64_t k = 0; k < batch && t_max > 0; ++k) {
+        if (!changed[k] || t[k] <= 0) continue;
+        GN_HIP(hipMemcpy2DAsync(sAt + (size_t)k * L.strideAt, (size_t)L.ldat * 8, At + (size_t)k * strideAt, (size_t)ldat * 8, (size_t)n * 8,
+                                (size_t)t_max, hipMemcpyHostToDevice, s));
+        GN_HIP(hipMemcpyAsync(scx + (size_t)k * t_max, cx + (size_t)k * t_max, (size_t)t_max * 8, hipMemcpyHostToDevice, s));
+    }
+    rc = solve_changed_core(h, {batch, m, n, t_max, L.J, L.ldj, L.strideJ, L.rx, L.At, L.ldat, L.strideAt, L.cx, dp, db, dd, nullptr, djA, djL,
+                                djJ, info, tk.data()}, changed, eps_rank);
+    if (rc) return rc;
+    for (int64_t k = 0; k < batch; ++k) {
+        if (!changed[k]) continue;
+        if (p) GN_HIP(hipMemcpyAsync(p + (size_t)k * n, dp + (size_t)k * n, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+        if (b && t_max > 0) GN_HIP(hipMemcpyAsync(b + (size_t)k * t_max, db + (size_t)k * t_max, (size_t)t_max * 8, hipMemcpyDeviceToHost, s));
+        if (d) GN_HIP(hipMemcpyAsync(d + (size_t)k * m, dd + (size_t)k * m, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        if (jpvtA && t_max > 0) GN_HIP(hipMemcpyAsync(jpvtA + (size_t)k * t_max, djA + (size_t)k * t_max, (size_t)t_max * 8, hipMemcpyDeviceToHost, s));
+        if (jpvtL && kA > 0) GN_HIP(hipMemcpyAsync(jpvtL + (size_t)k * kA, djL + (size_t)k * kA, (size_t)kA * 8, hipMemcpyDeviceToHost, s));
+        if (jpvtJ2) GN_HIP(hipMemcpyAsync(jpvtJ2 + (size_t)k * n, djJ + (size_t)k * n, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    }
+    GN_HIP(hipStreamSynchronize(s));
+    return 0;
+    GN_CATCH(h)
+}
+
+int enlsip_gn_get_jacobian_resolved(enlsip_gn_handle h, int64_t* count) {
+    if (!h) return -1;
+    if (!count) return -2;
+    *count = (int64_t)(h->jstage_problems + (h->split > 0 && h->child ? h->child->jstage_problems : 0));
+    return 0;
 }
 
 int enlsip_gn_get_constraint_refactored(enlsip_gn_handle h, int64_t* count) {

@@ -175,7 +175,16 @@ struct enlsip_gn_context {
     } fb;
     std::vector<int> refit;
     gn::DevBuf plist_buf;
+    gn::DevBuf info_stage;              // a changed-problems solve: the listed problems' info records in list order, before their scatter
     long long cstage_problems = 0;
+    // Changed-problems solve (enlsip_gn_solve_changed_batched*): the next solve_dev on this handle (parent, pipeline child) redoes the
+    // problems of `refit` only, constraint stage AND Jacobian side, from the resident J, rx; while it runs, run_plist / run_nlist are
+    // the device list every Jacobian-side launch is sized by (NULL outside of it: the whole part).  jstage_problems counts the
+    // problems the Jacobian-side kernels of the last solve_dev were launched over (enlsip_gn_get_jacobian_resolved sums the halves).
+    bool changed_once = false;
+    const int* run_plist = nullptr;
+    long long run_nlist = 0;
+    long long jstage_problems = 0;
     long long constraint_refactored = 0;   // ... summed over the handles (enlsip_gn_get_constraint_refactored)
     unsigned long long route = 0;       // ENLSIP_GN_ROUTE_* bits of the last solve (enlsip_gn_get_route)
     long long chunk0 = 0;               // first problem (index in the caller's batch) of the resident chunk: batches above the launch limit run in chunks

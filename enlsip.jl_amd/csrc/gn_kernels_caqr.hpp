@@ -59,6 +59,7 @@ struct CaqrArgs {
     long long tOff2;
     int xmap;           // level-0 far update of a pair, one problem with many tiles: > 0 = number of tiles, the grid is read
                         // XCD-locally (gn_kernels_update_v4.hpp: k_caqr_update_v4_pair)
+    const int* plist;   // device list of problem indices, one per grid entry of the problem dimension (NULL: entry i = problem i + prob0)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -339,7 +340,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? ENLSIP_FACTOR_OCC16 : (NW == 8 
     __shared__ double vsh[2][64 * RPL];
     __shared__ double taush[PB];
     __shared__ double gsh[PB][PB + 1];
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const ProbState st = a.state[prob];
     double x[PB / NW][RPL];
     // a passenger launch factors last panels narrower than 32 whose only trailing column rides along: no T beyond its diagonal
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(64 * NW, NW == 16 ? ENLSIP_FACTOR_OCC16 : (NW == 8 
 // ---------------------------------------------------------------------------------------------
 template <int RPL>
 __global__ __launch_bounds__(256) void k_caqr_update_refl(CaqrArgs a) {
-    const int prob = blockIdx.z + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.z, a.prob0);
     const ProbState st = a.state[prob];
     const int r0 = a.panel * PB;
     if (r0 >= st.kp) return;

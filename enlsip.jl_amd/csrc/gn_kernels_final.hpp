@@ -41,6 +41,7 @@ struct FinalArgs {
     long long* jL_out; long long sJLo;  const long long* jpvtL; long long sJL;
     long long* jJ_out; long long sJJo;
     ProbState* state;
+    const int* plist;   // device list of problem indices, one per grid entry of the problem dimension (NULL: entry i = problem i + prob0)
 };
 
 // LDS (doubles): vn1[nv] vn2[nv] ybuf[nv] pbuf[nv] mat[matd] + ints, sized by the host to the problem so that small
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(NTH) void k_pivot_solve(FinalArgs a) {
     double* blk = mat;
     int* sh_i = reinterpret_cast<int*>(mat + a.matd);
 
-    const int prob = blockIdx.x + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.x, a.prob0);
     ProbState* stp = a.state + prob;
     if (a.n2cap > 0 && stp->n2 > a.n2cap) return;     // its pivoted factors were not produced (stale permutation entries)
     const int rankA = stp->rankA, n2 = stp->n2, kp = stp->kp;

@@ -30,7 +30,7 @@ template <int NR>
 __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : ((NR == 64 && ENLSIP_PS64_OCC) ? ENLSIP_PS64_OCC : 1)) void k_pivot_small(FinalArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const int prob = blockIdx.x + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.x, a.prob0);
     ProbState* stp = a.state + prob;
     const int rankA = stp->rankA, n2 = stp->n2, kp = stp->kp;
     // a problem whose J2 is wider than the launch shape (rank-deficient A) is redone by the caller with the true width
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(64, 3) void k_pivot_small2(FinalArgs a, int nprob) 
     const int ln = threadIdx.x, lh = ln & 31, hb = ln & 32, half = ln >> 5;
     const int pidx = 2 * blockIdx.x + half;            // the lane's problem inside the launch
     const bool have = pidx < nprob;
-    const int prob_l = a.prob0 + (have ? pidx : 0);
+    const int prob_l = listed_prob(a.plist, have ? pidx : 0, a.prob0);
     const int n = a.n, m = a.m, t = a.t, kA = a.kA, ldr = a.ldr, ldw = a.ldw;
     int rankA = 0, n2 = 0, kp = 0;
     bool ok = false;
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(64, 3) void k_pivot_small2(FinalArgs a, int nprob) 
         const int hbu = 32 * hsel;
         if (2 * blockIdx.x + hsel >= nprob) continue;
         if (!__builtin_amdgcn_readlane((int)ok, hbu)) continue;
-        const int prob = a.prob0 + 2 * blockIdx.x + hsel;
+        const int prob = listed_prob(a.plist, 2 * blockIdx.x + hsel, a.prob0);
         const int n2u = __builtin_amdgcn_readlane(n2, hbu), kpu = __builtin_amdgcn_readlane(kp, hbu), rAu = __builtin_amdgcn_readlane(rankA, hbu);
         const int myposh = __shfl(mypos, hbu + lh);     // the half's positions in lanes 0..31
         ProbState* stp = a.state + prob;
@@ -434,7 +434,8 @@ __global__ __launch_bounds__(64, 3) void k_pivot_small2(FinalArgs a, int nprob) 
 }
 
 // Returns false when the launch shape is outside the kernel's range (the caller uses k_pivot_solve).
-inline bool launch_pivot_small(int kp_launch, int n2_launch, int batch, hipStream_t s, FinalArgs a) {
+// batch: the problems of the part (it picks the kernel form); nlaunch: the problems the grid covers (a.plist's length, or batch)
+inline bool launch_pivot_small(int kp_launch, int n2_launch, int batch, hipStream_t s, FinalArgs a, int nlaunch) {
     if (kp_launch > 64 || n2_launch + 1 > 64 || a.refactor != 1 || a.dsrc) return false;
     const long long mx = a.n > a.t ? a.n : a.t;
     a.nv = (int)((mx + 7) / 8 * 8);
@@ -443,12 +444,12 @@ inline bool launch_pivot_small(int kp_launch, int n2_launch, int batch, hipStrea
     if (kp_launch <= 32 && n2_launch + 1 <= 32 && batch > 1) {      // two problems per wave
         a.matd = kp_launch > 0 ? kp_launch : 1;
         GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_WAVE2);
-        hipLaunchKernelGGL(k_pivot_small2, dim3((batch + 1) / 2), dim3(64), final_small2_lds_bytes(a.matd, a.nv), s, a, batch);
+        hipLaunchKernelGGL(k_pivot_small2, dim3((nlaunch + 1) / 2), dim3(64), final_small2_lds_bytes(a.matd, a.nv), s, a, nlaunch);
         return true;
     }
     const size_t lds = final_small_lds_bytes(0, a.nv) + (size_t)a.matd * 8;
-    if (kp_launch <= 32) { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_WAVE32); hipLaunchKernelGGL(k_pivot_small<32>, dim3(batch), dim3(64), lds, s, a); }
-    else { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_WAVE64); hipLaunchKernelGGL(k_pivot_small<64>, dim3(batch), dim3(64), lds, s, a); }
+    if (kp_launch <= 32) { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_WAVE32); hipLaunchKernelGGL(k_pivot_small<32>, dim3(nlaunch), dim3(64), lds, s, a); }
+    else { GN_ROUTE(ENLSIP_GN_ROUTE_PIVOT_WAVE64); hipLaunchKernelGGL(k_pivot_small<64>, dim3(nlaunch), dim3(64), lds, s, a); }
     return true;
 }
 

@@ -24,6 +24,7 @@ struct JQ1Args {
     const ProbState* state;
     int prob0;
     double* VT;        long long sVT;     // k_jq1_v2 only: V T' of the (single) reflector block, n x 64 (ld n), built by k_vt
+    const int* plist;   // device list of problem indices, one per grid entry of the problem dimension (NULL: entry i = problem i + prob0)
 };
 
 // LDS (doubles): Jl[RB * n] Vl[KC * 65] Wv[RB * 64] Wt[RB * 64] red[256]
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void k_jq1(JQ1Args a) {
     double* Wt = Wv + Q1_RB * KBLK;
     double* red = Wt + Q1_RB * KBLK;
 
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const int row0 = blockIdx.x * Q1_RB;
     const double* J = a.J + prob * a.strideJ;
     const double* rx = a.rx + prob * a.stride_rx;

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256, 2) void k_jq1_mfma(JQ1Args a) {
     double* Tl = lds_a;                       // [j * 66 + k]
 
     const int n = a.n, m = a.m, kA = a.kA, ldw = a.ldw;
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const int row0 = blockIdx.x * QM_RB;
     const double* Jin = a.J + prob * a.strideJ;
     const double* rx = a.rx + prob * a.stride_rx;

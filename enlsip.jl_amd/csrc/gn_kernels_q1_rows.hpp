@@ -27,7 +27,7 @@ __global__ __launch_bounds__(256, (NMAX == 32 && ENLSIP_JR_OCC) ? ENLSIP_JR_OCC 
     __shared__ double taus[Q1R_MAXK];
     __shared__ double p1s[NMAX];
     const int n = a.n, m = a.m, kA = a.kA, ldw = a.ldw;
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const double* Jin = a.J + prob * a.strideJ;
     const double* rx = a.rx + prob * a.stride_rx;
     const double* FA = a.FA + prob * a.sFA;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 3) void k_jq1_rows2(JQ1Args a) {
     __shared__ double taus[Q1R_MAXK];
     __shared__ double p1s[64];
     const int n = a.n, m = a.m, kA = a.kA, ldw = a.ldw;
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const double* Jin = a.J + prob * a.strideJ;
     const double* rx = a.rx + prob * a.stride_rx;
     const double* FA = a.FA + prob * a.sFA;

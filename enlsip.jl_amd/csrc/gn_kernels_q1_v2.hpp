@@ -50,7 +50,7 @@ constexpr int Q2_VS = KBLK * Q2_LDV;         // doubles per wave image
 __global__ __launch_bounds__(256) void k_vt(JQ1Args a) {
     __shared__ __attribute__((aligned(16))) double Ts[KBLK * KBLK];      // Ts[k][j] = T[k][j] (zero below the diagonal)
     const int n = a.n;
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const double* FA = a.FA + prob * a.sFA;
     const double* TA = a.TA + prob * a.sTA;
     double* VT = a.VT + prob * a.sVT;
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
     __shared__ double dred[Q2_NW][Q2_RB];
 
     const int n = a.n, ldw = a.ldw;
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const int row0 = blockIdx.x * Q2_RB;
     const double* Jin = a.J + prob * a.strideJ;
     const double* rx = a.rx + prob * a.stride_rx;

@@ -61,7 +61,7 @@ constexpr int SB_STAT_OFF = 1 << 20;
 // reset of the per-problem block state; runs after k_qd_init
 // j_first: pivot steps already done by a launch-per-step head (hybrid stage; 0 otherwise)
 __global__ void k_sb_reset(SbArgs a, int n, int j_first) {
-    const int prob = blockIdx.y + a.q.prob0;
+    const int prob = listed_prob(a.q.plist, blockIdx.y, a.q.prob0);
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < n) a.inblk[prob * a.sIn + c] = -1;
     if (c == 0) {
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void k_sb_update_blk(SbArgs a) {
     __shared__ __attribute__((aligned(16))) double W2l[PB * PB];
     __shared__ double ssq[4][32];
 
-    const int prob = blockIdx.y + a.q.prob0;
+    const int prob = listed_prob(a.q.plist, blockIdx.y, a.q.prob0);
     const ProbState st = a.q.state[prob];
     if (a.q.n2cap > 0 && st.n2 > a.q.n2cap) return;      // wider than the launch shape: redone by the caller
     const int kp = st.kp, n2 = st.n2, ctot = n2 + 1;

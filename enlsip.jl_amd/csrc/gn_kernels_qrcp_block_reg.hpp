@@ -52,12 +52,15 @@ struct SbRegLds {             // bookkeeping of a block: keys, positions, candid
 // it, the <2> form a quarter.  Every block is therefore launched in up to three forms (run_qrcp_block) and a workgroup runs
 // only in the form that fits its problem's current row count: RPL_LOW = rows-per-lane of the next smaller form launched
 // beside this one (0: none) — problems that fit it are left to it.
-template <int RPL, int NWV, int RPL_LOW = 0>
+// LISTED: workgroup i works on problem a.q.plist[i] (a launch over a subset of the resident batch) instead of i + prob0.  A form of
+// its own, not a run-time test: the <8> form fills the register file to the last register, and the test cost it 8 more bytes of
+// scratch per lane on the whole-batch path.
+template <int RPL, int NWV, int RPL_LOW = 0, bool LISTED = false>
 __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k_sb_factor_reg(SbArgs a) {
     constexpr int NCW = SB_KMAX / NWV;
     constexpr int NT = 64 * NWV;
     __shared__ SbRegLds L;
-    const int prob = blockIdx.x + a.q.prob0;
+    const int prob = LISTED ? listed_prob(a.q.plist, blockIdx.x, 0) : (int)blockIdx.x + a.q.prob0;
     const ProbState st = a.q.state[prob];
     if (a.q.n2cap > 0 && st.n2 > a.q.n2cap) return;      // wider than the launch shape: redone by the caller
     const int kp = st.kp, n2 = st.n2;

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256, 4) void k_jq1_factor_small(JQ1Args q, CaqrArgs
     __shared__ double slab[SF_SLAB][64 * RPL];
 
     const int n = q.n, m = q.m, kA = q.kA, ldw = q.ldw;
-    const int prob = blockIdx.y + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.y, a.prob0);
     const ProbState st = a.state[prob];
     const double* Jin = q.J + prob * q.strideJ;
     const double* rx = q.rx + prob * q.stride_rx;

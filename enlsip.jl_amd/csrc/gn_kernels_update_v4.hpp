@@ -520,7 +520,7 @@ template <int RPL, bool PAIR>
 __device__ __forceinline__ void v4_rhs_body(const CaqrArgs& a, double (*part)[PB], double* w2s, double* Tl, const int g) {
     constexpr int TLD = PB + 1;
     constexpr int NWV = 4;                                               // waves of the block kernel's workgroup
-    const int prob = blockIdx.z + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.z, a.prob0);
     const ProbState st = a.state[prob];
     const int r0a = a.panel * PB;
     if (r0a >= st.kp) return;
@@ -632,7 +632,7 @@ __device__ __forceinline__ void v4_rhs_body(const CaqrArgs& a, double (*part)[PB
 // the plain kernel with a.pair == 2 serves the others (mixed-rank batches in the second attempt of a solve).
 template <bool TRI, bool PAIR>
 __device__ __forceinline__ bool v4_setup(const CaqrArgs& a, V4Ctx& c, int& nvu, int& ncols, const int g, const int yb) {
-    const int prob = blockIdx.z + a.prob0;
+    const int prob = listed_prob(a.plist, blockIdx.z, a.prob0);
     const ProbState st = a.state[prob];
     const int r0 = a.panel * PB;
     if (r0 >= st.kp) return false;

@@ -22,9 +22,10 @@ constexpr int GN_RESCALE_BAND = 400;           // inputs with 2^-400 <= max |ent
 // RAGGED: F_A of problem k has min(kA, tk[k]) reflectors — a problem without constraints has none to look at
 template <bool RAGGED>
 __device__ __forceinline__ void extreme_flags_body(ProbState* state, const double* Rt, long long sRt, const double* FA, long long sFA,
-                                                   int kA, int n2cap, int batch, const int* tk) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= batch) return;
+                                                   int kA, int n2cap, int batch, const int* tk, const int* plist) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= batch) return;
+    const int k = listed_prob(plist, idx, 0);
     const ProbState st = state[k];
     if (n2cap > 0 && st.n2 > n2cap) return;            // redone by the caller (second attempt): nothing of it is final yet
     const double tiny = 0x1p-440;
@@ -42,17 +43,23 @@ __device__ __forceinline__ void extreme_flags_body(ProbState* state, const doubl
     if (f) state[k].status = st.status | f;
 }
 __global__ __launch_bounds__(256) void k_extreme_flags(ProbState* state, const double* Rt, long long sRt, const double* FA, long long sFA,
-                                                       int kA, int n2cap, int batch) {
-    extreme_flags_body<false>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, nullptr);
+                                                       int kA, int n2cap, int batch, const int* plist) {
+    extreme_flags_body<false>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, nullptr, plist);
 }
 __global__ __launch_bounds__(256) void k_extreme_flags_ragged(ProbState* state, const double* Rt, long long sRt, const double* FA,
-                                                              long long sFA, int kA, int n2cap, int batch, const int* tk) {
-    extreme_flags_body<true>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, tk);
+                                                              long long sFA, int kA, int n2cap, int batch, const int* tk, const int* plist) {
+    extreme_flags_body<true>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, tk, plist);
 }
 
-__global__ __launch_bounds__(256) void k_clear_status_bits(ProbState* state, int bits, int batch) {
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k < batch) state[k].status &= ~bits;
+__global__ __launch_bounds__(256) void k_clear_status_bits(ProbState* state, int bits, int batch, const int* plist) {
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx < batch) state[listed_prob(plist, idx, 0)].status &= ~bits;
+}
+
+// dst[plist[i]] = src[i]: the info records of the listed problems of a changed-problems solve into the caller's device array
+__global__ __launch_bounds__(256) void k_scatter_info(enlsip_gn_info* dst, const enlsip_gn_info* src, const int* plist, int count) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < count) dst[plist[i]] = src[i];
 }
 
 // bits of max |x| over a rows x cols matrix (non-negative doubles order like their bit patterns; a NaN outranks everything, so

@@ -464,6 +464,51 @@ function gn_search_direction_factored_batched_hip(h::Handle, Js::Array{Float64,3
     return P, infos
 end
 
+"""    gn_search_direction_changed_batched_hip!(h, P, infos, m, t_max, As, cxs, changed, ε_rank) -> (P, infos)
+
+Only the problems whose working set changed, in place, on the fully solved ragged batch that is resident (the undo of
+src/enlsip_functions.jl:728-743, a second-order deletion :745-762 / :773-790): constraint stage and Jacobian side again for the
+problems with `changed[k]`, from the resident `J`, `rx` and `As[k]`, `cxs[k]`; the others (`As[k]` must have the row count they are
+resident with) are not touched, and their columns of `P` and entries of `infos` stay as they are."""
+function gn_search_direction_changed_batched_hip!(h::Handle, P::Matrix{Float64}, infos::Vector{Info}, m::Integer, t_max::Integer,
+                                                  As::Vector{Matrix{Float64}}, cxs::Vector{Vector{Float64}},
+                                                  changed::AbstractVector{Bool}, ε_rank::Float64)
+    n, B = size(P)
+    kA = min(n, t_max)
+    t, Ats, cxp = pack_working_sets(n, t_max, As, cxs)
+    flags = Int64[c ? 1 : 0 for c in changed]
+    b = zeros(Float64, max(t_max, 1), B); d = zeros(Float64, m, B)
+    jA = zeros(Int64, max(t_max, 1), B); jL = zeros(Int64, max(kA, 1), B); jJ = zeros(Int64, n, B)
+    GC.@preserve t flags Ats cxp P b d jA jL jJ infos check(h, ccall((:enlsip_gn_solve_changed_batched, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Info}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        h.ptr, B, m, n, t_max, t, flags, Ats, max(n, 1), n * max(t_max, 1), cxp, ε_rank, P, b, d, infos, jA, jL, jJ))
+    return P, infos
+end
+
+"""    gn_search_direction_changed_batched_dev_hip(h, B, m, n, t_max, t, changed, dAt, ldat, strideAt, dcx, ε_rank, dp, db, dd, dinfo)
+
+The same with DEVICE buffers: `dAt`, `ldat`, `strideAt`, `dcx` are those of the resident solve, the changed slots rewritten in place;
+`t` and `changed` stay host arrays; only the changed problems' output slots are written."""
+function gn_search_direction_changed_batched_dev_hip(h::Handle, B::Integer, m::Integer, n::Integer, t_max::Integer, t::Vector{Int64},
+                                                     changed::AbstractVector{Bool}, dAt::Ptr{Float64}, ldat::Integer,
+                                                     strideAt::Integer, dcx::Ptr{Float64}, ε_rank::Float64, dp::Ptr{Float64},
+                                                     db::Ptr{Float64}, dd::Ptr{Float64}, dinfo::Ptr{Info})
+    flags = Int64[c ? 1 : 0 for c in changed]
+    GC.@preserve t flags check(h, ccall((:enlsip_gn_solve_changed_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Float64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Info}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+        h.ptr, B, m, n, t_max, t, flags, dAt, ldat, strideAt, dcx, ε_rank, dp, db, dd, dinfo, Ptr{Int64}(0), Ptr{Int64}(0), Ptr{Int64}(0)))
+    return nothing
+end
+
+"""    jacobian_resolved_hip(h) -> problems the Jacobian-side kernels of the last solve on `h` were launched over"""
+function jacobian_resolved_hip(h::Handle)
+    c = Ref{Int64}(0)
+    check(h, ccall((:enlsip_gn_get_jacobian_resolved, LIB), Cint, (Ptr{Cvoid}, Ref{Int64}), h.ptr, c))
+    return Int(c[])
+end
+
 # ---- the consumers of a batched solve over a range of its problems (one call, a fixed number of launches) ----------------------
 #
 # A batched outer iteration: solve (ragged), first estimate over the batch, the host deletion test of update_working_set

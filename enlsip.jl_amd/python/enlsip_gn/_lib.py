@@ -78,6 +78,13 @@ PROTOTYPES = {
                                                        C.c_void_p, C.c_void_p, _i64, _i64, C.c_void_p, C.c_double, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_get_constraint_refactored": (C.c_int, [_h, _ip]),
+    "enlsip_gn_solve_changed_batched": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _i64,
+                                                  C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_solve_changed_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _i64,
+                                                      C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_jacobian_resolved": (C.c_int, [_h, _ip]),
     "enlsip_gn_factor_shape": (C.c_int, [_h, C.c_int, _i64, _ip, _ip]),
     "enlsip_gn_get_R": (C.c_int, [_h, C.c_int, _i64, C.c_void_p, _i64]),
     "enlsip_gn_get_diagR": (C.c_int, [_h, C.c_int, _i64, C.c_void_p]),

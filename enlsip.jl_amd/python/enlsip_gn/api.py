@@ -108,6 +108,7 @@ class GNSolver:
     def __init__(self, device: int = -1, flags: int = 0, tile_rows: int = 0, stream: int = 0):
         self._lib = L.load()
         self._h = C.c_void_p()
+        self._resident_m = None     # rows of the last ragged host-form solve made through this object (solve_changed_batched)
         opts = L.Opts(device=device, flags=flags, panel_width=0, tile_rows=tile_rows,
                       stream=C.c_void_p(stream) if stream else None)
         rc = self._lib.enlsip_gn_create(C.byref(self._h), C.byref(opts))
@@ -244,6 +245,7 @@ class GNSolver:
         """Like solve_batched, with problem k's own t[k] <= t_max: At (batch, t_max, n) and cx (batch, t_max) are padded
         (pack_ragged builds them); rows past t[k] are not read.  Outputs have the t_max layout with zeros past t[k]."""
         batch, n, m = J.shape
+        self._resident_m = m
         t = np.ascontiguousarray(t, dtype=np.int64)
         t_max = At.shape[1] if At is not None and At.ndim == 3 else 0
         kA = min(n, t_max)
@@ -302,6 +304,13 @@ class GNSolver:
             raise ValueError(f"refactor must have {batch} entries")
         return r
 
+    @staticmethod
+    def _changed_mask(changed, batch: int):
+        c = None if changed is None else np.ascontiguousarray(np.asarray(changed).astype(np.int64))
+        if c is None or c.shape != (batch,):
+            raise ValueError(f"changed must have {batch} entries")
+        return c
+
     def factor_constraints_batched(self, m: int, At: np.ndarray, cx: np.ndarray, t=None, eps_rank: float = SQRT_EPS):
         """Constraint stage of a whole ragged batch, nothing about J: At (batch, t_max, n), cx (batch, t_max), t (batch,) or None
         (all t_max), m: rows of the solve that follows.  Leaves F_A, F_L11 of every problem resident (first_lagrange_batched with
@@ -342,6 +351,7 @@ class GNSolver:
         if rx.shape != (batch, m):
             raise ValueError(f"rx must be ({batch}, {m})")
         r = self._refactor_mask(refactor, batch)
+        self._resident_m = m
         t_max = At.shape[1]
         kA = min(n, t_max)
         J = np.ascontiguousarray(J)
@@ -375,6 +385,57 @@ class GNSolver:
         """Problems the constraint kernels of the last factor_constraints_batched / solve_factored_batched were launched over."""
         c = C.c_int64(0)
         self._chk(self._lib.enlsip_gn_get_constraint_refactored(self._h, C.byref(c)))
+        return int(c.value)
+
+    # ---- only the problems whose working set changed, in place (src/enlsip_functions.jl:728-743, :745-762, :773-790) -------------
+    def solve_changed_batched(self, At: np.ndarray, cx: np.ndarray, t, changed, eps_rank: float = SQRT_EPS, m: Optional[int] = None):
+        """On the fully solved ragged batch this solver's last host-form solve left resident (solve_batched_ragged,
+        solve_factored_batched, or this call): the problems with a changed flag again, constraint stage and Jacobian side, from
+        the resident J, rx and their At / cx rows and t[k]; nothing of another problem is touched.  At (batch, t_max, n) and
+        cx (batch, t_max) in the resident layout (rows of unflagged problems are not read), t (batch,), changed (batch,) flags.
+        Returns the tuple of solve_batched_ragged; the slots of unflagged problems are left as they are made here: NaN in p, b, d,
+        zero in the pivots and the info records.  m: rows of the resident problems; needed only when they were not solved
+        through this object's solve_batched_ragged / solve_factored_batched (which remember it)."""
+        At, cx, t = self._ragged_A(At, cx, t)
+        batch, t_max, n = At.shape
+        if batch < 1:
+            raise ValueError("batch must be >= 1")
+        ch = self._changed_mask(changed, batch)
+        m = m if m is not None else self._resident_m
+        if m is None:
+            raise ValueError("solve_changed_batched: no ragged host-form solve was made through this object: pass m= (the rows "
+                             "of the resident problems)")
+        kA = min(n, t_max)
+        p, b, d = np.full((batch, n), np.nan), np.full((batch, t_max), np.nan), np.full((batch, m), np.nan)
+        jA = np.zeros((batch, t_max), np.int64)
+        jL = np.zeros((batch, kA), np.int64)
+        jJ = np.zeros((batch, n), np.int64)
+        info = (L.Info * batch)()
+        self._chk(self._lib.enlsip_gn_solve_changed_batched(
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(ch), _fptr(At) if t_max else None, max(n, 1), n * t_max,
+            _fptr(cx) if t_max else None, eps_rank, _fptr(p), _fptr(b), _fptr(d), C.cast(info, C.c_void_p), _fptr(jA), _fptr(jL),
+            _fptr(jJ)))
+        infos = [(int(i.rankA), int(i.rankJ2), int(i.code), int(i.dimA), int(i.dimJ2), int(i.status)) for i in info]
+        return p, b, d, infos, jA, jL, jJ
+
+    def solve_changed_batched_dev(self, batch, m, n, t_max, t, changed, dAt, ldat, strideAt, dcx, eps_rank=SQRT_EPS, dp=0, db=0, dd=0,
+                                  dinfo=0, djA=0, djL=0, djJ=0):
+        """Device pointers; t and changed stay host arrays.  dAt, ldat, strideAt, dcx are the buffers of the resident solve, the
+        flagged problems' slots rewritten in place; only the flagged problems' output slots are written."""
+        v = lambda x: C.c_void_p(x) if x else None
+        t = np.ascontiguousarray(t, dtype=np.int64)
+        if t.shape != (batch,):
+            raise ValueError(f"t must have {batch} entries")
+        ch = self._changed_mask(changed, batch)
+        self._chk(self._lib.enlsip_gn_solve_changed_batched_dev(
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(ch), v(dAt), ldat, strideAt, v(dcx), eps_rank, v(dp), v(db), v(dd),
+            v(dinfo), v(djA), v(djL), v(djJ)))
+
+    def jacobian_resolved(self) -> int:
+        """Problems the Jacobian-side kernels of the last solve were launched over (both pipelined halves): batch after a
+        whole-batch solve, the number of flags after solve_changed_batched."""
+        c = C.c_int64(0)
+        self._chk(self._lib.enlsip_gn_get_jacobian_resolved(self._h, C.byref(c)))
         return int(c.value)
 
     # ---- batch, device buffers (raw pointers, e.g. torch tensor .data_ptr()) ------------------

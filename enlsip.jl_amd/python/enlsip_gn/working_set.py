@@ -246,8 +246,9 @@ def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p
     :771), with the constraint stage run again only for the problems whose set changed.  ``A`` is the full (l x n) constraint
     Jacobian of every problem (a list, or one matrix shared by all).  Leaves in ``Ws[k]``, ``Cs[k]``, ``its[k]``, ``p_gns[k]``
     what ``update_working_set`` leaves for problem k and returns the (F_A, F_L11, F_J2) views per problem; the whole batch is
-    resident afterwards.  A later change of some working set (the undo of :728-743, a second-order deletion :745 / :773) takes the
-    pair of calls again on the final sets; the Jacobian side of the unchanged problems is then recomputed with the same result."""
+    resident afterwards.  A later change of some working set (the undo of :728-743, a second-order deletion :745 / :773) is one
+    ``solve_changed_batched`` call: the constraint stage and the Jacobian side again for exactly the problems whose set changed, in
+    place, in the padded layout (t_max) of the resident batch.  After the first pair there is no further whole-batch call."""
     B = len(Ws)
     m, n = Js[0].shape
     As_full = A if isinstance(A, (list, tuple)) else [A] * B
@@ -276,12 +277,21 @@ def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p
             its[k].dimA, its[k].dimJ2 = infos[k][0], infos[k][1]
             its[k].b_gn, its[k].d_gn = b[k, :Ws[k].t].copy(), d[k].copy()
 
-    def solve_again(ks):
-        """the pair of calls on the current working sets; results taken for the problems ks"""
+    def padded():
+        """the current working sets in the padded layout of the resident batch (no set outgrows the t_max it started with)"""
         At, cx, t = packed()
-        solver.factor_constraints_batched(m, At, cx, t, eps_rank)
-        take(solver.solve_factored_batched(J, rx, At, cx, t, None, eps_rank), ks)
-        return At.shape[1]
+        pad = t_max - At.shape[1]
+        if pad:
+            At = np.concatenate([At, np.zeros((B, pad, n))], axis=1)
+            cx = np.concatenate([cx, np.zeros((B, pad))], axis=1)
+        return At, cx, t
+
+    def solve_again(ks):
+        """the problems ks, whose working set changed, again on the resident batch; nothing else of it is touched"""
+        At, cx, t = padded()
+        flags = np.zeros(B, dtype=np.int64)
+        flags[list(ks)] = 1
+        take(solver.solve_changed_batched(At, cx, t, flags, eps_rank, m=m), ks)
 
     At, cx, t = packed()
     t_max = At.shape[1]
@@ -304,11 +314,7 @@ def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p
             C.A = np.delete(C.A, s - 1, axis=0)
         lams.append(lam)
     flags = np.array([1 if k in removed else 0 for k in range(B)], dtype=np.int64)
-    At, cx, t = packed()
-    if At.shape[1] != t_max:        # every longest working set lost a row: the padded layout of the factor call stays
-        pad = t_max - At.shape[1]
-        At = np.concatenate([At, np.zeros((B, pad, n))], axis=1)
-        cx = np.concatenate([cx, np.zeros((B, pad))], axis=1)
+    At, cx, t = padded()            # (every longest working set may have lost a row: the layout of the factor call stays)
     take(solver.solve_factored_batched(J, rx, At, cx, t, flags, eps_rank), range(B))        # :725 / :771
     undone = []
     for k, (s, cx_s, A_s, lam_s, ds_s, index_s) in removed.items():                         # :728-743
@@ -326,7 +332,7 @@ def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p
         C.A = rows * C.diag_scale[:, None] if C.scaling else rows.copy()
         undone.append(k)
     if undone:
-        t_max = solve_again(undone)
+        solve_again(undone)
     # second-order estimate where :745 / :773 ask for it: the problems that kept their set or got it back
     cand = [k for k in range(B) if (k not in removed or k in undone)
             and not (Ws[k].t != its[k].rankA or its[k].rankJ2 != min(m, n - its[k].rankA))]

@@ -248,6 +248,49 @@ int enlsip_gn_solve_factored_batched_dev(enlsip_gn_handle h, int64_t batch, int6
  * refactor == NULL: no constraint kernel is launched).  This, not the results, tells the call from a full re-solve. */
 int enlsip_gn_get_constraint_refactored(enlsip_gn_handle h, int64_t* count);
 
+/*
+ * Solve again only the problems whose working set changed, in place (update_working_set, src/enlsip_functions.jl:686-795: the
+ * second solve after the undo of a deletion, :728-743, and the third after a second-order deletion, :745-762 / :773-790; the
+ * direction itself is gn_search_direction's, :725 / :771).  The handle must hold a FULLY SOLVED ragged batch left by
+ * enlsip_gn_solve_batched_ragged*, enlsip_gn_solve_factored_batched* or an earlier call of this entry point, with the same batch, m,
+ * n, t_max; every other state returns -1 with a message (nothing resident, only F_A / F_L11 resident, a uniform
+ * enlsip_gn_solve_batched, a TSQR solve, a pipeline split that would now differ from the resident one).  A batch above the launch
+ * limit returns -2.  Workspace strides and the plan are those of the resident solve; J and rx are the resident ones (as
+ * enlsip_gn_gradient_batched reads them).
+ * changed is a HOST array of `batch` flags (NULL: -7).  All zero is legal: 0 is returned, nothing is launched or written.  A problem
+ * with changed[k] == 0 must come with the t[k] it is resident with (-6 names k); its At / cx slots are not read, no output slot of
+ * it is written and no byte of its resident state changes (a result held by ENLSIP_GN_DIM_HOLD stays held).  A problem with
+ * changed[k] != 0 may have any t[k] in 0..t_max: its constraint stage and its Jacobian side (J*Q1, the CAQR sweep, the pivoted QR of
+ * R0, the final kernel) run again over a device list of exactly those problems, into their own slots.  It gets its outputs, its
+ * resident factors and state record, its info and its t — bit for bit what enlsip_gn_solve_batched_ragged on the whole batch with
+ * the final working sets leaves for it (kernel forms are chosen from the part's whole problem count, only the grids follow the
+ * list; the launch width is max(n - min(n, min over all t[k]), widest resident J2 of the unchanged problems), widened for the
+ * changed problems alone when one of their A' turns out rank deficient) — and every later consumer answers for it.  A held result
+ * of a changed problem is dropped.  The magnitude contract holds: a changed problem beyond the plain range is solved on a
+ * one-problem handle from the resident inputs, one that was there returns to the batch when its data no longer needs it.
+ * Host form: the resident solve must be a host-form one; only the changed problems' At / cx are staged, into the staging area it
+ * reads.  Device form: dAt, ldat, strideAt, dcx must be the buffers the resident solve was made with, the changed slots rewritten
+ * in place (-8 otherwise).  Other argument errors: -9 ldat < n, -10 strideAt < ldat * t_max, -11 cx NULL while a changed t[k] > 0.
+ * Every argument and state error is raised before anything is staged or launched and leaves the resident state usable.
+ */
+int enlsip_gn_solve_changed_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                    const int64_t* changed,
+                                    const double* At, int64_t ldat, int64_t strideAt, const double* cx,
+                                    double eps_rank,
+                                    double* p, double* b, double* d, enlsip_gn_info* info,
+                                    int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2);
+/* Same, DEVICE buffers in and out (t and changed stay HOST arrays). */
+int enlsip_gn_solve_changed_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
+                                        const int64_t* changed,
+                                        const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx,
+                                        double eps_rank,
+                                        double* dp, double* db, double* dd, enlsip_gn_info* dinfo,
+                                        int64_t* djpvtA, int64_t* djpvtL, int64_t* djpvtJ2);
+/* Problems the Jacobian-side kernels of the last solve on h were launched over, summed over the pipelined halves: batch after a
+ * whole-batch solve, the number of flags after enlsip_gn_solve_changed_batched* (enlsip_gn_get_constraint_refactored reports the
+ * same number then). */
+int enlsip_gn_get_jacobian_resolved(enlsip_gn_handle h, int64_t* count);
+
 /* ---- accessors on the resident factors of problem `prob` of the last solve (host buffers) ---- */
 
 /* rows/cols of F.R for `which`: A: min(n,t) x t; L11: min(t,kA) x kA; J2: min(m,n2) x n2 */
