@@ -227,6 +227,12 @@ struct enlsip_gn_context {
     hipEvent_t nwb_ev[5] = {};
     bool nwb_timed = false;
     float newton_ms[4] = {};
+    // one-call subspace minimisation (gn_subspace_batched.inc): requests and previous iterates on the device, staging of the
+    // host-buffer form, the pinned copy of the final requests (chosen dimensions, status) and the form of the last call
+    gn::DevBuf ssb_req, ssb_io;
+    void* h_ssb = nullptr;
+    size_t h_ssb_cap = 0;
+    int subspace_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

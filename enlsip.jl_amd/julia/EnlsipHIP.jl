@@ -610,6 +610,63 @@ function resolve_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""    determine_solving_dim_hip(previous_dimR, rankR, predicted_linear_progress, obj_progress, prelin_previous_dim, diagR, y,
+                              previous_α, restart) -> newdim
+
+`determine_solving_dim` (src/enlsip_functions.jl:1041-1113, with `gn_previous_step` :909-932 and `subspace_min_previous_step`
+:864-904) on host data through the library's host entry point (no handle, no GPU): the routine the batched call below runs on the
+device.  `η` is not computed (discarded at :1150, :1169).  Throws a `BoundsError` where the reference does."""
+function determine_solving_dim_hip(previous_dimR::Integer, rankR::Integer, predicted_linear_progress::Float64, obj_progress::Float64,
+                                   prelin_previous_dim::Float64, diagR::Vector{Float64}, y::Vector{Float64}, previous_α::Float64,
+                                   restart::Bool)
+    (length(diagR) >= rankR && length(y) >= rankR) || error("diagR and y need rankR entries")
+    nd = Ref{Int64}(0)
+    rc = GC.@preserve diagR y ccall((:enlsip_gn_determine_solving_dim, LIB), Cint,
+        (Int64, Int64, Float64, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Float64, Int64, Ref{Int64}),
+        previous_dimR, rankR, predicted_linear_progress, obj_progress, prelin_previous_dim, diagR, y, previous_α, Int64(restart), nd)
+    rc == 5 && throw(BoundsError(y, previous_dimR))
+    rc == 0 || error("enlsip_gn_determine_solving_dim returned $rc")
+    return Int(nd[])
+end
+
+"""what `choose_subspace_dimensions` (src/enlsip_functions.jl:1118-1176) reads of `previous_iter`: enlsip_gn_subspace_prev"""
+struct SubspacePrev
+    previous_dimA::Int64            # :1144  abs(previous_iter.dimA) + t - previous_iter.t
+    previous_dimJ2::Int64           # :1165  abs(previous_iter.dimJ2) + previous_iter.t - t
+    restart::Int64                  # current_iter.restart
+    previous_alpha::Float64         # previous_iter.α
+    constraint_progress::Float64    # :1147  dot(prev.cx, prev.cx) - active_cx_sum
+    residual_progress::Float64      # :1168  dot(prev.rx, prev.rx) - rx_sum
+end
+
+"""    subspace_direction_batched_hip(h, m, n, t_max, prob0, prev, take) -> (P, b, d, infos, status)
+
+The subspace branch of `search_direction_analys` (src/enlsip_functions.jl:1249-1253, code = -1) for problems
+`prob0 .. prob0 + length(prev) - 1` of the resident batch in ONE call: b (:1251), `choose_subspace_dimensions` (:1118-1176) on the
+device — dimA from b and diag(F_L11.R), d (:1156-1163), dimJ2 from d and diag(F_J2.R), the max with the previous dimensions
+(:1171-1174) — and `sub_search_direction` (:1253) with the chosen pair, which `infos[j].dimA / .dimJ2` carry.  `take[j] == 0`
+leaves the problem alone.  status: 0; 1 / 2 the final dimA / dimJ2 is out of range (b, d written, no p); 5 the reference would
+throw a BoundsError (nothing written)."""
+function subspace_direction_batched_hip(h::Handle, m::Integer, n::Integer, t_max::Integer, prob0::Integer, prev::Vector{SubspacePrev},
+                                        take::Union{Nothing,Vector{Int64}} = nothing)
+    count = length(prev)
+    (take === nothing || length(take) == count) || error("take must have one entry per problem")
+    P = fill(NaN, n, count); b = fill(NaN, max(t_max, 1), count); d = fill(NaN, m, count)
+    infos = fill(Info(0, 0, 0, 0, 0, 0), count); st = fill(Cint(-1), count)
+    tk = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    GC.@preserve prev take P b d infos st batched_check(h, @ccall LIB.enlsip_gn_subspace_direction_batched(
+        h.ptr::Ptr{Cvoid}, prob0::Int64, count::Int64, tk::Ptr{Int64}, prev::Ptr{SubspacePrev}, P::Ptr{Float64}, b::Ptr{Float64},
+        d::Ptr{Float64}, infos::Ptr{Info}, st::Ptr{Cint})::Cint)
+    return P, b[1:t_max, :], d, infos, st
+end
+
+"""    subspace_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last one-call subspace direction"""
+function subspace_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_subspace_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

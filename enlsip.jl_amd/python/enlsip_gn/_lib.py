@@ -28,6 +28,12 @@ class Info(C.Structure):
                 ("dimA", C.c_int64), ("dimJ2", C.c_int64), ("status", C.c_int64)]
 
 
+class SubspacePrev(C.Structure):
+    """enlsip_gn_subspace_prev: what choose_subspace_dimensions (src/enlsip_functions.jl:1118-1176) reads of previous_iter"""
+    _fields_ = [("previous_dimA", C.c_int64), ("previous_dimJ2", C.c_int64), ("restart", C.c_int64),
+                ("previous_alpha", C.c_double), ("constraint_progress", C.c_double), ("residual_progress", C.c_double)]
+
+
 # enlsip_gn_allgather_fn: int (*)(void* ctx, const void* dsend, void* drecv, size_t bytes_per_rank, void* hip_stream)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -118,6 +124,13 @@ PROTOTYPES = {
     "enlsip_gn_get_diagR_batched": (C.c_int, [_h, C.c_int, _i64, _i64, C.c_void_p, _i64]),
     "enlsip_gn_get_resolve_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_get_resolve_q0_ms": (C.c_int, [_h, C.POINTER(C.c_float)]),
+    "enlsip_gn_determine_solving_dim": (C.c_int, [_i64, _i64, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double,
+                                                  _i64, _ip]),
+    "enlsip_gn_subspace_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p]),
+    "enlsip_gn_subspace_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_subspace_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

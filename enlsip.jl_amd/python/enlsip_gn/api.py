@@ -41,6 +41,25 @@ def _fptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def determine_solving_dim(previous_dimR: int, rankR: int, predicted_linear_progress: float, obj_progress: float,
+                          prelin_previous_dim: float, diagR, y, previous_alpha: float, restart: bool) -> int:
+    """determine_solving_dim (src/enlsip_functions.jl:1041-1113) on host data, through the library's host entry point (no GPU):
+    the dimension it picks.  Raises IndexError where the reference would index out of bounds (return 5)."""
+    dg = np.ascontiguousarray(diagR, dtype=np.float64)
+    yv = np.ascontiguousarray(y, dtype=np.float64)
+    if dg.size < rankR or yv.size < rankR:
+        raise ValueError("diagR and y need rankR entries")
+    nd = C.c_int64(0)
+    rc = L.load().enlsip_gn_determine_solving_dim(int(previous_dimR), int(rankR), float(predicted_linear_progress), float(obj_progress),
+                                                  float(prelin_previous_dim), _fptr(dg), _fptr(yv), float(previous_alpha),
+                                                  int(bool(restart)), C.byref(nd))
+    if rc == 5:
+        raise IndexError("determine_solving_dim: the reference indexes tau / rho out of bounds (previous_dimR > rankR)")
+    if rc:
+        raise GNError(f"enlsip_gn_determine_solving_dim returned {rc}")
+    return int(nd.value)
+
+
 @dataclass
 class GNResult:
     p: np.ndarray
@@ -649,6 +668,66 @@ class GNSolver:
         ms = C.c_float(0.0)
         self._chk(self._lib.enlsip_gn_get_resolve_q0_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    # ---- subspace minimisation in one call: the dimension choice on the device (src/enlsip_functions.jl:1118-1176, :1249-1253) ----
+    PREV_DTYPE = np.dtype([("previous_dimA", np.int64), ("previous_dimJ2", np.int64), ("restart", np.int64),
+                           ("previous_alpha", np.float64), ("constraint_progress", np.float64), ("residual_progress", np.float64)])
+
+    @classmethod
+    def pack_subspace_prev(cls, count: int, previous_dimA, previous_dimJ2, restart, previous_alpha, constraint_progress,
+                           residual_progress) -> np.ndarray:
+        """The `prev` array of subspace_direction_batched (enlsip_gn_subspace_prev, 48 bytes per problem): scalars broadcast to
+        `count` entries.  previous_dimA = abs(prev.dimA) + t - prev.t (:1144), previous_dimJ2 = abs(prev.dimJ2) + prev.t - t
+        (:1165), constraint_progress = dot(prev.cx, prev.cx) - active_cx_sum (:1147), residual_progress = dot(prev.rx, prev.rx)
+        - rx_sum (:1168)."""
+        out = np.zeros(count, dtype=cls.PREV_DTYPE)
+        for name, v in (("previous_dimA", previous_dimA), ("previous_dimJ2", previous_dimJ2), ("restart", restart),
+                        ("previous_alpha", previous_alpha), ("constraint_progress", constraint_progress),
+                        ("residual_progress", residual_progress)):
+            a = np.asarray(v)
+            if a.ndim > 1 or (a.ndim == 1 and a.shape != (count,)):
+                raise ValueError(f"pack_subspace_prev: {name} must be a scalar or have {count} entries")
+            out[name] = a
+        return out
+
+    def _prev_arg(self, count: int, prev):
+        if prev is None:
+            return None
+        pv = np.ascontiguousarray(prev)
+        if pv.dtype != self.PREV_DTYPE or pv.shape != (count,):
+            raise ValueError(f"prev must come from pack_subspace_prev with {count} entries")
+        return pv
+
+    def subspace_direction_batched(self, m: int, n: int, t_max: int, prev, prob0: int = 0, count: Optional[int] = None, take=None,
+                                   want=("p", "b", "d", "info", "status"), out: Optional[dict] = None):
+        """The subspace branch of search_direction_analys (:1251-1253) for problems prob0 .. prob0+count-1 in one call: b, the
+        chosen dimA, d, the chosen dimJ2 and p; info[:, 3:5] carry the chosen dimensions.  Returns (out, rc) as resolve_batched;
+        status 1 / 2: the final dimA / dimJ2 is out of range (b, d written, p not), 5: the reference would index out of bounds
+        (nothing written)."""
+        if count is None:
+            count = len(prev)
+        pv = self._prev_arg(count, prev)
+        tk = self._pack_take(count, take)
+        o = out if out is not None else self.resolve_outputs(count, m, n, t_max, want=want)
+        rc = self._chk_batched(self._lib.enlsip_gn_subspace_direction_batched(
+            self._h, prob0, count, _fptr(tk), _fptr(pv), _fptr(o["p"]), _fptr(o["b"]), _fptr(o["d"]), _fptr(o["info"]),
+            _fptr(o["status"])))
+        return o, rc
+
+    def subspace_direction_batched_dev(self, prob0: int, count: int, prev, take=None, dp: int = 0, db: int = 0, dd: int = 0,
+                                       dinfo: int = 0, dstatus: int = 0) -> int:
+        """Device form: prev and take stay host arrays, the outputs are raw device pointers (0 = NULL)."""
+        v = lambda x: C.c_void_p(x) if x else None
+        pv = self._prev_arg(count, prev)
+        tk = self._pack_take(count, take)
+        return self._chk_batched(self._lib.enlsip_gn_subspace_direction_batched_dev(
+            self._h, prob0, count, _fptr(tk), _fptr(pv), v(dp), v(db), v(dd), v(dinfo), v(dstatus)))
+
+    def subspace_form(self) -> int:
+        """Kernel form of the last subspace_direction_batched: 0 general, 1 one wave per problem, -1 none yet."""
+        f = C.c_int(0)
+        self._chk(self._lib.enlsip_gn_get_subspace_form(self._h, C.byref(f)))
+        return int(f.value)
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).

@@ -445,6 +445,65 @@ int enlsip_gn_get_resolve_form(enlsip_gn_handle h, int* form);
  * halves that ran a part of the range; 0 unless enlsip_gn_set_profiling was on (the events add stream bubbles) */
 int enlsip_gn_get_resolve_q0_ms(enlsip_gn_handle h, float* ms);
 
+/* ---- subspace minimisation in ONE call: the dimension choice on the device ---------------------------------------------------
+ * The three-call held flow above leaves choose_subspace_dimensions (src/enlsip_functions.jl:1118-1176) to the host: b and d cross
+ * PCIe so that determine_solving_dim (src/enlsip_functions.jl:1041-1113, with gn_previous_step :909-932 and
+ * subspace_min_previous_step :864-904) can read a vector, a diagonal and six scalars of the previous iterate.  These forms run
+ * that choice where b, d and the diagonals are, so the subspace branch of search_direction_analys
+ * (src/enlsip_functions.jl:1249-1253, code = -1) is one call for problems prob0 .. prob0+count-1.
+ *
+ * enlsip_gn_determine_solving_dim   determine_solving_dim (src/enlsip_functions.jl:1041-1113) on HOST data, no handle and no GPU:
+ *     *newdim; eta is not computed (its only caller discards it, :1150, :1169).  diagR, y: rankR entries.  Returns 0; 5 when the
+ *     reference would index outside tau / rho (previous_dimR > rankR outside a restart; Julia throws there); -2 newdim NULL or
+ *     rankR < 0, -4 diagR or y NULL with rankR > 0.  The same routine, compiled for the device, makes the choices below.
+ * enlsip_gn_subspace_prev           per problem, what choose_subspace_dimensions reads of previous_iter (host bookkeeping).
+ * enlsip_gn_subspace_direction_batched*   per taken problem (take: HOST array of count entries, NULL = all; take[j] == 0:
+ *     no output slot written, no state touched):
+ *         b = F_L11.Q' (-cx[F_A.p])                                             :1251
+ *         dimA by determine_solving_dim on b, diag(F_L11.R)                     :1144-1150   (rankA <= 0: dimA = 0, :1136-1140)
+ *         d = F_J2.Q' (-(rx + J1 p1(dimA)))                                     :1156-1163
+ *         dimJ2 by determine_solving_dim on d, diag(F_J2.R)                     :1165-1169
+ *         dimA, dimJ2 = max with the previous ones if !restart && alpha >= 0.2  :1171-1174
+ *         p = sub_search_direction with the final pair                          :1253
+ *     Where the max raised dimA, b, p1 and d are formed again with the final dimA before p, as the reference's call at :1253
+ *     does: p, b, d, info and the state afterwards are bitwise those of enlsip_gn_resolve_batched(dimA*, dimJ2*, -1) with the
+ *     returned pair (the same stage kernels), and a held result of a taken problem is dropped.  info[j].dimA / .dimJ2 carry the
+ *     chosen dimensions.  Slots, strides, ragged t[k] and zero padding are those of enlsip_gn_resolve_batched; prev is a HOST
+ *     array in both forms and goes up with the one request copy; any output pointer may be NULL.
+ *   status[j] (written for taken problems): 0; 1 / 2 the final dimA / dimJ2 lies outside 0..min(n, t[k]) / 0..min(m, n - rankA)
+ *     (the max with a previous dimension can do that): no p; b, the d the choice of dimJ2 read and info (with the pair) are
+ *     written; 5 the reference would index out of bounds (b[1:previous_dimA] with previous_dimA > t[k], d[1:previous_dimJ2] with
+ *     previous_dimJ2 > m, tau / rho past rankR): nothing is written.  What the previous dimensions and the resident ranks decide
+ *     is found before any launch and leaves the problem untouched; the one case that depends on the data (previous_dimR ==
+ *     rankR + 1 after a step shorter than 0.2) is found on the device, for dimJ2 after b, p1 and the state record were set for the
+ *     chosen dimA (a held result of that problem is dropped; one of a problem flagged earlier is kept).
+ *   Returns 0, 1 when some problem is flagged; negative as enlsip_gn_resolve_batched: -1 no resident factors (also after
+ *     enlsip_gn_factor_constraints), -2 count < 1, -3 the range leaves the resident batch, -4 prev is NULL.
+ *   The number of launches does not depend on count; ONE synchronisation per stream that ran a part of the range; no byte of b, d
+ *   or a diagonal crosses PCIe between the stages.  The range may straddle the pipelined halves; a problem on a rescue handle is
+ *   answered through enlsip_gn_resolve with the dimensions chosen by the host instantiation of the same routine.
+ * enlsip_gn_get_subspace_form   kernel form of the last call on this handle: 0 general (256 threads per problem), 1 one wave per
+ *     problem (n <= 64 and t_max <= 64), -1 none yet.
+ */
+typedef struct enlsip_gn_subspace_prev {
+    int64_t previous_dimA;        /* :1144  abs(previous_iter.dimA) + t - previous_iter.t   */
+    int64_t previous_dimJ2;       /* :1165  abs(previous_iter.dimJ2) + previous_iter.t - t  */
+    int64_t restart;              /* current_iter.restart                                    */
+    double  previous_alpha;       /* previous_iter.alpha                                     */
+    double  constraint_progress;  /* :1147  dot(prev.cx, prev.cx) - active_cx_sum            */
+    double  residual_progress;    /* :1168  dot(prev.rx, prev.rx) - rx_sum                   */
+} enlsip_gn_subspace_prev;
+int enlsip_gn_determine_solving_dim(int64_t previous_dimR, int64_t rankR, double predicted_linear_progress, double obj_progress,
+                                    double prelin_previous_dim, const double* diagR, const double* y, double previous_alpha,
+                                    int64_t restart, int64_t* newdim);
+int enlsip_gn_subspace_direction_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* take,
+                                         const enlsip_gn_subspace_prev* prev, double* p, double* b, double* d,
+                                         enlsip_gn_info* info, int* status);
+int enlsip_gn_subspace_direction_batched_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t* take,
+                                             const enlsip_gn_subspace_prev* prev, double* dp, double* db, double* dd,
+                                             enlsip_gn_info* dinfo, int* dstatus);
+int enlsip_gn_get_subspace_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
