@@ -1362,6 +1362,13 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
                     if (rc) return rc;
                 }
                 h->sc_eJ = sJ;
+                if (!sA) {
+                    // the constraint stage is not run again, so nothing resets the status it wrote: take back the bit 0 that the
+                    // final kernel of the first pass ORed in on the unscaled data (a diagonal that underflowed to zero there)
+                    hipLaunchKernelGGL(k_clear_status_bits, dim3(1), dim3(256), 0, s, h->state, 1, 1, (const int*)nullptr);
+                    GN_HIP(hipGetLastError());
+                    h->h_state[0].status &= ~1;
+                }
                 rc = sJ ? attempts(h->rs_J, m, m * n, h->rs_rx, sJ) : attempts(v.J, v.ldj, v.strideJ, v.rx, 0);
                 if (rc) return rc;
                 if (sJ) {

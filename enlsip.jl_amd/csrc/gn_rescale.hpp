@@ -1,5 +1,5 @@
-// Magnitudes beyond the range of plain sums of squares (entries above ~2^500 or below ~2^-500): LAPACK's behaviour on the same
-// inputs.  The reference's qr(., ColumnNorm()) (src/enlsip_functions.jl:223, :700, :769) runs dgeqp3, whose column norms (dnrm2)
+// Magnitudes beyond the range of plain sums of squares (entries outside 2^+-400, the band GN_RESCALE_BAND): LAPACK's behaviour on
+// the same inputs.  The reference's qr(., ColumnNorm()) (src/enlsip_functions.jl:223, :700, :769) runs dgeqp3, whose column norms (dnrm2)
 // and reflectors (dlarfg with its safmin loop) scale internally and never overflow or underflow; the kernels of this library
 // square plainly.  Instead of a scaled norm at every one of their norm sites, the rare case is DETECTED on the result and the
 // problem is solved again on a copy of its inputs scaled by a power of two — exact, so every factor comes out as
@@ -12,13 +12,17 @@
 namespace gn {
 
 constexpr int GN_FLAG_NONFINITE = 1 << 29;     // ProbState::status bits, host-internal: cleared before the caller sees status
+                                               // (NONFINITE: |R[0]| above 2^440, Inf or NaN; TINY: below 2^-440)
 constexpr int GN_FLAG_TINY = 1 << 30;
 constexpr int GN_RESCALE_BAND = 400;           // inputs with 2^-400 <= max |entry| <= 2^400 are never rescaled
 
 // first diagonal entries of F_A.R and F_J2.R: the largest column norm of each factorisation (pivoting puts it first).  Not
-// finite: a sum of squares overflowed (or the inputs held NaN / Inf).  Below 2^-440 (zero included): the squares of the largest
-// column sit at the bottom of the exponent range (or J / A is zero).  Both only nominate the problem: the host looks at the
-// magnitudes of its inputs before anything is redone.
+// finite: a sum of squares overflowed (or the inputs held NaN / Inf).  Above 2^440 (the same threshold for both factors): the
+// largest column norm squared may still be finite, but other plain sums of squares need not be — the column norms of
+// L11 = R_A', which are the ROW norms of R_A, reach sqrt(t) |R_A[0]|; ||rx||^2 may exceed every column norm of J.  Below 2^-440
+// (zero included): the squares of the largest column sit at the bottom of the exponent range (or J / A is zero).  All three only
+// nominate the problem: the host looks at the magnitudes of its inputs before anything is redone, and no input with
+// |R[0]| beyond 2^+-440 that is worth redoing lies inside the band 2^+-400.
 // RAGGED: F_A of problem k has min(kA, tk[k]) reflectors — a problem without constraints has none to look at
 template <bool RAGGED>
 __device__ __forceinline__ void extreme_flags_body(ProbState* state, const double* Rt, long long sRt, const double* FA, long long sFA,
@@ -28,16 +32,16 @@ __device__ __forceinline__ void extreme_flags_body(ProbState* state, const doubl
     const int k = listed_prob(plist, idx, 0);
     const ProbState st = state[k];
     if (n2cap > 0 && st.n2 > n2cap) return;            // redone by the caller (second attempt): nothing of it is final yet
-    const double tiny = 0x1p-440;
+    const double tiny = 0x1p-440, huge = 0x1p440;
     int f = 0;
     if (RAGGED ? (kA > 0 && tk[k] > 0) : kA > 0) {
         const double a = fabs(FA[k * sFA]);
-        if (!(a <= __builtin_huge_val()) || a == __builtin_huge_val()) f |= GN_FLAG_NONFINITE;
+        if (!(a <= huge)) f |= GN_FLAG_NONFINITE;       // NaN and Inf included
         else if (a < tiny) f |= GN_FLAG_TINY;
     }
     if (Rt && st.kp > 0) {
         const double r = fabs(Rt[k * sRt]);
-        if (!(r <= __builtin_huge_val()) || r == __builtin_huge_val()) f |= GN_FLAG_NONFINITE;
+        if (!(r <= huge)) f |= GN_FLAG_NONFINITE;
         else if (r < tiny) f |= GN_FLAG_TINY;
     }
     if (f) state[k].status = st.status | f;

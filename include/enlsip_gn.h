@@ -42,10 +42,13 @@
  *   - Factors stay resident on the device behind the handle until the next solve on it.
  *   - Magnitudes.  qr(., ColumnNorm()) of the reference is dgeqp3, whose norms and reflectors scale internally: inputs of any
  *     magnitude are factored alike and pseudo_rank's absolute first test (src/enlsip_functions.jl:19) decides the rank.  The
- *     kernels square plainly; enlsip_gn_solve*, _solve_batched*, _factor_constraints and _solve_factored therefore detect inputs
- *     whose entries leave the range of plain sums of squares (beyond about 2^+-500) on their result and solve them again on
- *     copies scaled by a power of two, with the resident factors and the outputs scaled back: ranks, pivots,
- *     p, b, d and every accessor are those of the caller's data, as LAPACK would return them.  NOT covered: the row shards of the
+ *     kernels square plainly; enlsip_gn_solve*, _solve_batched*, _factor_constraints and _solve_factored therefore detect such
+ *     inputs on their result: a problem is nominated when the first diagonal entry of F_A.R or of F_J2.R (the largest column norm)
+ *     is above 2^440, not finite, or below 2^-440, and a nominated problem whose largest |entry| of J, rx or of A', cx lies outside
+ *     the band 2^-400 .. 2^400 is solved again on copies scaled by a power of two, with the resident factors and the outputs scaled
+ *     back: ranks, pivots, p, b, d and every accessor are those of the caller's data, as LAPACK would return
+ *     them.  The range covered therefore starts at the band edge: inside the band plain sums of squares hold for every shape the
+ *     library takes; beyond it nothing is left to the plain kernels.  NOT covered: the row shards of the
  *     TSQR entry points (all shards of one matrix would have to agree on one scale before their local stages).
  */
 #ifndef ENLSIP_GN_H
