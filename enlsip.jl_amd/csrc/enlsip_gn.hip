@@ -334,6 +334,24 @@ static CaqrArgs caqr_args(enlsip_gn_handle h, int k, const LevelPlan& L) {
     return a;
 }
 
+// the final kernel (pivoted QR of R0 in its LDS forms, the solves, the outputs of v) at launch width n2_launch
+static FinalArgs final_args(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimJ2_ov, int abs_shift, int n2_launch) {
+    const Plan& P = h->plan;
+    FinalArgs fa{};
+    fa.m = (int)P.m; fa.n = (int)P.n; fa.t = (int)P.t; fa.kA = P.kA; fa.ldw = P.ldw; fa.ldr = P.ldr;
+    fa.eps_rank = eps_rank; fa.abs_shift = abs_shift; fa.dimJ2_override = (int)dimJ2_ov; fa.refactor = 1;
+    fa.W = h->W; fa.sW = P.sW; fa.Rt = h->Rt; fa.sRt = P.sRt; fa.tauJ = h->tauJ; fa.sTauJ = P.sTauJ;
+    fa.jpvtJ = h->jpvtJ; fa.sJJ = P.sJJ; fa.FA = h->FA; fa.sFA = P.sFA; fa.tauA = h->tauA; fa.sTauA = P.sTauA;
+    fa.p1 = h->p1; fa.sP1 = P.sP1; fa.bvec = h->bvec; fa.sB = P.sB; fa.zsave = h->zsave; fa.sZ = P.sZ;
+    fa.p_out = v.p; fa.sPo = P.n; fa.b_out = v.b; fa.sBo = P.t; fa.d_out = v.d; fa.sDo = P.m;
+    fa.jA_out = v.jpvtA; fa.sJAo = P.t; fa.jpvtA = h->jpvtA; fa.sJA = P.sJA;
+    fa.jL_out = v.jpvtL; fa.sJLo = P.kA; fa.jpvtL = h->jpvtL; fa.sJL = P.sJL;
+    fa.jJ_out = v.jpvtJ2; fa.sJJo = P.n;
+    fa.state = h->state; fa.plist = h->run_plist;
+    fa.n2cap = n2_launch;
+    return fa;
+}
+
 static void launch_factor(enlsip_gn_handle h, const CaqrArgs& a, int groups, hipStream_t st = nullptr) {
     if (!st) st = h->stream;
     dim3 grid(groups, (unsigned)launch_count(h));
@@ -1146,28 +1164,287 @@ static int next_rescue_handle(enlsip_gn_handle h, enlsip_gn_handle* out) {
     return 0;
 }
 
-static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
-    const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
-    if (!h->changed_once) {
-        h->split = 0;   // routing of accessors to the pipeline child is (re)established by the batched entry point
-        h->chunk0 = 0;  // ... and to the resident chunk by solve_chunked
+// ---------------------------------------------------------------------------------------------
+// the solve driver: solve_dev (and the constraint-only factor_dev) as a sequence of steps
+// ---------------------------------------------------------------------------------------------
+// The problems a solve_dev covers: its whole part, or the listed ones of a changed-problems solve (indices in the part).
+struct Covered {
+    long long count = 0;
+    const int* list = nullptr;      // host; NULL: problems 0 .. count - 1
+    long long operator[](long long i) const { return list ? list[(size_t)i] : i; }
+};
+constexpr int GN_NOMINATED = GN_FLAG_NONFINITE | GN_FLAG_TINY;       // the nomination bits of gn_rescale.hpp: host-internal
+
+// Residency bookkeeping of a call that replaces the whole part: nothing of the previous one stays addressable.
+// (The routing of the accessors to the pipeline child is re-established by the batched entry point, to the resident chunk by
+// solve_chunked; a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it.)
+static void begin_whole_part(enlsip_gn_handle h, const BatchOperands& inputs, bool keep_constraint_scale) {
+    h->split = 0;
+    h->chunk0 = 0;
+    h->factors_valid = false;
+    h->held.clear();
+    h->last = inputs;
+    h->sc_eJ = 0;
+    if (!keep_constraint_scale) h->sc_eA = 0;
+    h->rescue_prob.clear();
+}
+// ... of a changed-problems solve: a held re-solve of a listed problem is dropped; a listed problem that lived on a rescue handle
+// gives it back (the handle moves behind the ones in use)
+static void release_listed(enlsip_gn_handle h, const std::vector<int>& list) {
+    for (int k : list) {
+        if ((size_t)k < h->held.size()) h->held[(size_t)k] = {};
+        for (size_t j = 0; j < h->rescue_prob.size(); ++j)
+            if (h->rescue_prob[j] == k) {
+                enlsip_gn_handle r = h->rescue[j];
+                h->rescue.erase(h->rescue.begin() + (long)j);
+                h->rescue.push_back(r);
+                h->rescue_prob.erase(h->rescue_prob.begin() + (long)j);
+                break;
+            }
     }
+}
+
+// ragged batch: every problem's own t, kept on the host for the accessors and copied to the device for the constraint kernels
+static int upload_tk(enlsip_gn_handle h, const int* tk, long long batch) {
+    h->h_tk.assign(tk, tk + batch);
+    int rc = grow(h, h->tkbuf, (size_t)batch * sizeof(int));
+    if (rc) return rc;
+    GN_HIP(hipMemcpyAsync(h->tkbuf.p, h->h_tk.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+static void mark(enlsip_gn_handle h, int i) {
+    if (h->profiling) (void)hipEventRecord(h->ev[i], h->stream);
+}
+
+// The constraint step of a solve: for every problem (Fresh), or for the problems of h->refit only (Factored: those with a refactor
+// flag, Changed: the listed ones, which from here on are the launch set of the solve).  Without a list the resident F_A, F_L11, b,
+// p1, T and state records are those of enlsip_gn_factor_constraints*.
+static int constraint_step(enlsip_gn_handle h, const BatchOperands& v, const SolveMode& mode) {
+    if (mode.kind == SolveMode::Fresh) {
+        h->fb.valid = false;
+        return run_constraint_stage(h, v.batch, v.m, v.n, v.t, v.At, v.ldat, v.strideAt, v.cx, mode.eps_rank, mode.dimA_ov);
+    }
+    if (h->refit.empty()) return 0;
+    const size_t nl = h->refit.size();
+    int rc = grow(h, h->plist_buf, nl * sizeof(int));
+    if (rc) return rc;
+    GN_HIP(hipMemcpyAsync(h->plist_buf.p, h->refit.data(), nl * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    rc = run_constraint_stage(h, v.batch, v.m, v.n, v.t, v.At, v.ldat, v.strideAt, v.cx, mode.eps_rank, mode.dimA_ov, 0, 0,
+                              (const int*)h->plist_buf.p, (long long)nl);
+    if (rc) return rc;
+    if (mode.kind == SolveMode::Changed) { h->run_plist = (const int*)h->plist_buf.p; h->run_nlist = (long long)nl; }
+    return 0;
+}
+
+// The state records of the part from the device into the host mirror.  A changed-problems solve never writes the mirror's records
+// of the problems it leaves alone (a rescued problem's holds its rescue handle's record, not the device's): it reads back into a
+// buffer of its own and takes the listed records from there.
+static int fetch_states(enlsip_gn_handle h, const Covered& cov) {
+    const size_t batch = (size_t)h->plan.batch;
+    std::vector<ProbState> own;
+    if (cov.list) own.resize(batch);
+    GN_HIP(hipMemcpyAsync(cov.list ? own.data() : h->h_state, h->state, batch * sizeof(ProbState), hipMemcpyDeviceToHost, h->stream));
+    GN_HIP(hipStreamSynchronize(h->stream));
+    for (long long i = 0; cov.list && i < cov.count; ++i) h->h_state[cov[i]] = own[(size_t)cov[i]];
+    return 0;
+}
+
+// The Jacobian side (steps 2-4) of the covered problems for the J, rx given — the caller's, or their scaled copies with
+// abs_shift = their power of two: the choice of the launch width, then up to two attempts of J*Q1, CAQR, pivoted QR of R0, final
+// kernel, nomination and state read-back.  t_min: the smallest t of the part; upper_in: J is its own R0.
+static int jacobian_side(enlsip_gn_handle h, const BatchOperands& v, const SolveMode& mode, const Covered& cov, int t_min, bool upper_in,
+                         const double* dJ, long long ldj, long long strideJ, const double* drx, int abs_shift) {
+    const Plan& P = h->plan;
+    const long long batch = v.batch, m = v.m, n = v.n;
+    const int nlaunch = (int)cov.count;
+    hipStream_t s = h->stream;
+    // speculate rankA = min(n, t) (ragged: the smallest min(n, t_k), so that only a rank-deficient A' widens J2); verified after the solve
+    int n2_launch = (int)(n - std::min<long long>(n, t_min));
+    // a changed-problems solve launches with the width a solve of the whole part on the final sets ends with: no narrower than the
+    // widest J2 among the problems it leaves alone (one of them had a rank-deficient A')
+    if (cov.list) {
+        std::vector<char> in_list((size_t)batch, 0);
+        for (long long i = 0; i < cov.count; ++i) in_list[(size_t)cov[i]] = 1;
+        for (long long k = 0; k < batch; ++k)
+            if (!in_list[(size_t)k]) n2_launch = std::max(n2_launch, h->h_state[k].n2);
+    }
+    h->jstage_problems = cov.count;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        // 2. JQ1 = J*Q1, d_temp
+        const JQ1Args qa = jq1_args(h, dJ, ldj, strideJ, drx);
+        // one 256-row tile, one narrow panel (C5): J*Q1 and the panel factorisation in ONE launch, the tile handed over in LDS
+        const bool fused = h->fuse_small && !upper_in && !(h->flags & ENLSIP_GN_UPDATE_REFLECTORS) &&
+                           small_fused_applies(m, n, P.kA, n2_launch);
+        if (fused) {
+            CaqrArgs ca = caqr_args(h, 0, P.panels[0].levels[0]);
+            ca.npass = 1;
+            launch_jq1_factor_small(qa, ca, nlaunch, s);
+            GN_HIP(hipGetLastError());
+        } else launch_jq1_any(h, qa, nlaunch, s);
+        mark(h, 2);
+        GN_TRACE(h, "attempt %d n2_launch=%d: J*Q1 done%s", attempt, n2_launch, fused ? " (fused with the panel factorisation)" : "");
+        // 3. CAQR of [J2 | d]
+        if (!upper_in && !fused) {
+            int rc = run_caqr(h, n2_launch);
+            if (rc) return rc;
+        }
+        if (upper_in) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_UPPER_INPUT);
+        if (attempt > 0) GN_ROUTE(ENLSIP_GN_ROUTE_SECOND_ATTEMPT);
+        mark(h, 3);
+        GN_TRACE(h, "CAQR done");
+        // 4. pivoted QR of R0 + solves + outputs
+        FinalArgs fa = final_args(h, v, mode.eps_rank, mode.dimJ2_ov, abs_shift, n2_launch);
+        const int kp_launch = (int)std::min<long long>(m, n2_launch);
+        if ((size_t)kp_launch * (n2_launch + 1) > (size_t)CMAT_DOUBLES) {
+            // more than 512 rows do not fit the register form of the blocked factorisation: one launch per pivot step
+            // (6.5 us per step; an LDS-slab blocked form was measured at 14 us per step and is gone)
+            int rc = (kp_launch > 512 && !h->qrcp_hybrid) ? run_qrcp_dist(h, n2_launch) : run_qrcp_block(h, n2_launch);
+            if (rc) return rc;
+            fa.refactor = 2;
+        }
+        GN_TRACE(h, "pivoted QR of R0 done (refactor %d)", fa.refactor);
+        if (!launch_pivot_small(kp_launch, n2_launch, (int)batch, s, fa, nlaunch)) launch_pivot((int)std::min<long long>(m, n), nlaunch, s, fa);
+        mark(h, 4);
+        GN_TRACE(h, "final kernel done");
+        // nominate problems whose largest column norm overflowed or sits at the bottom of the exponent range (gn_rescale.hpp)
+        if (h->rescale_enabled && !h->h_tk.empty())
+            hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt,
+                               P.sRt, (const double*)h->FA, P.sFA, P.kA, n2_launch, nlaunch, (const int*)h->tkbuf.p, h->run_plist);
+        else if (h->rescale_enabled)
+            hipLaunchKernelGGL(k_extreme_flags, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt, P.sRt,
+                               (const double*)h->FA, P.sFA, P.kA, n2_launch, nlaunch, h->run_plist);
+        GN_HIP(hipGetLastError());
+        if (int rc = fetch_states(h, cov)) return rc;
+        int n2max = 0;
+        for (long long i = 0; i < cov.count; ++i) n2max = std::max(n2max, h->h_state[cov[i]].n2);
+        if (n2max <= n2_launch) break;
+        n2_launch = n2max;  // some A was rank deficient: J2 is wider than speculated, redo from J*Q1
+    }
+    return 0;
+}
+
+static bool any_nominated(enlsip_gn_handle h, const Covered& cov) {
+    for (long long i = 0; i < cov.count; ++i)
+        if (h->h_state[cov[i]].status & GN_NOMINATED) return true;
+    return false;
+}
+
+// Magnitudes beyond the range of plain sums of squares in a one-problem solve: LAPACK's result through a power-of-two scaling in
+// place (gn_rescale.hpp).  A resident constraint stage is not looked at.
+static int rescale_in_place(enlsip_gn_handle h, const BatchOperands& v, const SolveMode& mode, const Covered& cov, int t_min, bool upper_in) {
+    int sJ = 0, sA = 0;
+    BatchOperands looked = v;
+    if (mode.kind != SolveMode::Fresh) { looked.At = nullptr; looked.cx = nullptr; }
+    int rc = extreme_shifts(h, looked, &sJ, &sA);
+    if (rc) return rc;
+    if (!sJ && !sA) return 0;
+    GN_TRACE(h, "rescale: J, rx by 2^%d, A', cx by 2^%d", sJ, sA);
+    rc = scaled_copies(h, v, sJ, sA);
+    if (rc) return rc;
+    if (sA) {
+        h->sc_eA = sA;      // the stage on the scaled copies; what it leaves resident is scaled back
+        rc = run_constraint_stage(h, 1, v.m, v.n, v.t, v.At, v.ldat, v.strideAt, v.cx, mode.eps_rank, mode.dimA_ov);
+        if (rc) return rc;
+    }
+    h->sc_eJ = sJ;
+    if (!sA) {
+        // the constraint stage is not run again, so nothing resets the status it wrote: take back the bit 0 that the
+        // final kernel of the first pass ORed in on the unscaled data (a diagonal that underflowed to zero there)
+        hipLaunchKernelGGL(k_clear_status_bits, dim3(1), dim3(256), 0, h->stream, h->state, 1, 1, (const int*)nullptr);
+        GN_HIP(hipGetLastError());
+        h->h_state[0].status &= ~1;
+    }
+    rc = sJ ? jacobian_side(h, v, mode, cov, t_min, upper_in, h->rs_J, v.m, v.m * v.n, h->rs_rx, sJ)
+            : jacobian_side(h, v, mode, cov, t_min, upper_in, v.J, v.ldj, v.strideJ, v.rx, 0);
+    if (rc) return rc;
+    if (sJ) {
+        rc = unscale_jacobian_side(h, v.d);
+        if (rc) return rc;
+    }
+    GN_ROUTE(ENLSIP_GN_ROUTE_RESCALED);
+    return 0;
+}
+
+// A batch (or a ragged batch of one, whose problem is solved with its own t there): every nominated problem whose inputs are beyond
+// the band goes to a one-problem handle of its own, on which `run` does the caller's work (and which rescales in place); the
+// accessors are routed to it.  with_J: a shift of J, rx counts too (the constraint stage alone looks at A', cx only).
+static int rescue_nominated(enlsip_gn_handle h, const BatchOperands& v, const Covered& cov, bool with_J,
+                            const std::function<int(enlsip_gn_handle, const BatchOperands&)>& run) {
+    for (long long i = 0; i < cov.count; ++i) {
+        const long long k = cov[i];
+        if (!(h->h_state[k].status & GN_NOMINATED)) continue;
+        int sJ = 0, sA = 0;
+        BatchOperands one = v.slice(k, 1);      // offsets with the batch's strides (t_max) ...
+        if (v.tk) one.t = v.tk[k];              // ... and a problem of a ragged batch rescued with its own t
+        one.dinfo = nullptr; one.hinfo = nullptr; one.tk = nullptr;
+        int rc = extreme_shifts(h, one, &sJ, &sA);
+        if (rc) return rc;
+        if (!sA && !(with_J && sJ)) continue;
+        enlsip_gn_handle r = nullptr;
+        rc = next_rescue_handle(h, &r);
+        if (rc) return rc;
+        rc = run(r, one);
+        if (rc) { h->err = r->err; return rc; }
+        GN_HIP(hipSetDevice(h->device));
+        h->h_state[k] = r->h_state[0];
+        h->rescue_prob.push_back(k);
+    }
+    return 0;
+}
+
+// the nomination bits are host-internal: cleared on the host mirror and on the device
+static int clear_nominations(enlsip_gn_handle h, const Covered& cov) {
+    for (long long i = 0; i < cov.count; ++i) h->h_state[cov[i]].status &= ~GN_NOMINATED;
+    hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((cov.count + 255) / 256)), dim3(256), 0, h->stream, h->state, GN_NOMINATED,
+                       (int)cov.count, h->run_plist);
+    GN_HIP(hipGetLastError());
+    return 0;
+}
+
+// The info records of the covered problems, produced on the host from the state mirror: into the caller's host array, and / or
+// uploaded to its device array — whole, or the listed records in list order, scattered by one launch.  constraints_only: nothing
+// about J is resident, rankJ2 and dimJ2 are zero.
+static int publish_info(enlsip_gn_handle h, const BatchOperands& v, const Covered& cov, bool constraints_only) {
+    if (!v.hinfo && !v.dinfo) return 0;
+    hipStream_t s = h->stream;
+    std::vector<enlsip_gn_info> tmp((size_t)cov.count);
+    for (long long i = 0; i < cov.count; ++i) {
+        tmp[(size_t)i] = info_of(h->h_state[cov[i]]);
+        if (constraints_only) tmp[(size_t)i].rankJ2 = tmp[(size_t)i].dimJ2 = 0;
+        if (v.hinfo) v.hinfo[cov[i]] = tmp[(size_t)i];
+    }
+    if (!v.dinfo) return 0;
+    if (cov.list) {
+        int rc = grow(h, h->info_stage, tmp.size() * sizeof(enlsip_gn_info));
+        if (rc) return rc;
+        GN_HIP(hipMemcpyAsync(h->info_stage.p, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_scatter_info, dim3((unsigned)((cov.count + 255) / 256)), dim3(256), 0, s, v.dinfo,
+                           (const enlsip_gn_info*)h->info_stage.p, h->run_plist, (int)cov.count);
+        GN_HIP(hipGetLastError());
+    } else GN_HIP(hipMemcpyAsync(v.dinfo, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
+    GN_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// One solve of the problems of v on ONE handle (the caller's, a pipeline child, a rescue handle, the TSQR sub-handle); what kind of
+// solve is in `mode` alone.  mode.flags are those of this part: a Factored / Changed solve lists its flagged problems from them.
+static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, SolveMode mode) {
+    const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
     gn_route_acc = 0;
-    // a changed-problems solve (enlsip_gn_solve_changed_batched, which has checked the resident state): the problems of h->refit
-    // only, constraint stage and Jacobian side, into their own slots of the resident batch; nothing else of it is touched
-    const bool listed = h->changed_once;
-    h->changed_once = false;
-    const bool reuse = h->reuse_once || listed;
-    h->reuse_once = false;
-    if (!reuse) h->refit.clear();
+    // a changed-problems solve (enlsip_gn_solve_changed_batched, which has checked the resident state): the flagged problems only,
+    // constraint stage and Jacobian side, into their own slots of the resident batch; nothing else of it is touched
+    const bool listed = mode.kind == SolveMode::Changed;
+    const bool reuse = mode.kind != SolveMode::Fresh;
+    h->refit.clear();
+    for (long long k = 0; reuse && mode.flags && k < batch; ++k)
+        if (mode.flags[k]) h->refit.push_back((int)k);
     struct ListGuard {      // no launch after this solve is sized by its list
         enlsip_gn_handle h;
         ~ListGuard() { h->run_plist = nullptr; h->run_nlist = 0; }
     } list_guard{h};
-    const long long nlaunch = listed ? (long long)h->refit.size() : batch;       // problems every launch of this solve covers
-    auto prob_at = [&](long long i) -> long long { return listed ? h->refit[(size_t)i] : i; };
-    const bool upper_in = h->upper_once && t == 0 && m <= n;      // J is upper triangular (and unconstrained): it IS its own R0, Q0 = I
-    h->upper_once = false;
+    const Covered cov{listed ? (long long)h->refit.size() : batch, listed ? h->refit.data() : nullptr};
+    const bool upper_in = mode.upper_input && t == 0 && m <= n;   // J is upper triangular (and unconstrained): it IS its own R0, Q0 = I
     int rc = check_limits(h, batch, m, n, t);
     if (rc) return rc;
     if (v.ldj < m) { h->err = "ldj < m"; return -7; }
@@ -1175,51 +1452,14 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
     GN_HIP(hipSetDevice(h->device));
     rc = make_plan(h, batch, m, n, t);
     if (rc) return rc;
-    const Plan& P = h->plan;
-    h->eps_rank = eps_rank;
-    if (listed) {
-        // a held re-solve of a listed problem is dropped; a listed problem that lived on a rescue handle gives it back (the handle
-        // moves behind the ones in use)
-        for (int k : h->refit) {
-            if ((size_t)k < h->held.size()) h->held[(size_t)k] = {};
-            for (size_t j = 0; j < h->rescue_prob.size(); ++j)
-                if (h->rescue_prob[j] == k) {
-                    enlsip_gn_handle r = h->rescue[j];
-                    h->rescue.erase(h->rescue.begin() + (long)j);
-                    h->rescue.push_back(r);
-                    h->rescue_prob.erase(h->rescue_prob.begin() + (long)j);
-                    break;
-                }
-        }
-    } else {
-        h->factors_valid = false;
-        h->held.clear();
-        h->last = v.inputs();
-        h->sc_eJ = 0;
-        if (!reuse) h->sc_eA = 0;       // (a resident constraint stage keeps the scale enlsip_gn_factor_constraints gave it)
-        h->rescue_prob.clear();
-    }
-    hipStream_t s = h->stream;
-    // The state records of the part from the device into the host mirror.  A changed-problems solve never writes the mirror's
-    // records of the problems it leaves alone (a rescued problem's holds its rescue handle's record, not the device's): it reads
-    // back into a buffer of its own and takes the listed records from there.
-    std::vector<ProbState> fresh;
-    auto fetch_states = [&]() -> int {
-        if (listed) fresh.resize((size_t)batch);
-        GN_HIP(hipMemcpyAsync(listed ? fresh.data() : h->h_state, h->state, (size_t)batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
-        GN_HIP(hipStreamSynchronize(s));
-        if (listed)
-            for (int k : h->refit) h->h_state[k] = fresh[(size_t)k];
-        return 0;
-    };
-    // ragged batch: every problem's own t, kept on the host for the accessors and copied to the device for the constraint kernels
+    h->eps_rank = mode.eps_rank;
+    if (listed) release_listed(h, h->refit);
+    else begin_whole_part(h, v.inputs(), reuse);
     int t_min = (int)t;
     if (v.tk) {
-        h->h_tk.assign(v.tk, v.tk + batch);
-        for (int tk : h->h_tk) t_min = std::min(t_min, tk);
-        rc = grow(h, h->tkbuf, (size_t)batch * sizeof(int));
+        rc = upload_tk(h, v.tk, batch);
         if (rc) return rc;
-        GN_HIP(hipMemcpyAsync(h->tkbuf.p, h->h_tk.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s));
+        for (int tk : h->h_tk) t_min = std::min(t_min, tk);
     } else if (!reuse) {
         h->h_tk.clear();
     }
@@ -1234,205 +1474,37 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank
         h->oth_used = 0;
         h->upd_all_bytes = 0.0;
     }
-    auto mark = [&](int i) { if (h->profiling) (void)hipEventRecord(h->ev[i], s); };
-
-    mark(0);
+    mark(h, 0);
     h->constraints_only = false;
     // 1. constraint stage
     GN_TRACE(h, "solve m=%lld n=%lld t=%lld batch=%lld: constraint stage%s", m, n, t, batch, reuse ? " (resident)" : "");
     h->cstage_problems = 0;
     h->jstage_problems = 0;
-    if (!reuse) {       // enlsip_gn_solve_factored: F_A, F_L11, b, p1, T and the state record are those of enlsip_gn_factor_constraints
-        h->fb.valid = false;
-        rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov);
-        if (rc) return rc;
-    } else if (!h->refit.empty()) {     // enlsip_gn_solve_factored_batched: the stage again for the problems whose working set changed
-        const size_t nl = h->refit.size();
-        rc = grow(h, h->plist_buf, nl * sizeof(int));
-        if (rc) return rc;
-        GN_HIP(hipMemcpyAsync(h->plist_buf.p, h->refit.data(), nl * sizeof(int), hipMemcpyHostToDevice, s));
-        rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov, 0, 0, (const int*)h->plist_buf.p,
-                                  (long long)nl);
-        if (rc) return rc;
-        if (listed) { h->run_plist = (const int*)h->plist_buf.p; h->run_nlist = (long long)nl; }
-    }
-    mark(1);
-    GN_TRACE(h, "constraint stage done");
-
-    // steps 2-4 for the Jacobian side given (the caller's J, rx — or their scaled copies, abs_shift = their power of two)
-    auto attempts = [&](const double* dJ, long long ldj, long long strideJ, const double* drx, int abs_shift) -> int {
-    // speculate rankA = min(n, t) (ragged: the smallest min(n, t_k), so that only a rank-deficient A' widens J2); verified after the solve
-    int n2_launch = (int)(n - std::min<long long>(n, t_min));
-    // a changed-problems solve launches with the width a solve of the whole part on the final sets ends with: no narrower than the
-    // widest J2 among the problems it leaves alone (one of them had a rank-deficient A')
-    if (listed) {
-        std::vector<char> in_list((size_t)batch, 0);
-        for (int k : h->refit) in_list[(size_t)k] = 1;
-        for (long long k = 0; k < batch; ++k)
-            if (!in_list[(size_t)k]) n2_launch = std::max(n2_launch, h->h_state[k].n2);
-    }
-    h->jstage_problems = nlaunch;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        // 2. JQ1 = J*Q1, d_temp
-        const JQ1Args qa = jq1_args(h, dJ, ldj, strideJ, drx);
-        // one 256-row tile, one narrow panel (C5): J*Q1 and the panel factorisation in ONE launch, the tile handed over in LDS
-        const bool fused = h->fuse_small && !upper_in && !(h->flags & ENLSIP_GN_UPDATE_REFLECTORS) &&
-                           small_fused_applies(m, n, P.kA, n2_launch);
-        if (fused) {
-            CaqrArgs ca = caqr_args(h, 0, P.panels[0].levels[0]);
-            ca.npass = 1;
-            launch_jq1_factor_small(qa, ca, (int)nlaunch, s);
-            GN_HIP(hipGetLastError());
-        } else launch_jq1_any(h, qa, (int)nlaunch, s);
-        mark(2);
-        GN_TRACE(h, "attempt %d n2_launch=%d: J*Q1 done%s", attempt, n2_launch, fused ? " (fused with the panel factorisation)" : "");
-        // 3. CAQR of [J2 | d]
-        if (!upper_in && !fused) {
-            rc = run_caqr(h, n2_launch);
-            if (rc) return rc;
-        }
-        if (upper_in) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_UPPER_INPUT);
-        if (attempt > 0) GN_ROUTE(ENLSIP_GN_ROUTE_SECOND_ATTEMPT);
-        mark(3);
-        GN_TRACE(h, "CAQR done");
-        // 4. pivoted QR of R0 + solves + outputs
-        FinalArgs fa{};
-        fa.m = (int)m; fa.n = (int)n; fa.t = (int)t; fa.kA = P.kA; fa.ldw = P.ldw; fa.ldr = P.ldr;
-        fa.eps_rank = eps_rank; fa.abs_shift = abs_shift; fa.dimJ2_override = (int)dimJ2_ov; fa.refactor = 1;
-        fa.W = h->W; fa.sW = P.sW; fa.Rt = h->Rt; fa.sRt = P.sRt; fa.tauJ = h->tauJ; fa.sTauJ = P.sTauJ;
-        fa.jpvtJ = h->jpvtJ; fa.sJJ = P.sJJ; fa.FA = h->FA; fa.sFA = P.sFA; fa.tauA = h->tauA; fa.sTauA = P.sTauA;
-        fa.p1 = h->p1; fa.sP1 = P.sP1; fa.bvec = h->bvec; fa.sB = P.sB; fa.zsave = h->zsave; fa.sZ = P.sZ;
-        fa.p_out = v.p; fa.sPo = n; fa.b_out = v.b; fa.sBo = t; fa.d_out = v.d; fa.sDo = m;
-        fa.jA_out = v.jpvtA; fa.sJAo = t; fa.jpvtA = h->jpvtA; fa.sJA = P.sJA;
-        fa.jL_out = v.jpvtL; fa.sJLo = P.kA; fa.jpvtL = h->jpvtL; fa.sJL = P.sJL;
-        fa.jJ_out = v.jpvtJ2; fa.sJJo = n;
-        fa.state = h->state; fa.plist = h->run_plist;
-        fa.n2cap = n2_launch;
-        {
-            const int kp_launch = (int)std::min<long long>(m, n2_launch);
-            if ((size_t)kp_launch * (n2_launch + 1) > (size_t)CMAT_DOUBLES) {
-                // more than 512 rows do not fit the register form of the blocked factorisation: one launch per pivot step
-                // (6.5 us per step; an LDS-slab blocked form was measured at 14 us per step and is gone)
-                rc = (kp_launch > 512 && !h->qrcp_hybrid) ? run_qrcp_dist(h, n2_launch) : run_qrcp_block(h, n2_launch);
-                if (rc) return rc;
-                fa.refactor = 2;
-            }
-        }
-        GN_TRACE(h, "pivoted QR of R0 done (refactor %d)", fa.refactor);
-        if (!launch_pivot_small((int)std::min<long long>(m, n2_launch), n2_launch, (int)batch, s, fa, (int)nlaunch))
-            launch_pivot((int)std::min<long long>(m, n), (int)nlaunch, s, fa);
-        mark(4);
-        GN_TRACE(h, "final kernel done");
-        // nominate problems whose largest column norm overflowed or sits at the bottom of the exponent range (gn_rescale.hpp)
-        if (h->rescale_enabled && !h->h_tk.empty())
-            hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt,
-                               P.sRt, (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)nlaunch, (const int*)h->tkbuf.p, h->run_plist);
-        else if (h->rescale_enabled)
-            hipLaunchKernelGGL(k_extreme_flags, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)h->Rt, P.sRt,
-                               (const double*)h->FA, P.sFA, P.kA, n2_launch, (int)nlaunch, h->run_plist);
-        GN_HIP(hipGetLastError());
-        if (int rcf = fetch_states()) return rcf;
-        int n2max = 0;
-        for (long long i = 0; i < nlaunch; ++i) n2max = std::max(n2max, h->h_state[prob_at(i)].n2);
-        if (n2max <= n2_launch) break;
-        n2_launch = n2max;  // some A was rank deficient: J2 is wider than speculated, redo from J*Q1
-    }
-    return 0;
-    };
-    rc = attempts(v.J, v.ldj, v.strideJ, v.rx, 0);
+    rc = constraint_step(h, v, mode);
     if (rc) return rc;
-    // ---- magnitudes beyond the range of plain sums of squares: LAPACK's result through a power-of-two scaling (gn_rescale.hpp) ----
-    {
-        const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
-        bool flagged = false;
-        for (long long i = 0; i < nlaunch; ++i) flagged = flagged || (h->h_state[prob_at(i)].status & fl);
-        if (flagged && batch == 1 && !v.tk) {
-            int sJ = 0, sA = 0;
-            BatchOperands looked = v;
-            if (reuse) { looked.At = nullptr; looked.cx = nullptr; }
-            rc = extreme_shifts(h, looked, &sJ, &sA);
-            if (rc) return rc;
-            if (sJ || sA) {
-                GN_TRACE(h, "rescale: J, rx by 2^%d, A', cx by 2^%d", sJ, sA);
-                rc = scaled_copies(h, v, sJ, sA);
-                if (rc) return rc;
-                if (sA) {
-                    h->sc_eA = sA;
-                    rc = run_constraint_stage(h, 1, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, dimA_ov);     // on the scaled copies; scaled back
-                    if (rc) return rc;
-                }
-                h->sc_eJ = sJ;
-                if (!sA) {
-                    // the constraint stage is not run again, so nothing resets the status it wrote: take back the bit 0 that the
-                    // final kernel of the first pass ORed in on the unscaled data (a diagonal that underflowed to zero there)
-                    hipLaunchKernelGGL(k_clear_status_bits, dim3(1), dim3(256), 0, s, h->state, 1, 1, (const int*)nullptr);
-                    GN_HIP(hipGetLastError());
-                    h->h_state[0].status &= ~1;
-                }
-                rc = sJ ? attempts(h->rs_J, m, m * n, h->rs_rx, sJ) : attempts(v.J, v.ldj, v.strideJ, v.rx, 0);
-                if (rc) return rc;
-                if (sJ) {
-                    rc = unscale_jacobian_side(h, v.d);
-                    if (rc) return rc;
-                }
-                GN_ROUTE(ENLSIP_GN_ROUTE_RESCALED);
-            }
-        } else if (flagged) {
-            // a batch (or a ragged batch of one, whose problem is solved with its own t there): every nominated problem whose inputs are beyond the band goes to a one-problem handle of its own (which
-            // rescales in place as above); its outputs land in the caller's slots, the accessors are routed to it
-            for (long long i = 0; i < nlaunch; ++i) {
-                const long long k = prob_at(i);
-                if (!(h->h_state[k].status & fl)) continue;
-                int sJ = 0, sA = 0;
-                BatchOperands one = v.slice(k, 1);      // offsets with the batch's strides (t_max) ...
-                if (v.tk) one.t = v.tk[k];              // ... and a problem of a ragged batch rescued with its own t
-                one.dinfo = nullptr; one.hinfo = nullptr; one.tk = nullptr;
-                rc = extreme_shifts(h, one, &sJ, &sA);
-                if (rc) return rc;
-                if (!sJ && !sA) continue;
-                enlsip_gn_handle r = nullptr;
-                rc = next_rescue_handle(h, &r);
-                if (rc) return rc;
-                const unsigned long long route_here = gn_route_acc;
-                rc = solve_dev(r, one, eps_rank, dimA_ov, dimJ2_ov);
-                gn_route_acc = route_here | r->route;
-                if (rc) { h->err = r->err; return rc; }
-                GN_HIP(hipSetDevice(h->device));
-                h->h_state[k] = r->h_state[0];
-                h->rescue_prob.push_back(k);
-            }
-        }
-        if (flagged) {       // the nomination bits are host-internal
-            for (long long i = 0; i < nlaunch; ++i) h->h_state[prob_at(i)].status &= ~fl;
-            hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)nlaunch,
-                               h->run_plist);
-            GN_HIP(hipGetLastError());
-        }
-    }
-    if (v.hinfo)
-        for (long long i = 0; i < nlaunch; ++i) v.hinfo[prob_at(i)] = info_of(h->h_state[prob_at(i)]);
-    if (v.dinfo && listed) {        // the listed problems' records only: one upload in list order, scattered by one launch
-        std::vector<enlsip_gn_info> tmp((size_t)nlaunch);
-        for (long long i = 0; i < nlaunch; ++i) tmp[(size_t)i] = info_of(h->h_state[prob_at(i)]);
-        rc = grow(h, h->info_stage, tmp.size() * sizeof(enlsip_gn_info));
+    mark(h, 1);
+    GN_TRACE(h, "constraint stage done");
+    // 2-4. Jacobian side
+    rc = jacobian_side(h, v, mode, cov, t_min, upper_in, v.J, v.ldj, v.strideJ, v.rx, 0);
+    if (rc) return rc;
+    if (any_nominated(h, cov)) {
+        if (batch == 1 && !v.tk) rc = rescale_in_place(h, v, mode, cov, t_min, upper_in);
+        else rc = rescue_nominated(h, v, cov, true, [&](enlsip_gn_handle r, const BatchOperands& one) {
+            const unsigned long long route_here = gn_route_acc;
+            const int rcr = solve_dev(r, one, mode.fresh());        // its outputs land in the caller's slots
+            gn_route_acc = route_here | r->route;
+            return rcr;
+        });
         if (rc) return rc;
-        GN_HIP(hipMemcpyAsync(h->info_stage.p, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_scatter_info, dim3((unsigned)((nlaunch + 255) / 256)), dim3(256), 0, s, v.dinfo,
-                           (const enlsip_gn_info*)h->info_stage.p, h->run_plist, (int)nlaunch);
-        GN_HIP(hipGetLastError());
-        GN_HIP(hipStreamSynchronize(s));
-    } else if (v.dinfo) {
-        // info records are produced on the host from the state mirror and copied to the device buffer
-        std::vector<enlsip_gn_info> tmp((size_t)batch);
-        for (long long k = 0; k < batch; ++k) tmp[k] = info_of(h->h_state[k]);
-        GN_HIP(hipMemcpyAsync(v.dinfo, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
-        GN_HIP(hipStreamSynchronize(s));
+        rc = clear_nominations(h, cov);
+        if (rc) return rc;
     }
+    rc = publish_info(h, v, cov, false);
+    if (rc) return rc;
     if (h->profiling) {
         rc = collect_stage_ms(h);
         if (rc) return rc;
     }
-    h->refit.clear();
     h->factors_valid = true;
     h->route = gn_route_acc;
     return 0;
@@ -1799,40 +1871,36 @@ static int on_both_halves(enlsip_gn_handle h, long long batch, long long b0,
 }
 
 // One launch set over at most GN_MAX_LAUNCH_BATCH problems: either two pipelined halves on two streams or one solve_dev.
-// With a resident constraint stage (reuse_once) the halves are those the stage was placed on: enlsip_gn_factor_constraints_batched
+// With a resident constraint stage (mode Factored) the halves are those the stage was placed on: enlsip_gn_factor_constraints_batched
 // recorded its split, and the solve must come to the same one.
-static int solve_launchable(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
+static int solve_launchable(enlsip_gn_handle h, const BatchOperands& v, SolveMode mode) {
     h->split = 0;
     const long long batch = v.batch, m = v.m, n = v.n;
-    const bool factored = h->reuse_once;
-    const bool plain = (dimA_ov < 0 && dimJ2_ov < 0);
+    const bool plain = (mode.dimA_ov < 0 && mode.dimJ2_ov < 0);
     const long long b0 = plain ? pipeline_split_of(h, batch, m, n) : 0;
-    if (factored && b0 != (h->fb.valid ? h->fb.split : 0)) {
-        h->reuse_once = false;
+    if (mode.kind == SolveMode::Factored && b0 != (h->fb.valid ? h->fb.split : 0)) {
         h->err = "the batch would be split over the pipeline halves differently from the constraint stage that is resident "
                  "(profiling or the pipeline setting changed in between?): call enlsip_gn_factor_constraints_batched again";
         return -1;
     }
-    if (b0 > 0) {
-        if (factored) h->child->reuse_once = true;
+    if (b0 > 0)
         return on_both_halves(h, batch, b0, [&](enlsip_gn_handle hh, long long k0, long long cnt) {
-            return solve_dev(hh, v.slice(k0, cnt), eps_rank, -1, -1);
+            return solve_dev(hh, v.slice(k0, cnt), mode.part(k0));
         });
-    }
-    return solve_dev(h, v, eps_rank, dimA_ov, dimJ2_ov);
+    return solve_dev(h, v, mode);
 }
 
 // Any batch: consecutive chunks of at most GN_MAX_LAUNCH_BATCH problems (the problem index is a grid y / z dimension).  The
 // factors that stay resident are those of the LAST chunk; accessors address problems by their index in the whole batch and
 // report an error for the earlier chunks (gn_accessors.inc: map_resident).
-static int solve_chunked(enlsip_gn_handle h, const BatchOperands& v, double eps_rank, long long dimA_ov, long long dimJ2_ov) {
+static int solve_chunked(enlsip_gn_handle h, const BatchOperands& v, SolveMode mode) {
     h->chunk0 = 0;
     const long long batch = v.batch;
     const long long nchunks = (batch + GN_MAX_LAUNCH_BATCH - 1) / GN_MAX_LAUNCH_BATCH;
     const long long per = (batch + nchunks - 1) / nchunks;
     unsigned long long route_all = nchunks > 1 ? (1ull << ENLSIP_GN_ROUTE_CHUNKED) : 0ull;
     for (long long c0 = 0; c0 < batch; c0 += per) {
-        int rc = solve_launchable(h, v.slice(c0, std::min(per, batch - c0)), eps_rank, dimA_ov, dimJ2_ov);
+        int rc = solve_launchable(h, v.slice(c0, std::min(per, batch - c0)), mode.part(c0));
         if (rc) return rc;
         h->chunk0 = c0;
         route_all |= h->route;
@@ -1854,21 +1922,29 @@ int enlsip_gn_solve_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
     if (!drx) { h->err = "drx is NULL"; return -9; }
     if (t > 0 && (!dAt || !dcx)) { h->err = "dAt / dcx is NULL with t > 0"; return -10; }
     return solve_chunked(h, {batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, dp, db, dd, dinfo, (long long*)djpvtA,
-                             (long long*)djpvtL, (long long*)djpvtJ2}, eps_rank, -1, -1);
+                             (long long*)djpvtL, (long long*)djpvtJ2}, {SolveMode::Fresh, nullptr, false, -1, -1, eps_rank});
     GN_CATCH(h)
 }
 
 static int solve_factored_core(enlsip_gn_handle h, const BatchOperands& v, const int64_t* refactor, double eps_rank, bool host_form);
 
+// is any of the first `batch` refactor / changed flags set?  (NULL: none)
+static bool any_flag(const int64_t* flags, int64_t batch) {
+    for (int64_t k = 0; flags && k < batch; ++k)
+        if (flags[k]) return true;
+    return false;
+}
+
 // hv: the caller's host arrays (hinfo = the info records): staged packed (ld = m / n), solved, outputs copied back
-// factored: the constraint stage is resident and A', cx sit in their staging slots (enlsip_gn_solve_factored); batched_factored:
-// that of a whole batch (enlsip_gn_solve_factored_batched, which has checked the state), where the problems with a refactor flag
-// bring new A', cx into their slots
-static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_rank, long long dimA_ov, long long dimJ2_ov,
-                      bool factored = false, bool batched_factored = false, const int64_t* refactor = nullptr) {
+// mode Factored: the constraint stage is resident and A', cx sit in their staging slots — of one problem (enlsip_gn_solve_factored),
+// or, with per-problem t (hv.tk), of a whole batch (enlsip_gn_solve_factored_batched, which has checked the state), where the
+// problems with a refactor flag bring new A', cx into their slots
+static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, SolveMode mode) {
     if (!h) return -1;
     GN_TRY
-    const long long batch = hv.batch, m = hv.m, n = hv.n, t = hv.t;
+    const long long batch = hv.batch, m = hv.m, n = hv.n, t = hv.t, dimA_ov = mode.dimA_ov, dimJ2_ov = mode.dimJ2_ov;
+    const bool factored = mode.kind == SolveMode::Factored, batched_factored = factored && hv.tk;
+    const int64_t* refactor = mode.flags;
     int rc = check_limits(h, batch, m, n, t);
     if (rc) return rc;
     if (!hv.J) { h->err = "J is NULL"; return -6; }
@@ -1922,12 +1998,7 @@ static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_ra
     }
     GN_HIP(hipMemcpyAsync(drx, hv.rx, (size_t)batch * m * 8, hipMemcpyHostToDevice, s));
     if (t > 0 && !factored) GN_HIP(hipMemcpyAsync(dcx, hv.cx, (size_t)batch * t * 8, hipMemcpyHostToDevice, s));
-    if (batched_factored) {
-        rc = solve_factored_core(h, dv, refactor, eps_rank, true);
-    } else {
-        h->reuse_once = factored;      // A', cx (same staging slots) and the constraint factors are resident
-        rc = solve_chunked(h, dv, eps_rank, dimA_ov, dimJ2_ov);
-    }
+    rc = batched_factored ? solve_factored_core(h, dv, refactor, mode.eps_rank, true) : solve_chunked(h, dv, mode);
     if (rc) return rc;
     if (hv.p) GN_HIP(hipMemcpyAsync(hv.p, dp, (size_t)batch * n * 8, hipMemcpyDeviceToHost, s));
     if (hv.b && t > 0) GN_HIP(hipMemcpyAsync(hv.b, db, (size_t)batch * t * 8, hipMemcpyDeviceToHost, s));
@@ -1945,21 +2016,14 @@ static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, double eps_ra
 static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long long t, const double* dAt, long long ldat, const double* dcx,
                           double eps_rank, enlsip_gn_info* info) {
     GN_HIP(hipSetDevice(h->device));
-    h->split = 0;
-    h->chunk0 = 0;
     h->fb.valid = false;
-    h->refit.clear();
     int rc = make_plan(h, 1, m, n, t);
     if (rc) return rc;
     hipStream_t s = h->stream;
     BatchOperands v{1, m, n, t};     // no J, rx: the constraint side only
     v.At = dAt; v.ldat = ldat; v.strideAt = ldat * t; v.cx = dcx;
     h->eps_rank = eps_rank;
-    h->factors_valid = false;
-    h->held.clear();
-    h->last = v;
-    h->sc_eJ = 0; h->sc_eA = 0;
-    h->rescue_prob.clear();
+    begin_whole_part(h, v, false);
     h->h_tk.clear();
     rc = run_constraint_stage(h, 1, m, n, t, dAt, ldat, ldat * t, dcx, eps_rank, -1);
     if (rc) return rc;
@@ -1968,7 +2032,7 @@ static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long lon
                            h->plan.kA, 0, 1, (const int*)nullptr);
     GN_HIP(hipMemcpyAsync(h->h_state, h->state, sizeof(ProbState), hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
-    if (h->h_state[0].status & (GN_FLAG_NONFINITE | GN_FLAG_TINY)) {
+    if (h->h_state[0].status & GN_NOMINATED) {
         // A', cx beyond the range of plain sums of squares: the stage again on copies scaled by a power of two (gn_rescale.hpp)
         int sJ = 0, sA = 0;
         rc = extreme_shifts(h, v, &sJ, &sA);
@@ -1983,17 +2047,13 @@ static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long lon
             GN_HIP(hipStreamSynchronize(s));
             h->route |= (1ull << ENLSIP_GN_ROUTE_RESCALED);
         }
-        h->h_state[0].status &= ~(GN_FLAG_NONFINITE | GN_FLAG_TINY);
-        hipLaunchKernelGGL(k_clear_status_bits, dim3(1), dim3(256), 0, s, h->state, GN_FLAG_NONFINITE | GN_FLAG_TINY, 1, (const int*)nullptr);
-        GN_HIP(hipGetLastError());
+        rc = clear_nominations(h, {1});
+        if (rc) return rc;
     }
     h->factors_valid = true;
     h->constraints_only = true;
-    if (info) {
-        *info = info_of(h->h_state[0]);
-        info->rankJ2 = info->dimJ2 = 0;       // nothing about J is resident
-    }
-    return 0;
+    v.hinfo = info;
+    return publish_info(h, v, {1}, true);
 }
 
 int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const double* At, int64_t ldat,
@@ -2022,7 +2082,7 @@ int enlsip_gn_solve_factored(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t
                              const double* rx, double eps_rank, int64_t dimJ2_override, double* p, double* b, double* d,
                              enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
     return solve_host(h, {1, m, n, t, J, ldj, ldj * n, rx, nullptr, n, n * t, nullptr, p, b, d, nullptr, (long long*)jpvtA,
-                          (long long*)jpvtL, (long long*)jpvtJ2, info}, eps_rank, -1, dimJ2_override, true);
+                          (long long*)jpvtL, (long long*)jpvtJ2, info}, {SolveMode::Factored, nullptr, false, -1, dimJ2_override, eps_rank});
 }
 
 int enlsip_gn_solve_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t, const double* J,
@@ -2030,7 +2090,7 @@ int enlsip_gn_solve_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_
                             int64_t strideAt, const double* cx, double eps_rank, double* p, double* b, double* d,
                             enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
     return solve_host(h, {batch, m, n, t, J, ldj, strideJ, rx, At, ldat, strideAt, cx, p, b, d, nullptr, (long long*)jpvtA,
-                          (long long*)jpvtL, (long long*)jpvtJ2, info}, eps_rank, -1, -1);
+                          (long long*)jpvtL, (long long*)jpvtJ2, info}, {SolveMode::Fresh, nullptr, false, -1, -1, eps_rank});
 }
 
 // ---- ragged batch: one t per problem (update_working_set, src/enlsip_functions.jl:686-795, gives every problem its own W.t and
@@ -2075,7 +2135,7 @@ int enlsip_gn_solve_batched_ragged(enlsip_gn_handle h, int64_t batch, int64_t m,
     int rc = check_ragged(h, batch, m, n, t_max, t, J, ldj, rx, At, ldat, strideAt, cx, tk);
     if (rc) return rc;
     return solve_host(h, {batch, m, n, t_max, J, ldj, strideJ, rx, At, ldat, strideAt, cx, p, b, d, nullptr, (long long*)jpvtA,
-                          (long long*)jpvtL, (long long*)jpvtJ2, info, tk.data()}, eps_rank, -1, -1);
+                          (long long*)jpvtL, (long long*)jpvtJ2, info, tk.data()}, {SolveMode::Fresh, nullptr, false, -1, -1, eps_rank});
     GN_CATCH(h)
 }
 
@@ -2089,7 +2149,8 @@ int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_
     int rc = check_ragged(h, batch, m, n, t_max, t, dJ, ldj, drx, dAt, ldat, strideAt, dcx, tk);
     if (rc) return rc;
     return solve_chunked(h, {batch, m, n, t_max, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx, dp, db, dd, dinfo,
-                             (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()}, eps_rank, -1, -1);
+                             (long long*)djpvtA, (long long*)djpvtL, (long long*)djpvtJ2, nullptr, tk.data()},
+                         {SolveMode::Fresh, nullptr, false, -1, -1, eps_rank});
     GN_CATCH(h)
 }
 
@@ -2097,81 +2158,45 @@ int enlsip_gn_solve_batched_ragged_dev(enlsip_gn_handle h, int64_t batch, int64_
 // deletion decision, :725 / :771 after it), see include/enlsip_gn.h -------------------------------------------------------------
 
 // The constraint stage of the problems of v (device buffers, v.tk on the host) on ONE handle: the parent or a pipeline child.
+// The steps are solve_dev's; what differs: only a shift of A', cx sends a problem to a rescue handle, what runs there is the
+// constraint stage of one problem, and the info records carry nothing about J.
 static int factor_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_rank) {
     const long long batch = v.batch, m = v.m, n = v.n, t = v.t;
+    const Covered cov{batch};
     GN_HIP(hipSetDevice(h->device));
-    h->split = 0;
-    h->chunk0 = 0;
     gn_route_acc = 0;
-    h->reuse_once = false;
-    h->upper_once = false;
-    h->refit.clear();
     h->cstage_problems = 0;
     h->jstage_problems = 0;
     int rc = make_plan(h, batch, m, n, t);
     if (rc) return rc;
     const Plan& P = h->plan;
     h->eps_rank = eps_rank;
-    h->factors_valid = false;
-    h->held.clear();
-    h->last = v.inputs();           // J, rx absent: the consumers that need them say so
-    h->sc_eJ = 0; h->sc_eA = 0;
-    h->rescue_prob.clear();
+    begin_whole_part(h, v.inputs(), false);         // J, rx absent: the consumers that need them say so
     hipStream_t s = h->stream;
-    h->h_tk.assign(v.tk, v.tk + batch);
-    rc = grow(h, h->tkbuf, (size_t)batch * sizeof(int));
+    rc = upload_tk(h, v.tk, batch);
     if (rc) return rc;
-    GN_HIP(hipMemcpyAsync(h->tkbuf.p, h->h_tk.data(), (size_t)batch * sizeof(int), hipMemcpyHostToDevice, s));
     rc = run_constraint_stage(h, batch, m, n, t, v.At, v.ldat, v.strideAt, v.cx, eps_rank, -1);
     if (rc) return rc;
-    const int fl = GN_FLAG_NONFINITE | GN_FLAG_TINY;
     if (h->rescale_enabled && t > 0)
         hipLaunchKernelGGL(k_extreme_flags_ragged, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, (const double*)nullptr, 0LL,
                            (const double*)h->FA, P.sFA, P.kA, 0, (int)batch, (const int*)h->tkbuf.p, (const int*)nullptr);
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(h->h_state, h->state, (size_t)batch * sizeof(ProbState), hipMemcpyDeviceToHost, s));
-    GN_HIP(hipStreamSynchronize(s));
-    // A', cx beyond the range of plain sums of squares (gn_rescale.hpp): the problem's stage on a one-problem handle of its own,
-    // which rescales; the accessors and the first estimate are routed to it
-    bool flagged = false;
-    for (long long k = 0; k < batch; ++k) {
-        if (!(h->h_state[k].status & fl)) continue;
-        flagged = true;
-        int sJ = 0, sA = 0;
-        BatchOperands one = v.slice(k, 1);
-        one.t = v.tk[k];
-        one.tk = nullptr;
-        rc = extreme_shifts(h, one, &sJ, &sA);
+    rc = fetch_states(h, cov);
+    if (rc) return rc;
+    // A', cx beyond the range of plain sums of squares (gn_rescale.hpp): the accessors and the first estimate are routed to the
+    // rescue handle
+    if (any_nominated(h, cov)) {
+        rc = rescue_nominated(h, v, cov, false, [&](enlsip_gn_handle r, const BatchOperands& one) {
+            const int rcr = factor_one_dev(r, m, n, one.t, one.At, one.ldat, one.cx, eps_rank, nullptr);
+            if (!rcr) gn_route_acc |= r->route & (1ull << ENLSIP_GN_ROUTE_RESCALED);
+            return rcr;
+        });
         if (rc) return rc;
-        if (!sA) continue;
-        enlsip_gn_handle r = nullptr;
-        rc = next_rescue_handle(h, &r);
+        rc = clear_nominations(h, cov);
         if (rc) return rc;
-        rc = factor_one_dev(r, m, n, one.t, one.At, one.ldat, one.cx, eps_rank, nullptr);
-        if (rc) { h->err = r->err; return rc; }
-        gn_route_acc |= r->route & (1ull << ENLSIP_GN_ROUTE_RESCALED);
-        GN_HIP(hipSetDevice(h->device));
-        h->h_state[k] = r->h_state[0];
-        h->rescue_prob.push_back(k);
     }
-    if (flagged) {
-        for (long long k = 0; k < batch; ++k) h->h_state[k].status &= ~fl;
-        hipLaunchKernelGGL(k_clear_status_bits, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, h->state, fl, (int)batch,
-                           (const int*)nullptr);
-        GN_HIP(hipGetLastError());
-    }
-    if (v.hinfo || v.dinfo) {
-        std::vector<enlsip_gn_info> tmp((size_t)batch);
-        for (long long k = 0; k < batch; ++k) {
-            tmp[k] = info_of(h->h_state[k]);
-            tmp[k].rankJ2 = tmp[k].dimJ2 = 0;      // nothing about J is resident
-            if (v.hinfo) v.hinfo[k] = tmp[k];
-        }
-        if (v.dinfo) {
-            GN_HIP(hipMemcpyAsync(v.dinfo, tmp.data(), tmp.size() * sizeof(enlsip_gn_info), hipMemcpyHostToDevice, s));
-            GN_HIP(hipStreamSynchronize(s));
-        }
-    }
+    rc = publish_info(h, v, cov, true);
+    if (rc) return rc;
     h->factors_valid = true;
     h->constraints_only = true;
     h->route = gn_route_acc;
@@ -2224,26 +2249,17 @@ static int check_factored_call(enlsip_gn_handle h, const BatchOperands& v, const
     return 0;
 }
 
-// Both forms of enlsip_gn_solve_factored_batched (v: device buffers) after check_factored_call: which problems get their constraint
-// stage again, and the solve over the same halves.
+// Both forms of enlsip_gn_solve_factored_batched (v: device buffers) after check_factored_call: the solve over the same halves; each
+// half runs the constraint stage again for its problems with a refactor flag.
 static int solve_factored_core(enlsip_gn_handle h, const BatchOperands& v, const int64_t* refactor, double eps_rank, bool host_form) {
-    const long long batch = v.batch;
     auto& F = h->fb;
     if (!host_form && v.t > 0 && (v.At != F.At || v.ldat != F.ldat || v.strideAt != F.strideAt || v.cx != F.cx)) {
         h->err = "dAt, ldat, strideAt, dcx must be the buffers of the enlsip_gn_factor_constraints_batched_dev call (the slots of the "
                  "problems with a refactor flag rewritten in place)";
         return -11;
     }
-    const long long b0 = F.split > 0 ? F.split : batch;
-    h->refit.clear();
-    if (F.split > 0) h->child->refit.clear();
-    for (long long k = 0; refactor && k < batch; ++k)
-        if (refactor[k]) (k < b0 ? h : h->child)->refit.push_back((int)(k < b0 ? k : k - b0));
     h->chunk0 = 0;
-    h->reuse_once = true;
-    const int rc = solve_launchable(h, v, eps_rank, -1, -1);
-    h->reuse_once = false;
-    if (F.split > 0) h->child->reuse_once = false;
+    const int rc = solve_launchable(h, v, {SolveMode::Factored, refactor, false, -1, -1, eps_rank});
     F.valid = false;
     if (rc) return rc;
     h->constraint_refactored = h->cstage_problems + (h->split > 0 ? h->child->cstage_problems : 0);
@@ -2305,13 +2321,6 @@ int enlsip_gn_factor_constraints_batched(enlsip_gn_handle h, int64_t batch, int6
     GN_CATCH(h)
 }
 
-// the refactor flags decide whether A', cx are looked at at all
-static bool any_flag(const int64_t* refactor, int64_t batch) {
-    for (int64_t k = 0; refactor && k < batch; ++k)
-        if (refactor[k]) return true;
-    return false;
-}
-
 int enlsip_gn_solve_factored_batched(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t t_max, const int64_t* t,
                                      const int64_t* refactor, const double* J, int64_t ldj, int64_t strideJ, const double* rx,
                                      const double* At, int64_t ldat, int64_t strideAt, const double* cx, double eps_rank, double* p,
@@ -2328,7 +2337,7 @@ int enlsip_gn_solve_factored_batched(enlsip_gn_handle h, int64_t batch, int64_t 
     rc = check_factored_call(h, shape, refactor, true);
     if (rc) return rc;
     return solve_host(h, {batch, m, n, t_max, J, ldj, strideJ, rx, At, ldat, strideAt, cx, p, b, d, nullptr, (long long*)jpvtA,
-                          (long long*)jpvtL, (long long*)jpvtJ2, info, tk.data()}, eps_rank, -1, -1, true, true, refactor);
+                          (long long*)jpvtL, (long long*)jpvtJ2, info, tk.data()}, {SolveMode::Factored, refactor, false, -1, -1, eps_rank});
     GN_CATCH(h)
 }
 
@@ -2403,31 +2412,24 @@ static int solve_changed_core(enlsip_gn_handle h, const BatchOperands& v, const 
     const long long split = h->split;
     const enlsip_gn_handle c = split > 0 ? h->child : nullptr;
     const long long b0 = c ? split : batch;
-    h->refit.clear();
-    if (c) c->refit.clear();
-    for (long long k = 0; k < batch; ++k)
-        if (changed[k]) (k < b0 ? h : c)->refit.push_back((int)(k < b0 ? k : k - b0));
+    const SolveMode mode{SolveMode::Changed, changed, false, -1, -1, eps_rank};
     h->fb.valid = false;
-    const bool part0 = !h->refit.empty(), part1 = c && !c->refit.empty();
+    const bool part0 = any_flag(changed, b0), part1 = c && any_flag(changed + b0, batch - b0);     // the halves that run
     if (!part0) h->cstage_problems = h->jstage_problems = 0;
     if (c && !part1) c->cstage_problems = c->jstage_problems = 0;
     int rc = 0;
     if (part0 && part1) {
-        h->changed_once = c->changed_once = true;
         rc = on_both_halves(h, batch, b0, [&](enlsip_gn_handle hh, long long k0, long long cnt) {
-            return solve_dev(hh, v.slice(k0, cnt), eps_rank, -1, -1);
+            return solve_dev(hh, v.slice(k0, cnt), mode.part(k0));
         });
-        h->changed_once = c->changed_once = false;
     } else if (part0) {
-        h->changed_once = true;
-        rc = solve_dev(h, v.slice(0, b0), eps_rank, -1, -1);
+        rc = solve_dev(h, v.slice(0, b0), mode);
         if (!rc && c) h->route |= (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
     } else if (part1) {
         GN_HIP(hipSetDevice(h->device));
         rc = fork_after(h, c->stream);
         if (rc) return rc;
-        c->changed_once = true;
-        rc = solve_dev(c, v.slice(b0, batch - b0), eps_rank, -1, -1);
+        rc = solve_dev(c, v.slice(b0, batch - b0), mode.part(b0));
         if (rc) h->err = c->err;
         else h->route = c->route | (1ull << ENLSIP_GN_ROUTE_PIPELINE_SPLIT);
         GN_HIP(hipSetDevice(h->device));
@@ -2564,7 +2566,7 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
                     int64_t dimA_override, int64_t dimJ2_override, double* p, double* b, double* d,
                     enlsip_gn_info* info, int64_t* jpvtA, int64_t* jpvtL, int64_t* jpvtJ2) {
     return solve_host(h, {1, m, n, t, J, ldj, ldj * n, rx, At, ldat, ldat * t, cx, p, b, d, nullptr, (long long*)jpvtA,
-                          (long long*)jpvtL, (long long*)jpvtJ2, info}, eps_rank, dimA_override, dimJ2_override);
+                          (long long*)jpvtL, (long long*)jpvtJ2, info}, {SolveMode::Fresh, nullptr, false, dimA_override, dimJ2_override, eps_rank});
 }
 
 }  // extern "C"

@@ -77,6 +77,28 @@ struct BatchOperands {
     BatchOperands inputs() const { return {batch, m, n, t, J, ldj, strideJ, rx, At, ldat, strideAt, cx}; }
 };
 
+// What kind of solve one pass through the solve driver is (solve_host -> solve_chunked -> solve_launchable -> solve_dev), by value:
+// nothing about it is kept on a handle.
+struct SolveMode {
+    enum Kind { Fresh, Factored, Changed } kind = Fresh;
+    //   Fresh:    constraint stage and Jacobian side for every problem
+    //   Factored: the constraint stage is resident; it is run again for the flagged problems, the Jacobian side for all
+    //   Changed:  flagged problems only, both sides, into their own slots
+    const int64_t* flags = nullptr;   // whole-batch refactor / changed flags (host), sliced with the operands; NULL: none
+    bool upper_input = false;         // J is one gathered triangle (one-rank TSQR combine): upper triangular, no CAQR needed
+    long long dimA_ov = -1, dimJ2_ov = -1;
+    double eps_rank = 0.0;
+
+    // the mode of the problems from k0 on: goes with BatchOperands::slice(k0, count)
+    SolveMode part(long long k0) const {
+        SolveMode s = *this;
+        if (flags) s.flags = flags + k0;
+        return s;
+    }
+    // a rescaled problem on its rescue handle: solved whole, with the caller's truncation dimensions and threshold
+    SolveMode fresh() const { return {Fresh, nullptr, false, dimA_ov, dimJ2_ov, eps_rank}; }
+};
+
 }  // namespace gn
 
 struct enlsip_gn_context {
@@ -95,8 +117,6 @@ struct enlsip_gn_context {
         const double* qb = nullptr; long long sQb = 0;
         bool valid = false;
     } cdist;
-    bool upper_once = false;         // the next solve_dev gets an upper-triangular J (one gathered triangle of the TSQR combine stage): no CAQR needed
-    bool reuse_once = false;         // the next solve_dev skips the constraint stage (enlsip_gn_solve_factored)
     bool trace = false;              // ENLSIP_GN_TRACE=1: stage names on stderr with a stream synchronisation after each (fault hunting)
     bool constraints_only = false;   // resident: F_A, F_L11 only (enlsip_gn_factor_constraints); everything about J is absent
     double eps_rank = 0.0;
@@ -163,9 +183,8 @@ struct enlsip_gn_context {
     // Batched constraint stage (enlsip_gn_factor_constraints_batched*) and the solve that goes on with it
     // (enlsip_gn_solve_factored_batched*).  On the handle the caller holds: what the constraint call was made with, so that the solve
     // can tell whether it follows it — shape, pipeline split, each problem's t, the input buffers (device form: the caller's; host
-    // form: the staging area).  On every handle that runs a part (parent, pipeline child): the problems of its part whose
-    // constraint stage the next solve_dev runs again (indices in its part; device copy in plist_buf), and the number of problems
-    // the constraint kernels of its last call were launched over.
+    // form: the staging area).  On every handle that runs a part (parent, pipeline child): the number of problems the constraint
+    // kernels of its last call were launched over.
     struct {
         bool valid = false, host = false;
         long long batch = 0, m = 0, n = 0, t = 0, split = 0;
@@ -173,15 +192,18 @@ struct enlsip_gn_context {
         const double* cx = nullptr;
         std::vector<int> tk;
     } fb;
+    // The flagged problems of the part a Factored / Changed solve_dev is running on this handle (indices in its part), built by
+    // that solve_dev from its SolveMode's flags, and the device copy of the list.  Nothing fills them on behalf of a later call.
     std::vector<int> refit;
     gn::DevBuf plist_buf;
     gn::DevBuf info_stage;              // a changed-problems solve: the listed problems' info records in list order, before their scatter
     long long cstage_problems = 0;
-    // Changed-problems solve (enlsip_gn_solve_changed_batched*): the next solve_dev on this handle (parent, pipeline child) redoes the
-    // problems of `refit` only, constraint stage AND Jacobian side, from the resident J, rx; while it runs, run_plist / run_nlist are
-    // the device list every Jacobian-side launch is sized by (NULL outside of it: the whole part).  jstage_problems counts the
-    // problems the Jacobian-side kernels of the last solve_dev were launched over (enlsip_gn_get_jacobian_resolved sums the halves).
-    bool changed_once = false;
+    // Changed-problems solve (enlsip_gn_solve_changed_batched*): solve_dev redoes the problems of `refit` only, constraint stage AND
+    // Jacobian side, from the resident J, rx.  run_plist / run_nlist are the launch set of the solve IN PROGRESS: the device list
+    // every Jacobian-side launch is sized by (the launch helpers read it through launch_count).  They are set in exactly one place,
+    // the constraint step of a Changed solve_dev, and cleared by that solve_dev's scope guard: NULL outside of it (the whole part).
+    // jstage_problems counts the problems the Jacobian-side kernels of the last solve_dev were launched over
+    // (enlsip_gn_get_jacobian_resolved sums the halves).
     const int* run_plist = nullptr;
     long long run_nlist = 0;
     long long jstage_problems = 0;

@@ -227,9 +227,8 @@ int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank
         rc = grow(h, h->out_stage, ((size_t)n2 * 8 + sizeof(enlsip_gn_info)) + 1024);
         if (rc) return rc;
         long long* djJ = (long long*)h->out_stage.p;
-        h->sub->upper_once = (G == 1);      // one rank: the stacked matrix is that rank's triangle
         const BatchOperands v{1, ms, n2, 0, Jst, ms, 0, rxs, nullptr, 1, 0, nullptr, dp2, nullptr, dd, nullptr, nullptr, nullptr, djJ};
-        rc = solve_dev(h->sub, v, eps_rank, -1, -1);
+        rc = solve_dev(h->sub, v, {SolveMode::Fresh, nullptr, G == 1, -1, -1, eps_rank});      // one rank: the stacked matrix is that rank's triangle
         if (rc) { h->err = std::string("tsqr_combine/sub: ") + h->sub->err; return rc; }
         sinfo = info_of(h->sub->h_state[0]);       // its rankJ2, dimJ2 and status
         if (jpvtJ2) GN_HIP(hipMemcpyAsync(jpvtJ2, djJ, (size_t)n2 * 8, hipMemcpyDeviceToHost, s));
