@@ -1355,8 +1355,8 @@ static int rescale_in_place(enlsip_gn_handle h, const BatchOperands& v, const So
         GN_HIP(hipGetLastError());
         h->h_state[0].status &= ~1;
     }
-    rc = sJ ? jacobian_side(h, v, mode, cov, t_min, upper_in, h->rs_J, v.m, v.m * v.n, h->rs_rx, sJ)
-            : jacobian_side(h, v, mode, cov, t_min, upper_in, v.J, v.ldj, v.strideJ, v.rx, 0);
+    rc = sJ ? jacobian_side(h, v, mode, cov, t_min, upper_in, h->rs_J, v.m, v.m * v.n, h->rs_rx, sJ + mode.abs_shift)
+            : jacobian_side(h, v, mode, cov, t_min, upper_in, v.J, v.ldj, v.strideJ, v.rx, mode.abs_shift);
     if (rc) return rc;
     if (sJ) {
         rc = unscale_jacobian_side(h, v.d);
@@ -1485,7 +1485,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, SolveMode mode)
     mark(h, 1);
     GN_TRACE(h, "constraint stage done");
     // 2-4. Jacobian side
-    rc = jacobian_side(h, v, mode, cov, t_min, upper_in, v.J, v.ldj, v.strideJ, v.rx, 0);
+    rc = jacobian_side(h, v, mode, cov, t_min, upper_in, v.J, v.ldj, v.strideJ, v.rx, mode.abs_shift);
     if (rc) return rc;
     if (any_nominated(h, cov)) {
         if (batch == 1 && !v.tk) rc = rescale_in_place(h, v, mode, cov, t_min, upper_in);
@@ -1639,6 +1639,7 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->info_stage.p) (void)hipFree(h->info_stage.p);
     if (h->scratch.p) (void)hipFree(h->scratch.p);
     if (h->xbuf.p) (void)hipFree(h->xbuf.p);
+    if (h->tsqr_part.p) (void)hipFree(h->tsqr_part.p);
     tsqr_drop_comm(h);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_sbinfo) (void)hipHostFree(h->h_sbinfo);

@@ -88,6 +88,7 @@ struct SolveMode {
     bool upper_input = false;         // J is one gathered triangle (one-rank TSQR combine): upper triangular, no CAQR needed
     long long dimA_ov = -1, dimJ2_ov = -1;
     double eps_rank = 0.0;
+    int abs_shift = 0;                // J, rx arrive scaled by 2^abs_shift (TSQR combine of rescaled shards): the absolute rank test follows
 
     // the mode of the problems from k0 on: goes with BatchOperands::slice(k0, count)
     SolveMode part(long long k0) const {
@@ -96,7 +97,7 @@ struct SolveMode {
         return s;
     }
     // a rescaled problem on its rescue handle: solved whole, with the caller's truncation dimensions and threshold
-    SolveMode fresh() const { return {Fresh, nullptr, false, dimA_ov, dimJ2_ov, eps_rank}; }
+    SolveMode fresh() const { return {Fresh, nullptr, false, dimA_ov, dimJ2_ov, eps_rank, abs_shift}; }
 };
 
 }  // namespace gn
@@ -211,6 +212,9 @@ struct enlsip_gn_context {
     unsigned long long route = 0;       // ENLSIP_GN_ROUTE_* bits of the last solve (enlsip_gn_get_route)
     long long chunk0 = 0;               // first problem (index in the caller's batch) of the resident chunk: batches above the launch limit run in chunks
     long long tsqr_n2 = -1;             // n2 of the last tsqr_local on this handle
+    // exponents of the last TSQR call: the resident local stage is that of the shard times 2^-tsqr_e (0: not rescaled), the
+    // combine ran on the stacked blocks times 2^-tsqr_E (the largest exponent among the ranks)
+    int tsqr_e = 0, tsqr_E = 0;
     // communicator of enlsip_gn_solve_tsqr: an RCCL communicator (created here or handed in) or the caller's all-gather
     void* tsqr_comm = nullptr;
     bool tsqr_comm_owned = false;
@@ -221,6 +225,7 @@ struct enlsip_gn_context {
     int tsqr_tags_seen = -1;            // gathered messages of the last enlsip_gn_solve_tsqr whose header carried the rank of their slot
     int tsqr_transport = 0;             // what moved the triangles in the last enlsip_gn_solve_tsqr (ENLSIP_GN_TRANSPORT_*)
     gn::DevBuf xbuf;                    // send message + G received messages
+    gn::DevBuf tsqr_part;               // per-workgroup partial sums of the TSQR stages' ordered sums of squares
     float tsqr_ms[3] = {};              // local / exchange / combine of the last enlsip_gn_solve_tsqr (profiling on)
     long long *jpvtA = nullptr, *jpvtL = nullptr, *jpvtJ = nullptr;
     gn::ProbState* state = nullptr;

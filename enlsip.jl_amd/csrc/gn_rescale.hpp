@@ -55,6 +55,61 @@ __global__ __launch_bounds__(256) void k_extreme_flags_ragged(ProbState* state, 
     extreme_flags_body<true>(state, Rt, sRt, FA, sFA, kA, n2cap, batch, tk, plist);
 }
 
+// The same nomination for the local stage of a row shard (gn_tsqr.inc).  Its R is unpivoted, so no entry of it is "the largest
+// column norm": the maximum of |x| (bit patterns, as k_amax_bits takes it) runs over the whole n2 x n2 upper triangle of R in W
+// (rows < kp) and over the whole carried column d (all m rows: its tail can be huge while z is not).  ||R[:, j]|| <= sqrt(n) amax(R)
+// keeps every plain sum of squares of the stage in range when nothing is flagged.  F_A is replicated and pivoted: its first
+// diagonal entry is looked at as k_extreme_flags does.  acc: [0] the running maximum, [1] workgroups done; the last workgroup
+// decides and leaves both words zero for the next launch.
+__global__ __launch_bounds__(256) void k_tsqr_flags(ProbState* state, const double* W, int ldw, int n, int m, const double* FA, int kA,
+                                                    int n2cap, unsigned long long* acc) {
+    const ProbState st = *state;
+    const int rankA = st.rankA, n2 = st.n2, kp = st.kp;
+    // wider than launched: redone by the caller (second attempt), nothing of it is final yet
+    const bool skip = n2 > n2cap || rankA < 0 || n2 < 0 || rankA + n2 > n || kp < 0 || kp > m || kp > n2;
+    unsigned long long mx = 0ull;
+    if (!skip) {
+        for (int c = blockIdx.x; c < n2; c += gridDim.x) {
+            const double* col = W + (size_t)(rankA + c) * ldw;
+            const int rows = c + 1 < kp ? c + 1 : kp;
+            for (int i = threadIdx.x; i < rows; i += 256) {
+                const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(col[i]));
+                mx = b > mx ? b : mx;
+            }
+        }
+        const double* d = W + (size_t)n * ldw;
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < m; i += (long long)gridDim.x * 256) {
+            const unsigned long long b = (unsigned long long)__double_as_longlong(fabs(d[i]));
+            mx = b > mx ? b : mx;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned long long o = (unsigned long long)__shfl_xor((long long)mx, off, 64);
+        mx = o > mx ? o : mx;
+    }
+    if ((threadIdx.x & 63) == 0 && mx) atomicMax(acc, mx);
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    __threadfence();
+    if (atomicAdd(acc + 1, 1ull) != (unsigned long long)gridDim.x - 1) return;
+    __threadfence();
+    const unsigned long long bits = atomicExch(acc, 0ull);
+    atomicExch(acc + 1, 0ull);
+    if (skip) return;
+    const double tiny = 0x1p-440, huge = 0x1p440;
+    int f = 0;
+    if (kA > 0) {
+        const double a = fabs(FA[0]);
+        if (!(a <= huge)) f |= GN_FLAG_NONFINITE;
+        else if (a < tiny) f |= GN_FLAG_TINY;
+    }
+    const double r = __longlong_as_double((long long)bits);
+    if (!(r <= huge)) f |= GN_FLAG_NONFINITE;             // NaN and Inf included (a NaN outranks every number as a bit pattern)
+    else if (r < tiny && kp > 0) f |= GN_FLAG_TINY;        // zero included; without a row of R there is nothing to redo
+    if (f) state->status = st.status | f;
+}
+
 __global__ __launch_bounds__(256) void k_clear_status_bits(ProbState* state, int bits, int batch, const int* plist) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx < batch) state[listed_prob(plist, idx, 0)].status &= ~bits;

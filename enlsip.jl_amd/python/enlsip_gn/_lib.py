@@ -141,6 +141,11 @@ PROTOTYPES = {
                                            C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, _dp, _ip]),
     "enlsip_gn_tsqr_combine_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
                                              C.c_void_p, _dp, C.POINTER(Info), C.c_void_p]),
+    "enlsip_gn_tsqr_local_scaled_dev": (C.c_int, [_h, _i64, _i64, _i64, C.c_void_p, _i64, C.c_void_p, C.c_void_p, _i64,
+                                                  C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, _dp, _ip, _ip]),
+    "enlsip_gn_tsqr_combine_scaled_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                    C.c_void_p, C.c_void_p, _dp, C.POINTER(Info), C.c_void_p]),
+    "enlsip_gn_tsqr_get_scale": (C.c_int, [_h, _ip, _ip]),
     "enlsip_gn_tsqr_unique_id": (C.c_int, [C.c_void_p]),
     "enlsip_gn_tsqr_init_rccl": (C.c_int, [_h, C.c_void_p, C.c_int, C.c_int]),
     "enlsip_gn_tsqr_set_comm": (C.c_int, [_h, C.c_void_p, C.c_int, C.c_int]),

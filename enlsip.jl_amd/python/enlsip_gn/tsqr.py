@@ -10,6 +10,10 @@ and costs tens of microseconds against ~1 ms of local factorisation (SURVEY §5,
 The local and combine stages are the HIP library's ``enlsip_gn_tsqr_local_dev`` /
 ``enlsip_gn_tsqr_combine_dev``; they are injectable only so that the exchange / stacking logic can be
 exercised with the ``gloo`` backend on machines without a GPU (tests/test_tsqr_host.py).
+
+Magnitudes: with ``scaled=True`` the stages are ``enlsip_gn_tsqr_local_scaled_dev`` / ``enlsip_gn_tsqr_combine_scaled_dev``: a
+shard outside the band 2^-400 .. 2^400 is factored at a power-of-two scale of its own, and its exponent and tail^2 are gathered
+next to the triangles (still one exchange step).  ``tsqr_solve_lib`` does the same inside the library.
 """
 from __future__ import annotations
 
@@ -65,13 +69,60 @@ def hip_combine_stage(solver: GNSolver, G, n, n2, dRstack, dzstack, eps_rank):
     return p, dlead, float(ct.value), info, jp
 
 
+def hip_local_stage_scaled(solver: GNSolver, m_loc, n, t, dJ, ldj, drx, dAt, dcx, dR, dz, eps_rank):
+    """enlsip_gn_tsqr_local_scaled_dev on raw device pointers; returns (n2, tail_sq, e): R, z and tail_sq are those of the shard
+    times 2^-e (tail_sq: 2^-2e)."""
+    tail = C.c_double(0.0)
+    n2 = C.c_int64(0)
+    e = C.c_int64(0)
+    v = lambda x: C.c_void_p(x) if x else None
+    solver._chk(solver._lib.enlsip_gn_tsqr_local_scaled_dev(solver._h, m_loc, n, t, v(dJ), ldj, v(drx), v(dAt), max(n, 1),
+                                                            v(dcx), eps_rank, v(dR), v(dz), C.byref(tail), C.byref(n2),
+                                                            C.byref(e)))
+    return int(n2.value), float(tail.value), int(e.value)
+
+
+def hip_combine_stage_scaled(solver: GNSolver, G, n, n2, dRstack, dzstack, e, tail_sq, eps_rank):
+    """enlsip_gn_tsqr_combine_scaled_dev: ``e`` / ``tail_sq`` are the G ranks' exponents and tail^2 (each at its rank's scale);
+    returns (p, dlead, d_norm, info, jpvtJ2) of the unscaled problem."""
+    p = np.zeros(n)
+    dlead = np.zeros(n2)
+    jp = np.zeros(n2, dtype=np.int64)
+    dn = C.c_double(0.0)
+    info = L.Info()
+    ee = np.ascontiguousarray(e, dtype=np.int64)
+    tt = np.ascontiguousarray(tail_sq, dtype=np.float64)
+    assert ee.shape == (G,) and tt.shape == (G,)
+    v = lambda x: C.c_void_p(x) if x else None
+    solver._chk(solver._lib.enlsip_gn_tsqr_combine_scaled_dev(solver._h, G, n2, v(dRstack), v(dzstack),
+                                                              ee.ctypes.data_as(C.c_void_p), tt.ctypes.data_as(C.c_void_p),
+                                                              eps_rank, p.ctypes.data_as(C.c_void_p),
+                                                              dlead.ctypes.data_as(C.c_void_p), C.byref(dn), C.byref(info),
+                                                              jp.ctypes.data_as(C.c_void_p)))
+    return p, dlead, float(dn.value), info, jp
+
+
+def tsqr_scale(solver: GNSolver):
+    """(e_local, e_common) of the handle's last TSQR call (enlsip_gn_tsqr_get_scale); (0, 0) for inputs inside the band."""
+    a, b = C.c_int64(0), C.c_int64(0)
+    solver._chk(solver._lib.enlsip_gn_tsqr_get_scale(solver._h, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
 def tsqr_solve(solver: Optional[GNSolver], J_loc, rx_loc, At, cx, eps_rank: float = SQRT_EPS, group=None,
-               local_stage: Callable = None, combine_stage: Callable = None) -> TSQRResult:
+               local_stage: Callable = None, combine_stage: Callable = None, scaled: bool = False) -> TSQRResult:
     """Collective over ``group``.  ``J_loc``: torch tensor (n, m_loc) C-order == column-major
     m_loc x n on this rank's device; ``rx_loc`` (m_loc); ``At`` (t, n) C-order == column-major n x t
-    (replicated); ``cx`` (t).  Every rank returns the same result."""
+    (replicated); ``cx`` (t).  Every rank returns the same result.
+
+    ``scaled``: the stages that carry a per-rank exponent.  An injected ``local_stage`` then returns ``(n2, tail_sq, e)`` and an
+    injected ``combine_stage`` is called as ``combine_stage(G, n, n2, Rstack, zstack, e, tail_sq, eps_rank)`` with the gathered
+    exponents (int64, G) and tail^2 (G, each at its rank's scale) and returns ``d_norm`` where the unscaled one returns its part
+    of the sum of squares."""
     import torch
     import torch.distributed as dist
+    if scaled:
+        return _tsqr_solve_scaled(solver, J_loc, rx_loc, At, cx, eps_rank, group, local_stage, combine_stage)
 
     G = dist.get_world_size(group) if dist.is_initialized() else 1
     n, m_loc = J_loc.shape
@@ -118,6 +169,65 @@ def tsqr_solve(solver: Optional[GNSolver], J_loc, rx_loc, At, cx, eps_rank: floa
         p, dlead, ctail, rankA, rankJ2, code, jp = combine_stage(G, n, n2, Rstack, zstack, eps_rank)
     d_norm = float(np.sqrt(float(tails.item()) + ctail + float(np.dot(dlead, dlead))))
     return TSQRResult(p=p, dlead=dlead, d_norm=d_norm, rankA=rankA, rankJ2=rankJ2, code=code, jpvtJ2=jp, n2=n2)
+
+
+def _tsqr_solve_scaled(solver, J_loc, rx_loc, At, cx, eps_rank, group, local_stage, combine_stage) -> TSQRResult:
+    """tsqr_solve(scaled=True): the same exchange step, with (e_g, tail_g^2) gathered instead of the tails summed — a sum of
+    squares taken at different scales means nothing, and one taken at the largest scale may overflow."""
+    import torch
+    import torch.distributed as dist
+
+    G = dist.get_world_size(group) if dist.is_initialized() else 1
+    n, m_loc = J_loc.shape
+    t = 0 if At is None else At.shape[0]
+    dev = J_loc.device
+    R = torch.empty((n * n,), dtype=torch.float64, device=dev)
+    z = torch.empty((n,), dtype=torch.float64, device=dev)
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()
+    if local_stage is None:
+        n2, tail, e = hip_local_stage_scaled(solver, m_loc, n, t, J_loc.data_ptr(), m_loc, rx_loc.data_ptr(),
+                                             At.data_ptr() if t else 0, cx.data_ptr() if t else 0, R.data_ptr(), z.data_ptr(),
+                                             eps_rank)
+    else:
+        n2, tail, e = local_stage(J_loc, rx_loc, At, cx, R, z, eps_rank)
+    # ---- the one exchange step: triangles, vectors and (e_g, tail_g^2), the exponent as an exact small double --------------
+    Rstack = torch.empty((G * n2 * n2,), dtype=torch.float64, device=dev)
+    zstack = torch.empty((G * n2,), dtype=torch.float64, device=dev)
+    mine = torch.tensor([float(e), tail], dtype=torch.float64)
+    every = torch.empty((2 * G,), dtype=torch.float64)
+    if G > 1:
+        host_path = dev.type == "cuda" and dist.get_backend(group) != "nccl"      # rehearsal: several ranks on one GPU under gloo
+        if host_path:
+            Rc, zc = torch.empty(Rstack.shape, dtype=torch.float64), torch.empty(zstack.shape, dtype=torch.float64)
+            dist.all_gather_into_tensor(Rc, R[: n2 * n2].cpu().contiguous(), group=group)
+            dist.all_gather_into_tensor(zc, z[:n2].cpu().contiguous(), group=group)
+            dist.all_gather_into_tensor(every, mine, group=group)
+            Rstack.copy_(Rc); zstack.copy_(zc)
+        else:
+            dist.all_gather_into_tensor(Rstack, R[: n2 * n2].contiguous(), group=group)
+            dist.all_gather_into_tensor(zstack, z[:n2].contiguous(), group=group)
+            if dev.type == "cuda":
+                ev = every.to(dev)
+                dist.all_gather_into_tensor(ev, mine.to(dev), group=group)
+                every = ev.cpu()
+            else:
+                dist.all_gather_into_tensor(every, mine, group=group)
+    else:
+        Rstack.copy_(R[: n2 * n2])
+        zstack.copy_(z[:n2])
+        every.copy_(mine)
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()
+    pairs = every.numpy().reshape(G, 2)
+    es, tails = pairs[:, 0].astype(np.int64), pairs[:, 1].copy()
+    if combine_stage is None:
+        p, dlead, d_norm, info, jp = hip_combine_stage_scaled(solver, G, n, n2, Rstack.data_ptr(), zstack.data_ptr(), es, tails,
+                                                              eps_rank)
+        rankA, rankJ2, code = int(info.rankA), int(info.rankJ2), int(info.code)
+    else:
+        p, dlead, d_norm, rankA, rankJ2, code, jp = combine_stage(G, n, n2, Rstack, zstack, es, tails, eps_rank)
+    return TSQRResult(p=p, dlead=dlead, d_norm=float(d_norm), rankA=rankA, rankJ2=rankJ2, code=code, jpvtJ2=jp, n2=n2)
 
 
 # ---- the collective inside the library (enlsip_gn_solve_tsqr) --------------------------------------------------------------
@@ -214,40 +324,63 @@ def tsqr_stage_ms(solver: GNSolver):
     return {"local": float(arr[0]), "exchange": float(arr[1]), "combine": float(arr[2])}
 
 
-def tsqr_solve_shards_dev(solver: GNSolver, Jd, rxd, Atd, cxd, G: int, eps_rank: float = SQRT_EPS) -> TSQRResult:
+def tsqr_solve_shards_dev(solver: GNSolver, Jd, rxd, Atd, cxd, G: int, eps_rank: float = SQRT_EPS, scaled: bool = False,
+                          row_blocks=None) -> TSQRResult:
     """Single-process rehearsal on ONE GPU with the data already in HBM: ``Jd`` (n, m) C-order == column-major m x n,
     ``rxd`` (m), ``Atd`` (t, n) C-order == column-major n x t or None, ``cxd`` (t) or None.  The G row blocks are factored one after
     the other on the same handle and stacked exactly as the all-gather would (the handle's resident F_A / p1 come from the
-    last local stage, identical on every 'rank')."""
+    last local stage, identical on every 'rank').  ``row_blocks``: the G block heights (default: ``row_range``).  ``scaled``: the
+    stages that carry each block's exponent (magnitudes outside 2^-400 .. 2^400)."""
     import torch
     n, m = Jd.shape
     t = 0 if Atd is None else Atd.shape[0]
     dev = Jd.device
+    if row_blocks is None:
+        edges = [row_range(m, G, g) for g in range(G)]
+    else:
+        if len(row_blocks) != G or sum(row_blocks) != m or min(row_blocks) < 1:
+            raise ValueError("row_blocks must be G positive heights that add up to m")
+        ends = np.cumsum(row_blocks)
+        edges = [(int(b - a), int(b)) for a, b in zip(row_blocks, ends)]
     Rs, zs, tail_total, n2 = [], [], 0.0, None
+    es, tails = [], []
     for g in range(G):
-        lo, hi = row_range(m, G, g)
+        lo, hi = edges[g]
         Jl = Jd[:, lo:hi].contiguous()                 # column-major (hi - lo) x n
         rl = rxd[lo:hi].contiguous()
         R = torch.empty((n * n,), dtype=torch.float64, device=dev)      # k_tsqr_extract writes all n2 * n2 / n2 entries it hands back
         z = torch.empty((n,), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)                    # the library runs on its own stream
-        n2, tail = hip_local_stage(solver, hi - lo, n, t, Jl.data_ptr(), hi - lo, rl.data_ptr(),
-                                   Atd.data_ptr() if t else 0, cxd.data_ptr() if t else 0, R.data_ptr(), z.data_ptr(),
-                                   eps_rank)
+        if scaled:
+            n2, tail, e = hip_local_stage_scaled(solver, hi - lo, n, t, Jl.data_ptr(), hi - lo, rl.data_ptr(),
+                                                 Atd.data_ptr() if t else 0, cxd.data_ptr() if t else 0, R.data_ptr(),
+                                                 z.data_ptr(), eps_rank)
+            es.append(e)
+            tails.append(tail)
+        else:
+            n2, tail = hip_local_stage(solver, hi - lo, n, t, Jl.data_ptr(), hi - lo, rl.data_ptr(),
+                                       Atd.data_ptr() if t else 0, cxd.data_ptr() if t else 0, R.data_ptr(), z.data_ptr(),
+                                       eps_rank)
+            tail_total += tail
         Rs.append(R[: n2 * n2].clone())
         zs.append(z[:n2].clone())
-        tail_total += tail
         del Jl, rl
     Rstack = torch.cat(Rs).contiguous()
     zstack = torch.cat(zs).contiguous()
     torch.cuda.synchronize(dev)
+    if scaled:
+        p, dlead, d_norm, info, jp = hip_combine_stage_scaled(solver, G, n, n2, Rstack.data_ptr(), zstack.data_ptr(), es, tails,
+                                                              eps_rank)
+        return TSQRResult(p=p, dlead=dlead, d_norm=d_norm, rankA=int(info.rankA), rankJ2=int(info.rankJ2),
+                          code=int(info.code), jpvtJ2=jp, n2=n2)
     p, dlead, ctail, info, jp = hip_combine_stage(solver, G, n, n2, Rstack.data_ptr(), zstack.data_ptr(), eps_rank)
     d_norm = float(np.sqrt(tail_total + ctail + float(np.dot(dlead, dlead))))
     return TSQRResult(p=p, dlead=dlead, d_norm=d_norm, rankA=int(info.rankA), rankJ2=int(info.rankJ2),
                       code=int(info.code), jpvtJ2=jp, n2=n2)
 
 
-def tsqr_solve_shards(solver: GNSolver, J, rx, A_active, cx, G: int, eps_rank: float = SQRT_EPS) -> TSQRResult:
+def tsqr_solve_shards(solver: GNSolver, J, rx, A_active, cx, G: int, eps_rank: float = SQRT_EPS, scaled: bool = False,
+                      row_blocks=None) -> TSQRResult:
     """Same, host arrays in: ``J`` (m, n), ``rx`` (m), ``A_active`` (t, n), ``cx`` (t)."""
     import torch
     t = A_active.shape[0]
@@ -256,4 +389,4 @@ def tsqr_solve_shards(solver: GNSolver, J, rx, A_active, cx, G: int, eps_rank: f
     rxd = torch.tensor(np.asarray(rx), dtype=torch.float64, device=dev)
     Atd = torch.tensor(np.ascontiguousarray(A_active), dtype=torch.float64, device=dev) if t else None
     cxd = torch.tensor(np.asarray(cx), dtype=torch.float64, device=dev) if t else None
-    return tsqr_solve_shards_dev(solver, Jd, rxd, Atd, cxd, G, eps_rank)
+    return tsqr_solve_shards_dev(solver, Jd, rxd, Atd, cxd, G, eps_rank, scaled=scaled, row_blocks=row_blocks)

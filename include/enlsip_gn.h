@@ -48,8 +48,11 @@
  *     the band 2^-400 .. 2^400 is solved again on copies scaled by a power of two, with the resident factors and the outputs scaled
  *     back: ranks, pivots, p, b, d and every accessor are those of the caller's data, as LAPACK would return
  *     them.  The range covered therefore starts at the band edge: inside the band plain sums of squares hold for every shape the
- *     library takes; beyond it nothing is left to the plain kernels.  NOT covered: the row shards of the
- *     TSQR entry points (all shards of one matrix would have to agree on one scale before their local stages).
+ *     library takes; beyond it nothing is left to the plain kernels.  The row shards of enlsip_gn_solve_tsqr and of
+ *     enlsip_gn_tsqr_local_scaled_dev / _combine_scaled_dev are covered in the same way, shard by shard: the local result is
+ *     nominated on the largest |entry| of its (unpivoted) R and of its carried column, each rank scales ITS shard by a power of two
+ *     of its own, the exponent travels with the triangle and the combine stage brings the blocks to one scale.
+ *     Only the older stage pair enlsip_gn_tsqr_local_dev / _combine_dev, whose arguments cannot carry an exponent, stays plain.
  */
 #ifndef ENLSIP_GN_H
 #define ENLSIP_GN_H
@@ -581,6 +584,10 @@ int enlsip_gn_get_newton_stage_ms(enlsip_gn_handle h, float* ms);
  *          (n2 = n - rankA <= n is only known afterwards and is returned in *n2_out)
  *   dzloc  (Q_loc' d_loc)[1:n2]             (n doubles provided)
  *   tail_sq  ||(Q_loc' d_loc)[n2+1:]||^2    (host)
+ *
+ * Magnitudes: this pair computes plainly on the caller's data and is OUTSIDE the magnitude contract above — a J of magnitude 2^600
+ * comes back with rankJ2 = 0 or not finite.  Its arguments cannot carry a shard's exponent; use enlsip_gn_tsqr_local_scaled_dev /
+ * enlsip_gn_tsqr_combine_scaled_dev (below) or enlsip_gn_solve_tsqr where the inputs may leave the band 2^-400 .. 2^400.
  */
 int enlsip_gn_tsqr_local_dev(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t,
                              const double* dJ, int64_t ldj, const double* drx,
@@ -600,6 +607,31 @@ int enlsip_gn_tsqr_combine_dev(enlsip_gn_handle h, int64_t G, int64_t n2,
                                const double* dRstack, const double* dzstack, double eps_rank,
                                double* p, double* dlead, double* comb_tail_sq,
                                enlsip_gn_info* info, int64_t* jpvtJ2);
+/*
+ * The two stages with the magnitude contract of enlsip_gn_solve.  A shard whose local result is nominated (largest |entry| of its R
+ * or of its carried column above 2^440, not finite, or below 2^-440) and whose J, rx (A', cx) lie outside the band is factored
+ * again on copies scaled by a power of two chosen by this rank alone; *e_out is the exponent (0: not rescaled):
+ *   dRloc, dzloc, tail_sq are those of the shard times 2^-e (tail_sq times 2^-2e).
+ * J and rx share the exponent: it brings the larger of the two near 1, or both to the two sides of 1 when they lie more than 2^400
+ * apart, so that tail_sq stays a number.  A', cx are replicated: every rank reaches the same rankA and n2.
+ * The combine takes every rank's exponent e[g] and tail_sq[g] (HOST arrays of G entries, tail_sq[g] at rank g's scale) beside the
+ * gathered triangles, brings block g to the common scale 2^-max(e) (a block more than 2^1000 below the largest becomes zeros),
+ * and returns d_norm = ||d||_2 over all ranks instead of a partial sum of squares, so that the caller never adds squares that
+ * may overflow.  p, dlead (n2), d_norm, info, jpvtJ2 are those of the caller's data.
+ */
+int enlsip_gn_tsqr_local_scaled_dev(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t,
+                                    const double* dJ, int64_t ldj, const double* drx,
+                                    const double* dAt, int64_t ldat, const double* dcx, double eps_rank,
+                                    double* dRloc, double* dzloc, double* tail_sq, int64_t* n2_out, int64_t* e_out);
+int enlsip_gn_tsqr_combine_scaled_dev(enlsip_gn_handle h, int64_t G, int64_t n2,
+                                      const double* dRstack, const double* dzstack,
+                                      const int64_t* e, const double* tail_sq, double eps_rank,
+                                      double* p, double* dlead, double* d_norm,
+                                      enlsip_gn_info* info, int64_t* jpvtJ2);
+/* Exponents of the last TSQR call on the handle (either stage pair, or enlsip_gn_solve_tsqr): *e_local = this rank's shard was
+ * factored times 2^-e_local, *e_common = the combine ran at 2^-e_common (the largest exponent among the ranks).  Both 0 for
+ * inputs inside the band; then ENLSIP_GN_ROUTE_RESCALED is clear in enlsip_gn_get_route, otherwise set. */
+int enlsip_gn_tsqr_get_scale(enlsip_gn_handle h, int64_t* e_local, int64_t* e_common);
 
 /* ---- the same, as ONE collective call (every rank of the communicator calls it with its row block) -------------------------
  *
@@ -616,7 +648,8 @@ int enlsip_gn_tsqr_combine_dev(enlsip_gn_handle h, int64_t G, int64_t n2,
  *
  * enlsip_gn_solve_tsqr: rank g passes its m_loc rows of J and rx (device pointers; the row blocks may have different heights)
  * and the replicated At, cx.  One message per rank travels: the packed upper triangle of the local R (8 n2 (n2 + 1) / 2 bytes:
- * 4.2 MB at n2 = 1024), z = (Q_loc' d_loc)[1:n2], the squared norm of the local tail and the sender's n2; its length depends on n
+ * 4.2 MB at n2 = 1024), z = (Q_loc' d_loc)[1:n2], the squared norm of the local tail, the sender's n2 and the power of two its
+ * shard was scaled by (0 inside the band: see "Magnitudes" above); its length depends on n
  * alone, so the ranks' counts agree even if their n2 do not — that case (the ranks see different constraint ranks) returns -13.
  * A rank that fails BEFORE the exchange (bad arguments, out of memory, a HIP error in its local stage) leaves its peers waiting
  * in the all-gather: such a failure is fatal for the communicator.  After a failed enlsip_gn_tsqr_init_rccl the handle has no
