@@ -29,6 +29,7 @@
 #include "gn_kernels_lagrange_batched.hpp"
 #include "gn_kernels_resolve_batched.hpp"
 #include "gn_kernels_subspace_batched.hpp"
+#include "gn_kernels_deletion_batched.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_newton_batched.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
@@ -1630,6 +1631,8 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->ssb_req.p) (void)hipFree(h->ssb_req.p);
     if (h->ssb_io.p) (void)hipFree(h->ssb_io.p);
     if (h->h_ssb) (void)hipHostFree(h->h_ssb);
+    if (h->del_scr.p) (void)hipFree(h->del_scr.p);
+    if (h->h_del) (void)hipHostFree(h->h_del);
     if (h->h_nwflag) (void)hipHostFree(h->h_nwflag);
     for (hipEvent_t e : h->nwb_ev)
         if (e) (void)hipEventDestroy(e);
@@ -2578,5 +2581,6 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_lagrange_batched.inc"
 #include "gn_resolve_batched.inc"
 #include "gn_subspace_batched.inc"
+#include "gn_deletion_batched.inc"
 #include "gn_newton.inc"
 #include "gn_newton_batched.inc"

@@ -260,6 +260,12 @@ struct enlsip_gn_context {
     void* h_ssb = nullptr;
     size_t h_ssb_cap = 0;
     int subspace_form = -1;
+    // batched deletion test and working-set edit (gn_deletion_batched.inc): t / q / take / s of one call on the device and in pinned
+    // memory, and the form of the last call; nothing of the resident state
+    gn::DevBuf del_scr;
+    void* h_del = nullptr;
+    size_t h_del_cap = 0;
+    int deletion_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

@@ -667,6 +667,64 @@ function subspace_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""    check_constraint_deletion_hip(q, λ, scaling, diag_scale, grad_res) -> s
+
+`check_constraint_deletion` (src/enlsip_functions.jl:574-603) on host data through the library's host entry point (no handle, no
+GPU): the routine the batched call below runs on the device.  `t = length(λ)`; 0 = no constraint is deleted."""
+function check_constraint_deletion_hip(q::Integer, λ::Vector{Float64}, scaling::Bool, diag_scale::Vector{Float64}, grad_res::Float64)
+    t = length(λ)
+    length(diag_scale) >= t || error("diag_scale needs one entry per multiplier")
+    s = Ref{Int64}(0)
+    rc = GC.@preserve λ diag_scale ccall((:enlsip_gn_check_constraint_deletion, LIB), Cint,
+        (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Float64, Ref{Int64}), q, t, λ, diag_scale, Cint(scaling), grad_res, s)
+    rc == 0 || error("enlsip_gn_check_constraint_deletion returned $rc")
+    return Int(s[])
+end
+
+"""    delete_constraints_batched_dev_hip(h, B, n, t_max, t, q, take, scaling, dλ, ddiag_scale, dgrad_res, dAt, ldat, strideAt, dcx,
+                                       dsaved) -> s
+
+The deletion test (src/enlsip_functions.jl:574-603) of every taken problem on DEVICE buffers and, where it names row `s[k]`, its
+removal from `C.A'`, `C.cx`, `C.diag_scale` and `λ` in place (:708-719, :748-756, :776-785), the removed record going to `dsaved`
+(n + 3 per problem, `C_NULL` when no undo follows).  `t`, `q` and `take` (`nothing`: all) are host arrays; `dgrad_res == C_NULL` is
+`grad_res = 0.0`, the second-order test (:747 / :775).  `s` is 1-based, 0 = nothing; the caller decrements `t` and edits `W`."""
+function delete_constraints_batched_dev_hip(h::Handle, B::Integer, n::Integer, t_max::Integer, t::Vector{Int64}, q::Vector{Int64},
+                                            take::Union{Nothing,Vector{Int64}}, scaling::Bool, dλ::Ptr{Float64},
+                                            ddiag_scale::Ptr{Float64}, dgrad_res::Ptr{Float64}, dAt::Ptr{Float64}, ldat::Integer,
+                                            strideAt::Integer, dcx::Ptr{Float64}, dsaved::Ptr{Float64})
+    (length(t) == B && length(q) == B && (take === nothing || length(take) == B)) || error("t, q and take need B entries")
+    s = zeros(Int64, B)
+    tk = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    GC.@preserve t q take s check(h, ccall((:enlsip_gn_delete_constraints_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        h.ptr, B, n, t_max, t, q, tk, Cint(scaling), dλ, ddiag_scale, dgrad_res, dAt, ldat, strideAt, dcx, dsaved, s))
+    return s
+end
+
+"""    restore_constraints_batched_dev_hip(h, B, n, t_max, t, s, dλ, ddiag_scale, dAt, ldat, strideAt, dcx, dsaved)
+
+The undo of a first-order deletion (src/enlsip_functions.jl:731-739) for the problems with `s[k] != 0`, in place on DEVICE buffers:
+the exact inverse of `delete_constraints_batched_dev_hip`, `t[k]` being the count after the deletion.  The feasibility rule
+(:728-729) stays with the caller."""
+function restore_constraints_batched_dev_hip(h::Handle, B::Integer, n::Integer, t_max::Integer, t::Vector{Int64}, s::Vector{Int64},
+                                             dλ::Ptr{Float64}, ddiag_scale::Ptr{Float64}, dAt::Ptr{Float64}, ldat::Integer,
+                                             strideAt::Integer, dcx::Ptr{Float64}, dsaved::Ptr{Float64})
+    (length(t) == B && length(s) == B) || error("t and s need B entries")
+    GC.@preserve t s check(h, ccall((:enlsip_gn_restore_constraints_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int64, Int64,
+         Ptr{Float64}, Ptr{Float64}),
+        h.ptr, B, n, t_max, t, s, dλ, ddiag_scale, dAt, ldat, strideAt, dcx, dsaved))
+    return nothing
+end
+
+"""    deletion_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last delete / restore call on `h`"""
+function deletion_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_deletion_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

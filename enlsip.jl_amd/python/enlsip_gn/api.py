@@ -60,6 +60,22 @@ def determine_solving_dim(previous_dimR: int, rankR: int, predicted_linear_progr
     return int(nd.value)
 
 
+def check_constraint_deletion(q: int, lam, scaling: bool, diag_scale, grad_res: float) -> int:
+    """check_constraint_deletion (src/enlsip_functions.jl:574-603) on host data, through the library's host entry point (no GPU):
+    the 1-based index of the constraint to delete, 0 for none.  t = len(lam); the routine the batched kernels run."""
+    lv = np.ascontiguousarray(lam, dtype=np.float64)
+    dv = np.ascontiguousarray(diag_scale, dtype=np.float64)
+    t = lv.size
+    if dv.size < t:
+        raise ValueError("diag_scale needs one entry per multiplier")
+    s = C.c_int64(0)
+    rc = L.load().enlsip_gn_check_constraint_deletion(int(q), t, _fptr(lv) if t else None, _fptr(dv) if t else None,
+                                                      int(bool(scaling)), float(grad_res), C.byref(s))
+    if rc:
+        raise GNError(f"enlsip_gn_check_constraint_deletion returned {rc}")
+    return int(s.value)
+
+
 @dataclass
 class GNResult:
     p: np.ndarray
@@ -127,6 +143,7 @@ class GNSolver:
     def __init__(self, device: int = -1, flags: int = 0, tile_rows: int = 0, stream: int = 0):
         self._lib = L.load()
         self._h = C.c_void_p()
+        self._device = device       # -1: the current device
         self._resident_m = None     # rows of the last ragged host-form solve made through this object (solve_changed_batched)
         opts = L.Opts(device=device, flags=flags, panel_width=0, tile_rows=tile_rows,
                       stream=C.c_void_p(stream) if stream else None)
@@ -727,6 +744,45 @@ class GNSolver:
         """Kernel form of the last subspace_direction_batched: 0 general, 1 one wave per problem, -1 none yet."""
         f = C.c_int(0)
         self._chk(self._lib.enlsip_gn_get_subspace_form(self._h, C.byref(f)))
+        return int(f.value)
+
+    # ---- the deletion test and the working-set edit on device buffers (src/enlsip_functions.jl:574-603, :708-719, :731-739) --------
+    @staticmethod
+    def _host_i64(x, batch: int, name: str):
+        a = np.ascontiguousarray(np.asarray(x).astype(np.int64))
+        if a.shape != (batch,):
+            raise ValueError(f"{name} must have {batch} entries")
+        return a
+
+    def delete_constraints_batched_dev(self, batch, n, t_max, t, q, scaling, dlambda, ddiag_scale, dAt, ldat, strideAt, dcx,
+                                       dgrad_res=0, dsaved=0, take=None) -> np.ndarray:
+        """check_constraint_deletion per taken problem on the device buffers and, where it names a row, its removal in place
+        (A', cx, lambda, diag_scale in the padded ragged layout; the removed record into dsaved, n + 3 doubles per problem).  t, q,
+        take (None: all) stay host arrays; dgrad_res = 0: grad_res = 0.0 (the second-order test).  Returns s (batch,) int64,
+        1-based, 0 = nothing; t is the caller's to decrement."""
+        v = lambda x: C.c_void_p(x) if x else None
+        t = self._host_i64(t, batch, "t")
+        q = self._host_i64(q, batch, "q")
+        tk = None if take is None else self._host_i64(take, batch, "take")
+        s = np.zeros(batch, dtype=np.int64)
+        self._chk(self._lib.enlsip_gn_delete_constraints_batched_dev(
+            self._h, batch, n, t_max, _fptr(t), _fptr(q), _fptr(tk), int(bool(scaling)), v(dlambda), v(ddiag_scale), v(dgrad_res),
+            v(dAt), ldat, strideAt, v(dcx), v(dsaved), _fptr(s)))
+        return s
+
+    def restore_constraints_batched_dev(self, batch, n, t_max, t, s, dlambda, ddiag_scale, dAt, ldat, strideAt, dcx, dsaved):
+        """The exact inverse of delete_constraints_batched_dev for the problems with s[k] != 0; t[k] is the count after the
+        deletion.  The caller increments t."""
+        v = lambda x: C.c_void_p(x) if x else None
+        t = self._host_i64(t, batch, "t")
+        s = self._host_i64(s, batch, "s")
+        self._chk(self._lib.enlsip_gn_restore_constraints_batched_dev(
+            self._h, batch, n, t_max, _fptr(t), _fptr(s), v(dlambda), v(ddiag_scale), v(dAt), ldat, strideAt, v(dcx), v(dsaved)))
+
+    def deletion_form(self) -> int:
+        """Kernel form of the last delete / restore call: 0 general, 1 one wave per problem, -1 none yet."""
+        f = C.c_int(0)
+        self._chk(self._lib.enlsip_gn_get_deletion_form(self._h, C.byref(f)))
         return int(f.value)
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):

@@ -358,3 +358,126 @@ def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p
     for k in range(B):
         its[k].lam = lams[k]
     return [(solver.factor(FACTOR_A, k), solver.factor(FACTOR_L11, k), solver.factor(FACTOR_J2, k)) for k in range(B)]
+
+
+# ---- the same with the batch resident in device buffers: nothing but s and info crosses PCIe between the stages -------------------
+def update_working_set_batched_dev(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p_gns, its, eps_rank: float):
+    """``update_working_set_batched`` with J, rx, A', cx, diag_scale, lambda, grad_res and p in device buffers (torch tensors) and
+    only ``_dev`` entry points: the deletion test and the removal of a row (:574-603, :708-719, :748-756, :776-785) and the undo
+    (:731-739) are ``delete_constraints_batched_dev`` / ``restore_constraints_batched_dev`` on those buffers.  Per stage only s and
+    the info records come down; p, b, d, lambda and grad_res come down once at the end for the records.  t, the flags, ``active`` /
+    ``inactive`` and ``index_del`` are derived on the host from s, and the rows of ``C.A`` / ``C.cx`` / ``C.diag_scale`` (host inputs)
+    follow by the same index.  Same arguments, mutations and return value as ``update_working_set_batched``; the undo puts back the
+    row that was removed (the reference recomputes it from ``A`` and ``diag_scale``, :739: the same row), so ``A`` is not read.
+    A batch may mix problems with and without row scaling: the test and the edit then run once per kind, each over its own
+    problems (``take``), on a diag_scale buffer of that kind."""
+    import torch
+    B = len(Ws)
+    m, n = Js[0].shape
+    scal = np.array([1 if C.scaling else 0 for C in Cs], dtype=np.int64)
+    Ak = [np.asarray(C.A, dtype=np.float64).reshape(-1, n) for C in Cs]
+    At_h, cx_h, t = GNSolver.pack_ragged(Ak, [C.cx for C in Cs], n=n)
+    t = np.ascontiguousarray(t, dtype=np.int64)
+    t_max = At_h.shape[1]
+    tm1 = max(t_max, 1)
+    # diag_scale per kind: the scaled problems' (ones elsewhere: what the estimates' back-transform takes, as scales() of the host
+    # flow), and that of the problems without row scaling, which only the deletion test reads (:592)
+    ds_h, dsn_h = np.ones((B, tm1)), np.ones((B, tm1))
+    for k, C in enumerate(Cs):
+        (ds_h if C.scaling else dsn_h)[k, :Ws[k].t] = C.diag_scale
+    q = np.array([W.q for W in Ws], dtype=np.int64)
+    dev = torch.device("cuda", solver._device if solver._device >= 0 else torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    new = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+    dJ = up(np.stack([np.asfortranarray(Jk, dtype=np.float64).T for Jk in Js]))       # (B, n, m): problem k column-major
+    drx = up(np.stack([np.asarray(r, dtype=np.float64) for r in rxs]))
+    dG = up(np.stack([np.asarray(g, dtype=np.float64) for g in grad_fxs]))
+    dAt, dcx, dds = up(At_h.reshape(B, -1) if t_max else np.zeros((B, 1))), up(cx_h if t_max else np.zeros((B, 1))), up(ds_h)
+    ddsn = up(dsn_h)
+    dlam, dlam2, dgres, dsaved = new(B, tm1), new(B, tm1), new(B), new(B, n + 3)
+    dp, db, dd, dinfo = new(B, n), new(B, tm1), new(B, m), new(B, 6, dtype=torch.int64)
+    torch.cuda.synchronize(dev)
+    ptr = lambda x: x.data_ptr()
+    A_args = (ptr(dAt), max(n, 1), n * t_max, ptr(dcx))
+    pds = ptr(dds) if (scal.any() and t_max) else 0
+    kinds = [(mask, flag, buf) for mask, flag, buf in ((scal, True, dds), (1 - scal, False, ddsn)) if mask.any()]
+
+    def delete(dl, take=None, **kw):
+        """the deletion test and the edit, once per kind of row scaling over that kind's problems"""
+        s = np.zeros(B, dtype=np.int64)
+        for mask, flag, buf in kinds:
+            tk = mask if take is None else mask * take
+            if tk.any():
+                s += solver.delete_constraints_batched_dev(B, n, t_max, t, q, flag, ptr(dl), ptr(buf), *A_args, take=tk, **kw)
+        return s
+
+    def infos():
+        solver.synchronize()
+        return dinfo.cpu().numpy()
+
+    def drop_row(k, s):
+        """the host records of problem k after the deletion of row s (1-based); returns what the undo puts back"""
+        W, C, it = Ws[k], Cs[k], its[k]
+        rec = (C.cx[s - 1], C.A[s - 1, :].copy(), C.diag_scale[s - 1], int(W.active[s - 1]))
+        C.cx = np.delete(C.cx, s - 1)
+        C.diag_scale = np.delete(C.diag_scale, s - 1)
+        W.remove_constraint(s)
+        it.delete = True
+        it.index_del = rec[3]
+        C.A = np.delete(C.A, s - 1, axis=0)
+        return rec
+
+    solver.factor_constraints_batched_dev(B, m, n, t_max, t, *A_args, eps_rank)                                  # :700
+    solver.first_lagrange_batched_dev(0, B, ptr(dlam), dgrad_fx=ptr(dG), ddiag_scale=pds, eps_rank=eps_rank,
+                                      dgrad_res=ptr(dgres))                                                       # :704
+    s1 = delete(dlam, dgrad_res=ptr(dgres), dsaved=ptr(dsaved))                                                   # :705-723
+    removed = {int(k): (int(s1[k]),) + drop_row(int(k), int(s1[k])) for k in np.flatnonzero(s1)}
+    t = t - (s1 != 0)
+    out = dict(dp=ptr(dp), db=ptr(db), dd=ptr(dd), dinfo=ptr(dinfo))
+    solver.solve_factored_batched_dev(B, m, n, t_max, t, (s1 != 0).astype(np.int64), ptr(dJ), m, m * n, ptr(drx), *A_args,
+                                      eps_rank, **out)                                                            # :725 / :771
+    info = infos()
+    s_back = np.zeros(B, dtype=np.int64)
+    for k, (s, cx_s, A_s, ds_s, index_s) in removed.items():                                                      # :728-743
+        W, C, it = Ws[k], Cs[k], its[k]
+        # quirk Q1: rankA <= min(n, t), so the dot(A_s, p_gn) arm of :728 is never taken and As_p = 0.0
+        assert int(info[k, 0]) <= W.t
+        As_p = 0.0
+        if (As_p >= -cx_s) and (As_p > 0):
+            continue
+        s_back[k] = s
+        C.cx = np.insert(C.cx, s - 1, cx_s)
+        C.diag_scale = np.insert(C.diag_scale, s - 1, ds_s)
+        W.add_constraint(int(np.where(W.inactive == index_s)[0][0]) + 1)
+        it.index_del = 0
+        it.delete = False
+        C.A = np.insert(C.A, s - 1, A_s, axis=0)
+    if s_back.any():
+        for mask, _, buf in kinds:
+            if (mask * s_back).any():
+                solver.restore_constraints_batched_dev(B, n, t_max, t, mask * s_back, ptr(dlam), ptr(buf), *A_args, ptr(dsaved))
+        t = t + (s_back != 0)
+        solver.solve_changed_batched_dev(B, m, n, t_max, t, (s_back != 0).astype(np.int64), *A_args, eps_rank, **out)
+        info = infos()
+    # second-order estimate where :745 / :773 ask for it: the problems that kept their set or got it back
+    cand = np.array([1 if (k not in removed or s_back[k]) and not (Ws[k].t != info[k, 0] or info[k, 1] != min(m, n - info[k, 0]))
+                     else 0 for k in range(B)], dtype=np.int64)
+    if cand.any():
+        solver.second_lagrange_batched_dev(0, B, ptr(dp), ptr(dlam2), ddiag_scale=pds)
+        s2 = delete(dlam2, take=cand)
+        for k in np.flatnonzero(s2):
+            drop_row(int(k), int(s2[k]))
+        if s2.any():
+            t = t - (s2 != 0)
+            solver.solve_changed_batched_dev(B, m, n, t_max, t, (s2 != 0).astype(np.int64), *A_args, eps_rank, **out)
+    info = infos()
+    p, b, d, lam, lam2, gres = (x.cpu().numpy() for x in (dp, db, dd, dlam, dlam2, dgres))
+    for k in range(B):
+        W, it = Ws[k], its[k]
+        p_gns[k][:] = p[k]
+        it.rankA, it.rankJ2 = int(info[k, 0]), int(info[k, 1])
+        it.dimA, it.dimJ2 = int(info[k, 0]), int(info[k, 1])
+        it.b_gn, it.d_gn = b[k, :W.t].copy(), d[k].copy()
+        it.grad_res = float(gres[k])
+        it.lam = (lam2 if cand[k] else lam)[k, :W.t].copy()
+    return [(solver.factor(FACTOR_A, k), solver.factor(FACTOR_L11, k), solver.factor(FACTOR_J2, k)) for k in range(B)]

@@ -510,6 +510,64 @@ int enlsip_gn_subspace_direction_batched_dev(enlsip_gn_handle h, int64_t prob0, 
                                              enlsip_gn_info* dinfo, int* dstatus);
 int enlsip_gn_get_subspace_form(enlsip_gn_handle h, int* form);
 
+/* ---- the deletion test and the working-set edit of a batch, on the caller's device buffers -------------------------------------
+ * Between the stages of a batched update_working_set (src/enlsip_functions.jl:686-795: enlsip_gn_factor_constraints_batched_dev,
+ * enlsip_gn_first_lagrange_batched_dev, enlsip_gn_solve_factored_batched_dev, enlsip_gn_solve_changed_batched_dev,
+ * enlsip_gn_second_lagrange_batched_dev) stands check_constraint_deletion (:574-603), the removal of row s from C.A, C.cx,
+ * C.diag_scale and lambda (:708-719, :748-756, :776-785) and the re-insertion after a failed feasibility test (:731-739).  These
+ * entry points do that where lambda, grad_res, diag_scale, A' and cx are, so that "the flagged problems' slots rewritten in
+ * place" of the _dev solves needs no download, host loop and upload.  What stays with the caller is the bookkeeping the ragged
+ * ABI keeps on the host anyway: t, the active / inactive index lists, the 0/1 flags.
+ *
+ * enlsip_gn_check_constraint_deletion   check_constraint_deletion (src/enlsip_functions.jl:574-603) on HOST data, no handle and no
+ *     GPU: *s = the 1-based index of the constraint to delete, 0 for none.  lambda, diag_scale: t entries; q: the equalities, never
+ *     candidates (:591).  lambda_max is taken over all t entries and propagates a NaN as Julia's maximum does (then s = 0); row_i is
+ *     an IEEE division when scaling != 0 (:592); both tests of :593 are <=, so among equal minima the last index wins; the gate is
+ *     grad_res > -10 e (:598).  Returns 0; -2 s NULL, t < 0, q < 0 or q > t; -4 lambda or diag_scale NULL while t > q.  The same
+ *     routine, compiled for the device, makes the decisions below.
+ * enlsip_gn_delete_constraints_batched_dev   for every taken problem k (take: HOST array of batch entries, NULL = all) the test on
+ *     dlambda[k, 0:t[k]), ddiag_scale[k, 0:t[k]), q[k] and dgrad_res[k] (dgrad_res NULL: 0.0 for every problem, the second-order
+ *     test of :747 / :775), and where s[k] != 0, in place:
+ *         dsaved[k] = A_s (n), cx_s, lambda_s, diag_scale_s                                    :708-711   (dsaved may be NULL when
+ *                                                                                                no restore will follow)
+ *         columns s .. t-1 of the A' block one to the left, column t-1 zero                     :719 / :756 / :785
+ *         cx, lambda, diag_scale likewise; the vacated slot gets 0.0, 0.0 and 1.0               :713-715 / :751-753 / :779-781
+ *     i.e. the padded layout a host caller would upload.  t, q, take and s are HOST arrays of batch entries; s[k] (1-based, 0 =
+ *     nothing, also for a problem not taken) comes back in the host array; t is not written, the caller decrements it.  Device
+ *     buffers have the strides of the ragged solve: dlambda, ddiag_scale, dcx t_max per problem, dAt problem k's n x t[k]
+ *     column-major block at dAt + k * strideAt, dgrad_res 1, dsaved n + 3.  Nothing of a problem with s[k] == 0 or take[k] == 0 is
+ *     written, nor any byte between rows n and ldat or between ldat * t_max and strideAt.
+ * enlsip_gn_restore_constraints_batched_dev   for every problem with s[k] != 0 the exact inverse, t[k] being the count AFTER the
+ *     deletion: columns s-1 .. t-1 one to the right, the saved column at s-1, the same for cx, lambda and diag_scale (:731-733 and
+ *     what :739 rebuilds).  Afterwards the slot is byte for byte what it was before the delete.  The feasibility rule itself
+ *     (:728-729) stays a host line of the driver: its dot(A_s, p_gn) arm needs rankA > W.t, which cannot happen (rankA <=
+ *     min(n, t); quirk Q1 of SURVEY App. C), so there is no device dot product for it.
+ * enlsip_gn_get_deletion_form   kernel form of the last of the two calls on this handle: 0 general (one workgroup per problem, one
+ *     lane runs the routine above on an LDS copy), 1 one wave per problem (n <= 64 and t_max <= 64: four problems per workgroup,
+ *     the decision by cross-lane operations), -1 none yet.  The two forms give the same s on the same inputs.
+ * Both calls need no resident factors: they are legal in every handle state, between a factor call and its solve included, and
+ * touch nothing resident.  The number of launches does not depend on batch; one copy of the host records goes up, one copy of s
+ * comes back (delete), and the call returns after ONE synchronisation of the handle's stream.  The records live in a scratch the
+ * handle keeps.  Argument errors are raised before anything is launched and leave every buffer untouched (last_error names k):
+ *   -1 h NULL; -2 batch < 1; -3 n < 1 or t_max outside 0..1024 (this build); -4 t, q or s NULL, or dlambda,
+ *   ddiag_scale, dAt or dcx NULL while t_max > 0; -5 some t[k] outside 0..t_max (restore: 0..t_max-1 where s[k] != 0); -6 some q[k]
+ *   outside 0..t[k]; -7 restore: some s[k] outside 0..t[k]+1; -9 ldat < n; -10 strideAt < ldat * t_max; -12 restore: dsaved NULL
+ *   while some s[k] != 0.
+ */
+int enlsip_gn_check_constraint_deletion(int64_t q, int64_t t, const double* lambda, const double* diag_scale, int scaling,
+                                        double grad_res, int64_t* s);
+int enlsip_gn_delete_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t n, int64_t t_max,
+                                             const int64_t* t, const int64_t* q, const int64_t* take, int scaling,
+                                             double* dlambda, double* ddiag_scale, const double* dgrad_res,
+                                             double* dAt, int64_t ldat, int64_t strideAt, double* dcx,
+                                             double* dsaved, int64_t* s);
+int enlsip_gn_restore_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t n, int64_t t_max,
+                                              const int64_t* t, const int64_t* s,
+                                              double* dlambda, double* ddiag_scale,
+                                              double* dAt, int64_t ldat, int64_t strideAt, double* dcx,
+                                              const double* dsaved);
+int enlsip_gn_get_deletion_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
