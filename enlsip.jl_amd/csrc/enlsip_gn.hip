@@ -90,6 +90,19 @@ static int grow(enlsip_gn_handle h, DevBuf& b, size_t bytes) {
     return 0;
 }
 
+// The same for a call's pinned scratch: grown, never shrunk, the old block freed first.  A stream that was handed the old block
+// must have been synchronised before this is called: every caller synchronises its streams before it returns, so growing at the
+// start of a call is safe.
+static int grow_pinned(enlsip_gn_handle h, PinnedBuf& b, size_t bytes) {
+    if (b.cap >= bytes) return 0;
+    if (b.p) (void)hipHostFree(b.p);
+    b.p = nullptr;
+    b.cap = 0;
+    GN_HIP(hipHostMalloc(&b.p, bytes, hipHostMallocDefault));
+    b.cap = bytes;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------
 // plan: geometry + workspace carve for (batch, m, n, t)
 // ---------------------------------------------------------------------------------------------
@@ -247,10 +260,10 @@ template <class KernelT>
 static void big_lds(KernelT k, size_t bytes) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
-#define GN_LAUNCH_BIG(kern, grid, block, lds, stream, args) \
+#define GN_LAUNCH_BIG(kern, grid, block, lds, stream, ...) \
     do {                                                     \
         big_lds(kern, lds);                                  \
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, args); \
+        hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__); \
     } while (0)
 
 // dispatch helpers over the rows-per-lane instantiations of the single-workgroup kernels
@@ -1630,13 +1643,11 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->nwb_io.p) (void)hipFree(h->nwb_io.p);
     if (h->ssb_req.p) (void)hipFree(h->ssb_req.p);
     if (h->ssb_io.p) (void)hipFree(h->ssb_io.p);
-    if (h->h_ssb) (void)hipHostFree(h->h_ssb);
     if (h->del_scr.p) (void)hipFree(h->del_scr.p);
-    if (h->h_del) (void)hipHostFree(h->h_del);
-    if (h->h_nwflag) (void)hipHostFree(h->h_nwflag);
     for (hipEvent_t e : h->nwb_ev)
         if (e) (void)hipEventDestroy(e);
-    if (h->h_lagflag) (void)hipHostFree(h->h_lagflag);
+    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_nwflag, &h->h_lagflag})
+        if (b->p) (void)hipHostFree(b->p);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);
     if (h->info_stage.p) (void)hipFree(h->info_stage.p);

@@ -47,6 +47,12 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// pinned host memory that a call sizes for itself (grow_pinned): the host end of its asynchronous copies
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+
 // The operands of one batched solve: shape, inputs, outputs (device pointers, or host pointers before solve_host stages them).
 // Problem k's part of each array starts at a fixed stride, and slice() is the one place that knows them: J, A' by strideJ,
 // strideAt; rx, d by m; p, jpvtJ2 by n; cx, b, jpvtA by t (t_max of a ragged batch); jpvtL by min(n, t); the info records and
@@ -234,7 +240,7 @@ struct enlsip_gn_context {
     // batched consumers (gn_lagrange_batched.inc): staging of the host-buffer forms, device temporaries, pinned "some problem
     // flagged" word of the last launch; never a buffer the resident solve reads
     gn::DevBuf lagb_io, lagb_scr;
-    int* h_lagflag = nullptr;
+    gn::PinnedBuf h_lagflag;
     bool lagrange_small = true;         // ENLSIP_GN_LAGRANGE_SMALL=0: batched multiplier estimates in the general form only (A/B)
     int consumer_form = -1;             // form of the last batched multiplier estimate (enlsip_gn_get_consumer_form), -1: none yet
     // batched re-solve (gn_resolve_batched.inc): per-slot requests on the device, staging of the host-buffer form, the form of the
@@ -249,7 +255,7 @@ struct enlsip_gn_context {
     // batched Newton direction (gn_newton_batched.inc): device temporaries of a segment, staging of the host-buffer form, the form of
     // the last call, HIP events around its four stages (profiling on) and their times summed over the handles that ran a part
     gn::DevBuf nwb_ws, nwb_io;
-    int* h_nwflag = nullptr;            // pinned "some slot flagged" word of the last launch on this handle
+    gn::PinnedBuf h_nwflag;             // pinned "some slot flagged" word of the last launch on this handle
     int newton_form = -1;
     hipEvent_t nwb_ev[5] = {};
     bool nwb_timed = false;
@@ -257,14 +263,12 @@ struct enlsip_gn_context {
     // one-call subspace minimisation (gn_subspace_batched.inc): requests and previous iterates on the device, staging of the
     // host-buffer form, the pinned copy of the final requests (chosen dimensions, status) and the form of the last call
     gn::DevBuf ssb_req, ssb_io;
-    void* h_ssb = nullptr;
-    size_t h_ssb_cap = 0;
+    gn::PinnedBuf h_ssb;
     int subspace_form = -1;
     // batched deletion test and working-set edit (gn_deletion_batched.inc): t / q / take / s of one call on the device and in pinned
     // memory, and the form of the last call; nothing of the resident state
     gn::DevBuf del_scr;
-    void* h_del = nullptr;
-    size_t h_del_cap = 0;
+    gn::PinnedBuf h_del;
     int deletion_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;

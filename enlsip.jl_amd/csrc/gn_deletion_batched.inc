@@ -8,20 +8,16 @@ namespace {
 enum { DEL_MAX_T = 1024 };      // t_max of this build: the LDS copies of the general form.  n is not bounded: rows are strided by thread
 
 // the per-problem records of one call in pinned memory and on the device, the decisions behind them (hs, ds: may be null, the
-// restore has none); grown, never shrunk
+// restore has none); grown, never shrunk (grow, grow_pinned)
 int deletion_scratch(enlsip_gn_handle h, int64_t batch, DeletionMeta** hmeta, int** hs, DeletionMeta** dmeta, int** ds) {
     const size_t mb = (size_t)batch * sizeof(DeletionMeta), bytes = mb + (size_t)batch * sizeof(int);
     int rc = grow(h, h->del_scr, bytes);
     if (rc) return rc;
-    if (h->h_del_cap < bytes) {
-        if (h->h_del) (void)hipHostFree(h->h_del);
-        h->h_del = nullptr; h->h_del_cap = 0;
-        GN_HIP(hipHostMalloc(&h->h_del, bytes, hipHostMallocDefault));
-        h->h_del_cap = bytes;
-    }
-    *hmeta = (DeletionMeta*)h->h_del;
+    rc = grow_pinned(h, h->h_del, bytes);
+    if (rc) return rc;
+    *hmeta = (DeletionMeta*)h->h_del.p;
     *dmeta = (DeletionMeta*)h->del_scr.p;
-    if (hs) *hs = (int*)((char*)h->h_del + mb);
+    if (hs) *hs = (int*)((char*)h->h_del.p + mb);
     if (ds) *ds = (int*)((char*)h->del_scr.p + mb);
     return 0;
 }

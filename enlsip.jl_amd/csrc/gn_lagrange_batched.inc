@@ -58,7 +58,10 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const 
     const size_t o_y = o_g + (size_t)cnt * n * 8, o_b = o_y + (size_t)cnt * m * 8, bytes = o_b + (size_t)cnt * std::max(tmax, 1LL) * 8;
     int rc = grow(hh, hh->lagb_scr, bytes);
     if (rc) return rc;
-    if (est && !hh->h_lagflag) GN_HIP(hipHostMalloc((void**)&hh->h_lagflag, sizeof(int), hipHostMallocDefault));
+    if (est) {
+        rc = grow_pinned(hh, hh->h_lagflag, sizeof(int));
+        if (rc) return rc;
+    }
     char* scr = (char*)hh->lagb_scr.p;
     hipStream_t s = hh->stream;
     const unsigned cn = (unsigned)cnt;
@@ -116,7 +119,7 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const 
                 hipLaunchKernelGGL(k_lagrange_wave, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, s, a);
             else
                 hipLaunchKernelGGL(k_lagrange_batched, dim3(cn), dim3(256), 0, s, a);
-            GN_HIP(hipMemcpyAsync(hh->h_lagflag, scr, sizeof(int), hipMemcpyDeviceToHost, s));
+            GN_HIP(hipMemcpyAsync(hh->h_lagflag.p, scr, sizeof(int), hipMemcpyDeviceToHost, s));
         }
     }
     GN_HIP(hipGetLastError());
@@ -221,7 +224,7 @@ int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, con
     bool flagged = false;
     for (const ResidentSeg& sg : r.seg) {
         GN_HIP(hipStreamSynchronize(sg.hh->stream));
-        if (est) flagged = flagged || *sg.hh->h_lagflag != 0;
+        if (est) flagged = flagged || *(const int*)sg.hh->h_lagflag.p != 0;
     }
     if (!r.slots.empty()) {
         rc = consumer_per_problem(h, kind, prob0, count, r, io, flagged);

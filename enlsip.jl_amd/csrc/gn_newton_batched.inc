@@ -30,7 +30,8 @@ int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, co
     const size_t rq_b = (size_t)cnt * (sizeof(ResolveDims) + sizeof(int)) + sizeof(int);
     int rc = grow(hh, hh->nwb_ws, dbl * 8 + st_b + su_b + rq_b + 64);
     if (rc) return rc;
-    if (!hh->h_nwflag) GN_HIP(hipHostMalloc((void**)&hh->h_nwflag, sizeof(int), hipHostMallocDefault));
+    rc = grow_pinned(hh, hh->h_nwflag, sizeof(int));
+    if (rc) return rc;
     double* dX = (double*)hh->nwb_ws.p;
     double* dE = dX + (size_t)cnt * nn;
     double* drhs = dE + (size_t)cnt * nn;
@@ -99,7 +100,7 @@ int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, co
     else hipLaunchKernelGGL(k_newton_chol_batched<256>, dim3(cn), dim3(256), 0, s, a);
     if (timed) GN_HIP(hipEventRecord(hh->nwb_ev[4], s));
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(hh->h_nwflag, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(hh->h_nwflag.p, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
     return 0;
 }
 
@@ -141,7 +142,7 @@ int newton_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const NewtonIO&
     for (float& ms : h->newton_ms) ms = 0.f;
     for (const ResidentSeg& sg : r.seg) {
         GN_HIP(hipStreamSynchronize(sg.hh->stream));
-        flagged = flagged || *sg.hh->h_nwflag != 0;
+        flagged = flagged || *(const int*)sg.hh->h_nwflag.p != 0;
         if (sg.hh->nwb_timed)
             for (int e = 0; e < 4; ++e) {
                 float ms = 0.f;

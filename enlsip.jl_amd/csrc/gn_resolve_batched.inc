@@ -2,8 +2,9 @@
 // search_direction_analys does per problem at src/enlsip_functions.jl:1249-1253 — b = F_L11.Q' (-cx[F_A.p]), the d of
 // choose_subspace_dimensions (:1118-1176, :1156-1163) and sub_search_direction (:116-153) — in a number of launches and
 // synchronisations that does not depend on the size of the range.  The range and the driver of its half-segments are the shared
-// ones of gn_accessors.inc (resident_range, for_each_segment); the b / p1 / d stages are enqueued by resolve_stages, here, for the
-// batched Newton direction too.  Included at the end of enlsip_gn.hip.
+// ones of gn_accessors.inc (resident_range, for_each_segment).  What the calls that answer with p / b / d / info / status share is
+// here: resolve_stages (head, then resolve_d_stages; the batched Newton direction enqueues it too), resolve_tail_launch,
+// bind_outputs, write_alone_slot and the host-buffer form, staged_outputs_call.  Included at the end of enlsip_gn.hip.
 
 namespace {
 
@@ -50,21 +51,16 @@ int resolve_kpmax(enlsip_gn_handle hh, long long k0, long long cnt, const Resolv
     return kpmax;
 }
 
-// Enqueues on hh's stream the stages before the tail for problems k0 .. k0+cnt-1 of hh: b and p1 (head), d_temp, and
+// Enqueues on hh's stream the d stages for problems k0 .. k0+cnt-1 of hh, after a head that left p1: d_temp, and
 // d = F_J2.Q' d_temp as Q0' (one launch per (panel, level) of the CAQR plan) then Qt', into a.vec.  a.dims: the requests on the
-// device; kpmax: theirs.  b_only: b and p1 are all there is to compute.  q0_ev: null, or two events recorded around the Q0' launches.
-int resolve_stages(enlsip_gn_handle hh, const ResolveBatchArgs& a, long long k0, long long cnt, int kpmax, bool small, bool b_only,
-                   hipEvent_t* q0_ev) {
+// device; kpmax >= 0: theirs.  q0_ev: null, or two events recorded around the Q0' launches.
+int resolve_d_stages(enlsip_gn_handle hh, const ResolveBatchArgs& a, long long k0, long long cnt, int kpmax, hipEvent_t* q0_ev) {
     enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
-    if (kpmax < 0) return 0;
     const Plan& P = hh->plan;
     hipStream_t s = hh->stream;
-    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
     const unsigned cn = (unsigned)cnt;
-    if (small) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, s, a);
-    else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, s, a);
-    if (!b_only) hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
-    const int npan = b_only ? 0 : (kpmax + PB - 1) / PB;
+    hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
+    const int npan = (kpmax + PB - 1) / PB;
     if (q0_ev) {
         for (int e = 0; e < 2; ++e)
             if (!q0_ev[e]) GN_HIP(hipEventCreate(&q0_ev[e]));
@@ -78,8 +74,65 @@ int resolve_stages(enlsip_gn_handle hh, const ResolveBatchArgs& a, long long k0,
             else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, a.dims);
         }
     if (q0_ev) GN_HIP(hipEventRecord(q0_ev[1], s));
-    if (kpmax > 0 && !b_only) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
+    if (kpmax > 0) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
     return 0;
+}
+
+// Enqueues on hh's stream the stages before the tail: b and p1 (head), then the d stages.  kpmax < 0: no request runs them.
+// b_only: b and p1 are all there is to compute (q0_ev is null then).
+int resolve_stages(enlsip_gn_handle hh, const ResolveBatchArgs& a, long long k0, long long cnt, int kpmax, bool small, bool b_only,
+                   hipEvent_t* q0_ev) {
+    if (kpmax < 0) return 0;
+    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
+    const unsigned cn = (unsigned)cnt;
+    if (small) hipLaunchKernelGGL(k_resolve_head<64>, dim3(cn), dim3(64), lds, hh->stream, a);
+    else hipLaunchKernelGGL(k_resolve_head<256>, dim3(cn), dim3(256), lds, hh->stream, a);
+    return b_only ? 0 : resolve_d_stages(hh, a, k0, cnt, kpmax, q0_ev);
+}
+
+// the tail (triangular solve with dimJ2, p, the outputs) in the form that goes with the shape
+void resolve_tail_launch(enlsip_gn_handle hh, const ResolveBatchArgs& a, long long cnt, bool small) {
+    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
+    const unsigned cn = (unsigned)cnt;
+    if (small) hipLaunchKernelGGL((k_resolve_tail<1, 64>), dim3(cn), dim3(64), lds, hh->stream, a);
+    else if (hh->plan.n <= 512) hipLaunchKernelGGL((k_resolve_tail<8, 256>), dim3(cn), dim3(256), lds, hh->stream, a);
+    else hipLaunchKernelGGL((k_resolve_tail<0, 256>), dim3(cn), dim3(256), lds, hh->stream, a);
+}
+
+// the caller's output buffers as a segment whose first problem is slot j0 writes them
+void bind_outputs(ResolveBatchArgs& a, const ResolveIO& io, long long j0, const Plan& P) {
+    a.p_out = io.p ? io.p + j0 * P.n : nullptr;
+    a.b_out = (io.b && P.t > 0) ? io.b + j0 * P.t : nullptr;
+    a.d_out = io.d ? io.d + j0 * P.m : nullptr;
+    a.info_out = io.info ? io.info + j0 : nullptr;
+    a.status_out = io.status ? io.status + j0 : nullptr;
+}
+
+// Writes what the per-problem entry point answered for slot j (a problem on a rescue handle) into the caller's device buffers;
+// p, b, d, info: host, null for what this answer does not write.
+int write_alone_slot(enlsip_gn_handle h, const ResolveIO& io, long long j, const Plan& P, const double* p, const double* b,
+                     const double* d, const enlsip_gn_info* info, int status) {
+    if (io.p && p) GN_HIP(hipMemcpy(io.p + j * P.n, p, (size_t)P.n * 8, hipMemcpyHostToDevice));
+    if (io.b && b && P.t > 0) GN_HIP(hipMemcpy(io.b + j * P.t, b, (size_t)P.t * 8, hipMemcpyHostToDevice));
+    if (io.d && d) GN_HIP(hipMemcpy(io.d + j * P.m, d, (size_t)P.m * 8, hipMemcpyHostToDevice));
+    if (io.info && info) GN_HIP(hipMemcpy(io.info + j, info, sizeof(*info), hipMemcpyHostToDevice));
+    if (io.status) GN_HIP(hipMemcpy(io.status + j, &status, sizeof(int), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// The host-buffer form of a call with these five outputs: `host` staged through buf, dev(io) on the staged copies, the outputs
+// copied back unless dev failed.  The caller's arrays go in first so that the slots the call leaves alone come back as they were.
+template <class Dev>
+int staged_outputs_call(enlsip_gn_handle h, DevBuf& buf, int64_t count, const Plan& P, const ResolveIO& host, Dev&& dev) {
+    const size_t c = (size_t)count;
+    Staged a[5] = {{host.p, c * P.n * 8, true, true}, {host.b, c * P.t * 8, true, true}, {host.d, c * P.m * 8, true, true},
+                   {host.info, c * sizeof(enlsip_gn_info), true, true}, {host.status, c * sizeof(int), true, true}};
+    int rc = stage_in(h, buf, a, 5);
+    if (rc) return rc;
+    rc = dev(ResolveIO{(double*)a[0].dev, (double*)a[1].dev, (double*)a[2].dev, (enlsip_gn_info*)a[3].dev, (int*)a[4].dev});
+    if (rc < 0 || rc > 1) return rc;
+    const int rc2 = stage_out(h, a, 5);
+    return rc2 ? rc2 : rc;
 }
 
 // Enqueues the re-solve of one segment on its handle's stream: one copy of the requests, then 4 launches plus one per
@@ -95,22 +148,14 @@ int resolve_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDims
     GN_HIP(hipMemcpyAsync(ddims, dims, (size_t)cnt * sizeof(ResolveDims), hipMemcpyHostToDevice, s));
     ResolveBatchArgs a = resolve_args(hh, k0, cnt);
     a.dims = ddims;
-    a.p_out = io.p ? io.p + j0 * P.n : nullptr;
-    a.b_out = (io.b && P.t > 0) ? io.b + j0 * P.t : nullptr;
-    a.d_out = io.d ? io.d + j0 * P.m : nullptr;
-    a.info_out = io.info ? io.info + j0 : nullptr;
-    a.status_out = io.status ? io.status + j0 : nullptr;
+    bind_outputs(a, io, j0, P);
     // the stages before the tail run for the slots that do not start from a held result; b_only: every request of the call stops at
     // HOLD and no d is asked for.  Profiling on: HIP events around the Q0' launches, if there are any (enlsip_gn_get_resolve_q0_ms)
     const int kpmax = resolve_kpmax(hh, k0, cnt, dims);
     hh->rsb_timed = prof && !b_only && kpmax > 0;
     rc = resolve_stages(hh, a, k0, cnt, kpmax, small, b_only, hh->rsb_timed ? hh->rsb_ev : nullptr);
     if (rc) return rc;
-    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
-    const unsigned cn = (unsigned)cnt;
-    if (small) hipLaunchKernelGGL((k_resolve_tail<1, 64>), dim3(cn), dim3(64), lds, s, a);
-    else if (P.n <= 512) hipLaunchKernelGGL((k_resolve_tail<8, 256>), dim3(cn), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_resolve_tail<0, 256>), dim3(cn), dim3(256), lds, s, a);
+    resolve_tail_launch(hh, a, cnt, small);
     GN_HIP(hipGetLastError());
     GN_HIP(hipMemcpyAsync(hh->h_state + k0, hh->state + k0, (size_t)cnt * sizeof(ProbState), hipMemcpyDeviceToHost, s));
     return 0;
@@ -204,18 +249,14 @@ int resolve_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t*
                 else if (rc == -5) st = RS_CODE;
                 else if (rc) return rc;
             }
+            const enlsip_gn_info inf = info_of(at.hh->h_state[at.k]);
+            if (st) rc = write_alone_slot(h, io, j, P, nullptr, nullptr, nullptr, nullptr, st);
+            else rc = write_alone_slot(h, io, j, P, hold2 ? nullptr : hp.data(), hb.data(), hd_.data(), &inf, 0);
+            if (rc) return rc;
             if (!st) {
-                if (io.p && !hold2) GN_HIP(hipMemcpy(io.p + j * P.n, hp.data(), (size_t)P.n * 8, hipMemcpyHostToDevice));
-                if (io.b && P.t > 0) GN_HIP(hipMemcpy(io.b + j * P.t, hb.data(), (size_t)P.t * 8, hipMemcpyHostToDevice));
-                if (io.d) GN_HIP(hipMemcpy(io.d + j * P.m, hd_.data(), (size_t)P.m * 8, hipMemcpyHostToDevice));
-                if (io.info) {
-                    const enlsip_gn_info inf = info_of(at.hh->h_state[at.k]);
-                    GN_HIP(hipMemcpy(io.info + j, &inf, sizeof(inf), hipMemcpyHostToDevice));
-                }
                 if (hold2 && dimA[j] != ENLSIP_GN_DIM_HOLD && !b_only) at.hh->held[(size_t)at.k] = {(int)c, (int)dA};
                 else if (dimA[j] == ENLSIP_GN_DIM_HOLD) at.hh->held[(size_t)at.k] = was;
             }
-            if (io.status) GN_HIP(hipMemcpy(io.status + j, &st, sizeof(int), hipMemcpyHostToDevice));
             flagged = flagged || st != 0;
         }
     }
@@ -239,20 +280,10 @@ int enlsip_gn_resolve_batched(enlsip_gn_handle h, int64_t prob0, int64_t count, 
     if (!h) return -1;
     GN_TRY
     ResidentRange r;
-    int rc = resident_range(h, prob0, count, r);
+    const int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
-    const Plan& P = r.plan();
-    const size_t c = (size_t)count;
-    // staged through a buffer of its own; the caller's arrays go in first so that the slots the call leaves alone come back as they were
-    Staged a[5] = {{p, c * P.n * 8, true, true}, {b, c * P.t * 8, true, true}, {d, c * P.m * 8, true, true},
-                   {info, c * sizeof(enlsip_gn_info), true, true}, {status, c * sizeof(int), true, true}};
-    rc = stage_in(h, h->rsb_io, a, 5);
-    if (rc) return rc;
-    rc = resolve_dev(h, prob0, count, dimA, dimJ2, code,
-                     {(double*)a[0].dev, (double*)a[1].dev, (double*)a[2].dev, (enlsip_gn_info*)a[3].dev, (int*)a[4].dev});
-    if (rc < 0 || rc > 1) return rc;
-    const int rc2 = stage_out(h, a, 5);
-    return rc2 ? rc2 : rc;
+    return staged_outputs_call(h, h->rsb_io, count, r.plan(), {p, b, d, info, status},
+                               [&](const ResolveIO& io) { return resolve_dev(h, prob0, count, dimA, dimJ2, code, io); });
     GN_CATCH(h)
 }
 

@@ -1,6 +1,8 @@
 // One-call subspace minimisation over a contiguous range of the resident batch (kernels: gn_kernels_subspace_batched.hpp; the
 // choice: gn_subspace_choice.hpp): lines :1251-1253 of search_direction_analys with choose_subspace_dimensions
-// (src/enlsip_functions.jl:1118-1176) between the stages of the batched re-solve, which are enqueued by resolve_stages unchanged.
+// (src/enlsip_functions.jl:1118-1176) between the stages of the batched re-solve.  Its own kernels are the head, which chooses dimA,
+// and the choice of dimJ2; everything else is gn_resolve_batched.inc's: resolve_d_stages after the head, the whole resolve_stages
+// where dimA was raised, resolve_tail_launch, bind_outputs, write_alone_slot and the host-buffer form staged_outputs_call.
 // The range and its half-segments are the shared ones of gn_accessors.inc.  Included at the end of enlsip_gn.hip.
 
 namespace {
@@ -19,12 +21,8 @@ int subspace_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDim
     const size_t db = (size_t)cnt * sizeof(ResolveDims), pb = (size_t)cnt * sizeof(enlsip_gn_subspace_prev);
     int rc = grow(hh, hh->ssb_req, 2 * db + pb);
     if (rc) return rc;
-    if (hh->h_ssb_cap < db) {
-        if (hh->h_ssb) (void)hipHostFree(hh->h_ssb);
-        hh->h_ssb = nullptr; hh->h_ssb_cap = 0;
-        GN_HIP(hipHostMalloc(&hh->h_ssb, db, hipHostMallocDefault));
-        hh->h_ssb_cap = db;
-    }
+    rc = grow_pinned(hh, hh->h_ssb, db);
+    if (rc) return rc;
     hipStream_t s = hh->stream;
     ResolveDims* d1 = (ResolveDims*)hh->ssb_req.p;
     enlsip_gn_subspace_prev* dprev = (enlsip_gn_subspace_prev*)((char*)d1 + db);
@@ -36,17 +34,13 @@ int subspace_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDim
 
     ResolveBatchArgs a = resolve_args(hh, k0, cnt);
     a.dims = d1;
-    a.p_out = io.p ? io.p + j0 * P.n : nullptr;
-    a.b_out = (io.b && P.t > 0) ? io.b + j0 * P.t : nullptr;
-    a.d_out = io.d ? io.d + j0 * P.m : nullptr;
-    a.info_out = io.info ? io.info + j0 : nullptr;
-    a.status_out = io.status ? io.status + j0 : nullptr;
+    bind_outputs(a, io, j0, P);
     SubspaceArgs c{};
     c.dims = d1; c.dims2 = d2; c.prev = dprev;
     c.nc = (int)rup(std::max<long long>(std::min(P.n, P.t), 1), 8);
     c.nr = (int)rup(std::max<long long>(std::min(P.m, P.n), 1), 8);
     const size_t lds_h = subspace_head_lds_bytes(a.nv, a.blkd, c.nc), lds_j = subspace_dimj2_lds_bytes(c.nr);
-    // n, t <= 1024 in this build: at most 74 KB for the head (above 64 KB: the opt-in of big_lds) and 33 KB for the dimJ2 kernel
+    // n, t <= 1024 in this build: at most 74 KB for the head (above 64 KB: the opt-in of GN_LAUNCH_BIG) and 33 KB for the dimJ2 kernel
     const int kpmax = resolve_kpmax(hh, k0, cnt, dims);
     // the max with the previous dimA (:1171-1174) can raise dimA after d was formed: b, p1 and d are then computed again with the
     // final dimA, as sub_search_direction (:1253) does.  Whether any slot can need that is known here: dimA >= 1 where rankA > 0.
@@ -60,20 +54,9 @@ int subspace_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDim
     const unsigned cn = (unsigned)cnt;
     if (kpmax >= 0) {
         if (small) hipLaunchKernelGGL(k_subspace_head<64>, dim3(cn), dim3(64), lds_h, s, a, c);
-        else {
-            big_lds(k_subspace_head<256>, lds_h);
-            hipLaunchKernelGGL(k_subspace_head<256>, dim3(cn), dim3(256), lds_h, s, a, c);
-        }
-        hipLaunchKernelGGL(k_dtemp_batched, dim3((unsigned)(P.ldw + 255) / 256, cn), dim3(256), 0, s, a);
-        const int npan = (kpmax + PB - 1) / PB;
-        for (int k = 0; k < npan; ++k)
-            for (const LevelPlan& L : P.panels[k].levels) {
-                CaqrArgs ca = caqr_args(hh, k, L);
-                ca.ext_cols = 1; ca.C = a.vec - k0 * P.sVec; ca.sC = P.sVec; ca.prob0 = (int)k0;      // C: indexed from hh's problem 0
-                if (P.F == 16) hipLaunchKernelGGL(k_caqr_vec_batched<4>, dim3(L.groups, cn), dim3(256), 0, s, ca, a.dims);
-                else hipLaunchKernelGGL(k_caqr_vec_batched<2>, dim3(L.groups, cn), dim3(128), 0, s, ca, a.dims);
-            }
-        if (kpmax > 0) hipLaunchKernelGGL(k_vec_reflectors_batched, dim3(cn), dim3(64), 0, s, a);
+        else GN_LAUNCH_BIG(k_subspace_head<256>, dim3(cn), dim3(256), lds_h, s, a, c);
+        rc = resolve_d_stages(hh, a, k0, cnt, kpmax, nullptr);
+        if (rc) return rc;
     }
     if (small) hipLaunchKernelGGL(k_subspace_dimj2<64>, dim3(cn), dim3(64), lds_j, s, a, c);
     else hipLaunchKernelGGL(k_subspace_dimj2<256>, dim3(cn), dim3(256), lds_j, s, a, c);
@@ -83,12 +66,9 @@ int subspace_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const ResolveDim
         rc = resolve_stages(hh, a, k0, cnt, kpmax, small, false, nullptr);
         if (rc) return rc;
     }
-    const size_t lds = resolve_lds_bytes(a.nv, a.blkd);
-    if (small) hipLaunchKernelGGL((k_resolve_tail<1, 64>), dim3(cn), dim3(64), lds, s, a);
-    else if (P.n <= 512) hipLaunchKernelGGL((k_resolve_tail<8, 256>), dim3(cn), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_resolve_tail<0, 256>), dim3(cn), dim3(256), lds, s, a);
+    resolve_tail_launch(hh, a, cnt, small);
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(hh->h_ssb, d2, db, hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(hh->h_ssb.p, d2, db, hipMemcpyDeviceToHost, s));
     GN_HIP(hipMemcpyAsync(hh->h_state + k0, hh->state + k0, (size_t)cnt * sizeof(ProbState), hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -200,7 +180,7 @@ int subspace_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t
     bool flagged = false;
     for (const ResidentSeg& sg : r.seg) {
         GN_HIP(hipStreamSynchronize(sg.hh->stream));
-        const ResolveDims* res = (const ResolveDims*)sg.hh->h_ssb;
+        const ResolveDims* res = (const ResolveDims*)sg.hh->h_ssb.p;
         for (long long jj = 0; jj < sg.cnt; ++jj) {
             if (dims[(size_t)(sg.j0 + jj)].code == 0) continue;
             flagged = flagged || res[jj].status != 0;
@@ -220,16 +200,10 @@ int subspace_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t
             bool wrote_p = false;
             rc = subspace_alone(h, prob0 + j, at, P, prev[j], hp.data(), hb.data(), hd_.data(), &st, &wrote_p);
             if (rc) return rc;
-            if (st != CHOICE_OUT_OF_BOUNDS) {
-                if (io.p && wrote_p) GN_HIP(hipMemcpy(io.p + j * P.n, hp.data(), (size_t)P.n * 8, hipMemcpyHostToDevice));
-                if (io.b && P.t > 0) GN_HIP(hipMemcpy(io.b + j * P.t, hb.data(), (size_t)P.t * 8, hipMemcpyHostToDevice));
-                if (io.d) GN_HIP(hipMemcpy(io.d + j * P.m, hd_.data(), (size_t)P.m * 8, hipMemcpyHostToDevice));
-                if (io.info && wrote_p) {
-                    const enlsip_gn_info inf = info_of(at.hh->h_state[at.k]);
-                    GN_HIP(hipMemcpy(io.info + j, &inf, sizeof(inf), hipMemcpyHostToDevice));
-                }
-            }
-            if (io.status) GN_HIP(hipMemcpy(io.status + j, &st, sizeof(int), hipMemcpyHostToDevice));
+            const enlsip_gn_info inf = info_of(at.hh->h_state[at.k]);
+            if (st == CHOICE_OUT_OF_BOUNDS) rc = write_alone_slot(h, io, j, P, nullptr, nullptr, nullptr, nullptr, st);
+            else rc = write_alone_slot(h, io, j, P, wrote_p ? hp.data() : nullptr, hb.data(), hd_.data(), wrote_p ? &inf : nullptr, st);
+            if (rc) return rc;
             flagged = flagged || st != 0;
         }
     }
@@ -272,21 +246,11 @@ int enlsip_gn_subspace_direction_batched(enlsip_gn_handle h, int64_t prob0, int6
     if (!h) return -1;
     GN_TRY
     ResidentRange r;
-    int rc = resident_range(h, prob0, count, r);
+    const int rc = resident_range(h, prob0, count, r);
     if (rc) return rc;
     if (!prev) { h->err = "prev is a host array of count entries"; return -4; }
-    const Plan& P = r.plan();
-    const size_t c = (size_t)count;
-    // staged through a buffer of its own; the caller's arrays go in first so that the slots the call leaves alone come back as they were
-    Staged a[5] = {{p, c * P.n * 8, true, true}, {b, c * P.t * 8, true, true}, {d, c * P.m * 8, true, true},
-                   {info, c * sizeof(enlsip_gn_info), true, true}, {status, c * sizeof(int), true, true}};
-    rc = stage_in(h, h->ssb_io, a, 5);
-    if (rc) return rc;
-    rc = subspace_dev(h, prob0, count, take, prev,
-                      {(double*)a[0].dev, (double*)a[1].dev, (double*)a[2].dev, (enlsip_gn_info*)a[3].dev, (int*)a[4].dev});
-    if (rc < 0 || rc > 1) return rc;
-    const int rc2 = stage_out(h, a, 5);
-    return rc2 ? rc2 : rc;
+    return staged_outputs_call(h, h->ssb_io, count, r.plan(), {p, b, d, info, status},
+                               [&](const ResolveIO& io) { return subspace_dev(h, prob0, count, take, prev, io); });
     GN_CATCH(h)
 }
 

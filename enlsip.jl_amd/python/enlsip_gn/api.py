@@ -41,6 +41,11 @@ def _fptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dptr(x: int):
+    """a raw device pointer for the device forms; 0 is NULL"""
+    return C.c_void_p(x) if x else None
+
+
 def determine_solving_dim(previous_dimR: int, rankR: int, predicted_linear_progress: float, obj_progress: float,
                           prelin_previous_dim: float, diagR, y, previous_alpha: float, restart: bool) -> int:
     """determine_solving_dim (src/enlsip_functions.jl:1041-1113) on host data, through the library's host entry point (no GPU):
@@ -305,11 +310,10 @@ class GNSolver:
     def solve_batched_ragged_dev(self, batch, m, n, t_max, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx,
                                  eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):
         """Device pointers as solve_batched_dev; t stays a host array of batch entries."""
-        v = lambda x: C.c_void_p(x) if x else None
         t = np.ascontiguousarray(t, dtype=np.int64)
         self._chk(self._lib.enlsip_gn_solve_batched_ragged_dev(
-            self._h, batch, m, n, t_max, t.ctypes.data_as(C.c_void_p), v(dJ), ldj, strideJ, v(drx), v(dAt), ldat, strideAt,
-            v(dcx), eps_rank, v(dp), v(db), v(dd), v(dinfo), v(djA), v(djL), v(djJ)))
+            self._h, batch, m, n, t_max, t.ctypes.data_as(C.c_void_p), _dptr(dJ), ldj, strideJ, _dptr(drx), _dptr(dAt), ldat,
+            strideAt, _dptr(dcx), eps_rank, _dptr(dp), _dptr(db), _dptr(dd), _dptr(dinfo), _dptr(djA), _dptr(djL), _dptr(djJ)))
 
     # ---- batched constraint stage and the solve that goes on with it (src/enlsip_functions.jl:700-704, then :725 / :771) ----------
     @staticmethod
@@ -363,13 +367,12 @@ class GNSolver:
 
     def factor_constraints_batched_dev(self, batch, m, n, t_max, t, dAt, ldat, strideAt, dcx, eps_rank=SQRT_EPS, dinfo=0):
         """Device pointers; t stays a host array of batch entries (None: all t_max)."""
-        v = lambda x: C.c_void_p(x) if x else None
         if t is not None:
             t = np.ascontiguousarray(t, dtype=np.int64)
             if t.shape != (batch,):
                 raise ValueError(f"t must have {batch} entries")
         self._chk(self._lib.enlsip_gn_factor_constraints_batched_dev(
-            self._h, batch, m, n, t_max, _fptr(t), v(dAt), ldat, strideAt, v(dcx), eps_rank, v(dinfo)))
+            self._h, batch, m, n, t_max, _fptr(t), _dptr(dAt), ldat, strideAt, _dptr(dcx), eps_rank, _dptr(dinfo)))
 
     def solve_factored_batched(self, J: np.ndarray, rx: np.ndarray, At: np.ndarray, cx: np.ndarray, t=None, refactor=None,
                                eps_rank: float = SQRT_EPS):
@@ -407,15 +410,14 @@ class GNSolver:
                                    eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):
         """Device pointers as solve_batched_ragged_dev; t and refactor stay host arrays.  dAt, ldat, strideAt, dcx are those of
         factor_constraints_batched_dev, the flagged problems' slots rewritten in place."""
-        v = lambda x: C.c_void_p(x) if x else None
         if t is not None:
             t = np.ascontiguousarray(t, dtype=np.int64)
             if t.shape != (batch,):
                 raise ValueError(f"t must have {batch} entries")
         r = self._refactor_mask(refactor, batch)
         self._chk(self._lib.enlsip_gn_solve_factored_batched_dev(
-            self._h, batch, m, n, t_max, _fptr(t), _fptr(r), v(dJ), ldj, strideJ, v(drx), v(dAt), ldat, strideAt, v(dcx),
-            eps_rank, v(dp), v(db), v(dd), v(dinfo), v(djA), v(djL), v(djJ)))
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(r), _dptr(dJ), ldj, strideJ, _dptr(drx), _dptr(dAt), ldat, strideAt,
+            _dptr(dcx), eps_rank, _dptr(dp), _dptr(db), _dptr(dd), _dptr(dinfo), _dptr(djA), _dptr(djL), _dptr(djJ)))
 
     def constraint_refactored(self) -> int:
         """Problems the constraint kernels of the last factor_constraints_batched / solve_factored_batched were launched over."""
@@ -458,14 +460,13 @@ class GNSolver:
                                   dinfo=0, djA=0, djL=0, djJ=0):
         """Device pointers; t and changed stay host arrays.  dAt, ldat, strideAt, dcx are the buffers of the resident solve, the
         flagged problems' slots rewritten in place; only the flagged problems' output slots are written."""
-        v = lambda x: C.c_void_p(x) if x else None
         t = np.ascontiguousarray(t, dtype=np.int64)
         if t.shape != (batch,):
             raise ValueError(f"t must have {batch} entries")
         ch = self._changed_mask(changed, batch)
         self._chk(self._lib.enlsip_gn_solve_changed_batched_dev(
-            self._h, batch, m, n, t_max, _fptr(t), _fptr(ch), v(dAt), ldat, strideAt, v(dcx), eps_rank, v(dp), v(db), v(dd),
-            v(dinfo), v(djA), v(djL), v(djJ)))
+            self._h, batch, m, n, t_max, _fptr(t), _fptr(ch), _dptr(dAt), ldat, strideAt, _dptr(dcx), eps_rank, _dptr(dp), _dptr(db),
+            _dptr(dd), _dptr(dinfo), _dptr(djA), _dptr(djL), _dptr(djJ)))
 
     def jacobian_resolved(self) -> int:
         """Problems the Jacobian-side kernels of the last solve were launched over (both pipelined halves): batch after a
@@ -477,10 +478,9 @@ class GNSolver:
     # ---- batch, device buffers (raw pointers, e.g. torch tensor .data_ptr()) ------------------
     def solve_batched_dev(self, batch, m, n, t, dJ, ldj, strideJ, drx, dAt, ldat, strideAt, dcx,
                           eps_rank=SQRT_EPS, dp=0, db=0, dd=0, dinfo=0, djA=0, djL=0, djJ=0):
-        v = lambda x: C.c_void_p(x) if x else None
         self._chk(self._lib.enlsip_gn_solve_batched_dev(
-            self._h, batch, m, n, t, v(dJ), ldj, strideJ, v(drx), v(dAt), ldat, strideAt, v(dcx), eps_rank,
-            v(dp), v(db), v(dd), v(dinfo), v(djA), v(djL), v(djJ)))
+            self._h, batch, m, n, t, _dptr(dJ), ldj, strideJ, _dptr(drx), _dptr(dAt), ldat, strideAt, _dptr(dcx), eps_rank,
+            _dptr(dp), _dptr(db), _dptr(dd), _dptr(dinfo), _dptr(djA), _dptr(djL), _dptr(djJ)))
 
     # ---- resident factors ---------------------------------------------------------------------
     def factor(self, which: int, prob: int = 0) -> FactorView:
@@ -594,30 +594,30 @@ class GNSolver:
 
     # device forms: raw device pointers (e.g. torch tensor .data_ptr(), 0 = NULL); return the call's rc (0 or 1)
     def gradient_batched_dev(self, prob0: int, count: int, dgrad: int) -> int:
-        v = lambda x: C.c_void_p(x) if x else None
-        return self._chk_batched(self._lib.enlsip_gn_gradient_batched_dev(self._h, prob0, count, v(dgrad)))
+        return self._chk_batched(self._lib.enlsip_gn_gradient_batched_dev(self._h, prob0, count, _dptr(dgrad)))
 
     def jacobian_times_batched_dev(self, prob0: int, count: int, dp: int, dJp: int = 0, dAp: int = 0) -> int:
-        v = lambda x: C.c_void_p(x) if x else None
-        return self._chk_batched(self._lib.enlsip_gn_jacobian_times_batched_dev(self._h, prob0, count, v(dp), v(dJp), v(dAp)))
+        return self._chk_batched(self._lib.enlsip_gn_jacobian_times_batched_dev(
+            self._h, prob0, count, _dptr(dp), _dptr(dJp), _dptr(dAp)))
 
     def first_lagrange_batched_dev(self, prob0: int, count: int, dlambda: int, dgrad_fx: int = 0, ddiag_scale: int = 0,
                                    eps_rank: float = SQRT_EPS, dgrad_res: int = 0, dstatus: int = 0) -> int:
-        v = lambda x: C.c_void_p(x) if x else None
         return self._chk_batched(self._lib.enlsip_gn_first_lagrange_batched_dev(
-            self._h, prob0, count, v(dgrad_fx), v(ddiag_scale), eps_rank, v(dlambda), v(dgrad_res), v(dstatus)))
+            self._h, prob0, count, _dptr(dgrad_fx), _dptr(ddiag_scale), eps_rank, _dptr(dlambda), _dptr(dgrad_res), _dptr(dstatus)))
 
     def second_lagrange_batched_dev(self, prob0: int, count: int, dp_gn: int, dlambda: int, ddiag_scale: int = 0,
                                     eps_rank: float = SQRT_EPS, dstatus: int = 0) -> int:
-        v = lambda x: C.c_void_p(x) if x else None
         return self._chk_batched(self._lib.enlsip_gn_second_lagrange_batched_dev(
-            self._h, prob0, count, v(dp_gn), v(ddiag_scale), eps_rank, v(dlambda), v(dstatus)))
+            self._h, prob0, count, _dptr(dp_gn), _dptr(ddiag_scale), eps_rank, _dptr(dlambda), _dptr(dstatus)))
+
+    def _form(self, getter_name: str) -> int:
+        f = C.c_int(0)
+        self._chk(getattr(self._lib, getter_name)(self._h, C.byref(f)))
+        return int(f.value)
 
     def consumer_form(self) -> int:
         """Form of the last batched multiplier estimate: 0 general, 1 wave per problem, -1 none yet."""
-        f = C.c_int(0)
-        self._chk(self._lib.enlsip_gn_get_consumer_form(self._h, C.byref(f)))
-        return int(f.value)
+        return self._form("enlsip_gn_get_consumer_form")
 
     # ---- the subspace re-solve over a range of the resident batch (src/enlsip_functions.jl:1249-1253, :1118-1176, :116-153) ------
     @staticmethod
@@ -663,10 +663,9 @@ class GNSolver:
     def resolve_batched_dev(self, prob0: int, count: int, dimA, dimJ2, code=-1, dp: int = 0, db: int = 0, dd: int = 0,
                             dinfo: int = 0, dstatus: int = 0) -> int:
         """Device form: dimA / dimJ2 / code stay host arrays, the outputs are raw device pointers (0 = NULL)."""
-        v = lambda x: C.c_void_p(x) if x else None
         dA, dJ, cd = self.pack_resolve(count, dimA, dimJ2, code)
         return self._chk_batched(self._lib.enlsip_gn_resolve_batched_dev(
-            self._h, prob0, count, _fptr(dA), _fptr(dJ), _fptr(cd), v(dp), v(db), v(dd), v(dinfo), v(dstatus)))
+            self._h, prob0, count, _fptr(dA), _fptr(dJ), _fptr(cd), _dptr(dp), _dptr(db), _dptr(dd), _dptr(dinfo), _dptr(dstatus)))
 
     def diagR_batched(self, which: int, stride: int, prob0: int = 0, count: int = 1) -> np.ndarray:
         """diag(F.R) of problems prob0 .. prob0+count-1: (count, stride), zeros past each problem's own length."""
@@ -676,9 +675,7 @@ class GNSolver:
 
     def resolve_form(self) -> int:
         """Kernel form of the last resolve_batched: 0 general, 1 one wave per problem, -1 none yet."""
-        f = C.c_int(0)
-        self._chk(self._lib.enlsip_gn_get_resolve_form(self._h, C.byref(f)))
-        return int(f.value)
+        return self._form("enlsip_gn_get_resolve_form")
 
     def resolve_q0_ms(self) -> float:
         """HIP-event time of the Q0' launches of the last resolve_batched (set_profiling(True) before it; 0 otherwise)."""
@@ -734,17 +731,14 @@ class GNSolver:
     def subspace_direction_batched_dev(self, prob0: int, count: int, prev, take=None, dp: int = 0, db: int = 0, dd: int = 0,
                                        dinfo: int = 0, dstatus: int = 0) -> int:
         """Device form: prev and take stay host arrays, the outputs are raw device pointers (0 = NULL)."""
-        v = lambda x: C.c_void_p(x) if x else None
         pv = self._prev_arg(count, prev)
         tk = self._pack_take(count, take)
         return self._chk_batched(self._lib.enlsip_gn_subspace_direction_batched_dev(
-            self._h, prob0, count, _fptr(tk), _fptr(pv), v(dp), v(db), v(dd), v(dinfo), v(dstatus)))
+            self._h, prob0, count, _fptr(tk), _fptr(pv), _dptr(dp), _dptr(db), _dptr(dd), _dptr(dinfo), _dptr(dstatus)))
 
     def subspace_form(self) -> int:
         """Kernel form of the last subspace_direction_batched: 0 general, 1 one wave per problem, -1 none yet."""
-        f = C.c_int(0)
-        self._chk(self._lib.enlsip_gn_get_subspace_form(self._h, C.byref(f)))
-        return int(f.value)
+        return self._form("enlsip_gn_get_subspace_form")
 
     # ---- the deletion test and the working-set edit on device buffers (src/enlsip_functions.jl:574-603, :708-719, :731-739) --------
     @staticmethod
@@ -760,30 +754,27 @@ class GNSolver:
         (A', cx, lambda, diag_scale in the padded ragged layout; the removed record into dsaved, n + 3 doubles per problem).  t, q,
         take (None: all) stay host arrays; dgrad_res = 0: grad_res = 0.0 (the second-order test).  Returns s (batch,) int64,
         1-based, 0 = nothing; t is the caller's to decrement."""
-        v = lambda x: C.c_void_p(x) if x else None
         t = self._host_i64(t, batch, "t")
         q = self._host_i64(q, batch, "q")
-        tk = None if take is None else self._host_i64(take, batch, "take")
+        tk = self._pack_take(batch, take)
         s = np.zeros(batch, dtype=np.int64)
         self._chk(self._lib.enlsip_gn_delete_constraints_batched_dev(
-            self._h, batch, n, t_max, _fptr(t), _fptr(q), _fptr(tk), int(bool(scaling)), v(dlambda), v(ddiag_scale), v(dgrad_res),
-            v(dAt), ldat, strideAt, v(dcx), v(dsaved), _fptr(s)))
+            self._h, batch, n, t_max, _fptr(t), _fptr(q), _fptr(tk), int(bool(scaling)), _dptr(dlambda), _dptr(ddiag_scale),
+            _dptr(dgrad_res), _dptr(dAt), ldat, strideAt, _dptr(dcx), _dptr(dsaved), _fptr(s)))
         return s
 
     def restore_constraints_batched_dev(self, batch, n, t_max, t, s, dlambda, ddiag_scale, dAt, ldat, strideAt, dcx, dsaved):
         """The exact inverse of delete_constraints_batched_dev for the problems with s[k] != 0; t[k] is the count after the
         deletion.  The caller increments t."""
-        v = lambda x: C.c_void_p(x) if x else None
         t = self._host_i64(t, batch, "t")
         s = self._host_i64(s, batch, "s")
         self._chk(self._lib.enlsip_gn_restore_constraints_batched_dev(
-            self._h, batch, n, t_max, _fptr(t), _fptr(s), v(dlambda), v(ddiag_scale), v(dAt), ldat, strideAt, v(dcx), v(dsaved)))
+            self._h, batch, n, t_max, _fptr(t), _fptr(s), _dptr(dlambda), _dptr(ddiag_scale), _dptr(dAt), ldat, strideAt, _dptr(dcx),
+            _dptr(dsaved)))
 
     def deletion_form(self) -> int:
         """Kernel form of the last delete / restore call: 0 general, 1 one wave per problem, -1 none yet."""
-        f = C.c_int(0)
-        self._chk(self._lib.enlsip_gn_get_deletion_form(self._h, C.byref(f)))
-        return int(f.value)
+        return self._form("enlsip_gn_get_deletion_form")
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).
@@ -798,12 +789,7 @@ class GNSolver:
     # ---- the Newton direction over a range of the resident batch (src/enlsip_functions.jl:371-421) ---------------------------------
     @staticmethod
     def _pack_take(count: int, take):
-        if take is None:
-            return None
-        tk = np.ascontiguousarray(np.asarray(take).astype(np.int64))
-        if tk.shape != (count,):
-            raise ValueError(f"take must have {count} entries")
-        return tk
+        return None if take is None else GNSolver._host_i64(take, count, "take")
 
     def newton_direction_batched(self, Gammas: np.ndarray, prob0: int = 0, count: Optional[int] = None, take=None,
                                  out_p: Optional[np.ndarray] = None, out_status: Optional[np.ndarray] = None):
@@ -835,16 +821,13 @@ class GNSolver:
                                      take=None) -> int:
         """Device form: dGamma (column-major n x n per slot, ldg, strideG), dp (count x n) and dstatus are raw device pointers
         (0 = NULL); take stays a host array."""
-        v = lambda x: C.c_void_p(x) if x else None
         tk = self._pack_take(count, take)
         return self._chk_batched(self._lib.enlsip_gn_newton_direction_batched_dev(
-            self._h, prob0, count, v(dGamma), ldg, strideG, _fptr(tk), v(dp), v(dstatus)))
+            self._h, prob0, count, _dptr(dGamma), ldg, strideG, _fptr(tk), _dptr(dp), _dptr(dstatus)))
 
     def newton_form(self) -> int:
         """Kernel form of the last newton_direction_batched: 0 general, 1 one wave per problem, -1 none yet."""
-        f = C.c_int(0)
-        self._chk(self._lib.enlsip_gn_get_newton_form(self._h, C.byref(f)))
-        return int(f.value)
+        return self._form("enlsip_gn_get_newton_form")
 
     def newton_stage_ms(self):
         """HIP-event times of the four stages of the last newton_direction_batched (set_profiling(True) before it; zeros otherwise):

@@ -117,11 +117,11 @@ def same_images(got, want):
         assert got[nm].tobytes() == want[nm].tobytes(), nm
 
 
-def batch_t_q(t_max, seed):
+def batch_t_q(t_max, seed, batch=BATCH):
     rng = np.random.default_rng(seed)
-    t = rng.integers(0, t_max + 1, BATCH)
+    t = rng.integers(0, t_max + 1, batch)
     t[1], t[2] = 0, t_max
-    t[BATCH - 1] = t_max
+    t[batch - 1] = t_max
     q = np.array([rng.integers(0, tk + 1) for tk in t], dtype=np.int64)
     q[2] = 0
     return t.astype(np.int64), q
@@ -184,6 +184,38 @@ def test_decision_edit_and_restore(solver, n, t_max, padded):
         solver.restore_constraints_batched_dev(BATCH, n, t_max, t1, np.zeros(BATCH, dtype=np.int64), buf.ptr("lam"), buf.ptr("ds"),
                                                *buf.a_args(), 0)
         same_images(buf.download(), got)
+
+
+@pytest.mark.parametrize("n,t_max", [(8, 4), (80, 70)], ids=["wave", "general"])
+def test_scratch_growth_changes_no_result(n, t_max):
+    """the records of a call (device and pinned) grow between batch 3 and batch 40 on the SAME solver: the delete and the restore
+    at batch 40 answer bit for bit as on a solver that never made the smaller calls"""
+    from enlsip_gn import GNSolver
+
+    def delete_and_restore(s, batch):
+        t, q = batch_t_q(t_max, seed=40 * n + batch, batch=batch)
+        buf = Buffers(n, t_max, t, True, seed=batch)
+        buf.upload()
+        sd = s.delete_constraints_batched_dev(batch, n, t_max, t, q, True, buf.ptr("lam"), buf.ptr("ds"), *buf.a_args(),
+                                              dgrad_res=buf.ptr("gres"), dsaved=buf.ptr("saved"))
+        after = buf.download()
+        s.restore_constraints_batched_dev(batch, n, t_max, t - (sd != 0), sd, buf.ptr("lam"), buf.ptr("ds"), *buf.a_args(),
+                                          buf.ptr("saved"))
+        return sd, after, buf.download(), s.deletion_form()
+
+    grown, fresh = GNSolver(device=0), GNSolver(device=0)
+    try:
+        small = delete_and_restore(grown, 3)
+        got = delete_and_restore(grown, 40)
+        want = delete_and_restore(fresh, 40)
+        assert small[0].any() and want[0].any() and not want[0].all()      # rows were deleted and put back at both sizes
+        assert got[3] == want[3] == (1 if n <= 64 else 0)
+        assert got[0].tobytes() == want[0].tobytes()
+        same_images(got[1], want[1])
+        same_images(got[2], want[2])
+    finally:
+        grown.close()
+        fresh.close()
 
 
 # ---- 2. the edge inputs of the CPU file, through both forms ------------------------------------------------------------------------

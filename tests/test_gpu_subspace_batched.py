@@ -240,6 +240,52 @@ def test_range_over_the_pipelined_halves(monkeypatch):
         s.close()
 
 
+def growth_case(name):
+    """a resident batch, its previous iterates and the small range of the first call, which the whole-batch call outgrows"""
+    from enlsip_gn import GNSolver
+    if name == "halves":      # the batch of test_range_over_the_pipelined_halves: both half handles grow their own scratch
+        B, m, n, t = 130, 64, 8, 2
+        J = synth.normal_stream(10500, 0, B * m * n).reshape(B, n, m)
+        rx = synth.normal_stream(10500, 1, B * m).reshape(B, m)
+        At = synth.normal_stream(10500, 2, B * t * n).reshape(B, t, n)
+        cx = synth.normal_stream(10500, 3, B * t).reshape(B, t)
+        pv = GNSolver.pack_subspace_prev(B, [2 - (k % 2) for k in range(B)], [6 - (k % 4) for k in range(B)],
+                                         [int(k % 9 == 0) for k in range(B)], [(0.05, 0.5, 1.0)[k % 3] for k in range(B)],
+                                         [0.21 * float(cx[k] @ cx[k]) for k in range(B)], [0.1 * float(rx[k] @ rx[k]) for k in range(B)])
+        return (B, m, n, t), lambda s: s.solve_batched(J, rx, At, cx), pv, {"ENLSIP_GN_PIPELINE": "1"}
+    B, m, n, t = {"wave": (6, 64, 8, 3), "general": (6, 300, 80, 12)}[name]
+    probs = rb.make_batch(11000, B, m, n, t)
+    refs = [go.gn_subproblem(*p) for p in probs]
+    pv = pack_prev([prev_record(probs[k], t, rb.fabricated_previous(k, probs[k], refs[k], t), False) for k in range(B)])
+    return (B, m, n, t), lambda s: rb.solve(s, probs, t, False), pv, {}
+
+
+@pytest.mark.parametrize("name", ["wave", "general", "halves"])
+def test_scratch_growth_changes_no_result(name, monkeypatch):
+    """the per-call scratch (requests on the device, their pinned copy, the staging of the host-buffer form) grows between a call
+    over two problems and one over the whole batch on the SAME solver: the second call answers bit for bit as on a solver that
+    never made the first.  halves: the first range is the last problem of one pipelined half and the first of the other."""
+    (B, m, n, t), solve, pv, env = growth_case(name)
+    grown, fresh = rb.make_solver(monkeypatch, **env), rb.make_solver(monkeypatch, **env)
+    try:
+        solve(grown)
+        solve(fresh)
+        first = grown.pipeline_split() - 1 if name == "halves" else 0
+        assert first >= 0 and grown.pipeline_split() == fresh.pipeline_split()
+        _, rc = grown.subspace_direction_batched(m, n, t, pv[first:first + 2], first, 2)
+        assert rc in (0, 1)
+        got, rc_got = grown.subspace_direction_batched(m, n, t, pv, 0, B)
+        want, rc_want = fresh.subspace_direction_batched(m, n, t, pv, 0, B)
+        assert grown.subspace_form() == fresh.subspace_form() == (0 if name == "general" else 1)
+        print(f"{name}: rc {rc_got} / {rc_want}, statuses {sorted(set(int(x) for x in want['status']))}")
+        assert rc_got == rc_want == 0 and np.all(want["status"] == 0)      # every slot was answered in full
+        for key in ("p", "b", "d", "info", "status"):
+            assert got[key].tobytes() == want[key].tobytes(), key
+    finally:
+        grown.close()
+        fresh.close()
+
+
 def test_statuses_and_refusals(monkeypatch):
     B, m, n, t = 6, 300, 24, 5
     probs = rb.make_batch(10600, B, m, n, t)
