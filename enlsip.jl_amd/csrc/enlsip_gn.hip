@@ -68,8 +68,6 @@ using namespace gn;
         return 997;                                                                    \
     }
 
-static inline long long rup(long long x, long long a) { return (x + a - 1) / a * a; }
-
 #define GN_TRACE(h, ...)                                              \
     do {                                                              \
         if ((h)->trace) {                                             \
@@ -103,131 +101,29 @@ static int grow_pinned(enlsip_gn_handle h, PinnedBuf& b, size_t bytes) {
     return 0;
 }
 
+// A layout (gn_layout.hpp, gn_plan.hpp) in a device buffer / in a call's pinned scratch: measure, grow, place.
+template <class Layout, class... Shape>
+static int place_dev(enlsip_gn_handle h, DevBuf& b, Layout& L, const Shape&... shape) {
+    return place(L, [&](size_t bytes, void** base) { const int rc = grow(h, b, bytes); *base = b.p; return rc; }, shape...);
+}
+template <class Layout, class... Shape>
+static int place_pinned(enlsip_gn_handle h, PinnedBuf& b, Layout& L, const Shape&... shape) {
+    return place(L, [&](size_t bytes, void** base) { const int rc = grow_pinned(h, b, bytes); *base = b.p; return rc; }, shape...);
+}
+static_assert(PLAN_PB == PB && PLAN_KBLK == KBLK && PLAN_QD_CPW == QD_CPW && PLAN_QDCAND_BYTES == sizeof(QdCand) &&
+              PLAN_SBINFO_BYTES == sizeof(SbInfo), "gn_plan.hpp sizes the workspaces with the kernels' constants");
+// the pair rule lives in plan_geometry; the dispatch tests read its threshold from this file, so it is pinned here
+static_assert(PLAN_PAIR_MIN_WGS == 8192, "panel pairs from far_wgs >= 8192 on (plan_geometry)");
+
 // ---------------------------------------------------------------------------------------------
-// plan: geometry + workspace carve for (batch, m, n, t)
+// plan: geometry (gn_plan.hpp) + placed workspace for (batch, m, n, t)
 // ---------------------------------------------------------------------------------------------
 static int make_plan(enlsip_gn_handle h, long long batch, long long m, long long n, long long t) {
     Plan& P = h->plan;
     if (h->have_plan && P.batch == batch && P.m == m && P.n == n && P.t == t) return 0;
-    P = Plan();
-    P.batch = batch; P.m = m; P.n = n; P.t = t;
-    P.kA = (int)std::min(n, t);
-    P.RPL = (m <= 256 ? 256 : h->tile_rows) / 64;      // a problem of at most 256 rows is one 256-row tile
-    P.F = 2 * P.RPL;
-    P.ldw = (int)rup(std::max<long long>(m, 1), 32);
-    // a leading dimension that is a multiple of 4 KB puts the same row range of every column on the
-    // same few HBM channels (measured: 4x slower edge tiles at ldw = 4096): skew it by one 256-B block
-    if (P.ldw % 512 == 0) P.ldw += 32;
-    const long long kpmax = std::min(m, n);
-    P.ldr = (int)rup(std::max<long long>(kpmax, 1), 8);
-    P.npan_max = (int)((kpmax + PB - 1) / PB);
-    long long running = 0;
-    P.panels.resize(P.npan_max);
-    // panel pairs (gn_kernels_caqr.hpp): from three panels on; the reflector-by-reflector A/B path keeps the plain sweep
-    // ... and only where the far update is the bulk of the sweep: the pair costs two extra small launches per two panels
-    // (the first panel's level-0 and tree reflectors on the second panel's 32 columns), which a latency-bound sweep does not
-    // earn back.  Measured (MI355X): 384 x C2 +1.4 % solves/s and C4's 262144 rows 29.7 -> 27.4 ms with pairs, but a single
-    // C2 problem 5.17 -> 5.37 ms, 64 of them 10.35 -> 10.47 ms, a 32768-row C4 shard 16.8 -> 17.2 ms.  Rule: at least ~8192
-    // far-update workgroups in the first pair (tiles x 32-column blocks x problems); ENLSIP_GN_PAIR=1 forces pairs.
-    const long long far_wgs = batch * ((std::max<long long>(m, 1) + 64 * P.RPL - 1) / (64 * P.RPL)) * ((std::max<long long>(n - P.kA, 1) + 31) / 32);
-    P.pair = h->pair_enabled && !(h->flags & ENLSIP_GN_UPDATE_REFLECTORS) && P.npan_max >= 3 && (far_wgs >= 8192 || h->pair_forced);
-    const long long mpad = rup(std::max<long long>(m, 1), 32);    // NOT ldw: the skew rows are never touched
-    for (int k = 0; k < P.npan_max; ++k) {
-        const bool second = P.pair && (k & 1);                    // second panel of the pair (k - 1, k): keeps the first one's tiles
-        const long long anchor = 32LL * (k - (second ? 1 : 0));   // first row of tile 0
-        const int nb0 = (int)((mpad - anchor) / 32);              // 32-row blocks from the anchor to the padded m
-        const int ntiles = (nb0 + P.F - 1) / P.F;
-        const int last_units = nb0 - (ntiles - 1) * P.F;          // blocks of the last tile
-        auto push = [&](int level, int mode, long long base, int skip, int nblocks, int groups, long long S) {
-            LevelPlan L;
-            L.level = level; L.mode = mode; L.base = base; L.skip = skip;
-            L.nblocks = nblocks; L.groups = groups; L.S = S;
-            L.tOff = running;
-            running += groups;
-            P.panels[k].levels.push_back(L);
-        };
-        // level 0: the tiles (a tile that has no row of the second panel still gets its — zero — T block: the pair update indexes
-        // T by tile)
-        push(0, 0, anchor, second ? 1 : 0, nb0, ntiles, 32);
-        if (ntiles <= 1) continue;
-        int level = 1, nb;
-        long long S = 32LL * P.F, base = 32LL * k;
-        if (!second) nb = ntiles;
-        else {
-            // first tree level of the second panel: per tile the new R factor (rows 32..63) and, from tile 1 on, the rows 0..31
-            // the first panel's tree left behind (dense in these columns): mode 2
-            const int nblocks1 = (ntiles - (last_units == 1 ? 1 : 0)) + (ntiles - 1);
-            const int groups1 = (nblocks1 + P.F - 1) / P.F;
-            push(1, 2, anchor, 0, nblocks1, groups1, S);
-            if (groups1 <= 1) continue;
-            // group leaders: blocks F q of level 1 = (tile (F / 2) q, rows 32..63)
-            nb = groups1;
-            S = S * (P.F / 2);
-            level = 2;
-        }
-        while (true) {
-            const int groups = (nb + P.F - 1) / P.F;
-            push(level, 1, base, 0, nb, groups, S);
-            if (groups <= 1) break;
-            nb = groups;
-            S *= P.F;
-            ++level;
-        }
-    }
-    P.nTblocks = std::max<long long>(running, 1);
-    const long long nblkA = std::max<long long>((P.kA + KBLK - 1) / KBLK, 1);
-    auto pad = [](long long x) { return rup(std::max<long long>(x, 1), 32); };  // 256 B granules
-    P.sFA = pad(n * t); P.sTauA = pad(P.kA); P.sJA = pad(t);
-    P.sFL = pad(t * P.kA); P.sTauL = pad(P.kA); P.sJL = pad(P.kA);
-    P.sTA = pad(nblkA * KBLK * KBLK); P.sP1 = pad(t); P.sB = pad(t);
-    // 32 spare columns per problem: the trailing-update kernel reads (and discards) whole 32-column blocks
-    P.sW = pad((long long)P.ldw * (n + 1 + 32));
-    P.sT = pad(P.nTblocks * PB * PB);
-    P.sRt = pad((long long)P.ldr * (n + 1));
-    P.sTauJ = pad(kpmax); P.sJJ = pad(n); P.sZ = pad(kpmax);
-    P.sVec = pad((long long)P.ldw * 2);
-    // + 33 columns: k_sb_update_blk reads whole 32-column / 32-row blocks past the last valid element
-    P.sM = pad((long long)P.ldr * (n + 1 + 33)); P.sVb = pad((long long)P.ldr * (std::max<long long>(kpmax, 1) + 33));
-    P.sDiag = pad(kpmax); P.sVn = pad(n); P.sQI = pad(n);
-    P.qdGmax = (int)((n + 1 + QD_CPW - 1) / QD_CPW);
-    P.sCand = 2 * (long long)P.qdGmax;
-    const long long per_dbl = P.sFA + P.sTauA + P.sFL + P.sTauL + P.sTA + P.sP1 + P.sB + P.sW + P.sT + P.sRt +
-                              P.sTauJ + P.sZ + P.sVec + P.sM + P.sVb + P.sDiag + 2 * P.sVn + PB * PB;
-    const long long per_i64 = P.sJA + P.sJL + P.sJJ;
-    const long long per_i32 = 7 * P.sQI + 32;   // chosen + 2 x pos + 2 x colat + inblk + active list (n + 1 entries)
-    const size_t bytes = (size_t)batch * (per_dbl * 8 + per_i64 * 8 + per_i32 * 4 + P.sCand * sizeof(QdCand)) +
-                         (size_t)batch * (sizeof(ProbState) + sizeof(SbInfo)) + 8192;
-    int rc = grow(h, h->ws, bytes);
+    P = plan_geometry(batch, m, n, t, h->tile_rows, (h->flags & ENLSIP_GN_UPDATE_REFLECTORS) != 0, h->pair_enabled, h->pair_forced);
+    int rc = place_dev(h, h->ws, static_cast<WsLayout&>(*h), P);
     if (rc) return rc;
-    char* p = (char*)h->ws.p;
-    auto carve = [&](long long stride_elems) {
-        char* r = p;
-        p += (size_t)batch * stride_elems * 8;
-        return r;
-    };
-    h->W = (double*)carve(P.sW);
-    h->FA = (double*)carve(P.sFA); h->tauA = (double*)carve(P.sTauA);
-    h->FL = (double*)carve(P.sFL); h->tauL = (double*)carve(P.sTauL);
-    h->TA = (double*)carve(P.sTA); h->p1 = (double*)carve(P.sP1); h->bvec = (double*)carve(P.sB);
-    h->Tbuf = (double*)carve(P.sT); h->Rt = (double*)carve(P.sRt); h->tauJ = (double*)carve(P.sTauJ);
-    h->zsave = (double*)carve(P.sZ); h->vec = (double*)carve(P.sVec);
-    h->qdM = (double*)carve(P.sM); h->qdVb = (double*)carve(P.sVb); h->qdDiag = (double*)carve(P.sDiag);
-    h->qdVn1 = (double*)carve(P.sVn); h->qdVn2 = (double*)carve(P.sVn);
-    h->sbT = (double*)carve(PB * PB);
-    h->jpvtA = (long long*)carve(P.sJA); h->jpvtL = (long long*)carve(P.sJL); h->jpvtJ = (long long*)carve(P.sJJ);
-    h->qdChosen = (int*)p; p += (size_t)batch * P.sQI * 4;
-    h->qdPos = (int*)p; p += (size_t)batch * 2 * P.sQI * 4;
-    h->qdColat = (int*)p; p += (size_t)batch * 2 * P.sQI * 4;
-    h->qdCand = (void*)p; p += (size_t)batch * P.sCand * sizeof(QdCand);
-    h->state = (ProbState*)p;
-    p += (((size_t)batch * sizeof(ProbState) + 255) / 256) * 256;
-    h->small = (unsigned*)p;        // 256 bytes of scalars (tail sums of the TSQR stages)
-    p += 256;
-    h->sbInfo = (void*)p;
-    p += (((size_t)batch * sizeof(SbInfo) + 255) / 256) * 256;
-    h->sbInblk = (int*)p;
-    p += (size_t)batch * P.sQI * 4;
-    h->sbAct = (int*)p;
     if (h->h_state_cap < (size_t)batch) {
         if (h->h_state) GN_HIP(hipHostFree(h->h_state));
         h->h_state = nullptr;
@@ -726,7 +622,7 @@ static int run_qrcp_block(enlsip_gn_handle h, int n2_launch) {
     q = qd_args_r0(h, n2_launch);
     q.step = -1;
     a.info = (SbInfo*)h->sbInfo; a.inblk = h->sbInblk; a.sIn = P.sQI; a.blkid = 0;
-    a.Tsb = h->sbT; a.sTsb = PB * PB; a.act = h->sbAct; a.sAct = P.sQI + 32;
+    a.Tsb = h->sbT; a.sTsb = PB * PB; a.act = h->sbAct; a.sAct = P.sAct;
     a.dbg = nullptr;
     // a changed-problems solve: grids over the listed problems, the end-of-stage check over them too (the block records of the
     // others are whatever their own solve left); it neither uses nor renews the form hints, which belong to whole-part stages
@@ -913,7 +809,7 @@ static int extreme_shifts(enlsip_gn_handle h, const BatchOperands& v, int* shift
     hipStream_t s = h->stream;
     const long long m = v.m, n = v.n, t = v.t, ldj = v.ldj, ldat = v.ldat;
     const double *dJ = v.J, *drx = v.rx, *dAt = v.At, *dcx = v.cx;
-    unsigned long long* dmx = (unsigned long long*)(h->small + 32);      // 2 words of the handle's 256-byte scalar area
+    unsigned long long* dmx = h->small->amax;      // its first two words
     GN_HIP(hipMemsetAsync(dmx, 0, 16, s));
     if (dJ && drx) {
         hipLaunchKernelGGL(k_amax_bits, dim3((unsigned)n), dim3(256), 0, s, dJ, ldj, (int)m, (int)n, dmx);
@@ -976,33 +872,15 @@ static int run_constraint_dist(enlsip_gn_handle h, ConstraintArgs ca, long long 
     const Plan& P = h->plan;
     hipStream_t s = h->stream;
     const int kA = P.kA;
-    auto pad = [](long long x) { return rup(std::max<long long>(x, 1), 32); };
-    const long long ldc = rup(std::max(n, t), 8);
-    const long long sMc = pad(ldc * (t + 2)), sVbc = pad(ldc * (kA + 1)), sRtc = pad(ldc * (t + 2)), sLc = pad(ldc * (kA + 1));
-    const long long sVec = pad(std::max(n, t) + 1), sIc = pad(t + 1);
-    const int Gc = (int)((t + 1 + QD_CPW - 1) / QD_CPW);
-    const long long sCandc = 2LL * Gc;
-    const size_t bytes = (size_t)batch * ((sMc + sVbc + sRtc + sLc + 5 * sVec) * 8 + 5 * sIc * 4 + sCandc * sizeof(QdCand) +
-                                          2 * sizeof(ProbState)) + 4096;
-    int rc = grow(h, h->cws, bytes);
+    CwsLayout C;
+    int rc = place_dev(h, h->cws, C, batch, (long long)n, (long long)t, kA);
     if (rc) return rc;
-    char* p = (char*)h->cws.p;
-    auto carve = [&](size_t b) { char* r = p; p += (b + 255) / 256 * 256; return r; };
-    double* cM = (double*)carve((size_t)batch * sMc * 8);
-    double* cVb = (double*)carve((size_t)batch * sVbc * 8);
-    double* cRt = (double*)carve((size_t)batch * sRtc * 8);
-    double* cL = (double*)carve((size_t)batch * sLc * 8);
-    double* cDiag = (double*)carve((size_t)batch * sVec * 8);
-    double* cVn1 = (double*)carve((size_t)batch * sVec * 8);
-    double* cVn2 = (double*)carve((size_t)batch * sVec * 8);
-    double* cBq = (double*)carve((size_t)batch * sVec * 8);       // b_buff, later F_L11.Q' b_buff
-    double* cQb = (double*)carve((size_t)batch * sVec * 8);
-    int* cChosen = (int*)carve((size_t)batch * sIc * 4);
-    int* cPos = (int*)carve((size_t)batch * 2 * sIc * 4);
-    int* cColat = (int*)carve((size_t)batch * 2 * sIc * 4);
-    QdCand* cCand = (QdCand*)carve((size_t)batch * sCandc * sizeof(QdCand));
-    ProbState* stA = (ProbState*)carve((size_t)batch * sizeof(ProbState));
-    ProbState* stL = (ProbState*)carve((size_t)batch * sizeof(ProbState));
+    const long long ldc = C.ldc, sMc = C.sM, sVbc = C.sVb, sRtc = C.sRt, sLc = C.sL, sVec = C.sVec, sIc = C.sI, sCandc = C.sCand;
+    const int Gc = C.G;
+    double *cM = C.M, *cVb = C.Vb, *cRt = C.Rt, *cL = C.L, *cDiag = C.diag, *cVn1 = C.vn1, *cVn2 = C.vn2, *cBq = C.bq, *cQb = C.qb;
+    int *cChosen = C.chosen, *cPos = C.pos, *cColat = C.colat;
+    QdCand* cCand = (QdCand*)C.cand;
+    ProbState *stA = C.stA, *stL = C.stL;
     const unsigned gb = (unsigned)((batch + 255) / 256);
     if (tk) {
         hipLaunchKernelGGL(k_fake_state_ragged, dim3(gb), dim3(256), 0, s, stA, (int)batch, (int)n, tk, 0);
@@ -1981,25 +1859,14 @@ static int solve_host(enlsip_gn_handle h, const BatchOperands& hv, SolveMode mod
     if (dimJ2_ov > std::min(m, n)) { h->err = "dimJ2_override > min(m, n)"; return -17; }
     GN_HIP(hipSetDevice(h->device));
     const int kA = (int)std::min(n, t);
-    // staging: inputs packed (ld = m / n), outputs packed
-    const size_t inJ = (size_t)batch * m * n, inAt = (size_t)batch * n * t;
-    const size_t in_bytes = (inJ + (size_t)batch * m + inAt + (size_t)batch * t) * 8 + 1024;
-    rc = grow(h, h->in_stage, in_bytes);
+    StageIn in;       // inputs packed (ld = m / n), outputs packed
+    StageOut out;
+    rc = place_dev(h, h->in_stage, in, batch, m, n, t);
     if (rc) return rc;
-    const size_t out_dbl = (size_t)batch * (n + t + m);
-    const size_t out_i64 = (size_t)batch * (t + kA + n);
-    rc = grow(h, h->out_stage, (out_dbl + out_i64) * 8 + 1024);
+    rc = place_dev(h, h->out_stage, out, batch, m, n, t);
     if (rc) return rc;
-    double* dJ = (double*)h->in_stage.p;
-    double* drx = dJ + inJ;
-    double* dAt = drx + (size_t)batch * m;
-    double* dcx = dAt + inAt;
-    double* dp = (double*)h->out_stage.p;
-    double* db = dp + (size_t)batch * n;
-    double* dd = db + (size_t)batch * t;
-    long long* djA = (long long*)(dd + (size_t)batch * m);
-    long long* djL = djA + (size_t)batch * t;
-    long long* djJ = djL + (size_t)batch * kA;
+    double *dJ = in.J, *drx = in.rx, *dAt = in.At, *dcx = in.cx, *dp = out.p, *db = out.b, *dd = out.d;
+    long long *djA = out.jA, *djL = out.jL, *djJ = out.jJ;
     const BatchOperands dv{batch, m, n, t, dJ, m, m * n, drx, dAt, n, n * t, dcx, dp, db, dd, nullptr, djA, djL, djJ, hv.hinfo, hv.tk};
     hipStream_t s = h->stream;
     for (int64_t k = 0; k < batch; ++k) {
@@ -2079,12 +1946,10 @@ int enlsip_gn_factor_constraints(enlsip_gn_handle h, int64_t m, int64_t n, int64
     if (t > 0 && (!At || !cx)) return -5;
     if (t > 0 && ldat < n) return -6;
     GN_HIP(hipSetDevice(h->device));
-    // same staging layout as solve_host, so that a following solve of the same shape reuses the buffers
-    const size_t inJ = (size_t)m * n, inAt = (size_t)n * t;
-    rc = grow(h, h->in_stage, (inJ + (size_t)m + inAt + (size_t)t) * 8 + 1024);
+    StageIn in;       // solve_host's: a following solve of the same shape finds A', cx in their slots
+    rc = place_dev(h, h->in_stage, in, 1LL, (long long)m, (long long)n, (long long)t);
     if (rc) return rc;
-    double* dAt = (double*)h->in_stage.p + inJ + (size_t)m;
-    double* dcx = dAt + inAt;
+    double *dAt = in.At, *dcx = in.cx;
     hipStream_t s = h->stream;
     if (t > 0) {
         GN_HIP(hipMemcpy2DAsync(dAt, (size_t)n * 8, At, (size_t)ldat * 8, (size_t)n * 8, (size_t)t, hipMemcpyHostToDevice, s));
@@ -2317,12 +2182,10 @@ int enlsip_gn_factor_constraints_batched(enlsip_gn_handle h, int64_t batch, int6
     rc = check_launch_batch(h, batch);
     if (rc) return rc;
     GN_HIP(hipSetDevice(h->device));
-    // the staging layout of solve_host for this batch, whole: the solve that follows finds A', cx in their slots (and must not grow it)
-    const size_t inJ = (size_t)batch * m * n, inAt = (size_t)batch * n * t_max;
-    rc = grow(h, h->in_stage, (inJ + (size_t)batch * m + inAt + (size_t)batch * t_max) * 8 + 1024);
+    StageIn in;       // solve_host's for this batch, whole: the solve that follows finds A', cx in their slots (and must not grow it)
+    rc = place_dev(h, h->in_stage, in, (long long)batch, (long long)m, (long long)n, (long long)t_max);
     if (rc) return rc;
-    double* dAt = (double*)h->in_stage.p + inJ + (size_t)batch * m;
-    double* dcx = dAt + inAt;
+    double *dAt = in.At, *dcx = in.cx;
     hipStream_t s = h->stream;
     if (t_max > 0) {
         for (int64_t k = 0; k < batch; ++k)
@@ -2526,15 +2389,11 @@ int enlsip_gn_solve_changed_batched(enlsip_gn_handle h, int64_t batch, int64_t m
     if (!any) return nothing_changed(h);
     GN_HIP(hipSetDevice(h->device));
     const int kA = (int)std::min(n, t_max);
-    // outputs packed as solve_host packs them (the resident solve reads nothing of this buffer)
-    rc = grow(h, h->out_stage, ((size_t)batch * (n + t_max + m) + (size_t)batch * (t_max + kA + n)) * 8 + 1024);
+    StageOut out;     // packed as solve_host packs them (the resident solve reads nothing of this buffer)
+    rc = place_dev(h, h->out_stage, out, (long long)batch, (long long)m, (long long)n, (long long)t_max);
     if (rc) return rc;
-    double* dp = (double*)h->out_stage.p;
-    double* db = dp + (size_t)batch * n;
-    double* dd = db + (size_t)batch * t_max;
-    long long* djA = (long long*)(dd + (size_t)batch * m);
-    long long* djL = djA + (size_t)batch * t_max;
-    long long* djJ = djL + (size_t)batch * kA;
+    double *dp = out.p, *db = out.b, *dd = out.d;
+    long long *djA = out.jA, *djL = out.jL, *djJ = out.jJ;
     hipStream_t s = h->stream;
     // the changed problems' A', cx into the slots of the staging area the resident solve reads
     double* sAt = const_cast<double*>(L.At);

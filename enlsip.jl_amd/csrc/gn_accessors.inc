@@ -363,11 +363,10 @@ int enlsip_gn_resolve(enlsip_gn_handle h, int64_t prob, int64_t dimA, int64_t di
     GN_HIP(hipMemcpyAsync(h->state + prob, &fix, sizeof(ProbState), hipMemcpyHostToDevice, s));
     GN_HIP(hipStreamSynchronize(s));
     // (5) triangular solve with dimJ2, scatter, p = Q1 [p1; p2]
-    rc = grow(h, h->out_stage, (size_t)(n + t + m) * 8 + 1024);
+    StageOut out;
+    rc = place_dev(h, h->out_stage, out, 1LL, (long long)m, (long long)n, (long long)t);
     if (rc) return rc;
-    double* dp = (double*)h->out_stage.p;
-    double* db = dp + n;
-    double* dd = db + t;
+    double *dp = out.p, *db = out.b, *dd = out.d;
     FinalArgs fa{};
     fa.m = m; fa.n = n; fa.t = t; fa.kA = P.kA; fa.ldw = P.ldw; fa.ldr = P.ldr; fa.eps_rank = h->eps_rank;
     fa.dimJ2_override = (int)dimJ2; fa.refactor = 0; fa.prob0 = (int)prob; fa.dsrc = dv;

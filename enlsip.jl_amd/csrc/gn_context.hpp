@@ -8,39 +8,9 @@
 
 #include "../../include/enlsip_gn.h"
 #include "gn_device_utils.hpp"
+#include "gn_plan.hpp"
 
 namespace gn {
-
-struct LevelPlan {
-    int level;
-    int nblocks;      // 32-row blocks entering this level
-    int groups;       // workgroups (= blocks of the next level)
-    long long S;      // block stride (rows)
-    long long tOff;   // first T block index
-    int mode = 0;     // row geometry (CaqrArgs::mode): 0 level-0 tiles, 1 plain tree level, 2 first tree level of a pair's second panel
-    long long base = 0;   // row of block 0
-    int skip = 0;     // level 0: leading 32-row units of every tile that belong to the pair's first panel
-};
-struct PanelPlan {
-    std::vector<LevelPlan> levels;
-};
-
-struct Plan {
-    long long batch = 0, m = 0, n = 0, t = 0;
-    int kA = 0;
-    int RPL = 8;         // CAQR rows per lane (tile rows = 64 * RPL)
-    int F = 16;          // blocks per group
-    int ldw = 0, ldr = 0;
-    int npan_max = 0;    // panels if n2 = n
-    bool pair = false;   // panels (2K, 2K+1) share their tiles and one pass over the far trailing columns (gn_kernels_caqr.hpp, "Panel pairs")
-    long long nTblocks = 0;
-    std::vector<PanelPlan> panels;
-    // per-problem strides (elements)
-    long long sFA, sTauA, sJA, sFL, sTauL, sJL, sTA, sP1, sB, sW, sT, sRt, sTauJ, sJJ, sZ, sVec;
-    // distributed pivoted QR (gn_kernels_qrcp_dist.hpp)
-    long long sM, sVb, sDiag, sVn, sQI, sCand;
-    int qdGmax = 0;
-};
 
 struct DevBuf {
     void* p = nullptr;
@@ -52,6 +22,24 @@ struct PinnedBuf {
     void* p = nullptr;
     size_t cap = 0;
 };
+
+// The device scalars of a handle (WsLayout::small, 256 bytes of the main workspace): results of single-number reductions that the
+// host reads back or a following kernel accumulates into.  The members keep the 128-byte lines they were measured on.
+struct SmallScalars {
+    unsigned char unused0[32];
+    double tail_sum;                 // tail sum of squares of a TSQR stage (k_tsqr_extract, k_sumsq)
+    double unused1;
+    double tails[4];                 // k_tsqr_unpack: tail^2, the n2 check, the rank tags, E
+    unsigned char unused2[48];
+    // largest-magnitude bit patterns: J, A' (extreme_shifts: two words) or J, rx, A' (tsqr_shifts: three).  Shared on purpose: both
+    // run on the handle's one stream, each reads its words back and synchronises before it returns, so they never run concurrently.
+    unsigned long long amax[3];
+    unsigned long long unused3;
+    unsigned long long flag_acc[2];  // accumulator of k_tsqr_flags (it leaves it zero itself)
+    unsigned sum_count;              // arrival counter of ordered_sumsq
+    unsigned char unused4[76];
+};
+static_assert(sizeof(SmallScalars) == PLAN_SMALL_BYTES && sizeof(ProbState) == PLAN_STATE_BYTES, "gn_plan.hpp sizes the workspace with these");
 
 // The operands of one batched solve: shape, inputs, outputs (device pointers, or host pointers before solve_host stages them).
 // Problem k's part of each array starts at a fixed stride, and slice() is the one place that knows them: J, A' by strideJ,
@@ -108,7 +96,7 @@ struct SolveMode {
 
 }  // namespace gn
 
-struct enlsip_gn_context {
+struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed main workspace
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -128,14 +116,7 @@ struct enlsip_gn_context {
     bool constraints_only = false;   // resident: F_A, F_L11 only (enlsip_gn_factor_constraints); everything about J is absent
     double eps_rank = 0.0;
 
-    // workspace (one allocation, carved)
-    gn::DevBuf ws;
-    double *FA = nullptr, *tauA = nullptr, *FL = nullptr, *tauL = nullptr, *TA = nullptr, *p1 = nullptr,
-           *bvec = nullptr, *W = nullptr, *Tbuf = nullptr, *Rt = nullptr, *tauJ = nullptr, *zsave = nullptr,
-           *vec = nullptr, *qdM = nullptr, *qdVb = nullptr, *qdDiag = nullptr, *qdVn1 = nullptr, *qdVn2 = nullptr;
-    int *qdChosen = nullptr, *qdPos = nullptr, *qdColat = nullptr;
-    void* qdCand = nullptr;
-    unsigned* small = nullptr;
+    gn::DevBuf ws;                   // the main workspace: one allocation, placed by WsLayout
     // row counts the blocks of the previous blocked QRCP started with (min / max over the problems, by block id), valid for
     // sb_rows_kp == kp_launch and the same batch: which forms of the select / factor kernel a block id needs
     std::vector<int> sb_rows_min, sb_rows_max;
@@ -146,10 +127,6 @@ struct enlsip_gn_context {
     bool sb_form_hints = true;   // ENLSIP_GN_SB_FORM_HINTS=0: every block id in all three forms (A/B)
     bool qrcp_hybrid = true;     // pivoted QR of more than 512 rows: launch-per-step head, register blocks for the last 512 (ENLSIP_GN_QRCP_HYBRID=0: A/B)
     int sb_hint = 0;             // blocks the previous blocked QRCP needed (+1): size of the first launch chunk
-    double* sbT = nullptr;       // per problem: T factor of the current QRCP block (32 x 32)
-    void* sbInfo = nullptr;      // SbInfo per problem (device)
-    int* sbInblk = nullptr;      // per column block id (device)
-    int* sbAct = nullptr;        // per problem: columns the current block update touches (device)
     void* h_sbinfo = nullptr;    // pinned mirror of sbInfo
     int cu_count = 256;
     enlsip_gn_context* sub = nullptr;   // handle for the stacked problem of the TSQR combine stage
@@ -233,8 +210,6 @@ struct enlsip_gn_context {
     gn::DevBuf xbuf;                    // send message + G received messages
     gn::DevBuf tsqr_part;               // per-workgroup partial sums of the TSQR stages' ordered sums of squares
     float tsqr_ms[3] = {};              // local / exchange / combine of the last enlsip_gn_solve_tsqr (profiling on)
-    long long *jpvtA = nullptr, *jpvtL = nullptr, *jpvtJ = nullptr;
-    gn::ProbState* state = nullptr;
     // staging for the host-pointer API
     gn::DevBuf in_stage, out_stage, scratch, lag, newton;
     // batched consumers (gn_lagrange_batched.inc): staging of the host-buffer forms, device temporaries, pinned "some problem

@@ -9,16 +9,21 @@ enum { DEL_MAX_T = 1024 };      // t_max of this build: the LDS copies of the ge
 
 // the per-problem records of one call in pinned memory and on the device, the decisions behind them (hs, ds: may be null, the
 // restore has none); grown, never shrunk (grow, grow_pinned)
+struct DeletionScratch {
+    DeletionMeta* meta = nullptr;
+    int* s = nullptr;
+    void carve(Carver& c, int64_t batch) { c.take(meta, "meta", (size_t)batch); c.take(s, "s", (size_t)batch); }
+};
 int deletion_scratch(enlsip_gn_handle h, int64_t batch, DeletionMeta** hmeta, int** hs, DeletionMeta** dmeta, int** ds) {
-    const size_t mb = (size_t)batch * sizeof(DeletionMeta), bytes = mb + (size_t)batch * sizeof(int);
-    int rc = grow(h, h->del_scr, bytes);
+    DeletionScratch D, H;
+    int rc = place_dev(h, h->del_scr, D, batch);
     if (rc) return rc;
-    rc = grow_pinned(h, h->h_del, bytes);
+    rc = place_pinned(h, h->h_del, H, batch);
     if (rc) return rc;
-    *hmeta = (DeletionMeta*)h->h_del.p;
-    *dmeta = (DeletionMeta*)h->del_scr.p;
-    if (hs) *hs = (int*)((char*)h->h_del.p + mb);
-    if (ds) *ds = (int*)((char*)h->del_scr.p + mb);
+    *hmeta = H.meta;
+    *dmeta = D.meta;
+    if (hs) *hs = H.s;
+    if (ds) *ds = D.s;
     return 0;
 }
 

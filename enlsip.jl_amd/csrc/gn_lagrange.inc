@@ -3,11 +3,15 @@
 
 namespace {
 
-// device scratch layout (doubles): [0, n) grad / p   [1024, 1024 + t) b   [2048, 2048 + t) lambda   [3072, 3076) scalars
-// [4096, 4096 + t) diag_scale   [5120, 5120 + m) residual vector
-int lagrange_scratch(enlsip_gn_handle h, long long m) {
-    return grow(h, h->lag, (size_t)(5120 + std::max<long long>(m, 1)) * 8);
-}
+// device scratch of the per-problem consumers in h->lag: slots of 1024 doubles (n, t <= 1024 in this build), then the residual vector
+struct LagrangeScratch {
+    double *gp = nullptr, *b = nullptr, *lambda = nullptr, *scal = nullptr, *diag = nullptr, *r = nullptr;
+    void carve(Carver& c, long long m) {
+        c.take(gp, "grad / p", 1024); c.take(b, "b", 1024); c.take(lambda, "lambda", 1024); c.take(scal, "scalars", 1024);
+        c.take(diag, "diag_scale", 1024); c.take(r, "residual", (size_t)std::max<long long>(m, 1));
+    }
+};
+int lagrange_scratch(enlsip_gn_handle h, long long m, LagrangeScratch& L) { return place_dev(h, h->lag, L, m); }
 
 }  // namespace
 
@@ -21,9 +25,10 @@ int enlsip_gn_gradient(enlsip_gn_handle h, int64_t prob, double* grad) {
     const Plan& P = h->plan;
     const BatchOperands in = h->last.slice(prob, 1);
     GN_HIP(hipSetDevice(h->device));
-    rc = lagrange_scratch(h, P.m);
+    LagrangeScratch L;
+    rc = lagrange_scratch(h, P.m, L);
     if (rc) return rc;
-    double* d = (double*)h->lag.p;
+    double* d = L.gp;
     hipStream_t s = h->stream;
     hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)P.n + 3) / 4), dim3(256), 0, s, in.J, in.ldj, (int)P.m, (int)P.n, in.rx, d);
     GN_HIP(hipGetLastError());
@@ -42,12 +47,10 @@ int enlsip_gn_jacobian_times(enlsip_gn_handle h, int64_t prob, const double* p, 
     const BatchOperands in = h->last.slice(prob, 1);
     const int n = (int)P.n, t = prob_t(h, prob), m = (int)P.m;       // Ap: the problem's own active rows
     GN_HIP(hipSetDevice(h->device));
-    rc = lagrange_scratch(h, m);
+    LagrangeScratch L;
+    rc = lagrange_scratch(h, m, L);
     if (rc) return rc;
-    double* base = (double*)h->lag.p;
-    double* dp = base;                // n
-    double* dAp = base + 1024;        // t
-    double* dJp = base + 5120;        // m
+    double *dp = L.gp, *dAp = L.b, *dJp = L.r;      // n, t, m
     hipStream_t s = h->stream;
     GN_HIP(hipMemcpyAsync(dp, p, (size_t)n * 8, hipMemcpyHostToDevice, s));
     if (Jp) {
@@ -149,20 +152,21 @@ static int lagrange_common(enlsip_gn_handle h, int64_t prob, int mode, const dou
         return 0;
     }
     GN_HIP(hipSetDevice(h->device));
-    int rc = lagrange_scratch(h, m);
+    LagrangeScratch L;
+    int rc = lagrange_scratch(h, m, L);
     if (rc) return rc;
-    double* d = (double*)h->lag.p;
+    double* d = L.gp;
     hipStream_t s = h->stream;
     LagrangeArgs a{};
     a.mode = mode; a.n = n; a.t = t; a.kA = std::min(n, t); a.rank_solve = h->h_state[prob].rankA;
     a.FA = h->FA + prob * P.sFA; a.tauA = h->tauA + prob * P.sTauA; a.jpvtA = h->jpvtA + prob * P.sJA;
     const BatchOperands in = h->last.slice(prob, 1);
     a.cx = in.cx;
-    a.eps_rank = eps_rank; a.lambda = d + 2048; a.scal = d + 3072;
+    a.eps_rank = eps_rank; a.lambda = L.lambda; a.scal = L.scal;
     a.diag_scale = nullptr;
     if (diag_scale) {
-        GN_HIP(hipMemcpyAsync(d + 4096, diag_scale, (size_t)t * 8, hipMemcpyHostToDevice, s));
-        a.diag_scale = d + 4096;
+        GN_HIP(hipMemcpyAsync(L.diag, diag_scale, (size_t)t * 8, hipMemcpyHostToDevice, s));
+        a.diag_scale = L.diag;
     }
     if (mode == 1) {
         if (!a.cx) { h->err = "cx of the last solve is not available"; return -1; }
@@ -178,16 +182,16 @@ static int lagrange_common(enlsip_gn_handle h, int64_t prob, int mode, const dou
         if (!in.J || !in.rx) { h->err = "J / rx of the last solve are not available"; return -1; }
         GN_HIP(hipMemcpyAsync(d, host_vec, (size_t)n * 8, hipMemcpyHostToDevice, s));          // p_gn
         hipLaunchKernelGGL(k_gemv_n_add, dim3(((unsigned)m + 255) / 256), dim3(256), 0, s, in.J, in.ldj, m, n, d, in.rx,
-                           d + 5120);   // rx + J p
+                           L.r);   // rx + J p
         hipLaunchKernelGGL(k_gemv_t, dim3(((unsigned)t + 3) / 4), dim3(256), 0, s, h->W + prob * P.sW, (long long)P.ldw, m, t,
-                           d + 5120, d + 1024);                                                       // J1' (.)
-        a.vec = d + 1024;
+                           L.r, L.b);                                                       // J1' (.)
+        a.vec = L.b;
     }
     hipLaunchKernelGGL(k_lagrange, dim3(1), dim3(256), 0, s, a);
     GN_HIP(hipGetLastError());
     double scal[2] = {0.0, 0.0};
-    GN_HIP(hipMemcpyAsync(lambda, d + 2048, (size_t)t * 8, hipMemcpyDeviceToHost, s));
-    GN_HIP(hipMemcpyAsync(scal, d + 3072, 16, hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(lambda, L.lambda, (size_t)t * 8, hipMemcpyDeviceToHost, s));
+    GN_HIP(hipMemcpyAsync(scal, L.scal, 16, hipMemcpyDeviceToHost, s));
     GN_HIP(hipStreamSynchronize(s));
     if (grad_res && mode == 1) *grad_res = scal[0];
     const int st = (int)scal[1];

@@ -45,6 +45,17 @@ int consumer_needs(enlsip_gn_handle h, enlsip_gn_handle hh, int kind, const Cons
     }
 }
 
+// temporaries of a segment in lagb_scr: flag word | status (when the caller passes none) | grad (first, no grad_fx) | rx + J p (m) |
+// J1'(.) (t_max)
+struct LagbScratch {
+    int *flag = nullptr, *status = nullptr;
+    double *g = nullptr, *y = nullptr, *bv = nullptr;
+    void carve(Carver& c, long long cnt, long long m, long long n, long long tmax) {
+        c.take(flag, "flag", 1, 256); c.take(status, "status", (size_t)cnt, 256);
+        c.take(g, "grad", (size_t)(cnt * n), 256); c.take(y, "rx + J p", (size_t)(cnt * m)); c.take(bv, "J1'(.)", (size_t)(cnt * std::max(tmax, 1LL)));
+    }
+};
+
 // Enqueues the consumer for one segment on its handle's stream: at most three launches whatever the segment's size.
 int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const ConsumerIO& io, bool small) {
     enlsip_gn_handle h = hh;       // GN_HIP reports on `h`
@@ -53,16 +64,13 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const 
     const int* tk = hh->h_tk.empty() ? nullptr : (const int*)hh->tkbuf.p + k0;
     const BatchOperands in = hh->last.slice(k0, cnt);
     const bool est = kind == CONS_FIRST || kind == CONS_SECOND;
-    // temporaries: flag word | status (when the caller passes none) | grad (first, no grad_fx) | rx + J p (m) | J1'(.) (t_max)
-    const size_t o_st = 256, o_g = o_st + rup((long long)cnt * 4, 256);
-    const size_t o_y = o_g + (size_t)cnt * n * 8, o_b = o_y + (size_t)cnt * m * 8, bytes = o_b + (size_t)cnt * std::max(tmax, 1LL) * 8;
-    int rc = grow(hh, hh->lagb_scr, bytes);
+    LagbScratch scr;
+    int rc = place_dev(hh, hh->lagb_scr, scr, cnt, m, n, tmax);
     if (rc) return rc;
     if (est) {
         rc = grow_pinned(hh, hh->h_lagflag, sizeof(int));
         if (rc) return rc;
     }
-    char* scr = (char*)hh->lagb_scr.p;
     hipStream_t s = hh->stream;
     const unsigned cn = (unsigned)cnt;
     auto jt = [&](const double* x, long long sx, double* y) {          // J' x
@@ -92,21 +100,20 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const 
             a.eps_rank = io.eps_rank;
             a.lambda = io.out0 + j0 * tmax;
             a.grad_res = (kind == CONS_FIRST && io.out1) ? io.out1 + j0 : nullptr;
-            a.status = io.status ? io.status + j0 : (int*)(scr + o_st);
-            a.flag = (int*)scr;
-            GN_HIP(hipMemsetAsync(scr, 0, sizeof(int), s));
+            a.status = io.status ? io.status + j0 : scr.status;
+            a.flag = scr.flag;
+            GN_HIP(hipMemsetAsync(scr.flag, 0, sizeof(int), s));
             if (kind == CONS_FIRST) {
                 if (io.in) {
                     a.vec = io.in + j0 * n;
                 } else {       // gradient from the resident J, rx
-                    double* g = (double*)(scr + o_g);
+                    double* g = scr.g;
                     jt(in.rx, m, g);
                     a.vec = g;
                 }
                 a.svec = n;
             } else {
-                double* y = (double*)(scr + o_y);
-                double* bv = (double*)(scr + o_b);
+                double *y = scr.y, *bv = scr.bv;
                 hipLaunchKernelGGL(k_gemv_n_add_batched, dim3((unsigned)(m + 255) / 256, cn), dim3(256), 0, s, in.J, in.ldj, in.strideJ,
                                    (int)m, (int)n, io.in + j0 * n, n, in.rx, m, y, m);       // rx + J p
                 if (tmax > 0)
@@ -119,7 +126,7 @@ int consumer_launch(enlsip_gn_handle hh, int kind, const ResidentSeg& sg, const 
                 hipLaunchKernelGGL(k_lagrange_wave, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, s, a);
             else
                 hipLaunchKernelGGL(k_lagrange_batched, dim3(cn), dim3(256), 0, s, a);
-            GN_HIP(hipMemcpyAsync(hh->h_lagflag.p, scr, sizeof(int), hipMemcpyDeviceToHost, s));
+            GN_HIP(hipMemcpyAsync(hh->h_lagflag.p, scr.flag, sizeof(int), hipMemcpyDeviceToHost, s));
         }
     }
     GN_HIP(hipGetLastError());
@@ -146,7 +153,10 @@ int consumer_per_problem(enlsip_gn_handle h, int kind, int64_t prob0, int64_t co
     if (est) {      // statuses of the batched launch: the rescued slots' entries are replaced below
         st_all.assign((size_t)count, 0);
         for (const ResidentSeg& sg : r.seg) {
-            const int* src = io.status ? io.status + sg.j0 : (const int*)((char*)sg.hh->lagb_scr.p + 256);
+            LagbScratch scr;      // the segment's launch grew it: placed again
+            const int rc = place_dev(sg.hh, sg.hh->lagb_scr, scr, sg.cnt, m, n, tmax);
+            if (rc) return rc;
+            const int* src = io.status ? io.status + sg.j0 : scr.status;
             GN_HIP(hipMemcpy(st_all.data() + sg.j0, src, (size_t)sg.cnt * sizeof(int), hipMemcpyDeviceToHost));
         }
     }

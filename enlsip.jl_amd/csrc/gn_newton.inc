@@ -41,22 +41,12 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
         GN_HIP(hipStreamSynchronize(s));
         return 0;
     }
-    // workspace (doubles): Gam n^2 | Q n^2 | T1 n^2 | E n^2 | W22 n2^2 | Ut n2^2 | W21 n2 rankA | g n2 | d n2 | p2 n2 | pout n | flags
-    const size_t nn = (size_t)n * n, n22 = (size_t)n2 * n2;
-    rc = grow(h, h->newton, (4 * nn + 2 * n22 + (size_t)n2 * std::max(rankA, 1) + 3 * (size_t)n2 + n + 64) * 8);
+    NewtonWs N;
+    rc = place_dev(h, h->newton, N, (long long)n, (long long)n2, (long long)rankA);
     if (rc) return rc;
-    double* dG = (double*)h->newton.p;
-    double* dQ = dG + nn;
-    double* dT1 = dQ + nn;
-    double* dE = dT1 + nn;
-    double* dW22 = dE + nn;
-    double* dUt = dW22 + n22;
-    double* dW21 = dUt + n22;
-    double* dg = dW21 + (size_t)n2 * std::max(rankA, 1);
-    double* dd = dg + n2;
-    double* dp2 = dd + n2;
-    double* dpo = dp2 + n2;
-    int* dflag = (int*)(dpo + n);
+    double *dG = N.G, *dQ = N.Q, *dT1 = N.T1, *dE = N.E, *dW22 = N.W22, *dUt = N.Ut, *dW21 = N.W21, *dg = N.g, *dd = N.d, *dp2 = N.p2,
+           *dpo = N.pout;
+    int* dflag = N.flag;
     GN_HIP(hipMemcpy2DAsync(dG, (size_t)n * 8, Gamma, (size_t)ldg * 8, (size_t)n * 8, (size_t)n, hipMemcpyHostToDevice, s));
     GN_HIP(hipMemsetAsync(dflag, 0, 16, s));
     // J * F_A.Q into scratch (:384)

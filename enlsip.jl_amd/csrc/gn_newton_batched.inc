@@ -24,22 +24,23 @@ int newton_launch(enlsip_gn_handle hh, const ResidentSeg& sg, const int* req, co
     const long long k0 = sg.k0, j0 = sg.j0, cnt = sg.cnt;
     const int n = (int)P.n;
     const size_t nn = (size_t)n * n;
-    // workspace: X nn | E nn | rhs n per slot, vec sVec per slot, state records, status, requests (ResolveDims | req | flag)
-    const size_t dbl = (size_t)cnt * (2 * nn + n + (size_t)P.sVec);
-    const size_t st_b = (size_t)rup(cnt * (long long)sizeof(ProbState), 8), su_b = (size_t)rup(cnt * (long long)sizeof(int), 8);
-    const size_t rq_b = (size_t)cnt * (sizeof(ResolveDims) + sizeof(int)) + sizeof(int);
-    int rc = grow(hh, hh->nwb_ws, dbl * 8 + st_b + su_b + rq_b + 64);
+    // workspace: X nn | E nn | rhs n per slot, vec sVec per slot, state records, status, then ONE block that one copy of `pack` fills:
+    // the requests' ResolveDims | req | flag
+    struct { double *X = nullptr, *E = nullptr, *rhs = nullptr, *vec = nullptr; ProbState* st = nullptr; int *status = nullptr, *pack = nullptr;
+             void carve(Carver& c, size_t cnt, size_t nn, size_t n, size_t sVec) {
+                 c.take(X, "X", cnt * nn); c.take(E, "E", cnt * nn); c.take(rhs, "rhs", cnt * n); c.take(vec, "vec", cnt * sVec);
+                 c.take(st, "state", cnt, 8); c.take(status, "status", cnt); c.take(pack, "pack", cnt * 5 + 1, 8);
+             } } N;
+    static_assert(sizeof(ResolveDims) == 4 * sizeof(int), "pack: four words of dimensions, one request per slot, one flag");
+    int rc = place_dev(hh, hh->nwb_ws, N, (size_t)cnt, nn, (size_t)n, (size_t)P.sVec);
     if (rc) return rc;
     rc = grow_pinned(hh, hh->h_nwflag, sizeof(int));
     if (rc) return rc;
-    double* dX = (double*)hh->nwb_ws.p;
-    double* dE = dX + (size_t)cnt * nn;
-    double* drhs = dE + (size_t)cnt * nn;
-    double* dvec = drhs + (size_t)cnt * n;
-    ProbState* dst = (ProbState*)(dvec + (size_t)cnt * P.sVec);
-    int* dstatus = (int*)((char*)dst + st_b);
-    ResolveDims* ddims = (ResolveDims*)((char*)dstatus + su_b);
-    int* dreq = (int*)(ddims + cnt);
+    double *dX = N.X, *dE = N.E, *drhs = N.rhs, *dvec = N.vec;
+    ProbState* dst = N.st;
+    int* dstatus = N.status;
+    ResolveDims* ddims = (ResolveDims*)N.pack;
+    int* dreq = N.pack + 4 * cnt;
     int* dflag = dreq + cnt;
     hipStream_t s = hh->stream;
 

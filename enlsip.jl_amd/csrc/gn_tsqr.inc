@@ -215,7 +215,7 @@ static int tsqr_sum_area(enlsip_gn_handle h, double** part, unsigned** count) {
     int rc = grow(h, h->tsqr_part, (size_t)TSQR_SUM_BLOCKS * 8);
     if (rc) return rc;
     *part = (double*)h->tsqr_part.p;
-    *count = h->small + 44;
+    *count = &h->small->sum_count;
     GN_HIP(hipMemsetAsync(*count, 0, 4, h->stream));
     return 0;
 }
@@ -227,7 +227,7 @@ static int tsqr_sum_area(enlsip_gn_handle h, double** part, unsigned** count) {
 static int tsqr_shifts(enlsip_gn_handle h, long long m, long long n, long long t, const double* dJ, long long ldj, const double* drx,
                        const double* dAt, long long ldat, const double* dcx, int* shiftJ, int* shiftA) {
     hipStream_t s = h->stream;
-    unsigned long long* dmx = (unsigned long long*)(h->small + 32);      // 3 words of the handle's 256-byte scalar area
+    unsigned long long* dmx = h->small->amax;
     GN_HIP(hipMemsetAsync(dmx, 0, 24, s));
     hipLaunchKernelGGL(k_amax_bits, dim3((unsigned)n), dim3(256), 0, s, dJ, ldj, (int)m, (int)n, dmx);
     hipLaunchKernelGGL(k_amax_bits, dim3(1), dim3(256), 0, s, drx, m, (int)m, 1, dmx + 1);
@@ -284,7 +284,7 @@ static int tsqr_local_pass(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t
             const long long work = (long long)n2_launch * (n2_launch + 1) / 2 + m_loc;
             const unsigned blocks = (unsigned)std::min<long long>(256, std::max<long long>(1, work / 2048));
             hipLaunchKernelGGL(k_tsqr_flags, dim3(blocks), dim3(256), 0, s, h->state, (const double*)h->W, P.ldw, (int)n, (int)m_loc,
-                               (const double*)h->FA, P.kA, n2_launch, (unsigned long long*)(h->small + 40));
+                               (const double*)h->FA, P.kA, n2_launch, h->small->flag_acc);
             GN_HIP(hipGetLastError());
         }
         GN_HIP(hipMemcpyAsync(h->h_state, h->state, sizeof(ProbState), hipMemcpyDeviceToHost, s));
@@ -323,7 +323,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     h->h_tk.clear();
     gn_route_acc = 0;
     const bool detect = scaled && h->rescale_enabled;
-    if (detect) GN_HIP(hipMemsetAsync(h->small + 40, 0, 16, s));      // accumulator of k_tsqr_flags (it leaves it zero itself)
+    if (detect) GN_HIP(hipMemsetAsync(h->small->flag_acc, 0, sizeof h->small->flag_acc, s));      // accumulator of k_tsqr_flags (it leaves it zero itself)
     rc = tsqr_local_pass(h, m_loc, n, t, dJ, ldj, drx, dAt, ldat, dcx, eps_rank, detect);
     if (rc) return rc;
     if (h->h_state[0].status & (GN_FLAG_NONFINITE | GN_FLAG_TINY)) {
@@ -357,26 +357,28 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
 // E: the stacked problem is the whole one times 2^-E (k_tsqr_unpack); the absolute rank test follows (SolveMode::abs_shift), p, the
 // ranks and the pivots need nothing, and dlead / comb_tail_sq come back AT THAT SCALE: the caller takes its norms there, where no
 // square leaves the range, and scales back by 2^E afterwards.
+// the stacked problem of G blocks of n2 columns in h->scratch (grown, never shrunk: a second call with the same shape places again)
+int tsqr_scratch(enlsip_gn_handle h, int64_t G, int64_t n2, TsqrScratch& T) {
+    return place_dev(h, h->scratch, T, (long long)G, (long long)n2, h->plan.n);
+}
 int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank, int E, double* p, double* dlead,
                       double* comb_tail_sq, enlsip_gn_info* info, int64_t* jpvtJ2) {
     const Plan& P = h->plan;      // plan of the local stage: F_A, p1, state are resident
     hipStream_t s = h->stream;
     const long long n = P.n, ms = (long long)G * n2;
     const ProbState st = h->h_state[0];
-    double* Jst = (double*)h->scratch.p;
-    double* rxs = Jst + (size_t)ms * n2;
-    double* dp2 = rxs + ms;
-    double* dd = dp2 + n2;
-    double* dpo = dd + ms;
+    TsqrScratch T;
+    int rc = tsqr_scratch(h, G, n2, T);      // grown by the caller that stacked the problem: places only
+    if (rc) return rc;
+    double *Jst = T.Jst, *rxs = T.rxs, *dp2 = T.p2, *dd = T.d, *dpo = T.pout;
     enlsip_gn_info sinfo = {0, 0, 1, 0, 0, 0};
-    int rc;
     if (n2 > 0) {
         if (!h->sub) {
             rc = create_helper(h, &h->sub, h->stream);
             if (rc) { h->err = "tsqr_combine: cannot create the sub-handle"; return rc; }
         }
         // jpvt / info of the stacked (unconstrained) problem through the ordinary device-pointer solve
-        rc = grow(h, h->out_stage, ((size_t)n2 * 8 + sizeof(enlsip_gn_info)) + 1024);
+        rc = grow(h, h->out_stage, (size_t)n2 * 8);
         if (rc) return rc;
         long long* djJ = (long long*)h->out_stage.p;
         const BatchOperands v{1, ms, n2, 0, Jst, ms, 0, rxs, nullptr, 1, 0, nullptr, dp2, nullptr, dd, nullptr, nullptr, nullptr, djJ};
@@ -391,9 +393,9 @@ int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank
         unsigned* count = nullptr;
         rc = tsqr_sum_area(h, &part, &count);
         if (rc) return rc;
-        GN_HIP(hipMemsetAsync(h->small + 8, 0, 8, s));
-        if (ms > n2) hipLaunchKernelGGL(k_sumsq, dim3(64), dim3(256), 0, s, dd, (long long)n2, ms, (double*)(h->small + 8), part, count);
-        if (comb_tail_sq) GN_HIP(hipMemcpyAsync(comb_tail_sq, h->small + 8, 8, hipMemcpyDeviceToHost, s));
+        GN_HIP(hipMemsetAsync(&h->small->tail_sum, 0, 8, s));
+        if (ms > n2) hipLaunchKernelGGL(k_sumsq, dim3(64), dim3(256), 0, s, dd, (long long)n2, ms, &h->small->tail_sum, part, count);
+        if (comb_tail_sq) GN_HIP(hipMemcpyAsync(comb_tail_sq, &h->small->tail_sum, 8, hipMemcpyDeviceToHost, s));
     } else if (comb_tail_sq) {
         *comb_tail_sq = 0.0;
     }
@@ -407,11 +409,6 @@ int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank
     return 0;
 }
 
-int tsqr_scratch(enlsip_gn_handle h, int64_t G, int64_t n2) {
-    const size_t ms = (size_t)G * n2;
-    // Jst (ms x n2) | rxs (ms) | p2 (n2) | d (ms) | pout (n)
-    return grow(h, h->scratch, (ms * n2 + 2 * ms + (size_t)n2 + (size_t)h->plan.n + 64) * 8);
-}
 }  // namespace
 
 extern "C" {
@@ -427,7 +424,7 @@ static int tsqr_local_stage(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_
     if (rc) return rc;
     const Plan& P = h->plan;
     hipStream_t s = h->stream;
-    double* dsum = (double*)(h->small + 8);             // scratch double for the tail sum
+    double* dsum = &h->small->tail_sum;
     double* part = nullptr;
     unsigned* count = nullptr;
     rc = tsqr_sum_area(h, &part, &count);
@@ -467,12 +464,11 @@ int enlsip_gn_tsqr_combine_dev(enlsip_gn_handle h, int64_t G, int64_t n2, const 
     if (h->tsqr_n2 < 0 || n2 != h->tsqr_n2) { h->err = "tsqr_combine: n2 does not match the last tsqr_local on this handle"; return -3; }
     if (n2 > 0 && (!dRstack || !dzstack)) { h->err = "dRstack / dzstack is NULL"; return -4; }
     GN_HIP(hipSetDevice(h->device));
-    int rc = tsqr_scratch(h, G, n2);
+    TsqrScratch T;
+    int rc = tsqr_scratch(h, G, n2, T);
     if (rc) return rc;
     if (n2 > 0) {
-        double* Jst = (double*)h->scratch.p;
-        hipLaunchKernelGGL(k_tsqr_stack, dim3(512), dim3(256), 0, h->stream, dRstack, dzstack, (int)G, (int)n2, Jst,
-                           Jst + (size_t)G * n2 * n2);
+        hipLaunchKernelGGL(k_tsqr_stack, dim3(512), dim3(256), 0, h->stream, dRstack, dzstack, (int)G, (int)n2, T.Jst, T.rxs);
         GN_HIP(hipGetLastError());
     }
     return tsqr_combine_core(h, G, n2, eps_rank, 0, p, dlead, comb_tail_sq, info, jpvtJ2);
@@ -494,12 +490,12 @@ int enlsip_gn_tsqr_combine_scaled_dev(enlsip_gn_handle h, int64_t G, int64_t n2,
         E = std::max(E, e[g]);
     }
     GN_HIP(hipSetDevice(h->device));
-    int rc = tsqr_scratch(h, G, n2);
+    TsqrScratch T;
+    int rc = tsqr_scratch(h, G, n2, T);
     if (rc) return rc;
     hipStream_t s = h->stream;
     if (n2 > 0) {
-        double* Jst = (double*)h->scratch.p;
-        double* rxs = Jst + (size_t)G * n2 * n2;
+        double *Jst = T.Jst, *rxs = T.rxs;
         hipLaunchKernelGGL(k_tsqr_stack, dim3(512), dim3(256), 0, s, dRstack, dzstack, (int)G, (int)n2, Jst, rxs);
         GN_HIP(hipGetLastError());
         // block g arrived times 2^-e[g]: to the common scale 2^-E (nothing to do where the exponents agree)
@@ -632,10 +628,11 @@ int enlsip_gn_solve_tsqr(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t
     hipStream_t s = h->stream;
     const int64_t n2 = h->tsqr_n2;
     const size_t msg_len = ((size_t)TSQR_HDR + (size_t)n * (n + 1) / 2 + (size_t)n + 1) & ~(size_t)1;   // doubles per rank (from n, not n2), 16-byte granules
-    rc = grow(h, h->xbuf, (size_t)(G + 1) * msg_len * 8 + 256);
+    struct { double *send = nullptr, *recv = nullptr;      // the send message + G received messages
+             void carve(Carver& c, size_t len, int G) { c.take(send, "send", len, 16); c.take(recv, "recv", (size_t)G * len, 16); } } X;
+    rc = place_dev(h, h->xbuf, X, msg_len, G);
     if (rc) return rc;
-    double* send = (double*)h->xbuf.p;
-    double* recv = send + msg_len;
+    double *send = X.send, *recv = X.recv;
     GN_HIP(hipMemsetAsync(send, 0, TSQR_HDR * 8, s));
     double* part = nullptr;
     unsigned* count = nullptr;
@@ -667,13 +664,12 @@ int enlsip_gn_solve_tsqr(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t
     }
     if (ev) GN_HIP(hipEventRecord(ev[7], s));
     // ---- combine, redundantly on every rank ----------------------------------------------------------------------------------
-    rc = tsqr_scratch(h, G, n2);
+    TsqrScratch T;
+    rc = tsqr_scratch(h, G, n2, T);
     if (rc) return rc;
-    double* Jst = (double*)h->scratch.p;
-    double* tails = (double*)(h->small + 12);
+    double* tails = h->small->tails;
     if (n2 > 0) {
-        hipLaunchKernelGGL(k_tsqr_unpack, dim3(1024), dim3(256), 0, s, recv, (long long)msg_len, G, (int)n2, Jst,
-                           Jst + (size_t)G * n2 * n2, tails);
+        hipLaunchKernelGGL(k_tsqr_unpack, dim3(1024), dim3(256), 0, s, recv, (long long)msg_len, G, (int)n2, T.Jst, T.rxs, tails);
         GN_HIP(hipGetLastError());
     } else {
         GN_HIP(hipMemsetAsync(tails, 0, 32, s));

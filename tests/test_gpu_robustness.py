@@ -520,3 +520,53 @@ def test_update_table_and_stream_ceiling():
                 assert 1000.0 < gbs < 8000.0            # an MI355X streams 5-6 TB/s in place; anything else is a broken measurement
         finally:
             s.close()
+
+
+def test_one_handle_regrowing_its_workspaces_matches_fresh_handles():
+    """One handle through shapes that place the main workspace again (smaller, larger, smaller), use the distributed constraint
+    workspace for the first time (t > 64 and n t > 8192) and run the shared staging layout after a larger shape: every output of
+    every step is bit for bit that of a fresh handle given the same call."""
+    from enlsip_gn import GNSolver
+
+    def batch_inputs(seed, batch, m, n, t):
+        ps = [synth.make_problem(seed + k, m, n, t) for k in range(batch)]
+        J = np.ascontiguousarray(np.stack([np.asfortranarray(q[0]).T for q in ps]))                  # (batch, n, m): column-major m x n
+        rx = np.stack([q[1] for q in ps])
+        At = np.ascontiguousarray(np.stack([q[2].reshape(t, n) for q in ps])) if t else None         # (batch, t, n)
+        cx = np.stack([q[3] for q in ps]) if t else None
+        return J, rx, At, cx
+
+    def flat(out):      # every output of a call as a list of arrays
+        if isinstance(out, tuple):      # batched: jpvtJ2 of problem k is defined on its first n2 = n - rankA entries only
+            p, b, d, infos, jA, jL, jJ = out
+            jJ = jJ.copy()
+            for k, info in enumerate(infos):
+                jJ[k, jJ.shape[1] - info[0]:] = 0
+            return [p, b, d, np.asarray(infos), jA, jL, jJ]
+        return [out.p, out.b, out.d, np.array([out.rankA, out.rankJ2, out.code, out.dimA, out.dimJ2, out.status]), out.jpvtA, out.jpvtL,
+                out.jpvtJ2]
+
+    def factored(s):
+        J, rx, A, cx = synth.make_problem(5150, 33, 32, 1)
+        first = s.factor_constraints(33, A, cx)
+        return [np.array(first)] + flat(s.solve_factored(J, rx, 1))
+
+    steps = [lambda s: flat(s.solve_batched(*batch_inputs(5110, 3, 33, 32, 1))),
+             lambda s: flat(s.solve_batched(*batch_inputs(5120, 2, 200, 128, 65))),
+             lambda s: flat(s.solve_batched(*batch_inputs(5130, 2, 1056, 100, 0))),
+             lambda s: flat(s.solve_batched(*batch_inputs(5110, 3, 33, 32, 1))),
+             factored]
+    reused = GNSolver(device=0)
+    try:
+        for i, step in enumerate(steps):
+            got = step(reused)
+            fresh = GNSolver(device=0)
+            try:
+                want = step(fresh)
+            finally:
+                fresh.close()
+            assert len(got) == len(want)
+            for j, (a, b) in enumerate(zip(got, want)):
+                assert a.shape == b.shape and a.tobytes() == b.tobytes(), (i, j)
+    finally:
+        reused.close()
