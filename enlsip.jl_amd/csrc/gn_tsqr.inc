@@ -668,12 +668,10 @@ int enlsip_gn_solve_tsqr(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t
     rc = tsqr_scratch(h, G, n2, T);
     if (rc) return rc;
     double* tails = h->small->tails;
-    if (n2 > 0) {
-        hipLaunchKernelGGL(k_tsqr_unpack, dim3(1024), dim3(256), 0, s, recv, (long long)msg_len, G, (int)n2, T.Jst, T.rxs, tails);
-        GN_HIP(hipGetLastError());
-    } else {
-        GN_HIP(hipMemsetAsync(tails, 0, 32, s));
-    }
+    // n2 == 0: no triangle and no z to unpack (the loops over G n2 are empty), but the headers still carry what ||d|| is made of —
+    // d = d_temp, so the ranks' tail^2 at the common scale are the whole norm
+    hipLaunchKernelGGL(k_tsqr_unpack, dim3(n2 > 0 ? 1024 : 1), dim3(256), 0, s, recv, (long long)msg_len, G, (int)n2, T.Jst, T.rxs, tails);
+    GN_HIP(hipGetLastError());
     double ctail = 0.0;
     double tail_host[4] = {0.0, 0.0, -1.0, 0.0};      // tail^2, the n2 check, the rank tags, E; complete before this frame can be left
     {

@@ -325,14 +325,18 @@ def tsqr_stage_ms(solver: GNSolver):
 
 
 def tsqr_solve_shards_dev(solver: GNSolver, Jd, rxd, Atd, cxd, G: int, eps_rank: float = SQRT_EPS, scaled: bool = False,
-                          row_blocks=None) -> TSQRResult:
+                          row_blocks=None, in_place: bool = False) -> TSQRResult:
     """Single-process rehearsal on ONE GPU with the data already in HBM: ``Jd`` (n, m) C-order == column-major m x n,
     ``rxd`` (m), ``Atd`` (t, n) C-order == column-major n x t or None, ``cxd`` (t) or None.  The G row blocks are factored one after
     the other on the same handle and stacked exactly as the all-gather would (the handle's resident F_A / p1 come from the
     last local stage, identical on every 'rank').  ``row_blocks``: the G block heights (default: ``row_range``).  ``scaled``: the
-    stages that carry each block's exponent (magnitudes outside 2^-400 .. 2^400)."""
+    stages that carry each block's exponent (magnitudes outside 2^-400 .. 2^400).  ``in_place``: the local stage reads block g
+    where it lies, ``J + lo`` with ``ldj = m`` and ``rx + lo``, as a caller with one resident matrix would shard it (an odd ``lo``
+    gives a base that is 8-byte but not 16-byte aligned); default: a contiguous copy of the block with ``ldj = m_loc``."""
     import torch
     n, m = Jd.shape
+    if in_place and not (Jd.is_contiguous() and rxd.is_contiguous() and Jd.dtype == rxd.dtype == torch.float64):
+        raise ValueError("in_place needs contiguous float64 Jd and rxd")
     t = 0 if Atd is None else Atd.shape[0]
     dev = Jd.device
     if row_blocks is None:
@@ -346,19 +350,24 @@ def tsqr_solve_shards_dev(solver: GNSolver, Jd, rxd, Atd, cxd, G: int, eps_rank:
     es, tails = [], []
     for g in range(G):
         lo, hi = edges[g]
-        Jl = Jd[:, lo:hi].contiguous()                 # column-major (hi - lo) x n
-        rl = rxd[lo:hi].contiguous()
+        if in_place:
+            Jl, rl = None, None
+            pJ, ldj, prx = Jd.data_ptr() + 8 * lo, m, rxd.data_ptr() + 8 * lo
+        else:
+            Jl = Jd[:, lo:hi].contiguous()             # column-major (hi - lo) x n
+            rl = rxd[lo:hi].contiguous()
+            pJ, ldj, prx = Jl.data_ptr(), hi - lo, rl.data_ptr()
         R = torch.empty((n * n,), dtype=torch.float64, device=dev)      # k_tsqr_extract writes all n2 * n2 / n2 entries it hands back
         z = torch.empty((n,), dtype=torch.float64, device=dev)
         torch.cuda.synchronize(dev)                    # the library runs on its own stream
         if scaled:
-            n2, tail, e = hip_local_stage_scaled(solver, hi - lo, n, t, Jl.data_ptr(), hi - lo, rl.data_ptr(),
+            n2, tail, e = hip_local_stage_scaled(solver, hi - lo, n, t, pJ, ldj, prx,
                                                  Atd.data_ptr() if t else 0, cxd.data_ptr() if t else 0, R.data_ptr(),
                                                  z.data_ptr(), eps_rank)
             es.append(e)
             tails.append(tail)
         else:
-            n2, tail = hip_local_stage(solver, hi - lo, n, t, Jl.data_ptr(), hi - lo, rl.data_ptr(),
+            n2, tail = hip_local_stage(solver, hi - lo, n, t, pJ, ldj, prx,
                                        Atd.data_ptr() if t else 0, cxd.data_ptr() if t else 0, R.data_ptr(), z.data_ptr(),
                                        eps_rank)
             tail_total += tail
@@ -380,7 +389,7 @@ def tsqr_solve_shards_dev(solver: GNSolver, Jd, rxd, Atd, cxd, G: int, eps_rank:
 
 
 def tsqr_solve_shards(solver: GNSolver, J, rx, A_active, cx, G: int, eps_rank: float = SQRT_EPS, scaled: bool = False,
-                      row_blocks=None) -> TSQRResult:
+                      row_blocks=None, in_place: bool = False) -> TSQRResult:
     """Same, host arrays in: ``J`` (m, n), ``rx`` (m), ``A_active`` (t, n), ``cx`` (t)."""
     import torch
     t = A_active.shape[0]
@@ -389,4 +398,4 @@ def tsqr_solve_shards(solver: GNSolver, J, rx, A_active, cx, G: int, eps_rank: f
     rxd = torch.tensor(np.asarray(rx), dtype=torch.float64, device=dev)
     Atd = torch.tensor(np.ascontiguousarray(A_active), dtype=torch.float64, device=dev) if t else None
     cxd = torch.tensor(np.asarray(cx), dtype=torch.float64, device=dev) if t else None
-    return tsqr_solve_shards_dev(solver, Jd, rxd, Atd, cxd, G, eps_rank, scaled=scaled, row_blocks=row_blocks)
+    return tsqr_solve_shards_dev(solver, Jd, rxd, Atd, cxd, G, eps_rank, scaled=scaled, row_blocks=row_blocks, in_place=in_place)

@@ -230,6 +230,22 @@ def test_tsqr_driver_with_real_ranks_on_the_device(world):
 
 
 @pytest.mark.gpu
+def test_tsqr_driver_with_real_ranks_on_degenerate_cases():
+    """The message path (k_tsqr_pack / k_tsqr_unpack: a packed triangle and a message length taken from n, not n2) where something
+    is degenerate, with two real ranks (tests/tsqr_rank_worker.py, TSQR_CASES=edges): a rank-deficient A, n2 == 0, shards of 8 and
+    7 rows against n2 = 20, and a J2 whose stacked pivoted QR truncates — each through enlsip_gn_solve_tsqr and through
+    tsqr_solve(scaled=True), checked as tests/test_gpu_tsqr_edges.py checks them."""
+    import os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    world = 2
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+           "--master-port", "29548", os.path.join(root, "tests", "tsqr_rank_worker.py")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=dict(os.environ, TSQR_CASES="edges"))
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-1500:]
+    assert out.stdout.count(" ok") == 2 * 4 * world and "FAIL" not in out.stdout, out.stdout[-3000:]
+
+
+@pytest.mark.gpu
 def test_solve_tsqr_through_a_one_rank_rccl_communicator():
     """The RCCL leg of enlsip_gn_solve_tsqr on the one GPU there is: unique id, ncclCommInitRank with one rank, and the exchange
     itself as ncclAllGather on the handle's stream (an attached communicator is used even with one rank: a self-gather, so the

@@ -91,19 +91,27 @@ def safe_norm(x):
     return float(np.linalg.norm(np.ldexp(x, -k))), k
 
 
-def check_against_oracle(out, ref, tag):
+def check_against_oracle(out, ref, tag, lead_rows=None, pivots=True):
     """ranks, code, pivots on the leading rankJ2 positions, p to 1e-11, |dlead| to 1e-10 of its largest entry, d_norm to 1e-12
-    (the tolerances of tests/test_gpu_parity.py); `out`: a TSQRResult."""
+    (the tolerances of tests/test_gpu_parity.py); `out`: a TSQRResult.  `lead_rows`: compare only that many leading entries of
+    dlead (default: all n2) — for a J2 whose pivoted QR truncates (tests/tsqr_edge_cases.py): beyond rankJ2 the reflectors are built
+    from rounding dust, so the entries of Q'd there belong to an arbitrary basis and only their norm (inside d_norm) is defined.
+    `pivots=False`: do not compare jpvtJ2 — for a rank-deficient A (code -1), where J2 itself is defined only up to an orthogonal
+    factor on its right (tsqr_edge_cases.comparable)."""
     n2 = ref.p.size - ref.rankA
+    nl = n2 if lead_rows is None else int(lead_rows)
     assert (out.rankA, out.rankJ2, out.code) == (ref.rankA, ref.rankJ2, ref.code), tag
     r = ref.rankJ2
-    assert np.array_equal(np.asarray(out.jpvtJ2)[:r], ref.jpvtJ2[:r]), tag
+    if pivots:
+        assert np.array_equal(np.asarray(out.jpvtJ2)[:r], ref.jpvtJ2[:r]), tag
+    else:
+        assert sorted(np.asarray(out.jpvtJ2).tolist()) == list(range(1, n2 + 1)), tag
     assert np.all(np.isfinite(out.p)), tag
     np_ref = np.linalg.norm(ref.p)
     err_p = float(np.linalg.norm(out.p - ref.p) / (np_ref if np_ref > 0 else 1.0))
-    lead_ref = np.abs(ref.d[:n2])
+    lead_ref = np.abs(ref.d[:nl])
     _, k = safe_norm(lead_ref)
-    err_l = float(np.abs(np.ldexp(np.abs(out.dlead), -k) - np.ldexp(lead_ref, -k)).max() / np.ldexp(lead_ref, -k).max()) if n2 else 0.0
+    err_l = float(np.abs(np.ldexp(np.abs(out.dlead[:nl]), -k) - np.ldexp(lead_ref, -k)).max() / np.ldexp(lead_ref, -k).max()) if nl else 0.0
     nd, kd = safe_norm(ref.d)
     err_d = abs(float(np.ldexp(out.d_norm, -kd)) - nd) / nd
     print(f"{tag}: rel p {err_p:.2e}  lead {err_l:.2e}  d_norm {err_d:.2e}  ranks ({out.rankA}, {out.rankJ2})", flush=True)
