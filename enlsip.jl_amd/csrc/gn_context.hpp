@@ -245,6 +245,11 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf del_scr;
     gn::PinnedBuf h_del;
     int deletion_form = -1;
+    // batched line-search set-up (gn_linesearch_batched.inc): the inactive lists and per-problem records of one call on the device
+    // and in pinned memory, the partial sums and the five scalars per problem, and the form of the last call; nothing resident
+    gn::DevBuf ls_scr;
+    gn::PinnedBuf h_ls;
+    int linesearch_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

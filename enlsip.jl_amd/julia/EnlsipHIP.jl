@@ -725,6 +725,58 @@ function deletion_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""    upper_bound_steplength_hip(inactive, n_inactive, index_del, cx, Ap) -> (α_upp, index_α_upp)
+
+`upper_bound_steplength` (src/enlsip_functions.jl:2149-2178) on host data with `Ap = A * p` already formed, through the library's
+host entry point (no handle, no GPU): the routine the batched call below runs on the device.  `inactive` holds 1-based rows (0 =
+padding) of which the first `n_inactive` are walked in list order; `l = length(cx)`."""
+function upper_bound_steplength_hip(inactive::Vector{Int64}, n_inactive::Integer, index_del::Integer, cx::Vector{Float64},
+                                    Ap::Vector{Float64})
+    l = length(cx)
+    (length(Ap) == l && length(inactive) >= n_inactive) || error("cx and Ap need l entries, inactive n_inactive")
+    α = Ref{Float64}(0.0)
+    idx = Ref{Int64}(0)
+    rc = GC.@preserve inactive cx Ap ccall((:enlsip_gn_upper_bound_steplength, LIB), Cint,
+        (Int64, Int64, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ref{Float64}, Ref{Int64}),
+        l, n_inactive, inactive, index_del, cx, Ap, α, idx)
+    rc == 0 || error("enlsip_gn_upper_bound_steplength returned $rc")
+    return α[], Int(idx[])
+end
+
+"""    linesearch_setup_batched_dev_hip(h, B, m, n, l, dp, dA, lda, strideA, dcx, inactive, n_inactive, index_del, dJp, drx, dAp)
+        -> (α_upp, index_α_upp, sums)
+
+The line-search set-up of a batch on DEVICE buffers: `Ap = A * p` with the full constraint Jacobian into `dAp` (:2226-2229),
+`upper_bound_steplength` on it (:2149-2178) and, unless `dJp` and `drx` are `C_NULL`, the sums `dot(Jp,Jp)`, `dot(Jp,rx)`,
+`dot(rx,rx)` of :1561-1584 / :2269 as the columns of the 3 x B matrix `sums` (`nothing` without them).  `inactive` (l x B, zero
+padded: problem k's list is column k), `n_inactive` and `index_del` (`nothing`: 0) are host arrays."""
+function linesearch_setup_batched_dev_hip(h::Handle, B::Integer, m::Integer, n::Integer, l::Integer, dp::Ptr{Float64},
+                                          dA::Ptr{Float64}, lda::Integer, strideA::Integer, dcx::Ptr{Float64},
+                                          inactive::Matrix{Int64}, n_inactive::Vector{Int64},
+                                          index_del::Union{Nothing,Vector{Int64}}, dJp::Ptr{Float64}, drx::Ptr{Float64},
+                                          dAp::Ptr{Float64})
+    (size(inactive) == (l, B) && length(n_inactive) == B && (index_del === nothing || length(index_del) == B)) ||
+        error("inactive is l x B, n_inactive and index_del need B entries")
+    α = zeros(Float64, B)
+    idx = zeros(Int64, B)
+    with_sums = dJp != C_NULL && drx != C_NULL
+    sums = with_sums ? zeros(Float64, 3, B) : nothing
+    psums = with_sums ? pointer(sums) : Ptr{Float64}(C_NULL)
+    pdel = index_del === nothing ? Ptr{Int64}(C_NULL) : pointer(index_del)
+    GC.@preserve inactive n_inactive index_del α idx sums check(h, ccall((:enlsip_gn_linesearch_setup_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Int64}, Ptr{Int64},
+         Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+        h.ptr, B, m, n, l, dp, dA, lda, strideA, dcx, inactive, n_inactive, pdel, dJp, drx, dAp, α, idx, psums))
+    return α, idx, sums
+end
+
+"""    linesearch_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last line-search set-up on `h`"""
+function linesearch_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_linesearch_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

@@ -138,6 +138,11 @@ PROTOTYPES = {
     "enlsip_gn_restore_constraints_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                             C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p]),
     "enlsip_gn_get_deletion_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_upper_bound_steplength": (C.c_int, [_i64, _i64, C.c_void_p, _i64, C.c_void_p, C.c_void_p, _dp, _ip]),
+    "enlsip_gn_linesearch_setup_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.c_void_p, C.c_void_p, _i64, _i64, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_linesearch_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

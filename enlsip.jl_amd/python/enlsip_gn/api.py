@@ -81,6 +81,27 @@ def check_constraint_deletion(q: int, lam, scaling: bool, diag_scale, grad_res: 
     return int(s.value)
 
 
+def upper_bound_steplength(inactive, n_inactive: int, index_del: int, cx, Ap):
+    """upper_bound_steplength (src/enlsip_functions.jl:2149-2178) on host data with Ap = A * p already formed, through the
+    library's host entry point (no GPU): (alpha_upp, index_alpha_upp).  inactive: 1-based rows, 0 padding, of which the first
+    n_inactive are walked; l = len(cx); the routine the batched kernels run."""
+    iv = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
+    cv = np.ascontiguousarray(cx, dtype=np.float64)
+    av = np.ascontiguousarray(Ap, dtype=np.float64)
+    l = cv.size
+    if av.size != l:
+        raise ValueError("cx and Ap need l entries each")
+    if iv.size < n_inactive:
+        raise ValueError("inactive needs n_inactive entries")
+    alpha, idx = C.c_double(0.0), C.c_int64(0)
+    rc = L.load().enlsip_gn_upper_bound_steplength(l, int(n_inactive), _fptr(iv) if iv.size else None, int(index_del),
+                                                   _fptr(cv) if l else None, _fptr(av) if l else None, C.byref(alpha),
+                                                   C.byref(idx))
+    if rc:
+        raise GNError(f"enlsip_gn_upper_bound_steplength returned {rc}")
+    return float(alpha.value), int(idx.value)
+
+
 @dataclass
 class GNResult:
     p: np.ndarray
@@ -775,6 +796,31 @@ class GNSolver:
     def deletion_form(self) -> int:
         """Kernel form of the last delete / restore call: 0 general, 1 one wave per problem, -1 none yet."""
         return self._form("enlsip_gn_get_deletion_form")
+
+    # ---- the line-search set-up on device buffers (src/enlsip_functions.jl:2149-2178, :2226-2229, :1561-1584, :2269) ---------------
+    def linesearch_setup_batched_dev(self, batch, m, n, l, dp, dA, lda, strideA, dcx, inactive, n_inactive, dAp, index_del=None,
+                                     dJp=0, drx=0):
+        """Ap = A * p with the full constraint Jacobian into dAp (l per problem), upper_bound_steplength on it, and with dJp and
+        drx (m per problem; both or neither) the sums Jp.Jp, Jp.rx, rx.rx.  inactive (batch, l) and n_inactive, index_del (batch,;
+        None: 0) stay host arrays.  Returns (alpha_upp (batch,), index_alpha_upp (batch,) int64, sums (batch, 3) or None)."""
+        ni = self._host_i64(n_inactive, batch, "n_inactive")
+        idel = None if index_del is None else self._host_i64(index_del, batch, "index_del")
+        inact = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
+        if inact.size != batch * l:
+            raise ValueError(f"inactive must have {batch} x {l} entries")
+        if bool(dJp) != bool(drx):
+            raise ValueError("dJp and drx go together")
+        alpha = np.zeros(batch)
+        index = np.zeros(batch, dtype=np.int64)
+        sums = np.zeros((batch, 3)) if dJp else None
+        self._chk(self._lib.enlsip_gn_linesearch_setup_batched_dev(
+            self._h, batch, m, n, l, _dptr(dp), _dptr(dA), lda, strideA, _dptr(dcx), _fptr(inact) if inact.size else None, _fptr(ni),
+            _fptr(idel), _dptr(dJp), _dptr(drx), _dptr(dAp), _fptr(alpha), _fptr(index), _fptr(sums)))
+        return alpha, index, sums
+
+    def linesearch_form(self) -> int:
+        """Kernel form of the last linesearch_setup_batched_dev: 0 general, 1 one wave per problem, -1 none yet."""
+        return self._form("enlsip_gn_get_linesearch_form")
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).

@@ -568,6 +568,55 @@ int enlsip_gn_restore_constraints_batched_dev(enlsip_gn_handle h, int64_t batch,
                                               const double* dsaved);
 int enlsip_gn_get_deletion_form(enlsip_gn_handle h, int* form);
 
+/* ---- the line-search set-up of a batch, on the caller's device buffers ---------------------------------------------------------
+ * What compute_steplength (src/enlsip_functions.jl:2197-2293) does with the direction before the line search itself: the product
+ * with the FULL constraint Jacobian, `Ap = A * p` (:2226-2229), upper_bound_steplength on it (:2149-2178), and the three sums
+ * through which `Jp` enters the scalars of the set-up: dot(Jp,Jp), dot(Jp,rx) and dot(rx,rx) of penalty_weight_update (:1561-1584)
+ * and of the predicted reduction (:2269).  Jp itself is what enlsip_gn_jacobian_times_batched_dev leaves on the device.  The penalty
+ * weights, the merit function, the polynomial fit and the callbacks stay with the caller.
+ *
+ * enlsip_gn_upper_bound_steplength   upper_bound_steplength (src/enlsip_functions.jl:2149-2178) on HOST data, no handle and no GPU,
+ *     on an Ap that has already been formed.  inactive: n_inactive 1-based row indices, 0 for padding; cx, Ap: l entries.  The list is
+ *     walked in list order; an all-zero list looks at nothing (:2163); the entry equal to index_del is skipped (:2166); alpha_j =
+ *     -cx[j] / Ap[j] is an IEEE division; the test is cx[j] > 0 && Ap[j] < 0 && alpha_j < alpha_upper with a strict <, so among equal
+ *     minima the first list position wins and a row with a NaN is skipped; *alpha_upp = min(3.0, alpha_upper) while *index_alpha_upp
+ *     stays the minimising row even when its alpha_j is 3 or more; no row qualifies: 3.0 and 0.  Returns 0; -2 an output pointer
+ *     NULL, l < 0 or n_inactive outside 0..l; -4 inactive, cx or Ap NULL while n_inactive > 0; -5 a list entry outside 0..l.  The same
+ *     routine, compiled for the device, makes the decisions below.
+ * enlsip_gn_linesearch_setup_batched_dev   for every problem k: dAp[k, 0:l) = A_k * p_k (A_k: l x n column-major at dA + k *
+ *     strideA, lda >= l; dp n per problem), the bound on dcx[k, 0:l) (ALL constraint values), that product, the first n_inactive[k]
+ *     entries of inactive[k, 0:l) and index_del[k] (index_del NULL: 0 everywhere), and, when dJp, drx and sums are given (all three
+ *     or none), sums[3k .. 3k+2] = Jp.Jp, Jp.rx, rx.rx over the m entries of dJp[k], drx[k].  inactive, n_inactive, index_del,
+ *     alpha_upp, index_alpha_upp and sums are HOST arrays; everything with a d is a device buffer.  In the general form dAp[k] is bit
+ *     for bit what enlsip_gn_full_constraints_times returns for problem k (columns summed in ascending order); alpha_upp and
+ *     index_alpha_upp are what enlsip_gn_upper_bound_steplength returns on that dAp.  The sums are plain sums of products added in a
+ *     fixed order without floating-point atomics: a sum depends on m and the operands alone, not on the slot, the batch or the
+ *     call.  They are covered for operands inside the 2^+-400 band; beyond it they are not part of the magnitude contract (a product
+ *     may overflow or underflow where a scaled norm would not).  l == 0: 3.0 and 0 for every problem, the sums are still computed.
+ *     No byte outside dAp[k, 0:l) is written; no input is.
+ * enlsip_gn_get_linesearch_form   kernel form of the last call on this handle: 0 general (product: one thread per row, p in LDS;
+ *     bound: one workgroup per problem; sums: partial sums per workgroup, added in index order), 1 one wave per problem (n <= 64 and
+ *     l <= 64: four problems per workgroup, one launch, the arg-min by cross-lane operations), -1 none yet.  The two forms name the
+ *     same row on the same dAp.
+ * The call needs no resident factors: it is legal in every handle state, between a factor call and its solve included, and touches
+ * nothing resident.  The number of launches does not depend on batch (which may exceed the grid's y limit); one copy of the host
+ * records goes up, one copy of the five scalars per problem comes back, and the call returns after ONE synchronisation of the
+ * handle's stream.  The records live in a scratch the handle keeps.  Argument errors are raised before anything is launched and
+ * leave every buffer untouched (last_error names k):
+ *   -1 h NULL; -2 batch < 1 (or batch times the workgroups per problem beyond 2^31-1); -3 n outside 1..1024 (this build), l < 0 (or
+ *   above 2^27), or m < 1 while the sums are asked for; -4 n_inactive, alpha_upp or index_alpha_upp NULL, dp, dA, dcx, inactive or
+ *   dAp NULL while l > 0, or exactly one or two of dJp / drx / sums missing; -5 some n_inactive[k] outside 0..l; -6 a list entry or
+ *   index_del[k] outside 0..l; -9 lda < l; -10 strideA < lda * n.
+ */
+int enlsip_gn_upper_bound_steplength(int64_t l, int64_t n_inactive, const int64_t* inactive, int64_t index_del,
+                                     const double* cx, const double* Ap, double* alpha_upp, int64_t* index_alpha_upp);
+int enlsip_gn_linesearch_setup_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t l,
+                                           const double* dp, const double* dA, int64_t lda, int64_t strideA,
+                                           const double* dcx, const int64_t* inactive, const int64_t* n_inactive,
+                                           const int64_t* index_del, const double* dJp, const double* drx,
+                                           double* dAp, double* alpha_upp, int64_t* index_alpha_upp, double* sums);
+int enlsip_gn_get_linesearch_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
