@@ -31,6 +31,7 @@
 #include "gn_kernels_subspace_batched.hpp"
 #include "gn_kernels_deletion_batched.hpp"
 #include "gn_kernels_linesearch_batched.hpp"
+#include "gn_kernels_penalty_batched.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_newton_batched.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
@@ -1524,9 +1525,10 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->ssb_io.p) (void)hipFree(h->ssb_io.p);
     if (h->del_scr.p) (void)hipFree(h->del_scr.p);
     if (h->ls_scr.p) (void)hipFree(h->ls_scr.p);
+    if (h->pen_scr.p) (void)hipFree(h->pen_scr.p);
     for (hipEvent_t e : h->nwb_ev)
         if (e) (void)hipEventDestroy(e);
-    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_nwflag, &h->h_lagflag})
+    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_pen, &h->h_nwflag, &h->h_lagflag})
         if (b->p) (void)hipHostFree(b->p);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);
@@ -2455,5 +2457,6 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_subspace_batched.inc"
 #include "gn_deletion_batched.inc"
 #include "gn_linesearch_batched.inc"
+#include "gn_penalty_batched.inc"
 #include "gn_newton.inc"
 #include "gn_newton_batched.inc"

@@ -250,6 +250,12 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf ls_scr;
     gn::PinnedBuf h_ls;
     int linesearch_form = -1;
+    // batched penalty weights and merit function (gn_penalty_batched.inc): the active / inactive lists and per-problem records of one
+    // call on the device and in pinned memory, the partial sums of rx.rx and the scalars per problem (the two calls lay the same
+    // buffers out for themselves), and the form of the last penalty-weight call; nothing resident
+    gn::DevBuf pen_scr;
+    gn::PinnedBuf h_pen;
+    int penalty_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

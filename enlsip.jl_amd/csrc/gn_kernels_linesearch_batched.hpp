@@ -73,28 +73,45 @@ __global__ __launch_bounds__(256) void k_ls_product(LinesearchArgs a) {
     a.Ap[k * a.l + r] = s;
 }
 
+// The ordered partial sums, shared with the merit function (gn_kernels_penalty_batched.hpp).  Workgroup b of a problem's nblk: every
+// thread walks entries b*256 + tid + i*nblk*256 and `add(i, acc)` adds entry i's products to the thread's Q sums; then the wave
+// butterfly, the four waves in order, and Q partial sums at out[0:Q).  ws: Q x 4 doubles of LDS.  All 256 threads call it.
+template <int Q, class Add>
+__device__ __forceinline__ void ordered_partial_sums(int b, int nblk, long long m, double (*ws)[4], double* out, Add add) {
+    double acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = 0.0;
+    for (long long i = (long long)b * 256 + threadIdx.x; i < m; i += (long long)nblk * 256) add(i, acc);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        acc[q] = wave_allsum(acc[q]);
+        if (lane_id() == 0) ws[q][wave_id()] = acc[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < Q) {
+        const double* w = ws[threadIdx.x];
+        out[threadIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
+    }
+}
+
+// ... and their sum: lane b of one wave holds partial b of sum q (nblk <= 64, stride Q), added by the fixed-shape butterfly
+__device__ __forceinline__ double ordered_partials_total(const double* pt, int nblk, int Q, int q) {
+    const int ln = lane_id();
+    return wave_allsum(ln < nblk ? pt[ln * Q + q] : 0.0);
+}
+
 __global__ __launch_bounds__(256) void k_ls_sums_part(LinesearchArgs a) {
     __shared__ double ws[3][4];
     const long long k = blockIdx.x / a.nblk;
     const int b = (int)(blockIdx.x % a.nblk);
     const double* jp = a.Jp + k * a.m;
     const double* rx = a.rx + k * a.m;
-    double jj = 0.0, jr = 0.0, rr = 0.0;
-    for (long long i = (long long)b * 256 + threadIdx.x; i < a.m; i += (long long)a.nblk * 256) {
+    ordered_partial_sums<3>(b, a.nblk, a.m, ws, a.part + ((size_t)k * a.nblk + b) * 3, [=](long long i, double (&s)[3]) {
         const double x = jp[i], y = rx[i];
-        jj += x * x;
-        jr += x * y;
-        rr += y * y;
-    }
-    jj = wave_allsum(jj);
-    jr = wave_allsum(jr);
-    rr = wave_allsum(rr);
-    if (lane_id() == 0) { ws[0][wave_id()] = jj; ws[1][wave_id()] = jr; ws[2][wave_id()] = rr; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const double* w = ws[threadIdx.x];
-        a.part[((size_t)k * a.nblk + b) * 3 + threadIdx.x] = ((w[0] + w[1]) + w[2]) + w[3];
-    }
+        s[0] += x * x;
+        s[1] += x * y;
+        s[2] += y * y;
+    });
 }
 
 __global__ __launch_bounds__(256) void k_ls_bound(LinesearchArgs a) {
@@ -139,7 +156,7 @@ __global__ __launch_bounds__(256) void k_ls_bound(LinesearchArgs a) {
         const double* pt = a.part + (size_t)k * a.nblk * 3;
 #pragma unroll
         for (int q = 0; q < 3; ++q) {
-            const double t = wave_allsum(tid < a.nblk ? pt[tid * 3 + q] : 0.0);
+            const double t = ordered_partials_total(pt, a.nblk, 3, q);
             if (tid == 0) o->sums[q] = t;
         }
     }

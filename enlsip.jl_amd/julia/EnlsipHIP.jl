@@ -777,6 +777,79 @@ function linesearch_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""    penalty_weight_update_hip(w_old, active, t, dimA, norm_code, active_Ap, cx, K, JpJp, Jprx, rxrx) -> (w, dψ0, ψ0, atwa, branch)
+
+`penalty_weight_update` (src/enlsip_functions.jl:1545-1629) with ψ(0) of :2243 and `atwa` of :2268 on host data, through the
+library's host entry point (no handle, no GPU): the routine the batched call below runs on the device.  `active_Ap` holds the `t`
+entries of `C.A * p`, already divided by `diag_scale` where scaling is on; `K` is the l x 4 matrix whose column ii is `K[ii]` of
+the reference and is updated in place; `Jp` and `rx` enter through the three sums of the set-up call."""
+function penalty_weight_update_hip(w_old::Vector{Float64}, active::Vector{Int64}, t::Integer, dimA::Integer, norm_code::Integer,
+                                   active_Ap::Vector{Float64}, cx::Vector{Float64}, K::Matrix{Float64}, JpJp::Float64,
+                                   Jprx::Float64, rxrx::Float64)
+    l = length(w_old)
+    (length(cx) == l && size(K) == (l, 4) && length(active) >= t && length(active_Ap) >= t) ||
+        error("cx needs l entries, K is l x 4, active and active_Ap need t entries")
+    w = zeros(Float64, l)
+    sc = zeros(Float64, 3)
+    br = Ref{Cint}(0)
+    rc = GC.@preserve w_old active active_Ap cx K w sc ccall((:enlsip_gn_penalty_weight_update, LIB), Cint,
+        (Int64, Int64, Ptr{Int64}, Int64, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Float64, Float64, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ref{Cint}),
+        l, t, active, dimA, norm_code, w_old, active_Ap, cx, JpJp, Jprx, rxrx, K, w, sc, br)
+    rc == 0 || error("enlsip_gn_penalty_weight_update returned $rc")
+    return w, sc[1], sc[2], sc[3], Int(br[])
+end
+
+"""    penalty_weights_batched_dev_hip(h, B, l, t_max, t, dimA, active, take, norm_code, scaling, dw_old, dactive_Ap, ddiag_scale,
+                                    dcx, dK, sums, dw) -> (scalars, branch)
+
+`penalty_weight_update` (:2238) for every taken problem of a batch on DEVICE buffers: `dw` (l per problem) and `dK` (4 l per
+problem) are written there, the division `active_Ap ./ diag_scale` (:2231-2233) happens inside when `scaling`.  `t`, `dimA`,
+`active` (t_max x B, zero padded: problem k's list is column k), `take` (`nothing`: all) and `sums` (3 x B, as the set-up call
+returns them) are host arrays.  Returns `scalars` (3 x B: dψ0, ψ0, atwa) and `branch`; both 0 for a problem not taken."""
+function penalty_weights_batched_dev_hip(h::Handle, B::Integer, l::Integer, t_max::Integer, t::Vector{Int64}, dimA::Vector{Int64},
+                                         active::Matrix{Int64}, take::Union{Nothing,Vector{Int64}}, norm_code::Integer,
+                                         scaling::Bool, dw_old::Ptr{Float64}, dactive_Ap::Ptr{Float64},
+                                         ddiag_scale::Ptr{Float64}, dcx::Ptr{Float64}, dK::Ptr{Float64}, sums::Matrix{Float64},
+                                         dw::Ptr{Float64})
+    (size(active) == (t_max, B) && length(t) == B && length(dimA) == B && size(sums) == (3, B) &&
+     (take === nothing || length(take) == B)) || error("active is t_max x B, sums 3 x B, t, dimA and take need B entries")
+    scalars = zeros(Float64, 3, B)
+    branch = zeros(Cint, B)
+    ptake = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    GC.@preserve t dimA active take sums scalars branch check(h, ccall((:enlsip_gn_penalty_weights_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Cint, Cint, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}),
+        h.ptr, B, l, t_max, t, dimA, active, ptake, norm_code, scaling ? 1 : 0, dw_old, dactive_Ap, ddiag_scale, dcx, dK, sums, dw,
+        scalars, branch))
+    return scalars, branch
+end
+
+"""    penalty_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last penalty-weight call on `h`"""
+function penalty_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_penalty_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
+"""    merit_batched_dev_hip(h, B, m, l, t_max, t, active, inactive, n_inactive, take, drx, dcx, dw) -> ψ
+
+The merit function `psi` (:1307-1340) of one evaluated trial point per problem on DEVICE buffers `drx` (m per problem), `dcx` and
+`dw` (l per problem).  `t`, `active` (t_max x B), `inactive` (l x B), `n_inactive` and `take` (`nothing`: all) are host arrays."""
+function merit_batched_dev_hip(h::Handle, B::Integer, m::Integer, l::Integer, t_max::Integer, t::Vector{Int64},
+                               active::Matrix{Int64}, inactive::Matrix{Int64}, n_inactive::Vector{Int64},
+                               take::Union{Nothing,Vector{Int64}}, drx::Ptr{Float64}, dcx::Ptr{Float64}, dw::Ptr{Float64})
+    (size(active) == (t_max, B) && size(inactive) == (l, B) && length(t) == B && length(n_inactive) == B &&
+     (take === nothing || length(take) == B)) || error("active is t_max x B, inactive l x B, t, n_inactive and take need B entries")
+    ψ = zeros(Float64, B)
+    ptake = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    GC.@preserve t active inactive n_inactive take ψ check(h, ccall((:enlsip_gn_merit_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h.ptr, B, m, l, t_max, t, active, inactive, n_inactive, ptake, drx, dcx, dw, ψ))
+    return ψ
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

@@ -143,6 +143,15 @@ PROTOTYPES = {
                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_get_linesearch_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_penalty_weight_update": (C.c_int, [_i64, _i64, C.c_void_p, _i64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_int)]),
+    "enlsip_gn_penalty_weights_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_penalty_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_merit_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

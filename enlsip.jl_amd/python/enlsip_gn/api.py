@@ -102,6 +102,34 @@ def upper_bound_steplength(inactive, n_inactive: int, index_del: int, cx, Ap):
     return float(alpha.value), int(idx.value)
 
 
+def penalty_weight_update(w_old, active, t: int, dimA: int, norm_code: int, active_Ap, cx, K, JpJp: float, Jprx: float, rxrx: float):
+    """penalty_weight_update (src/enlsip_functions.jl:1545-1629) with psi(0) of :2243 and atwa of :2268 on host data, through the
+    library's host entry point (no GPU): the routine the batched kernels run.  active: 1-based constraints of which the first t
+    count; active_Ap: t entries of C.A * p (already divided by diag_scale where scaling is on); K: (4, l), updated IN PLACE when it
+    is a C-contiguous float64 array (else a copy is updated and returned); Jp and rx enter through the three sums.  Returns
+    (w (l,), dpsi0, psi0, atwa, branch, K)."""
+    wo = np.ascontiguousarray(w_old, dtype=np.float64)
+    l = wo.size
+    av = np.ascontiguousarray(np.asarray(active).astype(np.int64))
+    ap = np.ascontiguousarray(active_Ap, dtype=np.float64)
+    cv = np.ascontiguousarray(cx, dtype=np.float64)
+    Kv = K if isinstance(K, np.ndarray) and K.dtype == np.float64 and K.flags.c_contiguous else np.array(K, dtype=np.float64, order="C")
+    if Kv.shape != (4, l) or cv.size != l:
+        raise ValueError("K must be (4, l) and cx (l,)")
+    if av.size < t or ap.size < t:
+        raise ValueError("active and active_Ap need t entries")
+    w = np.zeros(l)
+    sc = np.zeros(3)
+    br = C.c_int(0)
+    rc = L.load().enlsip_gn_penalty_weight_update(l, int(t), _fptr(av) if av.size else None, int(dimA), int(norm_code),
+                                                  _fptr(wo) if l else None, _fptr(ap) if ap.size else None, _fptr(cv) if l else None,
+                                                  float(JpJp), float(Jprx), float(rxrx), _fptr(Kv) if l else None,
+                                                  _fptr(w) if l else None, _fptr(sc), C.byref(br))
+    if rc:
+        raise GNError(f"enlsip_gn_penalty_weight_update returned {rc}")
+    return w, float(sc[0]), float(sc[1]), float(sc[2]), int(br.value), Kv
+
+
 @dataclass
 class GNResult:
     p: np.ndarray
@@ -821,6 +849,51 @@ class GNSolver:
     def linesearch_form(self) -> int:
         """Kernel form of the last linesearch_setup_batched_dev: 0 general, 1 one wave per problem, -1 none yet."""
         return self._form("enlsip_gn_get_linesearch_form")
+
+    # ---- the penalty weights and the merit function on device buffers (src/enlsip_functions.jl:1545-1629, :2243, :2268, :1307-1340)
+    def penalty_weights_batched_dev(self, batch, l, t_max, t, dimA, active, norm_code, scaling, dw_old, dactive_Ap, ddiag_scale, dcx,
+                                    dK, sums, dw, take=None):
+        """penalty_weight_update per taken problem on the device buffers: dw (l per problem) and dK (4 l per problem) are written
+        there.  t, dimA (batch,), active (batch, t_max; 1-based, 0 padded), take (None: all) and sums (batch, 3: Jp.Jp, Jp.rx, rx.rx
+        as linesearch_setup_batched_dev returns them) stay host arrays.  dw may be dw_old.  Returns (scalars (batch, 3): dpsi0, psi0,
+        atwa; branch (batch,) int32); both 0 for a problem not taken."""
+        t = self._host_i64(t, batch, "t")
+        dimA = self._host_i64(dimA, batch, "dimA")
+        act = np.ascontiguousarray(np.asarray(active).astype(np.int64))
+        if act.size != batch * t_max:
+            raise ValueError(f"active must have {batch} x {t_max} entries")
+        sm = np.ascontiguousarray(sums, dtype=np.float64)
+        if sm.size != 3 * batch:
+            raise ValueError(f"sums must have {batch} x 3 entries")
+        tk = self._pack_take(batch, take)
+        scalars = np.zeros((batch, 3))
+        branch = np.zeros(batch, dtype=np.int32)
+        self._chk(self._lib.enlsip_gn_penalty_weights_batched_dev(
+            self._h, batch, l, t_max, _fptr(t), _fptr(dimA), _fptr(act) if act.size else None, _fptr(tk), int(norm_code),
+            int(bool(scaling)), _dptr(dw_old), _dptr(dactive_Ap), _dptr(ddiag_scale), _dptr(dcx), _dptr(dK), _fptr(sm), _dptr(dw),
+            _fptr(scalars), _fptr(branch)))
+        return scalars, branch
+
+    def penalty_form(self) -> int:
+        """Kernel form of the last penalty_weights_batched_dev: 0 general, 1 one wave per problem, -1 none yet."""
+        return self._form("enlsip_gn_get_penalty_form")
+
+    def merit_batched_dev(self, batch, m, l, t_max, t, active, inactive, n_inactive, drx, dcx, dw, take=None) -> np.ndarray:
+        """psi (:1307-1340) of a batch of evaluated trial points: drx (m per problem), dcx, dw (l per problem) on the device; t,
+        n_inactive (batch,), active (batch, t_max), inactive (batch, l) (1-based, 0 padded) and take (None: all) stay host arrays.
+        Returns psi (batch,), 0 for a problem not taken."""
+        t = self._host_i64(t, batch, "t")
+        ni = self._host_i64(n_inactive, batch, "n_inactive")
+        act = np.ascontiguousarray(np.asarray(active).astype(np.int64))
+        inact = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
+        if act.size != batch * t_max or inact.size != batch * l:
+            raise ValueError(f"active must have {batch} x {t_max} entries, inactive {batch} x {l}")
+        tk = self._pack_take(batch, take)
+        psi = np.zeros(batch)
+        self._chk(self._lib.enlsip_gn_merit_batched_dev(
+            self._h, batch, m, l, t_max, _fptr(t), _fptr(act) if act.size else None, _fptr(inact) if inact.size else None, _fptr(ni),
+            _fptr(tk), _dptr(drx), _dptr(dcx), _dptr(dw), _fptr(psi)))
+        return psi
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).

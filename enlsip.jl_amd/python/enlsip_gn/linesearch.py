@@ -1,8 +1,10 @@
 """The set-up of the line search (``compute_steplength``, src/enlsip_functions.jl:2197-2293) before the line search itself, over
 the HIP library: the products ``Jp = J * p``, ``Ap = A * p`` and ``active_Ap = C.A * p`` (:2226-2229), ``upper_bound_steplength``
 (:2149-2178, called at :2252) and the three sums through which ``Jp`` enters ``penalty_weight_update`` (:1561-1584) and the predicted
-reduction (:2269).  The penalty weights, the merit function, the polynomial fit and the callbacks stay with the caller, and so does
-the division ``active_Ap ./ diag_scale`` (:2231-2233).
+reduction (:2269); then the penalty weights (``penalty_weight_update``, :2238, :1545-1629) with ``psi(0)`` (:2243), ``atwa`` and the
+predicted reduction (:2267-2269), and the merit function ``psi`` (:1307-1340) of evaluated trial points.  The division ``active_Ap
+./ diag_scale`` (:2231-2233) happens inside the penalty-weight call.  The polynomial fit, ``check_derivatives``, the first guess
+``alpha0`` and the callbacks stay with the caller.
 """
 from __future__ import annotations
 
@@ -71,3 +73,61 @@ def linesearch_setup_batched_dev(solver: GNSolver, Ws, its, dp, dA, dcx, drx, t_
         B, m, n, l, dp.data_ptr(), dA.data_ptr() if l else 0, lda, strideA, dcx.data_ptr() if l else 0, inactive, n_inactive,
         dAp.data_ptr() if l else 0, index_del=index_del, dJp=dJp.data_ptr(), drx=drx.data_ptr())
     return LinesearchSetup(dJp, dAp[:, :l], dact[:, :t_max], alpha, index, sums[:, 0].copy(), sums[:, 1].copy(), sums[:, 2].copy())
+
+
+def pack_active(Ws, t_max: int):
+    """The host records of the penalty-weight and merit calls: ``active`` (B, t_max) zero padded and ``t`` per problem."""
+    B = len(Ws)
+    active = np.zeros((B, t_max), dtype=np.int64)
+    t = np.zeros(B, dtype=np.int64)
+    for k, W in enumerate(Ws):
+        t[k] = W.t
+        active[k, :W.t] = np.asarray(W.active[:W.t], dtype=np.int64)
+    return active, t
+
+
+@dataclass
+class PenaltyWeights:
+    w: object                           # device (B, l): the new weights; w_old where the problem is not taken     :2238 / :2286
+    dpsi0: np.ndarray                   # (B,) psi'(0)                                                            :1628
+    psi0: np.ndarray                    # (B,) psi(0)                                                             :2243
+    atwa: np.ndarray                    # (B,)                                                                    :2268
+    branch: np.ndarray                  # (B,) int32: the arm of the weight update taken (include/enlsip_gn.h)
+    predicted_reduction: np.ndarray     # (B,)                                                                    :2267-2269
+
+
+def penalty_weights_batched_dev(solver: GNSolver, Ws, its, setup: LinesearchSetup, dw_old, dK, dcx, ddiag_scale, weight_code: int,
+                                scaling: bool) -> PenaltyWeights:
+    """``penalty_weight_update`` (:2238) for the problems of a ``LinesearchSetup``, everything in device buffers (torch tensors):
+    dw_old (B, l) the previous weights, dK (B, 4, l) the weight histories (updated in place), dcx (B, l) ALL constraint values,
+    ddiag_scale (B, t_max) (None without scaling).  its[k].dimA is the dimension the direction was computed with; problems with
+    its[k].code == 2 are not taken (:2284-2290): their w is w_old and their scalars are 0.  Only the scalars come down."""
+    B = len(Ws)
+    l = Ws[0].l
+    t_max = setup.active_Ap.shape[-1]
+    active, t = pack_active(Ws, t_max)
+    dimA = np.array([it.dimA for it in its], dtype=np.int64)
+    take = np.array([0 if it.code == 2 else 1 for it in its], dtype=np.int64)
+    sums = np.stack([setup.JpJp, setup.Jprx, setup.rxrx], axis=1)
+    dw = dw_old.clone()
+    ptr = lambda x: x.data_ptr() if x is not None and x.numel() else 0
+    act_Ap = setup.active_Ap if setup.active_Ap.is_contiguous() else setup.active_Ap.contiguous()
+    scalars, branch = solver.penalty_weights_batched_dev(
+        B, l, t_max, t, dimA, active, weight_code, scaling, ptr(dw_old), ptr(act_Ap), ptr(ddiag_scale) if scaling else 0, ptr(dcx),
+        ptr(dK), sums, ptr(dw), take=take)
+    upp = np.minimum(1.0, setup.alpha_upp)                                                       # :2267
+    pred = upp * (-2.0 * setup.Jprx - upp * setup.JpJp + (2.0 - upp ** 2) * scalars[:, 2])       # :2269
+    pred = np.where(take != 0, pred, 0.0)
+    return PenaltyWeights(dw, scalars[:, 0].copy(), scalars[:, 1].copy(), scalars[:, 2].copy(), branch, pred)
+
+
+def merit_batched_dev(solver: GNSolver, Ws, drx, dcx, dw, take=None) -> np.ndarray:
+    """``psi`` (:1307-1340) of one trial point per problem: drx (B, m) and dcx (B, l) the residuals and ALL constraint values at the
+    trial points, dw (B, l) the weights (device tensors).  Returns psi (B,)."""
+    B = len(Ws)
+    l = Ws[0].l
+    t_max = max([W.t for W in Ws] + [0])
+    active, t = pack_active(Ws, t_max)
+    inactive, n_inactive, _ = pack_inactive(Ws)
+    ptr = lambda x: x.data_ptr() if x.numel() else 0
+    return solver.merit_batched_dev(B, drx.shape[-1], l, t_max, t, active, inactive, n_inactive, ptr(drx), ptr(dcx), ptr(dw), take=take)

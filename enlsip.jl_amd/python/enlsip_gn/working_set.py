@@ -79,6 +79,7 @@ class IterationRecord:                 # hot-path fields of src/structures.jl:63
     lam: np.ndarray = field(default_factory=lambda: np.zeros(0))
     delete: bool = False
     index_del: int = 0
+    code: int = 0                      # method_code of the direction (2: undamped step, no line search; :2284-2290)
 
 
 def pseudo_rank(diag_T, eps_rank: float) -> int:      # src/enlsip_functions.jl:17-31

@@ -617,6 +617,83 @@ int enlsip_gn_linesearch_setup_batched_dev(enlsip_gn_handle h, int64_t batch, in
                                            double* dAp, double* alpha_upp, int64_t* index_alpha_upp, double* sums);
 int enlsip_gn_get_linesearch_form(enlsip_gn_handle h, int* form);
 
+/* ---- the penalty weights and the merit function of a batch, on the caller's device buffers -------------------------------------
+ * What compute_steplength (src/enlsip_functions.jl:2197-2293) does next with what the set-up left: penalty_weight_update (:2238,
+ * :1545-1629, with max_norm_weight_update! :1504-1539, euclidean_norm_weight_update :1429-1497, min_norm_w! :1374-1423 and assort!
+ * :1344-1360), psi(0) of :2243, atwa of :2268, and the merit function psi (:1307-1340) of trial points whose residuals and
+ * constraints the caller has evaluated into device buffers.  The callbacks, the polynomial fit (linesearch_constrained,
+ * :1940-2147), check_derivatives and the first guess alpha0 stay with the caller.
+ *
+ * enlsip_gn_penalty_weight_update   penalty_weight_update on HOST data, no handle and no GPU.  active: t 1-based constraint numbers,
+ *     distinct as a working set's are; active_Ap: the t entries of C.A * p, already divided by diag_scale where scaling is on
+ *     (:2231-2233); w_old, cx: l entries; norm_code 0 (maximum norm) or 2 (Euclidean norm) (:1606-1611); K: the four histories of
+ *     l entries, row ii (K[ii+1] of the reference) at K + ii*l, in and out; w: the new weights, l entries (w == w_old is allowed);
+ *     scalars = dpsi0 (:1628), psi0 = 0.5 * (rxrx + sum w[k] cx[k]^2 over active) (:2243), atwa = sum w[k] active_Ap[i]^2 (:2268);
+ *     *branch: 0 norm_code 0, or t == 0; 1 ztw >= mu && dimA < t; 2 ztw < mu && dimA < t; 3 ztw < mu && dimA == t (the ctrl = 1
+ *     arm); 4 ztw >= mu && dimA == t (or a NaN ztw), the arm that changes nothing but still runs assort!.
+ *     One stated deviation: Jp and rx enter only through the three sums the set-up call returns.  nrm_Jp = sqrt(JpJp), nrm_Jp^2 is
+ *     nrm_Jp * nrm_Jp as in the Julia, Jp_rx = Jprx instead of the dot of the two normalised vectors multiplied back (:1567-1584),
+ *     and nrm_rx is unused.  Everything on the t- and l-vectors is literal, the divide by nrm_Ap / nrm_cx and the multiply back at
+ *     :1610 included, and so are the reference's quirks: min_norm_w! starts from w[:] = K[4] over all l entries, not from
+ *     previous_w (:1383, :1447); buff >= w_old[i], y_elem > 0, w[k] > K[ii][k] and abs(alpha_w - 1) <= delta keep their strictness;
+ *     norm(y, Inf) <= eps gives c = 1 (:1398) and is taken over the whole of y, stale entries included; assort! does not stop after
+ *     an insertion (:1351-1357); the maximum-norm arm reads and writes only K[ii][1] and reads w[active[1]], with active[1] == 0
+ *     (t == 0) treated as 1 (:1515-1518); rmy / nrm_Ap is an IEEE division, also by zero (:1514).  With norm_code 0 and l == 0,
+ *     where the Julia would throw at :1516, w stays empty and K untouched (both may then be NULL).  All sums run in index order,
+ *     norm(y) is the square root of that sum of squares, and only + - * / and sqrt are used, never contracted: host and device
+ *     give the same bits.  Like the three sums, the routine is covered for operands inside the 2^+-400 band and is not part of the
+ *     magnitude contract.  Returns 0; before anything is written: -2 scalars or branch NULL (K or w NULL while l > 0), l < 0,
+ *     t outside 0..l, dimA outside 0..t, or norm_code not 0 / 2; -4 w_old NULL while l > 0, or active, active_Ap or cx NULL while
+ *     t > 0; -5 an active entry outside 1..l.  The same routine, compiled for the device, does the work below.
+ * enlsip_gn_penalty_weights_batched_dev   for every taken problem k (take: HOST array of batch entries, NULL = all; the problems of
+ *     the method_code == 2 arm, :2284-2290, are not taken) that routine on dw_old[k], dcx[k], dK[k] (l, l and 4*l per problem, row
+ *     ii at + ii*l), dactive_Ap[k, 0:t[k]) divided by ddiag_scale[k, 0:t[k]) when scaling != 0 (an IEEE division, both t_max per
+ *     problem: exactly what enlsip_gn_jacobian_times_batched_dev and the ragged layout leave), active[k, 0:t[k]) (HOST, batch x
+ *     t_max, 0 padded), dimA[k] and sums[3k .. 3k+2] = Jp.Jp, Jp.rx, rx.rx as the set-up call returns them.  dw[k] (l per problem)
+ *     and dK[k] are written on the device; scalars (3 per problem) and branch come back in HOST arrays.  t, dimA, active, take,
+ *     sums, scalars, branch are HOST arrays; everything with a d is a device buffer.  w, K, scalars and branch of problem k are bit
+ *     for bit what enlsip_gn_penalty_weight_update returns on the downloaded inputs of problem k.  dw == dw_old (the same
+ *     pointer) is legal; any other overlap of an output with an input is not checked and not supported.  A problem with
+ *     take[k] == 0 has no byte written on the device; its host outputs are 0.  Nothing past t[k] of a t_max-strided buffer is
+ *     read, and an entry of K that does not move is not written.
+ * enlsip_gn_get_penalty_form   kernel form of the last enlsip_gn_penalty_weights_batched_dev on this handle: 0 general (one
+ *     workgroup per problem: it gathers the active entries into LDS, one lane runs the routine, the workgroup does the l-wide copy,
+ *     the scatter and assort!), 1 one wave per problem (t_max <= 64 and l <= 64: four problems per workgroup, the same steps),
+ *     -1 none yet.  The serial part is the same code in both, so the two forms give the same bits.
+ * enlsip_gn_merit_batched_dev   psi[k] = 0.5 * (dot(rx_k, rx_k) + sum over active[k, 0:t[k]) of w[j] cx[j]^2 + sum over the j of
+ *     inactive[k, 0:n_inactive[k]) with cx[j] < 0 of w[j] cx[j]^2) (:1322-1339) on drx (m per problem), dcx and dw (l per problem).
+ *     The test cx[j] < 0 is literal: -0.0, 0 and a NaN do not enter.  A 0 in either list is padding and is skipped.  rx.rx is the
+ *     ordered partial-sum scheme of the set-up call's general form; the constraint terms are added one by one in list order, the
+ *     active list first.  No floating-point atomics: a value depends on m, l, the lists and the operands alone, not on the slot,
+ *     the batch or the call.  psi of a problem not taken is 0.  t, active (batch x t_max), inactive (batch x l), n_inactive, take
+ *     and psi are HOST arrays.
+ * All three device calls need no resident factors: they are legal in every handle state and touch nothing resident.  The number
+ * of launches does not depend on batch (which may exceed the grid's y limit); one copy of the host records goes up, one copy of
+ * the scalars comes back, and a call returns after ONE synchronisation of the handle's stream.  The records live in a scratch
+ * the handle keeps.  t_max is at most 1024 in this build, l at most 2^27.  Argument errors are raised before anything is launched
+ * and leave every buffer untouched (last_error names k):
+ *   -1 h NULL; -2 batch < 1; -3 l or t_max out of range, t_max > l, norm_code not 0 / 2 (merit: m < 0); -4 a required pointer
+ *   NULL (penalty: t, dimA, sums, scalars, branch; dw_old, dK, dw while l > 0; active, dactive_Ap, dcx while t_max > 0;
+ *   ddiag_scale only while scaling != 0 and t_max > 0; merit: t, n_inactive, psi; drx while m > 0; dcx, dw, inactive while l > 0;
+ *   active while t_max > 0); -5 some t[k] outside 0..t_max (merit: or n_inactive[k] outside 0..l); -6 penalty: some dimA[k] outside
+ *   0..t[k] or an active entry outside 1..l within the first t[k]; merit: a list entry outside 0..l.
+ */
+int enlsip_gn_penalty_weight_update(int64_t l, int64_t t, const int64_t* active, int64_t dimA, int norm_code,
+                                    const double* w_old, const double* active_Ap, const double* cx,
+                                    double JpJp, double Jprx, double rxrx, double* K, double* w,
+                                    double* scalars, int* branch);
+int enlsip_gn_penalty_weights_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t l, int64_t t_max,
+                                          const int64_t* t, const int64_t* dimA, const int64_t* active,
+                                          const int64_t* take, int norm_code, int scaling,
+                                          const double* dw_old, const double* dactive_Ap, const double* ddiag_scale,
+                                          const double* dcx, double* dK, const double* sums, double* dw,
+                                          double* scalars, int* branch);
+int enlsip_gn_get_penalty_form(enlsip_gn_handle h, int* form);
+int enlsip_gn_merit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t l, int64_t t_max,
+                                const int64_t* t, const int64_t* active, const int64_t* inactive,
+                                const int64_t* n_inactive, const int64_t* take,
+                                const double* drx, const double* dcx, const double* dw, double* psi);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
