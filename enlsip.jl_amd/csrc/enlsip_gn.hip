@@ -32,6 +32,8 @@
 #include "gn_kernels_deletion_batched.hpp"
 #include "gn_kernels_linesearch_batched.hpp"
 #include "gn_kernels_penalty_batched.hpp"
+#include "gn_kernels_linesearch_fit_batched.hpp"
+#include "gn_linesearch_fit.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_newton_batched.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
@@ -2458,5 +2460,6 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_deletion_batched.inc"
 #include "gn_linesearch_batched.inc"
 #include "gn_penalty_batched.inc"
+#include "gn_linesearch_fit_batched.inc"
 #include "gn_newton.inc"
 #include "gn_newton_batched.inc"

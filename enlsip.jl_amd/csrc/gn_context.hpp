@@ -252,7 +252,8 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     int linesearch_form = -1;
     // batched penalty weights and merit function (gn_penalty_batched.inc): the active / inactive lists and per-problem records of one
     // call on the device and in pinned memory, the partial sums of rx.rx and the scalars per problem (the two calls lay the same
-    // buffers out for themselves), and the form of the last penalty-weight call; nothing resident
+    // buffers out for themselves, and so does the polynomial fit of gn_linesearch_fit_batched.inc), and the form of the last
+    // penalty-weight call; nothing resident
     gn::DevBuf pen_scr;
     gn::PinnedBuf h_pen;
     int penalty_form = -1;

@@ -850,6 +850,94 @@ function merit_batched_dev_hip(h::Handle, B::Integer, m::Integer, l::Integer, t_
     return ψ
 end
 
+"""    linesearch_coefficients_hip(active, t, inactive, n_inactive, rx, rx_new, Jp, cx, cx_new, Ap, w, α_k) -> sums
+
+The six dot products v0·v0, v0·v1, v0·v2, v1·v1, v1·v2, v2·v2 of `coefficients_linesearch!` (src/enlsip_functions.jl:1665-1689)
+with the scaling of `v1 = [Jp; Ap]` (:1986-1998) on host data, through the library's host entry point (no handle, no GPU).  `Ap` is
+the UNSCALED `A * p`; neither `Jp` nor `Ap` is written.  The terms are added in the order residuals, active list, inactive list."""
+function linesearch_coefficients_hip(active::Vector{Int64}, t::Integer, inactive::Vector{Int64}, n_inactive::Integer,
+                                     rx::Vector{Float64}, rx_new::Vector{Float64}, Jp::Vector{Float64}, cx::Vector{Float64},
+                                     cx_new::Vector{Float64}, Ap::Vector{Float64}, w::Vector{Float64}, α_k::Float64)
+    m, l = length(rx), length(cx)
+    (length(rx_new) == m && length(Jp) == m && length(cx_new) == l && length(Ap) == l && length(w) == l &&
+     length(active) >= t && length(inactive) >= n_inactive) || error("rx, rx_new, Jp need m entries, cx, cx_new, Ap, w need l")
+    sums = zeros(Float64, 6)
+    rc = GC.@preserve active inactive rx rx_new Jp cx cx_new Ap w sums ccall((:enlsip_gn_linesearch_coefficients, LIB), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}),
+        m, l, t, active, inactive, n_inactive, rx, rx_new, Jp, cx, cx_new, Ap, w, α_k, sums)
+    rc == 0 || error("enlsip_gn_linesearch_coefficients returned $rc")
+    return sums
+end
+
+"""    linesearch_fit_hip(sums, α_k, x_min, α_min, α_max) -> (α_kp1, pk, α_hat, sα, β_hat, sβ, arm)
+
+`minrm` (src/enlsip_functions.jl:1841-1862) on the six sums and the choice of :2023-2026; `arm` 0 Newton–Raphson, 1 one root,
+2 two roots."""
+function linesearch_fit_hip(sums::Vector{Float64}, α_k::Float64, x_min::Float64, α_min::Float64, α_max::Float64)
+    length(sums) == 6 || error("sums needs 6 entries")
+    out = zeros(Float64, 6)
+    arm = Ref{Cint}(0)
+    rc = GC.@preserve sums out ccall((:enlsip_gn_linesearch_fit, LIB), Cint,
+        (Ptr{Float64}, Float64, Float64, Float64, Float64, Ptr{Float64}, Ref{Cint}), sums, α_k, x_min, α_min, α_max, out, arm)
+    rc == 0 || error("enlsip_gn_linesearch_fit returned $rc")
+    return out[1], out[2], out[3], out[4], out[5], out[6], Int(arm[])
+end
+
+"""    minrn_hip(x1, y1, x2, y2, x3, y3, α_min, α_max, p_max) -> (α, pα): `minrn` (src/enlsip_functions.jl:1708-1735)"""
+function minrn_hip(x1::Float64, y1::Float64, x2::Float64, y2::Float64, x3::Float64, y3::Float64, α_min::Float64, α_max::Float64,
+                   p_max::Float64)
+    α = Ref{Float64}(0.0)
+    pα = Ref{Float64}(0.0)
+    rc = ccall((:enlsip_gn_minrn, LIB), Cint,
+        (Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Float64, Ref{Float64}, Ref{Float64}),
+        x1, y1, x2, y2, x3, y3, α_min, α_max, p_max, α, pα)
+    rc == 0 || error("enlsip_gn_minrn returned $rc")
+    return α[], pα[]
+end
+
+"""    check_reduction_hip(ψ_α, ψ_k, approx_k, η, diff_psi) -> Bool: `check_reduction` (src/enlsip_functions.jl:1870-1886)"""
+function check_reduction_hip(ψ_α::Float64, ψ_k::Float64, approx_k::Float64, η::Float64, diff_psi::Float64)
+    likely = Ref{Cint}(0)
+    rc = ccall((:enlsip_gn_check_reduction, LIB), Cint, (Float64, Float64, Float64, Float64, Float64, Ref{Cint}),
+        ψ_α, ψ_k, approx_k, η, diff_psi, likely)
+    rc == 0 || error("enlsip_gn_check_reduction returned $rc")
+    return likely[] != 0
+end
+
+"""    linesearch_fit_batched_dev_hip(h, B, m, l, t_max, t, active, inactive, n_inactive, take, α_k, x_min, α_min, α_max, drx,
+                                   drx_new, dJp, dcx, dcx_new, dAp, dw; psi=false) -> (sums, out, arm, ψ_new)
+
+The polynomial fit of the line search for every taken problem of a batch: the six sums on DEVICE buffers (`drx`, `drx_new`, `dJp`
+m per problem; `dcx`, `dcx_new`, `dAp`, `dw` l per problem; none is written), then `linesearch_fit_hip`'s routine on the host inside
+the same call.  `t`, `active` (t_max x B), `inactive` (l x B), `n_inactive`, `take` (`nothing`: all), `α_k`, `x_min`, `α_min`,
+`α_max` are host arrays.  Returns `sums` (6 x B), `out` (6 x B: α_kp1, pk, α_hat, sα, β_hat, sβ), `arm` and, with `psi=true`, ψ of
+`(drx_new, dcx_new, dw)` as `merit_batched_dev_hip` returns it (else `nothing`); zeros for a problem not taken."""
+function linesearch_fit_batched_dev_hip(h::Handle, B::Integer, m::Integer, l::Integer, t_max::Integer, t::Vector{Int64},
+                                        active::Matrix{Int64}, inactive::Matrix{Int64}, n_inactive::Vector{Int64},
+                                        take::Union{Nothing,Vector{Int64}}, α_k::Vector{Float64}, x_min::Vector{Float64},
+                                        α_min::Vector{Float64}, α_max::Vector{Float64}, drx::Ptr{Float64}, drx_new::Ptr{Float64},
+                                        dJp::Ptr{Float64}, dcx::Ptr{Float64}, dcx_new::Ptr{Float64}, dAp::Ptr{Float64},
+                                        dw::Ptr{Float64}; psi::Bool=false)
+    (size(active) == (t_max, B) && size(inactive) == (l, B) && length(t) == B && length(n_inactive) == B && length(α_k) == B &&
+     length(x_min) == B && length(α_min) == B && length(α_max) == B && (take === nothing || length(take) == B)) ||
+        error("active is t_max x B, inactive l x B, every other host array needs B entries")
+    sums = zeros(Float64, 6, B)
+    out = zeros(Float64, 6, B)
+    arm = zeros(Cint, B)
+    ψ = psi ? zeros(Float64, B) : nothing
+    ptake = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    pψ = psi ? pointer(ψ) : Ptr{Float64}(C_NULL)
+    GC.@preserve t active inactive n_inactive take α_k x_min α_min α_max sums out arm ψ check(h,
+        ccall((:enlsip_gn_linesearch_fit_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}, Ptr{Float64}),
+        h.ptr, B, m, l, t_max, t, active, inactive, n_inactive, ptake, α_k, x_min, α_min, α_max, drx, drx_new, dJp, dcx, dcx_new,
+        dAp, dw, sums, out, arm, pψ))
+    return sums, out, arm, ψ
+end
+
 """    newton_search_direction_hip(h, Γ_mat) -> (p, error)
 
 `newton_search_direction` (src/enlsip_functions.jl:348-423) after its two Hessian sums: the caller runs `hessian_res!` /

@@ -130,6 +130,65 @@ def penalty_weight_update(w_old, active, t: int, dimA: int, norm_code: int, acti
     return w, float(sc[0]), float(sc[1]), float(sc[2]), int(br.value), Kv
 
 
+def linesearch_coefficients(active, t: int, inactive, n_inactive: int, rx, rx_new, Jp, cx, cx_new, Ap, w, alpha_k: float) -> np.ndarray:
+    """The six dot products v0.v0, v0.v1, v0.v2, v1.v1, v1.v2, v2.v2 of coefficients_linesearch! (src/enlsip_functions.jl:1665-1689)
+    with the scaling of v1 = [Jp; Ap] (:1986-1998) on host data, through the library's host entry point (no GPU).  active / inactive:
+    1-based constraints of which the first t / n_inactive count (t + n_inactive == l); Ap is the UNSCALED A * p.  No vector is
+    built and nothing is written; the terms are added in the order residuals, active list, inactive list."""
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    rx, rx_new, Jp, cx, cx_new, Ap, w = (f(a) for a in (rx, rx_new, Jp, cx, cx_new, Ap, w))
+    m, l = rx.size, cx.size
+    if rx_new.size != m or Jp.size != m or cx_new.size != l or Ap.size != l or w.size != l:
+        raise ValueError("rx, rx_new, Jp need m entries each and cx, cx_new, Ap, w l entries each")
+    av = np.ascontiguousarray(np.asarray(active).astype(np.int64))
+    iv = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
+    if av.size < t or iv.size < n_inactive:
+        raise ValueError("active needs t entries and inactive n_inactive")
+    sums = np.zeros(6)
+    p = lambda a: _fptr(a) if a.size else None
+    rc = L.load().enlsip_gn_linesearch_coefficients(m, l, int(t), p(av), p(iv), int(n_inactive), p(rx), p(rx_new), p(Jp), p(cx),
+                                                    p(cx_new), p(Ap), p(w), float(alpha_k), _fptr(sums))
+    if rc:
+        raise GNError(f"enlsip_gn_linesearch_coefficients returned {rc}")
+    return sums
+
+
+def linesearch_fit(sums, alpha_k: float, x_min: float, alpha_min: float, alpha_max: float):
+    """minrm (src/enlsip_functions.jl:1841-1862) on the six sums and the choice of :2023-2026, through the library's host entry
+    point (no GPU).  Returns (out (6,): alpha_kp1, pk, alpha_hat, s_alpha, beta_hat, s_beta; arm: 0 Newton-Raphson, 1 one root,
+    2 two roots)."""
+    sv = np.ascontiguousarray(sums, dtype=np.float64)
+    if sv.size != 6:
+        raise ValueError("sums needs 6 entries")
+    out = np.zeros(6)
+    arm = C.c_int(0)
+    rc = L.load().enlsip_gn_linesearch_fit(_fptr(sv), float(alpha_k), float(x_min), float(alpha_min), float(alpha_max), _fptr(out),
+                                           C.byref(arm))
+    if rc:
+        raise GNError(f"enlsip_gn_linesearch_fit returned {rc}")
+    return out, int(arm.value)
+
+
+def minrn(x1, y1, x2, y2, x3, y3, alpha_min, alpha_max, p_max):
+    """minrn (src/enlsip_functions.jl:1708-1735) through the library's host entry point (no GPU): (alpha, p_alpha)."""
+    a, pa = C.c_double(0.0), C.c_double(0.0)
+    rc = L.load().enlsip_gn_minrn(float(x1), float(y1), float(x2), float(y2), float(x3), float(y3), float(alpha_min),
+                                  float(alpha_max), float(p_max), C.byref(a), C.byref(pa))
+    if rc:
+        raise GNError(f"enlsip_gn_minrn returned {rc}")
+    return float(a.value), float(pa.value)
+
+
+def check_reduction(psi_alpha, psi_k, approx_k, eta, diff_psi) -> bool:
+    """check_reduction (src/enlsip_functions.jl:1870-1886) through the library's host entry point (no GPU)."""
+    likely = C.c_int(0)
+    rc = L.load().enlsip_gn_check_reduction(float(psi_alpha), float(psi_k), float(approx_k), float(eta), float(diff_psi),
+                                            C.byref(likely))
+    if rc:
+        raise GNError(f"enlsip_gn_check_reduction returned {rc}")
+    return bool(likely.value)
+
+
 @dataclass
 class GNResult:
     p: np.ndarray
@@ -894,6 +953,36 @@ class GNSolver:
             self._h, batch, m, l, t_max, _fptr(t), _fptr(act) if act.size else None, _fptr(inact) if inact.size else None, _fptr(ni),
             _fptr(tk), _dptr(drx), _dptr(dcx), _dptr(dw), _fptr(psi)))
         return psi
+
+    # ---- the polynomial fit of the line search on device buffers (src/enlsip_functions.jl:1665-1689, :1986-1998, :1841-1862) ----------
+    def linesearch_fit_batched_dev(self, batch, m, l, t_max, t, active, inactive, n_inactive, alpha_k, x_min, alpha_min, alpha_max,
+                                   drx, drx_new, dJp, dcx, dcx_new, dAp, dw, take=None, psi=False):
+        """The six sums of coefficients_linesearch! per taken problem on the device buffers (drx, drx_new, dJp m per problem; dcx,
+        dcx_new, dAp, dw l per problem; none is written) and linesearch_fit on them, on the host inside the call.  t, n_inactive,
+        alpha_k, x_min, alpha_min, alpha_max (batch,), active (batch, t_max), inactive (batch, l) and take (None: all) stay host
+        arrays.  Returns (sums (batch, 6), out (batch, 6): alpha_kp1, pk, alpha_hat, s_alpha, beta_hat, s_beta; arm (batch,) int32;
+        psi_new (batch,) = psi of (drx_new, dcx_new, dw) as merit_batched_dev returns it, or None); zeros for a problem not taken."""
+        t = self._host_i64(t, batch, "t")
+        ni = self._host_i64(n_inactive, batch, "n_inactive")
+        act = np.ascontiguousarray(np.asarray(active).astype(np.int64))
+        inact = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
+        if act.size != batch * t_max or inact.size != batch * l:
+            raise ValueError(f"active must have {batch} x {t_max} entries, inactive {batch} x {l}")
+        sc = []
+        for name, v in (("alpha_k", alpha_k), ("x_min", x_min), ("alpha_min", alpha_min), ("alpha_max", alpha_max)):
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.size != batch:
+                raise ValueError(f"{name} must have {batch} entries")
+            sc.append(v)
+        tk = self._pack_take(batch, take)
+        sums, out = np.zeros((batch, 6)), np.zeros((batch, 6))
+        arm = np.zeros(batch, dtype=np.int32)
+        psi_new = np.zeros(batch) if psi else None
+        self._chk(self._lib.enlsip_gn_linesearch_fit_batched_dev(
+            self._h, batch, m, l, t_max, _fptr(t), _fptr(act) if act.size else None, _fptr(inact) if inact.size else None, _fptr(ni),
+            _fptr(tk), _fptr(sc[0]), _fptr(sc[1]), _fptr(sc[2]), _fptr(sc[3]), _dptr(drx), _dptr(drx_new), _dptr(dJp), _dptr(dcx),
+            _dptr(dcx_new), _dptr(dAp), _dptr(dw), _fptr(sums), _fptr(out), _fptr(arm), _fptr(psi_new)))
+        return sums, out, arm, psi_new
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):
         """newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums: Gamma = r_mat - c_mat (n x n).

@@ -3,8 +3,10 @@ the HIP library: the products ``Jp = J * p``, ``Ap = A * p`` and ``active_Ap = C
 (:2149-2178, called at :2252) and the three sums through which ``Jp`` enters ``penalty_weight_update`` (:1561-1584) and the predicted
 reduction (:2269); then the penalty weights (``penalty_weight_update``, :2238, :1545-1629) with ``psi(0)`` (:2243), ``atwa`` and the
 predicted reduction (:2267-2269), and the merit function ``psi`` (:1307-1340) of evaluated trial points.  The division ``active_Ap
-./ diag_scale`` (:2231-2233) happens inside the penalty-weight call.  The polynomial fit, ``check_derivatives``, the first guess
-``alpha0`` and the callbacks stay with the caller.
+./ diag_scale`` (:2231-2233) happens inside the penalty-weight call.  Then the line search itself: the polynomial fit of
+``linesearch_constrained`` (:1940-2143: ``coefficients_linesearch!`` :1665-1689, ``minrm`` :1841-1862 and the choice of :2023-2026) as
+one call per batch, and ``linesearch_constrained_batched``, the whole state machine of :1940-2143 over a batch with the callbacks
+as the only thing left to the caller.  ``check_derivatives`` and the first guess ``alpha0`` stay with the caller.
 """
 from __future__ import annotations
 
@@ -12,6 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import api as _api
 from .api import GNSolver, upper_bound_steplength as _upper_bound_steplength
 
 
@@ -131,3 +134,217 @@ def merit_batched_dev(solver: GNSolver, Ws, drx, dcx, dw, take=None) -> np.ndarr
     inactive, n_inactive, _ = pack_inactive(Ws)
     ptr = lambda x: x.data_ptr() if x.numel() else 0
     return solver.merit_batched_dev(B, drx.shape[-1], l, t_max, t, active, inactive, n_inactive, ptr(drx), ptr(dcx), ptr(dw), take=take)
+
+
+# ---- the polynomial fit and the line search itself (src/enlsip_functions.jl:1940-2143) ---------------------------------------------
+@dataclass
+class LinesearchFit:
+    sums: np.ndarray            # (B, 6) v0.v0, v0.v1, v0.v2, v1.v1, v1.v2, v2.v2                      :1849, :1749-1751
+    out: np.ndarray             # (B, 6) alpha_kp1, pk (after the choice of :2023-2026), alpha_hat, s_alpha, beta_hat, s_beta
+    arm: np.ndarray             # (B,) int32: 0 Newton-Raphson, 1 one root, 2 two roots                :1754-1778
+    psi: object                 # (B,) psi of the trial point, or None                                 :2000
+
+
+def linesearch_fit_batched_dev(solver: GNSolver, Ws, setup: LinesearchSetup, drx, dcx, drx_new, dcx_new, dw, alpha_k, x_min,
+                               alpha_min, alpha_max, take=None, psi=False) -> LinesearchFit:
+    """``coefficients_linesearch!`` and ``minrm`` with the choice (:2010-2026) for the problems of a ``LinesearchSetup``: drx, drx_new
+    (B, m) the residuals at x and at the trial point, dcx, dcx_new (B, l) ALL constraint values there, dw (B, l) the weights (device
+    tensors); setup.Jp and setup.Ap are the UNSCALED products (nothing is written).  alpha_k, x_min, alpha_min, alpha_max: (B,)
+    host arrays.  With psi the merit function of the trial point comes back from the same call."""
+    B = len(Ws)
+    l = Ws[0].l
+    t_max = max([W.t for W in Ws] + [0])
+    active, t = pack_active(Ws, t_max)
+    inactive, n_inactive, _ = pack_inactive(Ws)
+    # contiguous views, kept alive until the call has returned
+    bufs = [x if x.is_contiguous() else x.contiguous() for x in (drx, drx_new, setup.Jp, dcx, dcx_new, setup.Ap, dw)]
+    sums, out, arm, psi_new = solver.linesearch_fit_batched_dev(
+        B, drx.shape[-1], l, t_max, t, active, inactive, n_inactive, alpha_k, x_min, alpha_min, alpha_max,
+        *[x.data_ptr() if x.numel() else 0 for x in bufs], take=take, psi=psi)
+    return LinesearchFit(sums, out, arm, psi_new)
+
+
+class HostLinesearchBackend:
+    """The two calls the batched line search needs, on host arrays (NumPy in place of device tensors) through the library's host
+    routines, no GPU: the merit function as a plain ordered sum (residuals in index order, the active list, the inactive list,
+    :1322-1339) and the fit as ``linesearch_coefficients`` + ``linesearch_fit`` per problem."""
+
+    @staticmethod
+    def _psi(W, rx, cx, w) -> float:
+        s = 0.0
+        for v in rx:
+            s += float(v) * float(v)
+        c = 0.0
+        for j in W.active[:W.t]:
+            c += float(w[j - 1]) * (float(cx[j - 1]) * float(cx[j - 1]))
+        for j in W.inactive[:W.l - W.t]:
+            if cx[j - 1] < 0.0:
+                c += float(w[j - 1]) * (float(cx[j - 1]) * float(cx[j - 1]))
+        return 0.5 * (s + c)
+
+    def merit(self, Ws, rx, cx, w, take=None) -> np.ndarray:
+        return np.array([self._psi(W, rx[k], cx[k], w[k]) if take is None or take[k] else 0.0 for k, W in enumerate(Ws)])
+
+    def fit(self, Ws, setup, rx, cx, rx_new, cx_new, w, alpha_k, x_min, alpha_min, alpha_max, take=None, psi=False) -> LinesearchFit:
+        B = len(Ws)
+        sums, out, arm = np.zeros((B, 6)), np.zeros((B, 6)), np.zeros(B, dtype=np.int32)
+        for k, W in enumerate(Ws):
+            if take is not None and not take[k]:
+                continue
+            sums[k] = _api.linesearch_coefficients(W.active, W.t, W.inactive, W.l - W.t, rx[k], rx_new[k], setup.Jp[k], cx[k],
+                                                   cx_new[k], setup.Ap[k], w[k], alpha_k[k])
+            out[k], arm[k] = _api.linesearch_fit(sums[k], alpha_k[k], x_min[k], alpha_min[k], alpha_max[k])
+        return LinesearchFit(sums, out, arm, self.merit(Ws, rx_new, cx_new, w, take) if psi else None)
+
+
+class _DeviceLinesearchBackend:
+    """the same two calls on device tensors through a GNSolver"""
+
+    def __init__(self, solver):
+        self.solver = solver
+
+    def merit(self, Ws, drx, dcx, dw, take=None):
+        return merit_batched_dev(self.solver, Ws, drx, dcx, dw, take=take)
+
+    def fit(self, Ws, setup, *args, **kw):
+        return linesearch_fit_batched_dev(self.solver, Ws, setup, *args, **kw)
+
+
+# the terminals of linesearch_constrained, as LinesearchResult.terminal names them
+FIRST_FIT = "first_fit"                 # :2036-2062 accepted after the first minrm, the reduce loop never entered
+FIRST_FIT_MINRN = "first_fit_minrn"     # :2036-2062 the same arm after at least one minrn round
+SECOND_FIT = "second_fit"               # :2078-2092 the second minrm at the new point
+SECOND_MINRN = "second_minrn"           # :2094-2096 minrn at the new point
+ARMIJO = "armijo"                       # :2133-2137 goldstein_armijo_step, left by its sufficient-decrease test
+ARMIJO_ERROR = "armijo_error"           # the same, left with gac_error
+
+
+@dataclass
+class LinesearchResult:
+    alpha: np.ndarray           # (B,) the step lengths                                                :2142
+    gac_error: np.ndarray       # (B,) bool
+    rounds: int                 # calls of `evaluate`
+    terminal: list              # per problem, one of the names above
+    n_eval: np.ndarray          # (B,) int64: evaluations (psi calls of the reference) per problem
+
+
+def _one_linesearch(alpha0, psi0, dpsi0, alpha_min, alpha_max, p_max):
+    """linesearch_constrained (:1940-2143) for one problem as a generator.  It yields what it needs next and is sent the answer:
+    ("fit", alpha_k, x_min, evaluate) -> (psi or None, sums, out); ("psi", alpha) -> psi.  Returns (alpha, gac_error, terminal)."""
+    eta, tau, gamma = 0.3, 0.25, 0.4                                            # :1965-1967
+    a_k = min(alpha0, alpha_max)                                                # :1974
+    a_km1, psi_km1 = 0.0, psi0
+    # :2000-2026.  The fit's x_min depends on the psi the same call returns (:2019): the call is made with x_min = alpha_k, the
+    # value of the usual case diff_psi >= 0, and otherwise the scalar stage is redone on the returned sums by the host routine,
+    # which is what the call runs
+    psi_k, sums, out = yield ("fit", a_k, a_k, True)
+    diff_psi = psi0 - psi_k
+    if not diff_psi >= 0:
+        out, _ = _api.linesearch_fit(sums, a_k, 0.0, alpha_min, alpha_max)
+    a_kp1, pk = float(out[0]), float(out[1])
+    a_km2, psi_km2 = a_km1, psi_km1
+    a_km1, psi_km1 = a_k, psi_k
+    a_k = a_kp1
+    psi_k = yield ("psi", a_k)                                                  # :2033
+    refresh = False
+    if (-diff_psi <= tau * dpsi0 * a_km1) or (psi_km1 < gamma * psi0):          # :2036
+        diff_psi = psi0 - psi_k
+        refresh = True                                                          # this arm's loop refreshes diff_psi (:2055)
+        terminal = FIRST_FIT
+    else:
+        diff_psi = psi0 - psi_k                                                 # :2068
+        if (-diff_psi <= tau * dpsi0 * a_k) or (psi_k < gamma * psi0):          # :2071
+            if psi0 <= psi_km1:                                                 # :2075: a second minrm at the point just evaluated
+                _, sums, out = yield ("fit", a_k, a_k, False)
+                a_kp1, pk = float(out[0]), float(out[1])
+                a_km1, psi_km1 = 0.0, psi0
+                terminal = SECOND_FIT
+            else:
+                a_kp1, pk = _api.minrn(a_k, psi_k, a_km1, psi_km1, a_km2, psi_km2, alpha_min, alpha_max, p_max)
+                terminal = SECOND_MINRN
+            a_km2, psi_km2 = a_km1, psi_km1
+            a_km1, psi_km1 = a_k, psi_k
+            a_k = a_kp1
+            psi_k = yield ("psi", a_k)                                          # :2107
+        else:                                                                   # goldstein_armijo_step (:1893-1923) from alpha_k
+            u = a_k
+            ex = (p_max * u < _api.SQRT_EPS) or (u <= alpha_min)
+            psi_u = yield ("psi", u)
+            while (not ex) and (psi_u > psi0 + tau * u * dpsi0):
+                u *= 0.5
+                psi_u = yield ("psi", u)
+                ex = (p_max * u < _api.SQRT_EPS) or (u <= alpha_min)
+            return u, bool(ex), ARMIJO_ERROR if ex else ARMIJO
+    # the reduce loop of both arms (:2043-2062, :2111-2130).  The second arm does NOT refresh diff_psi: :2100 assigns `diff`,
+    # :2111 reads `diff_psi`, the value of :2068
+    while _api.check_reduction(psi_km1, psi_k, pk, eta, diff_psi):
+        a_kp1, pk = _api.minrn(a_k, psi_k, a_km1, psi_km1, a_km2, psi_km2, alpha_min, alpha_max, p_max)
+        a_km2, psi_km2 = a_km1, psi_km1
+        a_km1, psi_km1 = a_k, psi_k
+        a_k = a_kp1
+        psi_k = yield ("psi", a_k)
+        if refresh:
+            diff_psi = psi0 - psi_k
+            terminal = FIRST_FIT_MINRN
+    if (psi_km1 - pk >= eta * diff_psi) and (psi_k < psi_km1):                  # :2058, :2126
+        a_km1, psi_km1 = a_k, psi_k
+    return a_km1, False, terminal
+
+
+def linesearch_constrained_batched(backend, Ws, evaluate, setup: LinesearchSetup, drx, dcx, dw, alpha0, psi0, dpsi0, alpha_low,
+                                   alpha_upp, p_max) -> LinesearchResult:
+    """``linesearch_constrained`` (:1940-2143) for every problem of a batch, each with its own state; a round evaluates only the
+    problems still running.
+
+    backend: a ``GNSolver`` (drx, dcx, dw and the buffers of ``evaluate`` are device tensors) or a ``HostLinesearchBackend`` (NumPy
+    arrays).  Every psi goes through the backend's merit call, every minrm through its fit call; minrn and check_reduction are the
+    library's host routines.  ``evaluate(alpha, take) -> (drx_new, dcx_new)``: the caller's callback.  It evaluates the residuals
+    and ALL constraints at x_k + alpha[k] p_k for the problems with take[k] != 0 into its two buffers ((B, m) and (B, l), the same
+    two at every call), leaves the rows of the other problems as they are, and returns the buffers.  setup: Jp and Ap as the set-up
+    call left them (unscaled); alpha0, psi0, dpsi0, alpha_low, alpha_upp, p_max (= max |p_k|, :1979): (B,) host arrays.
+
+    The Goldstein-Armijo arm runs as rounds of halving with its own exit test, its first round at the step it starts from, as
+    :1911 evaluates it.  Returns a ``LinesearchResult``."""
+    B = len(Ws)
+    be = _DeviceLinesearchBackend(backend) if isinstance(backend, GNSolver) else backend
+    f = lambda a: np.ascontiguousarray(a, dtype=np.float64).reshape(B)
+    alpha0, psi0, dpsi0, alpha_low, alpha_upp, p_max = (f(a) for a in (alpha0, psi0, dpsi0, alpha_low, alpha_upp, p_max))
+    gens = [_one_linesearch(alpha0[k], psi0[k], dpsi0[k], alpha_low[k], alpha_upp[k], p_max[k]) for k in range(B)]
+    req = [next(g) for g in gens]
+    alpha, gac = np.zeros(B), np.zeros(B, dtype=bool)
+    terminal = [None] * B
+    n_eval = np.zeros(B, dtype=np.int64)
+    rounds = 0
+    point = np.zeros(B)                 # the step every problem was last evaluated at
+    bufs = None
+    while any(r is not None for r in req):
+        answer = [None] * B
+        ev = np.array([1 if r is not None and (r[0] == "psi" or r[3]) else 0 for r in req], dtype=np.int64)
+        if ev.any():
+            for k in np.flatnonzero(ev):
+                point[k] = req[k][1]
+            bufs = evaluate(point.copy(), ev.copy())
+            rounds += 1
+            n_eval += ev
+        for with_psi in (True, False):      # the fits of this pass: with the evaluation (and psi) first, then those without
+            fk = np.array([1 if r is not None and r[0] == "fit" and bool(r[3]) == with_psi else 0 for r in req], dtype=np.int64)
+            if fk.any():
+                a_k = np.array([r[1] if fk[k] else 0.0 for k, r in enumerate(req)])
+                x_min = np.array([r[2] if fk[k] else 0.0 for k, r in enumerate(req)])
+                got = be.fit(Ws, setup, drx, dcx, bufs[0], bufs[1], dw, a_k, x_min, alpha_low, alpha_upp, take=fk, psi=with_psi)
+                for k in np.flatnonzero(fk):
+                    answer[k] = (float(got.psi[k]) if with_psi else None, got.sums[k].copy(), got.out[k].copy())
+        pk = np.array([1 if r is not None and r[0] == "psi" else 0 for r in req], dtype=np.int64)
+        if pk.any():
+            psi = be.merit(Ws, bufs[0], bufs[1], dw, take=pk)
+            for k in np.flatnonzero(pk):
+                answer[k] = float(psi[k])
+        for k in range(B):
+            if req[k] is None:
+                continue
+            try:
+                req[k] = gens[k].send(answer[k])
+            except StopIteration as done:
+                alpha[k], gac[k], terminal[k] = done.value
+                req[k] = None
+    return LinesearchResult(alpha, gac, rounds, terminal, n_eval)

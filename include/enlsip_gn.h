@@ -573,7 +573,7 @@ int enlsip_gn_get_deletion_form(enlsip_gn_handle h, int* form);
  * with the FULL constraint Jacobian, `Ap = A * p` (:2226-2229), upper_bound_steplength on it (:2149-2178), and the three sums
  * through which `Jp` enters the scalars of the set-up: dot(Jp,Jp), dot(Jp,rx) and dot(rx,rx) of penalty_weight_update (:1561-1584)
  * and of the predicted reduction (:2269).  Jp itself is what enlsip_gn_jacobian_times_batched_dev leaves on the device.  The penalty
- * weights, the merit function, the polynomial fit and the callbacks stay with the caller.
+ * weights, the merit function and the polynomial fit are the calls of the next two sections; the callbacks stay with the caller.
  *
  * enlsip_gn_upper_bound_steplength   upper_bound_steplength (src/enlsip_functions.jl:2149-2178) on HOST data, no handle and no GPU,
  *     on an Ap that has already been formed.  inactive: n_inactive 1-based row indices, 0 for padding; cx, Ap: l entries.  The list is
@@ -621,8 +621,8 @@ int enlsip_gn_get_linesearch_form(enlsip_gn_handle h, int* form);
  * What compute_steplength (src/enlsip_functions.jl:2197-2293) does next with what the set-up left: penalty_weight_update (:2238,
  * :1545-1629, with max_norm_weight_update! :1504-1539, euclidean_norm_weight_update :1429-1497, min_norm_w! :1374-1423 and assort!
  * :1344-1360), psi(0) of :2243, atwa of :2268, and the merit function psi (:1307-1340) of trial points whose residuals and
- * constraints the caller has evaluated into device buffers.  The callbacks, the polynomial fit (linesearch_constrained,
- * :1940-2147), check_derivatives and the first guess alpha0 stay with the caller.
+ * constraints the caller has evaluated into device buffers.  The polynomial fit (linesearch_constrained, :1940-2147) is the next
+ * section; the callbacks, check_derivatives and the first guess alpha0 stay with the caller.
  *
  * enlsip_gn_penalty_weight_update   penalty_weight_update on HOST data, no handle and no GPU.  active: t 1-based constraint numbers,
  *     distinct as a working set's are; active_Ap: the t entries of C.A * p, already divided by diag_scale where scaling is on
@@ -693,6 +693,75 @@ int enlsip_gn_merit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
                                 const int64_t* t, const int64_t* active, const int64_t* inactive,
                                 const int64_t* n_inactive, const int64_t* take,
                                 const double* drx, const double* dcx, const double* dw, double* psi);
+
+/* ---- the polynomial fit of the line search, on host scalars and on the caller's device buffers ---------------------------------
+ * What linesearch_constrained (src/enlsip_functions.jl:1940-2143) does between two callback evaluations.  At its first trial point,
+ * and once more on the arm of :2078-2092, it builds v0, v_buff and v2 of length m + l (coefficients_linesearch!, :1665-1689, through
+ * concatenate!, :1635-1659), scales v1 = [Jp; Ap] (:1986-1998), takes six dot products of them (minrm, :1849; parameters_rm,
+ * :1749-1751) and turns the six numbers into the next step length (:1739-1862 and the choice of :2023-2026).  With these calls every
+ * step of the line search between two evaluations of the callbacks exists in the library; the callbacks stay with the caller.
+ *
+ * enlsip_gn_linesearch_coefficients   the six sums on HOST data, no handle and no GPU.  active: t 1-based constraint numbers,
+ *     inactive: n_inactive of them, together a partition of 1..l as a working set's lists are (t + n_inactive == l; duplicates are
+ *     the caller's contract and are not checked); rx, rx_new, Jp: m entries; cx, cx_new, Ap, w: l entries, Ap the UNSCALED A * p.
+ *     No vector is materialised; the elements are formed literally: residual i: v0 = rx[i], v1 = Jp[i], vb = rx_new[i]; constraint
+ *     k: v0 = sqrt(w[k]) * cx[k], v1 = sqrt(w[k]) * Ap[k], vb = sqrt(w[k]) * cx_new[k], where an INACTIVE entry is 0 instead when
+ *     cx[k] > 0 (v0, and v1: it reads the OLD cx, :1996) or cx_new[k] > 0 (vb); v2 = ((vb - v0) / alpha_k - v1) / alpha_k, two IEEE
+ *     divisions, alpha_k == 0 not special-cased.  sums = v0.v0, v0.v1, v0.v2, v1.v1, v1.v2, v2.v2, each product rounded and then
+ *     added, never contracted, in this order: the m residual terms in index order, then the active list in list order, then the
+ *     inactive list in list order.  The reference scales JpAp in place (:1986); this routine writes neither Jp nor Ap.  Returns 0;
+ *     -2 sums NULL or a size out of range (m, l < 0, t or n_inactive outside 0..l); -4 a needed input pointer NULL; -5
+ *     t + n_inactive != l; -6 a list entry outside 1..l.
+ * enlsip_gn_linesearch_fit   minrm (:1841-1862) with parameters_rm, newton_raphson, one_root, two_roots and bounds on the six sums,
+ *     and the choice alpha_kp1 != beta && p_beta < pk && beta <= alpha_k (:2023-2026).  out = alpha_kp1, pk (after the choice),
+ *     alpha_hat, s_alpha, beta_hat, s_beta (as minrm returns them); *arm 0 Newton-Raphson, 1 one root, 2 two roots.  Kept as
+ *     written: the d = 1.0 sentinel (:1747), so the Newton arm ends in beta_hat = alpha_hat; (a3, a2, a1) are the FIRST three
+ *     coefficients of ds (:1757); alpha_old == beta_hat is tested on the unclamped value after bounds (:1854-1856); the Newton loop
+ *     runs while (error > 1e-4 || iter < 3) && iter < 50 and leaves on |dds| < eps; every comparison keeps its strictness.  Horner
+ *     evaluation is unfused (Polynomials.jl may fuse, which moves a value by a rounding); a^2, a^3 are products; pow, cbrt, acos,
+ *     cos are the host libm's.  Where the Julia would throw or divide by zero (dds_best == 0, normv2 == 0 on the analytic arm, an
+ *     acos argument that rounding pushed past 1) the IEEE value is taken; the Newton loop is bounded, so a NaN input ends the
+ *     routine.  Returns 0; -2 out or arm NULL; -4 sums NULL.
+ * enlsip_gn_minrn   minrn (:1708-1735) with minimize_quadratic (:1692-1702): (0, 0) when two of the abscissae are closer than
+ *     sqrt(eps) / p_max (:1719), else the clamped minimiser of the parabola and its value there.  Returns 0; -2 an output NULL.
+ * enlsip_gn_check_reduction   check_reduction (:1870-1886): *likely 1 or 0.  Returns 0; -2 likely NULL.
+ * enlsip_gn_linesearch_fit_batched_dev   for every taken problem k the six sums on drx, drx_new, dJp (m per problem) and dcx,
+ *     dcx_new, dAp, dw (l per problem) with the HOST records t, active (batch x t_max), inactive (batch x l), n_inactive, take
+ *     (NULL = all) and alpha_k; then enlsip_gn_linesearch_fit on the HOST, inside the call, with alpha_k[k], x_min[k], alpha_min[k],
+ *     alpha_max[k]: out[6k .. 6k+5] and arm[k] are bit for bit that routine on the returned sums[6k .. 6k+5].  (The scalar stage
+ *     branches on cbrt, acos and cos, which differ between the host libm and the device library, and the step length has to reach
+ *     the host for the next callback evaluation anyway.)  The m residual terms are added by the ordered partial-sum scheme of the
+ *     set-up call's general form with six accumulators, the constraint terms one by one in list order, the active list first.  No
+ *     floating-point atomics: a sum depends on m, l, the lists and the operands alone, not on the slot, the batch or the call; it
+ *     lies within 2 (m + l) u sum |x||y| of the exact dot product of the elements.  psi_new (HOST, may be NULL): psi of (drx_new,
+ *     dcx_new, dw) by the merit kernels in the same call from the same uploaded records, bit for bit what
+ *     enlsip_gn_merit_batched_dev returns (the reference needs both at the same point, :2000 with :2010).  A problem with
+ *     take[k] == 0 gets zeros in sums, out, arm and psi_new.  No device buffer of the caller is written.  The call needs no
+ *     resident factors: it is legal in every handle state and touches nothing resident.  The number of launches does not depend on
+ *     batch (which may exceed the grid's y limit); one copy of the host records goes up, one copy of the sums (and psi) comes back,
+ *     and the call returns after ONE synchronisation of the handle's stream.  t_max is at most 1024 in this build, l at most 2^27.
+ *     Argument errors are raised before anything is launched and leave everything untouched (last_error names k):
+ *       -1 h NULL; -2 batch < 1; -3 m, l or t_max out of range, t_max > l; -4 a required pointer NULL (t, n_inactive, alpha_k,
+ *       x_min, alpha_min, alpha_max, sums, out, arm; drx, drx_new, dJp while m > 0; dcx, dcx_new, dAp, dw, inactive while l > 0;
+ *       active while t_max > 0); -5 some t[k] outside 0..t_max, n_inactive[k] outside 0..l, or t[k] + n_inactive[k] != l; -6 a list
+ *       entry outside 1..l within the used part of a list.
+ */
+int enlsip_gn_linesearch_coefficients(int64_t m, int64_t l, int64_t t, const int64_t* active, const int64_t* inactive,
+                                      int64_t n_inactive, const double* rx, const double* rx_new, const double* Jp,
+                                      const double* cx, const double* cx_new, const double* Ap, const double* w,
+                                      double alpha_k, double* sums);
+int enlsip_gn_linesearch_fit(const double* sums, double alpha_k, double x_min, double alpha_min, double alpha_max,
+                             double* out, int* arm);
+int enlsip_gn_minrn(double x1, double y1, double x2, double y2, double x3, double y3, double alpha_min, double alpha_max,
+                    double p_max, double* alpha, double* p_alpha);
+int enlsip_gn_check_reduction(double psi_alpha, double psi_k, double approx_k, double eta, double diff_psi, int* likely);
+int enlsip_gn_linesearch_fit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t l, int64_t t_max,
+                                         const int64_t* t, const int64_t* active, const int64_t* inactive,
+                                         const int64_t* n_inactive, const int64_t* take,
+                                         const double* alpha_k, const double* x_min, const double* alpha_min,
+                                         const double* alpha_max, const double* drx, const double* drx_new,
+                                         const double* dJp, const double* dcx, const double* dcx_new, const double* dAp,
+                                         const double* dw, double* sums, double* out, int* arm, double* psi_new);
 
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
