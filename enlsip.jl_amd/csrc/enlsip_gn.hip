@@ -114,6 +114,13 @@ template <class Layout, class... Shape>
 static int place_pinned(enlsip_gn_handle h, PinnedBuf& b, Layout& L, const Shape&... shape) {
     return place(L, [&](size_t bytes, void** base) { const int rc = grow_pinned(h, b, bytes); *base = b.p; return rc; }, shape...);
 }
+// The records of a call on the caller's buffers (gn_batch_records.hpp): the same layout in the device buffer and in pinned memory,
+// there without the partial sums (`part` per problem), which stay on the device.
+template <class Layout, class... Shape>
+static int place_records(enlsip_gn_handle h, DevBuf& d, PinnedBuf& p, Layout& D, Layout& H, int64_t part, const Shape&... shape) {
+    const int rc = place_dev(h, d, D, shape..., part);
+    return rc ? rc : place_pinned(h, p, H, shape..., (int64_t)0);
+}
 static_assert(PLAN_PB == PB && PLAN_KBLK == KBLK && PLAN_QD_CPW == QD_CPW && PLAN_QDCAND_BYTES == sizeof(QdCand) &&
               PLAN_SBINFO_BYTES == sizeof(SbInfo), "gn_plan.hpp sizes the workspaces with the kernels' constants");
 // the pair rule lives in plan_geometry; the dispatch tests read its threshold from this file, so it is pinned here

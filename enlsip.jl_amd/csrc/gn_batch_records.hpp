@@ -1,0 +1,157 @@
+// The batched calls on the caller's device buffers (gn_deletion_batched.inc, gn_linesearch_batched.inc, gn_penalty_batched.inc,
+// gn_linesearch_fit_batched.inc): the records they upload and download, the checks and the packing of their host arguments, and
+// their scratch layouts.  Host-only, nothing of HIP: tests/batch_records_check.cpp runs all of it on the CPU.  The
+// kernel headers include it for the records.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+
+#include "gn_layout.hpp"
+
+namespace gn {
+
+// ---- records: the kernels read them as they stand; sizes and field offsets are pinned in tests/batch_records_check.cpp ------------
+struct DeletionMeta {
+    int t, q;        // the problem's constraint count (restore: after the deletion) and its number of equalities
+    int take;        // delete: 0 leaves the problem alone
+    int s;           // restore: the 1-based row to put back, 0 for none
+};
+
+struct LsMeta {
+    int n_inactive;     // used entries of the problem's list
+    int index_del;      // the row :2166 skips, 0 for none
+};
+
+struct LsOut {
+    double alpha_upp;
+    double sums[3];     // Jp.Jp, Jp.rx, rx.rx
+    long long index_alpha_upp;
+};
+
+struct PenaltyMeta {
+    double sums[3];     // Jp.Jp, Jp.rx, rx.rx as the set-up call returns them
+    int t, dimA;
+    int take;           // 0 leaves the problem alone
+    int pad;
+};
+
+struct PenaltyOut {
+    double scalars[3];  // dpsi0, psi0, atwa
+    int branch;
+    int pad;
+};
+
+struct MeritMeta {
+    int t, n_inactive;
+    int take;
+    int pad;
+};
+
+constexpr int LS_SUM_ROWS = 1024;       // rows per partial-sum workgroup until nblk reaches LS_MAX_NBLK
+constexpr int LS_MAX_NBLK = 64;         // one partial per lane of the adding wave
+constexpr int BATCH_MAX_T = 1024;       // t_max of this build: the LDS copies of the general forms (k_delete_general, PW_MAX_T)
+
+// ---- checks of the host arguments: 0, or the message in err and the code ------------------------------------------------------------
+inline int fail(std::string& err, int code, std::string msg) { err = std::move(msg); return code; }
+
+inline int check_batch(std::string& err, int64_t batch) {
+    return batch < 1 || batch > 0x7fffffff ? fail(err, -2, "batch must be in 1..2^31-1") : 0;
+}
+inline int check_l(std::string& err, int64_t l) { return l < 0 || l > (1LL << 27) ? fail(err, -3, "l must be in 0..2^27") : 0; }
+inline int check_t_max(std::string& err, int64_t t_max) {
+    return t_max < 0 || t_max > BATCH_MAX_T ? fail(err, -3, "t_max must be in 0..1024 in this build") : 0;
+}
+// the shape of the penalty, merit and fit calls
+inline int check_shape(std::string& err, int64_t batch, int64_t l, int64_t t_max) {
+    int rc;
+    if ((rc = check_batch(err, batch)) || (rc = check_l(err, l)) || (rc = check_t_max(err, t_max))) return rc;
+    return t_max > l ? fail(err, -3, "t_max > l") : 0;
+}
+
+struct Range { int64_t lo, hi; const char* text; };     // lo..hi, and what a message calls it ("0..t_max")
+
+// the failing end of the two checks below, "name[k] outside <text>" or with i >= 0 "name[k][i] outside <text>": a function of its
+// own so that the checks stay small enough to be inlined into the callers' loops over the batch
+inline int outside(std::string& err, int code, const char* name, int64_t k, int64_t i, const char* text) {
+    return fail(err, code, std::string(name) + "[" + std::to_string(k) + (i < 0 ? "]" : "][" + std::to_string(i) + "]") + " outside " + text);
+}
+// v = name[k] of a per-problem count
+inline int check_count(std::string& err, int code, const char* name, int64_t k, int64_t v, Range r) {
+    return v < r.lo || r.hi < v ? outside(err, code, name, k, -1, r.text) : 0;
+}
+// row k of a ragged list: its first cnt entries; nothing behind them is read
+inline int check_list(std::string& err, int code, const char* name, int64_t k, const int64_t* row, int64_t cnt, Range r) {
+    for (int64_t i = 0; i < cnt; ++i)
+        if (row[i] < r.lo || r.hi < row[i]) return outside(err, code, name, k, i, r.text);
+    return 0;
+}
+
+// batch rows of `stride` ints: the first cnt[k] entries of row k of src, 0 behind them
+inline void pack_rows(int* dst, const int64_t* src, const int64_t* cnt, int64_t batch, int64_t stride) {
+    for (int64_t k = 0; k < batch; ++k) {
+        const int64_t* from = src + k * stride;
+        int* to = dst + k * stride;
+        for (int64_t i = 0; i < cnt[k]; ++i) to[i] = (int)from[i];
+        std::fill(to + cnt[k], to + stride, 0);
+    }
+}
+
+inline int take_flag(const int64_t* take, int64_t k) { return (take && take[k] == 0) ? 0 : 1; }     // no array: every problem
+
+// workgroups per problem of an ordered partial sum over m rows, and whether batch * max(per_problem, 1) workgroups fit a grid
+inline int64_t sum_blocks(int64_t m) { return std::min<int64_t>(LS_MAX_NBLK, (m + LS_SUM_ROWS - 1) / LS_SUM_ROWS); }
+inline bool grid_fits(int64_t batch, int64_t per_problem) { return batch * std::max<int64_t>(per_problem, 1) <= 0x7fffffff; }
+
+// ---- scratch layouts (gn_layout.hpp) ------------------------------------------------------------------------------------------------
+// A call places its layout twice, in its device buffer and in pinned memory, and moves the records by ONE copy up and ONE down.
+// That needs the moved arrays at equal offsets on both sides, so they come first and the partial sums, which only the device side
+// has (0 per problem in pinned memory), come last.  up_bytes / down_bytes are read off the placed arrays, never from the shape again.
+template <class T>
+size_t bytes_since(const Carver& c, const T* first) { return c.off - (size_t)((const char*)first - c.base); }
+
+// up [meta | list], down out.  Deletion: no list (stride 0), out = s; set-up: list = inactive, 3 * nblk partial sums; penalty: active
+template <class Meta, class Out>
+struct RecordScratch {
+    Meta* meta = nullptr;
+    int* list = nullptr;
+    Out* out = nullptr;
+    double* part = nullptr;
+    size_t up_bytes = 0, down_bytes = 0;
+    void carve(Carver& c, int64_t batch, int64_t stride, int64_t part_per_problem) {
+        c.take(meta, "meta", (size_t)batch);
+        c.take(list, "list", (size_t)batch * (size_t)stride);
+        up_bytes = bytes_since(c, meta);
+        c.take(out, "out", (size_t)batch, 8);
+        down_bytes = bytes_since(c, out);
+        c.take(part, "part", (size_t)batch * (size_t)part_per_problem);
+    }
+};
+using DeletionScratch = RecordScratch<DeletionMeta, int>;
+using LinesearchScratch = RecordScratch<LsMeta, LsOut>;
+using PenaltyScratch = RecordScratch<PenaltyMeta, PenaltyOut>;
+
+// The merit call and, with fit, the polynomial fit: up [meta | act | inact | alpha], down [sums | psi] (a fit without psi_new
+// leaves the last psi_bytes of it where they are); the partial sums of the fit (6 * nblk per problem) and of the merit kernels
+// (nblk) stay on the device.  alpha, sums and part exist with fit only.
+struct MeritScratch {
+    MeritMeta* meta = nullptr;
+    int *act = nullptr, *inact = nullptr;
+    double *alpha = nullptr, *sums = nullptr, *psi = nullptr, *part = nullptr, *mpart = nullptr;
+    size_t up_bytes = 0, down_bytes = 0, psi_bytes = 0;
+    void carve(Carver& c, int64_t batch, int64_t t_max, int64_t l, bool fit, int64_t nblk) {
+        c.take(meta, "meta", (size_t)batch, 8);
+        c.take(act, "act", (size_t)batch * (size_t)t_max);
+        c.take(inact, "inact", (size_t)batch * (size_t)l);
+        if (fit) c.take(alpha, "alpha", (size_t)batch);
+        up_bytes = bytes_since(c, meta);
+        if (fit) c.take(sums, "sums", (size_t)batch * 6);
+        c.take(psi, "psi", (size_t)batch);
+        psi_bytes = bytes_since(c, psi);
+        down_bytes = fit ? bytes_since(c, sums) : psi_bytes;
+        if (fit) c.take(part, "part", (size_t)batch * (size_t)nblk * 6);
+        c.take(mpart, "mpart", (size_t)batch * (size_t)nblk);
+    }
+};
+
+}  // namespace gn

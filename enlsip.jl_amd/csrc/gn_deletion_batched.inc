@@ -1,38 +1,18 @@
 // The deletion test and the working-set edit of a batch on the caller's device buffers (kernels: gn_kernels_deletion_batched.hpp; the
 // test: gn_deletion_test.hpp): check_constraint_deletion (src/enlsip_functions.jl:574-603) with the removal of :708-719 / :748-756 /
 // :776-785, and the re-insertion of :731-739.  Neither call needs or touches anything resident: the handle lends its device, its
-// stream and a small scratch for t / q / take / s.  Included at the end of enlsip_gn.hip.
+// stream and a small scratch for t / q / take / s (DeletionScratch: the records up, the decisions down; the restore brings
+// nothing down).  Included at the end of enlsip_gn.hip.
 
 namespace {
 
-enum { DEL_MAX_T = 1024 };      // t_max of this build: the LDS copies of the general form.  n is not bounded: rows are strided by thread
-
-// the per-problem records of one call in pinned memory and on the device, the decisions behind them (hs, ds: may be null, the
-// restore has none); grown, never shrunk (grow, grow_pinned)
-struct DeletionScratch {
-    DeletionMeta* meta = nullptr;
-    int* s = nullptr;
-    void carve(Carver& c, int64_t batch) { c.take(meta, "meta", (size_t)batch); c.take(s, "s", (size_t)batch); }
-};
-int deletion_scratch(enlsip_gn_handle h, int64_t batch, DeletionMeta** hmeta, int** hs, DeletionMeta** dmeta, int** ds) {
-    DeletionScratch D, H;
-    int rc = place_dev(h, h->del_scr, D, batch);
-    if (rc) return rc;
-    rc = place_pinned(h, h->h_del, H, batch);
-    if (rc) return rc;
-    *hmeta = H.meta;
-    *dmeta = D.meta;
-    if (hs) *hs = H.s;
-    if (ds) *ds = D.s;
-    return 0;
-}
-
-// the checks both calls share; anything wrong is reported before a launch
+// the checks both calls share; anything wrong is reported before a launch.  n is not bounded: rows are strided by thread
 int deletion_check_shape(enlsip_gn_handle h, int64_t batch, int64_t n, int64_t t_max, const int64_t* t, const double* dlambda,
                          const double* ddiag_scale, const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx) {
-    if (batch < 1 || batch > 0x7fffffff) { h->err = "batch must be in 1..2^31-1"; return -2; }
+    int rc;
+    if ((rc = check_batch(h->err, batch))) return rc;
     if (n < 1 || n > 0x3fffffff) { h->err = "n must be at least 1"; return -3; }
-    if (t_max < 0 || t_max > DEL_MAX_T) { h->err = "t_max must be in 0..1024 in this build"; return -3; }
+    if ((rc = check_t_max(h->err, t_max))) return rc;
     if (!t) { h->err = "t is a host array of batch entries"; return -4; }
     if (t_max > 0 && (!dlambda || !ddiag_scale || !dAt || !dcx)) {
         h->err = "dlambda, ddiag_scale, dAt and dcx are required when t_max > 0";
@@ -75,32 +55,29 @@ int enlsip_gn_delete_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, 
     int rc = deletion_check_shape(h, batch, n, t_max, t, dlambda, ddiag_scale, dAt, ldat, strideAt, dcx);
     if (rc) return rc;
     if (!q || !s) { h->err = "q and s are host arrays of batch entries"; return -4; }
-    for (int64_t k = 0; k < batch; ++k) {
-        if (t[k] < 0 || t[k] > t_max) { h->err = "t[" + std::to_string(k) + "] outside 0..t_max"; return -5; }
-        if (q[k] < 0 || q[k] > t[k]) { h->err = "q[" + std::to_string(k) + "] outside 0..t[k]"; return -6; }
-    }
+    for (int64_t k = 0; k < batch; ++k)      // per problem: the lower k wins
+        if ((rc = check_count(h->err, -5, "t", k, t[k], {0, t_max, "0..t_max"})) ||
+            (rc = check_count(h->err, -6, "q", k, q[k], {0, t[k], "0..t[k]"}))) return rc;
     if (t_max == 0) {      // no constraint anywhere: nothing to test
         std::fill(s, s + batch, (int64_t)0);
         return 0;
     }
     GN_HIP(hipSetDevice(h->device));
-    DeletionMeta *hm, *dm;
-    int *hs, *dsd;
-    rc = deletion_scratch(h, batch, &hm, &hs, &dm, &dsd);
-    if (rc) return rc;
-    for (int64_t k = 0; k < batch; ++k) hm[k] = {(int)t[k], (int)q[k], (take && take[k] == 0) ? 0 : 1, 0};
+    DeletionScratch D, H;
+    if ((rc = place_records(h, h->del_scr, h->h_del, D, H, 0, batch, (int64_t)0))) return rc;
+    for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], (int)q[k], take_flag(take, k), 0};
     hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(dm, hm, (size_t)batch * sizeof(DeletionMeta), hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     DeletionArgs a = deletion_args(batch, n, t_max, scaling, dlambda, ddiag_scale, dgrad_res, dAt, ldat, strideAt, dcx, dsaved);
-    a.meta = dm; a.s_out = dsd;
+    a.meta = D.meta; a.s_out = D.out;
     const bool wave = deletion_wave_form(n, t_max);
     h->deletion_form = wave ? 1 : 0;
     if (wave) hipLaunchKernelGGL(k_delete_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_delete_general, dim3((unsigned)batch), dim3(256), 0, st, a);
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(hs, dsd, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
-    for (int64_t k = 0; k < batch; ++k) s[k] = hs[k];
+    std::copy(H.out, H.out + batch, s);
     return 0;
     GN_CATCH(h)
 }
@@ -115,25 +92,21 @@ int enlsip_gn_restore_constraints_batched_dev(enlsip_gn_handle h, int64_t batch,
     if (!s) { h->err = "s is a host array of batch entries"; return -4; }
     bool any = false;
     for (int64_t k = 0; k < batch; ++k) {
-        const int64_t hi = s[k] != 0 ? t_max - 1 : t_max;
-        if (t[k] < 0 || t[k] > hi) {
-            h->err = "t[" + std::to_string(k) + "] outside 0..t_max (0..t_max-1 where a row comes back)";
-            return -5;
-        }
-        if (s[k] < 0 || s[k] > t[k] + 1) { h->err = "s[" + std::to_string(k) + "] outside 0..t[k]+1"; return -7; }
+        const int64_t hi = s[k] != 0 ? t_max - 1 : t_max;      // a row that comes back needs room
+        if ((rc = check_count(h->err, -5, "t", k, t[k], {0, hi, "0..t_max (0..t_max-1 where a row comes back)"})) ||
+            (rc = check_count(h->err, -7, "s", k, s[k], {0, t[k] + 1, "0..t[k]+1"}))) return rc;
         any = any || s[k] != 0;
     }
     if (!any) return 0;
     if (!dsaved) { h->err = "dsaved is NULL while some s[k] != 0"; return -12; }
     GN_HIP(hipSetDevice(h->device));
-    DeletionMeta *hm, *dm;
-    rc = deletion_scratch(h, batch, &hm, nullptr, &dm, nullptr);
-    if (rc) return rc;
-    for (int64_t k = 0; k < batch; ++k) hm[k] = {(int)t[k], 0, 1, (int)s[k]};
+    DeletionScratch D, H;
+    if ((rc = place_records(h, h->del_scr, h->h_del, D, H, 0, batch, (int64_t)0))) return rc;
+    for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], 0, 1, (int)s[k]};
     hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(dm, hm, (size_t)batch * sizeof(DeletionMeta), hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     DeletionArgs a = deletion_args(batch, n, t_max, 0, dlambda, ddiag_scale, nullptr, dAt, ldat, strideAt, dcx, (double*)dsaved);
-    a.meta = dm;
+    a.meta = D.meta;
     const bool wave = deletion_wave_form(n, t_max);
     h->deletion_form = wave ? 1 : 0;
     if (wave) hipLaunchKernelGGL(k_restore_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);

@@ -17,16 +17,11 @@
 //             holds for -0.0 against +0.0 exactly where <= held in the loop; a NaN v_i passes neither.  A NaN anywhere in
 //             lambda[0:t) makes sq_rel NaN in the loop, so nothing passes and the gate of :598 is false: s = 0, by one ballot.
 #pragma once
+#include "gn_batch_records.hpp"
 #include "gn_device_utils.hpp"
 #include "gn_deletion_test.hpp"
 
 namespace gn {
-
-struct DeletionMeta {
-    int t, q;        // the problem's constraint count (restore: after the deletion) and its number of equalities
-    int take;        // delete: 0 leaves the problem alone
-    int s;           // restore: the 1-based row to put back, 0 for none
-};
 
 struct DeletionArgs {
     const DeletionMeta* meta;

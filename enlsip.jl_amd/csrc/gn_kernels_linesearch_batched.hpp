@@ -22,21 +22,11 @@
 //                            m and the butterfly.
 // A sum depends on m and the operands only, never on the slot, the batch size or the arrival order.
 #pragma once
+#include "gn_batch_records.hpp"
 #include "gn_device_utils.hpp"
 #include "gn_steplength_bound.hpp"
 
 namespace gn {
-
-struct LsMeta {
-    int n_inactive;     // used entries of the problem's list
-    int index_del;      // the row :2166 skips, 0 for none
-};
-
-struct LsOut {
-    double alpha_upp;
-    double sums[3];     // Jp.Jp, Jp.rx, rx.rx
-    long long index_alpha_upp;
-};
 
 struct LinesearchArgs {
     const LsMeta* meta;
@@ -54,8 +44,6 @@ struct LinesearchArgs {
 };
 
 constexpr int LS_MAX_N = 1024;          // p in LDS (general form)
-constexpr int LS_SUM_ROWS = 1024;       // rows per partial-sum workgroup until nblk reaches LS_MAX_NBLK
-constexpr int LS_MAX_NBLK = 64;         // one partial per lane of the adding wave
 
 __global__ __launch_bounds__(256) void k_ls_product(LinesearchArgs a) {
     __shared__ double sp[LS_MAX_N];

@@ -21,24 +21,12 @@
 // for an inactive entry that fails cx[j] < 0), and the terms are added to the running sum one by one in list order (v_readlane of
 // lane 0, 1, ...): active list first, then inactive, as :1322-1337.  No floating-point atomics anywhere.
 #pragma once
+#include "gn_batch_records.hpp"
 #include "gn_device_utils.hpp"
 #include "gn_kernels_linesearch_batched.hpp"
 #include "gn_penalty_weights.hpp"
 
 namespace gn {
-
-struct PenaltyMeta {
-    double sums[3];     // Jp.Jp, Jp.rx, rx.rx as the set-up call returns them
-    int t, dimA;
-    int take;           // 0 leaves the problem alone
-    int pad;
-};
-
-struct PenaltyOut {
-    double scalars[3];  // dpsi0, psi0, atwa
-    int branch;
-    int pad;
-};
 
 struct PenaltyArgs {
     const PenaltyMeta* meta;
@@ -133,12 +121,6 @@ __global__ __launch_bounds__(256) void k_penalty(PenaltyArgs a) {
 }
 
 // ---- the merit function ----------------------------------------------------------------------------------------------------------
-struct MeritMeta {
-    int t, n_inactive;
-    int take;
-    int pad;
-};
-
 struct MeritArgs {
     const MeritMeta* meta;
     const int* act;             // stride t_max: 1-based constraints, 0 padding

@@ -5,31 +5,8 @@
 // the last place and the routine branches on their results, so a device copy could not be pinned to the host routine, and the
 // step length has to reach the host for the next callback evaluation anyway.  With psi_new the merit kernels of
 // gn_kernels_penalty_batched.hpp run on (drx_new, dcx_new, dw) from the same uploaded records.  The call needs or touches nothing
-// resident: the handle lends its device, its stream and the scratch of the merit call.  Included at the end of enlsip_gn.hip.
-
-namespace {
-
-// one call's records: up goes [meta | act | inact | alpha] in one copy, down comes [sums | psi] in one copy; the partial sums stay
-// on the device (the pinned side has none)
-struct FitScratch {
-    MeritMeta* meta = nullptr;
-    int *act = nullptr, *inact = nullptr;
-    double *alpha = nullptr, *sums = nullptr, *psi = nullptr, *part = nullptr, *mpart = nullptr;
-    void carve(Carver& c, int64_t batch, int64_t t_max, int64_t l, int64_t nblk) {
-        c.take(meta, "meta", (size_t)batch, 8);
-        c.take(act, "act", (size_t)batch * (size_t)t_max);
-        c.take(inact, "inact", (size_t)batch * (size_t)l);
-        c.take(alpha, "alpha", (size_t)batch);
-        c.take(sums, "sums", (size_t)batch * 6);
-        c.take(psi, "psi", (size_t)batch);
-        c.take(part, "part", (size_t)batch * (size_t)nblk * 6);
-        c.take(mpart, "mpart", (size_t)batch * (size_t)nblk);
-    }
-    // meta .. alpha are adjacent in both layouts (the padding in front of alpha is the same on both sides)
-    size_t up_bytes(int64_t batch) const { return (size_t)((const char*)(alpha + batch) - (const char*)meta); }
-};
-
-}  // namespace
+// resident: the handle lends its device, its stream and the scratch of the merit call (MeritScratch with fit).  Included at the
+// end of enlsip_gn.hip.
 
 extern "C" {
 
@@ -82,7 +59,7 @@ int enlsip_gn_linesearch_fit_batched_dev(enlsip_gn_handle h, int64_t batch, int6
                                          double* out, int* arm, double* psi_new) {
     if (!h) return -1;
     GN_TRY
-    int rc = penalty_check_shape(h, batch, l, t_max);
+    int rc = check_shape(h->err, batch, l, t_max);
     if (rc) return rc;
     if (m < 0 || m > 0x7fffffff) { h->err = "m must be in 0..2^31-1"; return -3; }
     if (!t || !n_inactive || !alpha_k || !x_min || !alpha_min || !alpha_max || !sums || !out || !arm) {
@@ -96,60 +73,33 @@ int enlsip_gn_linesearch_fit_batched_dev(enlsip_gn_handle h, int64_t batch, int6
     }
     if (t_max > 0 && !active) { h->err = "active is required when t_max > 0"; return -4; }
     for (int64_t k = 0; k < batch; ++k) {
-        if (t[k] < 0 || t[k] > t_max) { h->err = "t[" + std::to_string(k) + "] outside 0..t_max"; return -5; }
-        if (n_inactive[k] < 0 || n_inactive[k] > l) { h->err = "n_inactive[" + std::to_string(k) + "] outside 0..l"; return -5; }
+        if ((rc = check_count(h->err, -5, "t", k, t[k], {0, t_max, "0..t_max"})) ||
+            (rc = check_count(h->err, -5, "n_inactive", k, n_inactive[k], {0, l, "0..l"}))) return rc;
         if (t[k] + n_inactive[k] != l) { h->err = "t[" + std::to_string(k) + "] + n_inactive[" + std::to_string(k) + "] != l"; return -5; }
     }
-    for (int64_t k = 0; k < batch; ++k) {
-        const int64_t* ra = active + k * t_max;
-        for (int64_t i = 0; i < t[k]; ++i)
-            if (ra[i] < 1 || ra[i] > l) {
-                h->err = "active[" + std::to_string(k) + "][" + std::to_string(i) + "] outside 1..l";
-                return -6;
-            }
-        const int64_t* ri = inactive + k * l;
-        for (int64_t i = 0; i < n_inactive[k]; ++i)
-            if (ri[i] < 1 || ri[i] > l) {
-                h->err = "inactive[" + std::to_string(k) + "][" + std::to_string(i) + "] outside 1..l";
-                return -6;
-            }
-    }
-    const int64_t nblk = std::min<int64_t>(LS_MAX_NBLK, (m + LS_SUM_ROWS - 1) / LS_SUM_ROWS);
-    if (batch * std::max<int64_t>(nblk, 1) > 0x7fffffff) { h->err = "batch * partial-sum workgroups exceeds the grid"; return -2; }
+    for (int64_t k = 0; k < batch; ++k)      // entries from 1, as enlsip_gn_linesearch_coefficients asks: the used entries are the l constraints
+        if ((rc = check_list(h->err, -6, "active", k, active + k * t_max, t[k], {1, l, "1..l"})) ||
+            (rc = check_list(h->err, -6, "inactive", k, inactive + k * l, n_inactive[k], {1, l, "1..l"}))) return rc;
+    const int64_t nblk = sum_blocks(m);
+    if (!grid_fits(batch, nblk)) { h->err = "batch * partial-sum workgroups exceeds the grid"; return -2; }
     GN_HIP(hipSetDevice(h->device));
-    FitScratch D, H;
-    rc = place_dev(h, h->pen_scr, D, batch, t_max, l, nblk);
-    if (rc) return rc;
-    rc = place_pinned(h, h->h_pen, H, batch, t_max, l, (int64_t)0);
-    if (rc) return rc;
-    for (int64_t k = 0; k < batch; ++k) {
-        H.meta[k] = {(int)t[k], (int)n_inactive[k], (take && take[k] == 0) ? 0 : 1, 0};
-        int* da = H.act + k * t_max;
-        for (int64_t i = 0; i < t_max; ++i) da[i] = i < t[k] ? (int)active[k * t_max + i] : 0;
-        int* di = H.inact + k * l;
-        for (int64_t i = 0; i < l; ++i) di[i] = i < n_inactive[k] ? (int)inactive[k * l + i] : 0;
-        H.alpha[k] = alpha_k[k];
-    }
+    MeritScratch D, H;
+    if ((rc = place_records(h, h->pen_scr, h->h_pen, D, H, nblk, batch, t_max, l, true))) return rc;
+    for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], (int)n_inactive[k], take_flag(take, k), 0};
+    pack_rows(H.act, active, t, batch, t_max);
+    pack_rows(H.inact, inactive, n_inactive, batch, l);
+    std::copy(alpha_k, alpha_k + batch, H.alpha);
     hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes(batch), hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     FitArgs a{};
     a.meta = D.meta; a.act = D.act; a.inact = D.inact; a.alpha = D.alpha; a.part = D.part; a.out = D.sums;
     a.count = (int)batch; a.m = (int)m; a.l = (int)l; a.t_max = (int)t_max; a.nblk = (int)nblk;
     a.rx = drx; a.rx_new = drx_new; a.Jp = dJp; a.cx = dcx; a.cx_new = dcx_new; a.Ap = dAp; a.w = dw;
-    const unsigned waves = (unsigned)((batch + 3) / 4);
     if (nblk > 0) hipLaunchKernelGGL(k_fit_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_fit_total, dim3(waves), dim3(256), 0, st, a);
-    if (psi_new) {
-        MeritArgs ma{};
-        ma.meta = D.meta; ma.act = D.act; ma.inact = D.inact; ma.part = D.mpart; ma.out = D.psi;
-        ma.count = (int)batch; ma.m = (int)m; ma.l = (int)l; ma.t_max = (int)t_max; ma.nblk = (int)nblk;
-        ma.rx = drx_new; ma.cx = dcx_new; ma.w = dw;
-        if (nblk > 0) hipLaunchKernelGGL(k_merit_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, ma);
-        hipLaunchKernelGGL(k_merit_total, dim3(waves), dim3(256), 0, st, ma);
-    }
+    hipLaunchKernelGGL(k_fit_total, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+    if (psi_new) launch_merit(st, {D.meta, D.act, D.inact, D.mpart, D.psi, a.count, a.m, a.l, a.t_max, a.nblk, drx_new, dcx_new, dw});
     GN_HIP(hipGetLastError());
-    // sums and psi are adjacent in both layouts: one copy
-    GN_HIP(hipMemcpyAsync(H.sums, D.sums, (size_t)batch * (psi_new ? 7 : 6) * sizeof(double), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipMemcpyAsync(H.sums, D.sums, H.down_bytes - (psi_new ? 0 : H.psi_bytes), hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
     for (int64_t k = 0; k < batch; ++k) {
         double* o = out + 6 * k;

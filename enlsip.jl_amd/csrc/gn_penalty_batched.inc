@@ -1,51 +1,19 @@
 // The penalty weights and the merit function of a batch on the caller's device buffers (kernels: gn_kernels_penalty_batched.hpp;
 // the routine: gn_penalty_weights.hpp): penalty_weight_update (src/enlsip_functions.jl:1545-1629) with psi(0) of :2243 and atwa of
 // :2268, and psi of :1307-1340 on evaluated trial points.  Neither call needs or touches anything resident: the handle lends its
-// device, its stream and a scratch for the host records, the partial sums and the scalars.  Included at the end of enlsip_gn.hip.
+// device, its stream and a scratch for the host records, the partial sums and the scalars (PenaltyScratch, MeritScratch).  Included
+// at the end of enlsip_gn.hip.
 
 namespace {
 
-// one call's records: up goes [meta | list] in one copy, down comes out in one copy
-struct PenaltyScratch {
-    PenaltyMeta* meta = nullptr;
-    int* list = nullptr;
-    PenaltyOut* out = nullptr;
-    void carve(Carver& c, int64_t batch, int64_t t_max) {
-        c.take(meta, "meta", (size_t)batch);
-        c.take(list, "list", (size_t)batch * (size_t)t_max);
-        c.take(out, "out", (size_t)batch, 8);
-    }
-    size_t up_bytes(int64_t batch, int64_t t_max) const {
-        return (size_t)batch * sizeof(PenaltyMeta) + (size_t)batch * (size_t)t_max * sizeof(int);
-    }
-};
-
-// the same for the merit function: [meta | act | inact] up, out down; part stays on the device (the pinned side has none)
-struct MeritScratch {
-    MeritMeta* meta = nullptr;
-    int *act = nullptr, *inact = nullptr;
-    double *out = nullptr, *part = nullptr;
-    void carve(Carver& c, int64_t batch, int64_t t_max, int64_t l, int64_t nblk) {
-        c.take(meta, "meta", (size_t)batch);
-        c.take(act, "act", (size_t)batch * (size_t)t_max);
-        c.take(inact, "inact", (size_t)batch * (size_t)l);
-        c.take(out, "out", (size_t)batch, 8);
-        c.take(part, "part", (size_t)batch * (size_t)nblk);
-    }
-    size_t up_bytes(int64_t batch, int64_t t_max, int64_t l) const {
-        return (size_t)batch * sizeof(MeritMeta) + (size_t)batch * (size_t)(t_max + l) * sizeof(int);
-    }
-};
-
 bool penalty_wave_form(int64_t t_max, int64_t l) { return t_max <= 64 && l <= 64; }
 
-// the shape checks both calls share
-int penalty_check_shape(enlsip_gn_handle h, int64_t batch, int64_t l, int64_t t_max) {
-    if (batch < 1 || batch > 0x7fffffff) { h->err = "batch must be in 1..2^31-1"; return -2; }
-    if (l < 0 || l > (1LL << 27)) { h->err = "l must be in 0..2^27"; return -3; }
-    if (t_max < 0 || t_max > PW_MAX_T) { h->err = "t_max must be in 0..1024 in this build"; return -3; }
-    if (t_max > l) { h->err = "t_max > l"; return -3; }
-    return 0;
+static_assert(PW_MAX_T == BATCH_MAX_T, "check_t_max bounds t_max by the LDS copies of k_penalty");
+
+// psi of (a.rx, a.cx, a.w) on uploaded records: the launch pair of the merit call and of the fit call's psi_new
+void launch_merit(hipStream_t st, const MeritArgs& a) {
+    if (a.nblk > 0) hipLaunchKernelGGL(k_merit_part, dim3((unsigned)((int64_t)a.count * a.nblk)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_merit_total, dim3((unsigned)((a.count + 3) / 4)), dim3(256), 0, st, a);
 }
 
 }  // namespace
@@ -111,7 +79,7 @@ int enlsip_gn_penalty_weights_batched_dev(enlsip_gn_handle h, int64_t batch, int
                                           int* branch) {
     if (!h) return -1;
     GN_TRY
-    int rc = penalty_check_shape(h, batch, l, t_max);
+    int rc = check_shape(h->err, batch, l, t_max);
     if (rc) return rc;
     if (norm_code != 0 && norm_code != 2) { h->err = "norm_code must be 0 or 2"; return -3; }
     if (!t || !dimA || !sums || !scalars || !branch) {
@@ -121,35 +89,21 @@ int enlsip_gn_penalty_weights_batched_dev(enlsip_gn_handle h, int64_t batch, int
     if (l > 0 && (!dw_old || !dK || !dw)) { h->err = "dw_old, dK and dw are required when l > 0"; return -4; }
     if (t_max > 0 && (!active || !dactive_Ap || !dcx)) { h->err = "active, dactive_Ap and dcx are required when t_max > 0"; return -4; }
     if (t_max > 0 && scaling != 0 && !ddiag_scale) { h->err = "ddiag_scale is required when scaling is on and t_max > 0"; return -4; }
-    for (int64_t k = 0; k < batch; ++k)
-        if (t[k] < 0 || t[k] > t_max) { h->err = "t[" + std::to_string(k) + "] outside 0..t_max"; return -5; }
-    for (int64_t k = 0; k < batch; ++k) {
-        if (dimA[k] < 0 || dimA[k] > t[k]) { h->err = "dimA[" + std::to_string(k) + "] outside 0..t[k]"; return -6; }
-        const int64_t* row = active + k * t_max;
-        for (int64_t i = 0; i < t[k]; ++i)
-            if (row[i] < 1 || row[i] > l) {
-                h->err = "active[" + std::to_string(k) + "][" + std::to_string(i) + "] outside 1..l";
-                return -6;
-            }
-    }
+    for (int64_t k = 0; k < batch; ++k)      // every t[k] before any dimA[k] or list
+        if ((rc = check_count(h->err, -5, "t", k, t[k], {0, t_max, "0..t_max"}))) return rc;
+    for (int64_t k = 0; k < batch; ++k)      // entries from 1: the kernel gathers w_old[j - 1] for every used entry
+        if ((rc = check_count(h->err, -6, "dimA", k, dimA[k], {0, t[k], "0..t[k]"})) ||
+            (rc = check_list(h->err, -6, "active", k, active + k * t_max, t[k], {1, l, "1..l"}))) return rc;
     const bool wave = penalty_wave_form(t_max, l);
     h->penalty_form = wave ? 1 : 0;
     GN_HIP(hipSetDevice(h->device));
     PenaltyScratch D, H;
-    rc = place_dev(h, h->pen_scr, D, batch, t_max);
-    if (rc) return rc;
-    rc = place_pinned(h, h->h_pen, H, batch, t_max);
-    if (rc) return rc;
-    for (int64_t k = 0; k < batch; ++k) {
-        H.meta[k] = {{sums[3 * k], sums[3 * k + 1], sums[3 * k + 2]}, (int)t[k], (int)dimA[k], (take && take[k] == 0) ? 0 : 1, 0};
-        const int64_t* row = active + k * t_max;
-        int* dst = H.list + k * t_max;
-        for (int64_t i = 0; i < t[k]; ++i) dst[i] = (int)row[i];
-        for (int64_t i = t[k]; i < t_max; ++i) dst[i] = 0;
-    }
+    if ((rc = place_records(h, h->pen_scr, h->h_pen, D, H, 0, batch, t_max))) return rc;
+    for (int64_t k = 0; k < batch; ++k)
+        H.meta[k] = {{sums[3 * k], sums[3 * k + 1], sums[3 * k + 2]}, (int)t[k], (int)dimA[k], take_flag(take, k), 0};
+    pack_rows(H.list, active, t, batch, t_max);
     hipStream_t st = h->stream;
-    // meta and list are adjacent in both layouts (int-aligned records): one copy
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes(batch, t_max), hipMemcpyHostToDevice, st));
+    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     PenaltyArgs a{};
     a.meta = D.meta; a.list = D.list; a.out = D.out;
     a.count = (int)batch; a.l = (int)l; a.t_max = (int)t_max; a.norm_code = norm_code; a.scaling = scaling != 0;
@@ -157,7 +111,7 @@ int enlsip_gn_penalty_weights_batched_dev(enlsip_gn_handle h, int64_t batch, int
     if (wave) hipLaunchKernelGGL((k_penalty<64, 64>), dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((k_penalty<256, PW_MAX_T>), dim3((unsigned)batch), dim3(256), 0, st, a);
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, (size_t)batch * sizeof(PenaltyOut), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
     for (int64_t k = 0; k < batch; ++k) {
         const bool taken = H.meta[k].take != 0;
@@ -179,59 +133,34 @@ int enlsip_gn_merit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
                                 const double* drx, const double* dcx, const double* dw, double* psi) {
     if (!h) return -1;
     GN_TRY
-    int rc = penalty_check_shape(h, batch, l, t_max);
+    int rc = check_shape(h->err, batch, l, t_max);
     if (rc) return rc;
     if (m < 0 || m > 0x7fffffff) { h->err = "m must be in 0..2^31-1"; return -3; }
     if (!t || !n_inactive || !psi) { h->err = "t, n_inactive and psi are host arrays of batch entries"; return -4; }
     if (m > 0 && !drx) { h->err = "drx is required when m > 0"; return -4; }
     if (l > 0 && (!dcx || !dw || !inactive)) { h->err = "dcx, dw and inactive are required when l > 0"; return -4; }
     if (t_max > 0 && !active) { h->err = "active is required when t_max > 0"; return -4; }
-    for (int64_t k = 0; k < batch; ++k) {
-        if (t[k] < 0 || t[k] > t_max) { h->err = "t[" + std::to_string(k) + "] outside 0..t_max"; return -5; }
-        if (n_inactive[k] < 0 || n_inactive[k] > l) { h->err = "n_inactive[" + std::to_string(k) + "] outside 0..l"; return -5; }
-    }
-    for (int64_t k = 0; k < batch; ++k) {
-        const int64_t* ra = active + k * t_max;
-        for (int64_t i = 0; i < t[k]; ++i)
-            if (ra[i] < 0 || ra[i] > l) {
-                h->err = "active[" + std::to_string(k) + "][" + std::to_string(i) + "] outside 0..l";
-                return -6;
-            }
-        const int64_t* ri = inactive + k * l;
-        for (int64_t i = 0; i < n_inactive[k]; ++i)
-            if (ri[i] < 0 || ri[i] > l) {
-                h->err = "inactive[" + std::to_string(k) + "][" + std::to_string(i) + "] outside 0..l";
-                return -6;
-            }
-    }
-    const int64_t nblk = std::min<int64_t>(LS_MAX_NBLK, (m + LS_SUM_ROWS - 1) / LS_SUM_ROWS);
-    if (batch * std::max<int64_t>(nblk, 1) > 0x7fffffff) { h->err = "batch * partial-sum workgroups exceeds the grid"; return -2; }
+    for (int64_t k = 0; k < batch; ++k)
+        if ((rc = check_count(h->err, -5, "t", k, t[k], {0, t_max, "0..t_max"})) ||
+            (rc = check_count(h->err, -5, "n_inactive", k, n_inactive[k], {0, l, "0..l"}))) return rc;
+    for (int64_t k = 0; k < batch; ++k)      // entries from 0: a 0 is padding to k_merit_total
+        if ((rc = check_list(h->err, -6, "active", k, active + k * t_max, t[k], {0, l, "0..l"})) ||
+            (rc = check_list(h->err, -6, "inactive", k, inactive + k * l, n_inactive[k], {0, l, "0..l"}))) return rc;
+    const int64_t nblk = sum_blocks(m);
+    if (!grid_fits(batch, nblk)) { h->err = "batch * partial-sum workgroups exceeds the grid"; return -2; }
     GN_HIP(hipSetDevice(h->device));
     MeritScratch D, H;
-    rc = place_dev(h, h->pen_scr, D, batch, t_max, l, nblk);
-    if (rc) return rc;
-    rc = place_pinned(h, h->h_pen, H, batch, t_max, l, (int64_t)0);
-    if (rc) return rc;
-    for (int64_t k = 0; k < batch; ++k) {
-        H.meta[k] = {(int)t[k], (int)n_inactive[k], (take && take[k] == 0) ? 0 : 1, 0};
-        int* da = H.act + k * t_max;
-        for (int64_t i = 0; i < t_max; ++i) da[i] = i < t[k] ? (int)active[k * t_max + i] : 0;
-        int* di = H.inact + k * l;
-        for (int64_t i = 0; i < l; ++i) di[i] = i < n_inactive[k] ? (int)inactive[k * l + i] : 0;
-    }
+    if ((rc = place_records(h, h->pen_scr, h->h_pen, D, H, nblk, batch, t_max, l, false))) return rc;
+    for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], (int)n_inactive[k], take_flag(take, k), 0};
+    pack_rows(H.act, active, t, batch, t_max);
+    pack_rows(H.inact, inactive, n_inactive, batch, l);
     hipStream_t st = h->stream;
-    // meta, act and inact are adjacent in both layouts (int-aligned records): one copy
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes(batch, t_max, l), hipMemcpyHostToDevice, st));
-    MeritArgs a{};
-    a.meta = D.meta; a.act = D.act; a.inact = D.inact; a.part = D.part; a.out = D.out;
-    a.count = (int)batch; a.m = (int)m; a.l = (int)l; a.t_max = (int)t_max; a.nblk = (int)nblk;
-    a.rx = drx; a.cx = dcx; a.w = dw;
-    if (nblk > 0) hipLaunchKernelGGL(k_merit_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_merit_total, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
+    launch_merit(st, {D.meta, D.act, D.inact, D.mpart, D.psi, (int)batch, (int)m, (int)l, (int)t_max, (int)nblk, drx, dcx, dw});
     GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, (size_t)batch * sizeof(double), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipMemcpyAsync(H.psi, D.psi, H.down_bytes, hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
-    std::copy(H.out, H.out + batch, psi);
+    std::copy(H.psi, H.psi + batch, psi);
     return 0;
     GN_CATCH(h)
 }

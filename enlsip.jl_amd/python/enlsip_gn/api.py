@@ -856,6 +856,16 @@ class GNSolver:
             raise ValueError(f"{name} must have {batch} entries")
         return a
 
+    @staticmethod
+    def _host_lists(batch: int, *lists):
+        """(name, x, stride) per ragged index list -> the host int64 pointer to its batch x stride entries, NULL when empty (a
+        pointer keeps its array alive)"""
+        arrs = [np.ascontiguousarray(np.asarray(x).astype(np.int64)) for _, x, _ in lists]
+        if any(a.size != batch * stride for a, (_, _, stride) in zip(arrs, lists)):
+            (name, _, stride), rest = lists[0], lists[1:]
+            raise ValueError(f"{name} must have {batch} x {stride} entries" + "".join(f", {n} {batch} x {st}" for n, _, st in rest))
+        return [_fptr(a) if a.size else None for a in arrs]
+
     def delete_constraints_batched_dev(self, batch, n, t_max, t, q, scaling, dlambda, ddiag_scale, dAt, ldat, strideAt, dcx,
                                        dgrad_res=0, dsaved=0, take=None) -> np.ndarray:
         """check_constraint_deletion per taken problem on the device buffers and, where it names a row, its removal in place
@@ -892,16 +902,14 @@ class GNSolver:
         None: 0) stay host arrays.  Returns (alpha_upp (batch,), index_alpha_upp (batch,) int64, sums (batch, 3) or None)."""
         ni = self._host_i64(n_inactive, batch, "n_inactive")
         idel = None if index_del is None else self._host_i64(index_del, batch, "index_del")
-        inact = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
-        if inact.size != batch * l:
-            raise ValueError(f"inactive must have {batch} x {l} entries")
+        inact, = self._host_lists(batch, ("inactive", inactive, l))
         if bool(dJp) != bool(drx):
             raise ValueError("dJp and drx go together")
         alpha = np.zeros(batch)
         index = np.zeros(batch, dtype=np.int64)
         sums = np.zeros((batch, 3)) if dJp else None
         self._chk(self._lib.enlsip_gn_linesearch_setup_batched_dev(
-            self._h, batch, m, n, l, _dptr(dp), _dptr(dA), lda, strideA, _dptr(dcx), _fptr(inact) if inact.size else None, _fptr(ni),
+            self._h, batch, m, n, l, _dptr(dp), _dptr(dA), lda, strideA, _dptr(dcx), inact, _fptr(ni),
             _fptr(idel), _dptr(dJp), _dptr(drx), _dptr(dAp), _fptr(alpha), _fptr(index), _fptr(sums)))
         return alpha, index, sums
 
@@ -918,9 +926,7 @@ class GNSolver:
         atwa; branch (batch,) int32); both 0 for a problem not taken."""
         t = self._host_i64(t, batch, "t")
         dimA = self._host_i64(dimA, batch, "dimA")
-        act = np.ascontiguousarray(np.asarray(active).astype(np.int64))
-        if act.size != batch * t_max:
-            raise ValueError(f"active must have {batch} x {t_max} entries")
+        act, = self._host_lists(batch, ("active", active, t_max))
         sm = np.ascontiguousarray(sums, dtype=np.float64)
         if sm.size != 3 * batch:
             raise ValueError(f"sums must have {batch} x 3 entries")
@@ -928,7 +934,7 @@ class GNSolver:
         scalars = np.zeros((batch, 3))
         branch = np.zeros(batch, dtype=np.int32)
         self._chk(self._lib.enlsip_gn_penalty_weights_batched_dev(
-            self._h, batch, l, t_max, _fptr(t), _fptr(dimA), _fptr(act) if act.size else None, _fptr(tk), int(norm_code),
+            self._h, batch, l, t_max, _fptr(t), _fptr(dimA), act, _fptr(tk), int(norm_code),
             int(bool(scaling)), _dptr(dw_old), _dptr(dactive_Ap), _dptr(ddiag_scale), _dptr(dcx), _dptr(dK), _fptr(sm), _dptr(dw),
             _fptr(scalars), _fptr(branch)))
         return scalars, branch
@@ -943,15 +949,11 @@ class GNSolver:
         Returns psi (batch,), 0 for a problem not taken."""
         t = self._host_i64(t, batch, "t")
         ni = self._host_i64(n_inactive, batch, "n_inactive")
-        act = np.ascontiguousarray(np.asarray(active).astype(np.int64))
-        inact = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
-        if act.size != batch * t_max or inact.size != batch * l:
-            raise ValueError(f"active must have {batch} x {t_max} entries, inactive {batch} x {l}")
+        act, inact = self._host_lists(batch, ("active", active, t_max), ("inactive", inactive, l))
         tk = self._pack_take(batch, take)
         psi = np.zeros(batch)
         self._chk(self._lib.enlsip_gn_merit_batched_dev(
-            self._h, batch, m, l, t_max, _fptr(t), _fptr(act) if act.size else None, _fptr(inact) if inact.size else None, _fptr(ni),
-            _fptr(tk), _dptr(drx), _dptr(dcx), _dptr(dw), _fptr(psi)))
+            self._h, batch, m, l, t_max, _fptr(t), act, inact, _fptr(ni), _fptr(tk), _dptr(drx), _dptr(dcx), _dptr(dw), _fptr(psi)))
         return psi
 
     # ---- the polynomial fit of the line search on device buffers (src/enlsip_functions.jl:1665-1689, :1986-1998, :1841-1862) ----------
@@ -964,10 +966,7 @@ class GNSolver:
         psi_new (batch,) = psi of (drx_new, dcx_new, dw) as merit_batched_dev returns it, or None); zeros for a problem not taken."""
         t = self._host_i64(t, batch, "t")
         ni = self._host_i64(n_inactive, batch, "n_inactive")
-        act = np.ascontiguousarray(np.asarray(active).astype(np.int64))
-        inact = np.ascontiguousarray(np.asarray(inactive).astype(np.int64))
-        if act.size != batch * t_max or inact.size != batch * l:
-            raise ValueError(f"active must have {batch} x {t_max} entries, inactive {batch} x {l}")
+        act, inact = self._host_lists(batch, ("active", active, t_max), ("inactive", inactive, l))
         sc = []
         for name, v in (("alpha_k", alpha_k), ("x_min", x_min), ("alpha_min", alpha_min), ("alpha_max", alpha_max)):
             v = np.ascontiguousarray(v, dtype=np.float64)
@@ -979,9 +978,9 @@ class GNSolver:
         arm = np.zeros(batch, dtype=np.int32)
         psi_new = np.zeros(batch) if psi else None
         self._chk(self._lib.enlsip_gn_linesearch_fit_batched_dev(
-            self._h, batch, m, l, t_max, _fptr(t), _fptr(act) if act.size else None, _fptr(inact) if inact.size else None, _fptr(ni),
-            _fptr(tk), _fptr(sc[0]), _fptr(sc[1]), _fptr(sc[2]), _fptr(sc[3]), _dptr(drx), _dptr(drx_new), _dptr(dJp), _dptr(dcx),
-            _dptr(dcx_new), _dptr(dAp), _dptr(dw), _fptr(sums), _fptr(out), _fptr(arm), _fptr(psi_new)))
+            self._h, batch, m, l, t_max, _fptr(t), act, inact, _fptr(ni), _fptr(tk), _fptr(sc[0]), _fptr(sc[1]), _fptr(sc[2]),
+            _fptr(sc[3]), _dptr(drx), _dptr(drx_new), _dptr(dJp), _dptr(dcx), _dptr(dcx_new), _dptr(dAp), _dptr(dw), _fptr(sums),
+            _fptr(out), _fptr(arm), _fptr(psi_new)))
         return sums, out, arm, psi_new
 
     def newton_direction(self, Gamma: np.ndarray, prob: int = 0):

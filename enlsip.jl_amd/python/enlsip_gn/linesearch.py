@@ -89,6 +89,14 @@ def pack_active(Ws, t_max: int):
     return active, t
 
 
+def pack_working_sets(Ws, t_max=None):
+    """The host records of a batch of working sets: ``(B, l, t_max, active, t, inactive, n_inactive)``; t_max None: the largest t."""
+    if t_max is None:
+        t_max = max([W.t for W in Ws] + [0])
+    inactive, n_inactive, _ = pack_inactive(Ws)
+    return (len(Ws), Ws[0].l, t_max) + pack_active(Ws, t_max) + (inactive, n_inactive)
+
+
 @dataclass
 class PenaltyWeights:
     w: object                           # device (B, l): the new weights; w_old where the problem is not taken     :2238 / :2286
@@ -105,10 +113,7 @@ def penalty_weights_batched_dev(solver: GNSolver, Ws, its, setup: LinesearchSetu
     dw_old (B, l) the previous weights, dK (B, 4, l) the weight histories (updated in place), dcx (B, l) ALL constraint values,
     ddiag_scale (B, t_max) (None without scaling).  its[k].dimA is the dimension the direction was computed with; problems with
     its[k].code == 2 are not taken (:2284-2290): their w is w_old and their scalars are 0.  Only the scalars come down."""
-    B = len(Ws)
-    l = Ws[0].l
-    t_max = setup.active_Ap.shape[-1]
-    active, t = pack_active(Ws, t_max)
+    B, l, t_max, active, t, _, _ = pack_working_sets(Ws, setup.active_Ap.shape[-1])
     dimA = np.array([it.dimA for it in its], dtype=np.int64)
     take = np.array([0 if it.code == 2 else 1 for it in its], dtype=np.int64)
     sums = np.stack([setup.JpJp, setup.Jprx, setup.rxrx], axis=1)
@@ -127,11 +132,7 @@ def penalty_weights_batched_dev(solver: GNSolver, Ws, its, setup: LinesearchSetu
 def merit_batched_dev(solver: GNSolver, Ws, drx, dcx, dw, take=None) -> np.ndarray:
     """``psi`` (:1307-1340) of one trial point per problem: drx (B, m) and dcx (B, l) the residuals and ALL constraint values at the
     trial points, dw (B, l) the weights (device tensors).  Returns psi (B,)."""
-    B = len(Ws)
-    l = Ws[0].l
-    t_max = max([W.t for W in Ws] + [0])
-    active, t = pack_active(Ws, t_max)
-    inactive, n_inactive, _ = pack_inactive(Ws)
+    B, l, t_max, active, t, inactive, n_inactive = pack_working_sets(Ws)
     ptr = lambda x: x.data_ptr() if x.numel() else 0
     return solver.merit_batched_dev(B, drx.shape[-1], l, t_max, t, active, inactive, n_inactive, ptr(drx), ptr(dcx), ptr(dw), take=take)
 
@@ -151,11 +152,7 @@ def linesearch_fit_batched_dev(solver: GNSolver, Ws, setup: LinesearchSetup, drx
     (B, m) the residuals at x and at the trial point, dcx, dcx_new (B, l) ALL constraint values there, dw (B, l) the weights (device
     tensors); setup.Jp and setup.Ap are the UNSCALED products (nothing is written).  alpha_k, x_min, alpha_min, alpha_max: (B,)
     host arrays.  With psi the merit function of the trial point comes back from the same call."""
-    B = len(Ws)
-    l = Ws[0].l
-    t_max = max([W.t for W in Ws] + [0])
-    active, t = pack_active(Ws, t_max)
-    inactive, n_inactive, _ = pack_inactive(Ws)
+    B, l, t_max, active, t, inactive, n_inactive = pack_working_sets(Ws)
     # contiguous views, kept alive until the call has returned
     bufs = [x if x.is_contiguous() else x.contiguous() for x in (drx, drx_new, setup.Jp, dcx, dcx_new, setup.Ap, dw)]
     sums, out, arm, psi_new = solver.linesearch_fit_batched_dev(

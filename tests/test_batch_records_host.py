@@ -1,0 +1,59 @@
+"""The host side of the batched calls on the caller's device buffers (csrc/gn_batch_records.hpp) on the CPU: the record structs, the
+argument checks, the packing and the scratch layouts.  tests/batch_records_check.cpp, a stand-alone program built with
+-fsanitize=address,undefined, asserts them on buffers of exactly their used size; nothing is loaded into Python.  Where a GPU is
+present the program is built without the sanitizers (they run on CPU-only machines) and the same assertions hold.
+
+Each of these mutations of the header fails the named assertion: the upper bound of check_list turned from < into <=
+(list_check_accepts_hi), the zero padding of pack_rows dropped (pack_zero_pads), two fields of MeritMeta swapped
+(record_MeritMeta)."""
+import os
+import shutil
+import subprocess
+from pathlib import Path
+
+import pytest
+
+ROOT = Path(__file__).resolve().parents[1]
+CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+HEADER = ROOT / "enlsip.jl_amd" / "csrc" / "gn_batch_records.hpp"
+
+GROUPS = (["record_" + r for r in ("DeletionMeta", "LsMeta", "LsOut", "PenaltyMeta", "PenaltyOut", "MeritMeta", "constants")] +
+          ["shape_checks", "count_check", "list_check_reads_only_the_used_entries", "list_check_accepts_hi", "list_check_names_k_and_i",
+           "list_check_lo_is_an_argument", "list_check_null_list_of_stride_0", "pack_copies_the_used_part", "pack_zero_pads",
+           "pack_stride_0", "take_flag", "sum_blocks", "grid_fits"])
+LAYOUTS = ["layout_" + n for n in ("deletion", "linesearch", "penalty", "merit", "fit", "merit_prefix_is_the_fit_prefix")]
+
+
+@pytest.fixture(scope="module")
+def clang():
+    c = CLANG if os.path.exists(CLANG) else shutil.which("clang++")
+    if not c:
+        pytest.skip("clang++ not found")
+    return c
+
+
+@pytest.fixture(scope="module")
+def lines(clang, tmp_path_factory):
+    import torch
+    exe = tmp_path_factory.mktemp("batch_records") / "batch_records_check"
+    san = [] if torch.cuda.is_available() else ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    subprocess.run([clang, "-std=c++17", "-O1", "-g", *san, str(ROOT / "tests" / "batch_records_check.cpp"), "-o", str(exe)],
+                   check=True, capture_output=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env=env)
+    assert "AddressSanitizer" not in out.stderr and "runtime error" not in out.stderr, out.stderr
+    assert out.returncode == 0, out.stdout[-4000:] + out.stderr
+    return out.stdout.splitlines()
+
+
+def test_the_header_compiles_alone_without_hip(clang):
+    subprocess.run([clang, "-std=c++17", "-Wall", "-Werror", "-Wno-pragma-once-outside-header", "-fsyntax-only", "-x", "c++", str(HEADER)],
+                   check=True, capture_output=True, timeout=300)
+
+
+def test_every_named_assertion_ran_and_held(lines):
+    assert [ln for ln in lines if ln.startswith("FAIL")] == []
+    ok = [ln.split()[1] for ln in lines if ln.startswith("ok ")]
+    assert ok[:len(GROUPS)] == GROUPS
+    assert ok[len(GROUPS):] == LAYOUTS * 4          # the four shapes (batch, t_max, l, nblk) of the program
+    assert lines[-1] == "0 failures"

@@ -296,6 +296,8 @@ def test_argument_errors_leave_the_buffers(solver):
         assert got == want and msg, (i, got, want, msg)
         seen.add(msg)
     assert len(seen) >= 10                         # the messages differ by condition
+    # two faults at once: the checks run per problem, so the lower k wins
+    assert delete(t=bad(t, 1, 5), q=bad(q, 0, 5)) == -6 and b"q[0]" in L.enlsip_gn_last_error(h)
     assert np.all(s == -9)
     same_images(buf.download(), before)
     assert restore(sb=np.zeros(B, dtype=np.int64), saved=0) == 0      # nothing comes back: no record is needed

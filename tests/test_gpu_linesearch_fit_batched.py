@@ -245,6 +245,9 @@ def test_argument_errors_write_nothing(solver):
               (-5, dict(ni=edited(b["n_inactive"], 0, -1)), "[0]"), (-5, dict(ni=edited(b["n_inactive"], 3, l - 2)), "[3]"),
               (-6, dict(active=edited(b["active"], (2, 1), l + 1)), "[2]"), (-6, dict(active=edited(b["active"], (0, 0), 0)), "[0]"),
               (-6, dict(inactive=edited(b["inactive"], (1, 0), -1)), "[1]"), (-6, dict(inactive=edited(b["inactive"], (3, 2), 0)), "[3]")]
+    # two faults at once: t[k] and n_inactive[k] are checked problem by problem, then active and inactive row by row
+    cases += [(-5, dict(t=edited(b["t"], 1, t_max + 1), ni=edited(b["n_inactive"], 0, -1)), "n_inactive[0]"),
+              (-6, dict(active=edited(b["active"], (2, 1), l + 1), inactive=edited(b["inactive"], (1, 0), -1)), "inactive[1]")]
     for want, kw, names in cases:
         got = call(**kw)
         assert got == want, (want, got, list(kw))

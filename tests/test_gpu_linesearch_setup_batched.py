@@ -272,6 +272,10 @@ def test_argument_errors_leave_everything_untouched(solver):
         (-6, dict(index_del=edited("index_del", 3, None, l + 1)), "[3]"), (-6, dict(index_del=edited("index_del", 0, None, -1)), "[0]"),
         (-9, dict(lda=l - 1), None), (-10, dict(strideA=c.lda * n - 1), None),
     ]
+    # two faults at once: every n_inactive[k] is checked before any index_del[k] or list, the lists before the leading dimension
+    kq = int(np.flatnonzero(b["n_inactive"] > 0)[0])
+    cases.append((-5, dict(n_inactive=edited("n_inactive", 2, None, l + 1), index_del=edited("index_del", 2, None, l + 1)), "n_inactive[2]"))
+    cases.append((-6, dict(inactive=edited("inactive", kq, 0, -1), lda=l - 1), f"inactive[{kq}][0]"))
     if ni3:
         cases.append((-6, dict(inactive=edited("inactive", 3, ni3 - 1, l + 1)), "[3]"))
         cases.append((-6, dict(inactive=edited("inactive", 3, 0, -1)), "[3]"))

@@ -302,6 +302,9 @@ def test_argument_errors_write_nothing(solver, form1):
         (-5, dict(t=edited(c.t, 2, t_max + 1)), "[2]"), (-5, dict(t=edited(c.t, 1, -1)), "[1]"),
         (-6, dict(dimA=edited(c.dimA, 0, int(c.t[0]) + 1)), "[0]"), (-6, dict(dimA=edited(c.dimA, 3, -1)), "[3]"),
         (-6, dict(active=edited(c.active, (k3, 0), 0)), f"[{k3}]"), (-6, dict(active=edited(c.active, (k3, int(c.t[k3]) - 1), l + 1)), f"[{k3}]"),
+        # two faults at once: every t[k] is checked before any dimA[k], and dimA[k] before the list of row k and of the rows behind it
+        (-5, dict(t=edited(c.t, 2, t_max + 1), dimA=edited(c.dimA, 0, -1)), "t[2]"),
+        (-6, dict(dimA=edited(c.dimA, 0, -1), active=edited(c.active, (k3, 0), 0)), "dimA[0]"),
     ]
     for want, kw, names in cases:
         got = call(**kw)
@@ -555,6 +558,10 @@ def test_merit_argument_errors(solver):
              (-6, dict(active=edited(b["active"], (1, 1), l + 1))), (-6, dict(inactive=edited(b["inactive"], (2, 0), -1)))]
     for want, kw in cases:
         assert call(**kw) == want, (want, list(kw))
+    # two faults at once: t[k] and n_inactive[k] are checked problem by problem, then active and inactive row by row
+    for want, kw, name in [(-5, dict(t=edited(b["t"], 1, t_max + 1), n_inactive=edited(b["n_inactive"], 0, -1)), "n_inactive[0]"),
+                           (-6, dict(active=edited(b["active"], (2, 1), l + 1), inactive=edited(b["inactive"], (1, 0), -1)), "inactive[1]")]:
+        assert call(**kw) == want and name in L.enlsip_gn_last_error(solver._h).decode(), (want, name)
     assert np.all(psi == SENT)
     assert call(inactive=edited(b["inactive"], (0, 3), l + 7)) == 0      # past n_inactive: not read
     assert np.all(psi != SENT)
