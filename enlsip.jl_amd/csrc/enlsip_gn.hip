@@ -33,6 +33,7 @@
 #include "gn_kernels_linesearch_batched.hpp"
 #include "gn_kernels_penalty_batched.hpp"
 #include "gn_kernels_linesearch_fit_batched.hpp"
+#include "gn_kernels_addition_batched.hpp"
 #include "gn_linesearch_fit.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_newton_batched.hpp"
@@ -1535,9 +1536,10 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->del_scr.p) (void)hipFree(h->del_scr.p);
     if (h->ls_scr.p) (void)hipFree(h->ls_scr.p);
     if (h->pen_scr.p) (void)hipFree(h->pen_scr.p);
+    if (h->add_scr.p) (void)hipFree(h->add_scr.p);
     for (hipEvent_t e : h->nwb_ev)
         if (e) (void)hipEventDestroy(e);
-    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_pen, &h->h_nwflag, &h->h_lagflag})
+    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_pen, &h->h_add, &h->h_nwflag, &h->h_lagflag})
         if (b->p) (void)hipHostFree(b->p);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);
@@ -2468,5 +2470,6 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_linesearch_batched.inc"
 #include "gn_penalty_batched.inc"
 #include "gn_linesearch_fit_batched.inc"
+#include "gn_addition_batched.inc"
 #include "gn_newton.inc"
 #include "gn_newton_batched.inc"

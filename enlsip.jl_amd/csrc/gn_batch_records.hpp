@@ -1,5 +1,5 @@
 // The batched calls on the caller's device buffers (gn_deletion_batched.inc, gn_linesearch_batched.inc, gn_penalty_batched.inc,
-// gn_linesearch_fit_batched.inc): the records they upload and download, the checks and the packing of their host arguments, and
+// gn_linesearch_fit_batched.inc, gn_addition_batched.inc): the records they upload and download, the checks and the packing of their host arguments, and
 // their scratch layouts.  Host-only, nothing of HIP: tests/batch_records_check.cpp runs all of it on the CPU.  The
 // kernel headers include it for the records.
 #pragma once
@@ -45,6 +45,18 @@ struct PenaltyOut {
 struct MeritMeta {
     int t, n_inactive;
     int take;
+    int pad;
+};
+
+struct AdditionMeta {
+    int t, q;
+    int take;               // 0 leaves the problem alone, 1 walk and rebuild, 2 rebuild only
+    int index_alpha_upp;    // the constraint the delta arm of :623 looks at, 0 for none
+};
+
+struct AdditionOut {
+    int t;                  // the count the walk left (take 2: as given)
+    int added, status;      // of the walk (gn_violated_constraints.hpp), 0 without one
     int pad;
 };
 
@@ -98,6 +110,8 @@ inline void pack_rows(int* dst, const int64_t* src, const int64_t* cnt, int64_t 
 }
 
 inline int take_flag(const int64_t* take, int64_t k) { return (take && take[k] == 0) ? 0 : 1; }     // no array: every problem
+// the three kinds of the addition call: 0 nothing, 2 rebuild only, anything else (and no array) walk and rebuild
+inline int addition_take(const int64_t* take, int64_t k) { return !take_flag(take, k) ? 0 : (take && take[k] == 2) ? 2 : 1; }
 
 // workgroups per problem of an ordered partial sum over m rows, and whether batch * max(per_problem, 1) workgroups fit a grid
 inline int64_t sum_blocks(int64_t m) { return std::min<int64_t>(LS_MAX_NBLK, (m + LS_SUM_ROWS - 1) / LS_SUM_ROWS); }
@@ -130,6 +144,47 @@ struct RecordScratch {
 using DeletionScratch = RecordScratch<DeletionMeta, int>;
 using LinesearchScratch = RecordScratch<LsMeta, LsOut>;
 using PenaltyScratch = RecordScratch<PenaltyMeta, PenaltyOut>;
+// The addition call: list = [active, batch rows of l | inactive, batch rows of l] (stride 2 l), no partial sums.  The kernels edit
+// the lists where they are, so what comes down in ONE copy is [list | out]: the two arrays are neighbours on both sides.
+using AdditionScratch = RecordScratch<AdditionMeta, AdditionOut>;
+inline size_t addition_down_bytes(const AdditionScratch& s, int64_t batch) {
+    return (size_t)((const char*)(s.out + batch) - (const char*)s.list);
+}
+
+// ---- the addition call's checks of its host arguments (the codes of include/enlsip_gn.h); the pointers only as "is it there" -------
+struct AdditionShape { int64_t batch, n, l, t_max, lda, strideA, ldat, strideAt; };
+inline int check_addition(std::string& err, const AdditionShape& s, const int64_t* q, const int64_t* t, const int64_t* active,
+                          const int64_t* inactive, const int64_t* index_alpha_upp, const int64_t* take, bool host_outputs,
+                          bool device_inputs, bool device_outputs) {
+    int rc;
+    if ((rc = check_batch(err, s.batch))) return rc;
+    if (s.n < 1 || s.n > 0x3fffffff) return fail(err, -3, "n must be at least 1");
+    if (s.l < 0 || s.l > BATCH_MAX_T) return fail(err, -3, "l must be in 0..1024 in this build");
+    if ((rc = check_t_max(err, s.t_max))) return rc;
+    if (s.t_max > s.l) return fail(err, -3, "t_max > l");
+    if (!q || !t || !host_outputs) return fail(err, -4, "q, t, added and status are host arrays of batch entries");
+    if (s.l > 0 && (!active || !inactive)) return fail(err, -4, "active and inactive are host arrays of batch x l entries");
+    if (s.t_max > 0 && (!device_inputs || !device_outputs))
+        return fail(err, -4, "dA, dcx_all, dAt, dcx and ddiag_scale are required when t_max > 0");
+    const int64_t bnd = std::min(s.l, s.n);
+    for (int64_t k = 0; k < s.batch; ++k) {      // per problem: the lower k wins; nothing of a problem that is not taken is read
+        const int tk = addition_take(take, k);
+        if (!tk) continue;
+        if ((rc = check_count(err, -5, "t", k, t[k], {0, s.t_max, "0..t_max"}))) return rc;
+        if (tk == 1 && std::max(t[k], bnd) > s.t_max)
+            return fail(err, -5, "t_max < max(t[" + std::to_string(k) + "], min(l, n)): the walk of problem " + std::to_string(k) +
+                                     " could outgrow its slot");
+        if ((rc = check_count(err, -6, "q", k, q[k], {0, t[k], "0..t[k]"})) ||
+            (rc = check_list(err, -7, "active", k, active + k * s.l, t[k], {0, s.l, "0..l"})) ||
+            (rc = check_list(err, -7, "inactive", k, inactive + k * s.l, s.l - t[k], {0, s.l, "0..l"})) ||
+            (index_alpha_upp && (rc = check_count(err, -7, "index_alpha_upp", k, index_alpha_upp[k], {0, s.l, "0..l"})))) return rc;
+    }
+    if (s.lda < s.l) return fail(err, -9, "lda < l");
+    if (s.ldat < s.n) return fail(err, -9, "ldat < n");
+    if (s.strideA < s.lda * s.n) return fail(err, -10, "strideA < lda * n");
+    if (s.strideAt < s.ldat * s.t_max) return fail(err, -10, "strideAt < ldat * t_max");
+    return 0;
+}
 
 // The merit call and, with fit, the polynomial fit: up [meta | act | inact | alpha], down [sums | psi] (a fit without psi_new
 // leaves the last psi_bytes of it where they are); the partial sums of the fit (6 * nblk per problem) and of the merit kernels

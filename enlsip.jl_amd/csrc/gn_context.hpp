@@ -257,6 +257,11 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf pen_scr;
     gn::PinnedBuf h_pen;
     int penalty_form = -1;
+    // batched working-set additions and rebuild of the active constraints (gn_addition_batched.inc): the records and both index
+    // lists of one call on the device and in pinned memory, and the form of the last call; nothing resident
+    gn::DevBuf add_scr;
+    gn::PinnedBuf h_add;
+    int addition_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

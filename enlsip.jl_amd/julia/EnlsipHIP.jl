@@ -725,6 +725,70 @@ function deletion_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""    evaluate_violated_constraints_hip(l, n, q, t, active, inactive, cx, index_α_upp) -> (t, added, status)
+
+`evaluate_violated_constraints` (src/enlsip_functions.jl:608-650) on host data through the library's host entry point (no handle,
+no GPU): the routine the batched call below runs on the device.  `active` and `inactive` hold `l` entries each (1-based, the
+first `t` / `l - t` used, 0 behind) and are edited in place.  `status == 1`: the reference would repeat a swap pass for ever; the
+lists are left in that unchanged state.  `status == 2`: the pass cap `(l+1)^2` (never observed)."""
+function evaluate_violated_constraints_hip(l::Integer, n::Integer, q::Integer, t::Integer, active::Vector{Int64},
+                                           inactive::Vector{Int64}, cx::Vector{Float64}, index_α_upp::Integer)
+    (length(active) == l && length(inactive) == l && length(cx) == l) || error("active, inactive and cx need l entries")
+    tt = Ref{Int64}(t); added = Ref{Int64}(0); status = Ref{Int64}(0)
+    rc = GC.@preserve active inactive cx ccall((:enlsip_gn_evaluate_violated_constraints, LIB), Cint,
+        (Int64, Int64, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ref{Int64}, Ref{Int64}),
+        l, n, q, tt, active, inactive, cx, index_α_upp, added, status)
+    rc == 0 || error("enlsip_gn_evaluate_violated_constraints returned $rc")
+    return Int(tt[]), added[] != 0, Int(status[])
+end
+
+"""    gather_active_constraints_hip(active, t, A, cx, scaling) -> (At, cx_active, diag_scale)
+
+`active_C.A = A[active, :]`, `active_C.cx = cx[active]` (src/enlsip_functions.jl:2854-2855) and `evaluate_scaling!`
+(src/structures.jl:160-178) on host data through the library's host entry point: `At` is the `n x t` matrix `A'` of the solve."""
+function gather_active_constraints_hip(active::Vector{Int64}, t::Integer, A::Matrix{Float64}, cx::Vector{Float64}, scaling::Bool)
+    l, n = size(A)
+    (length(cx) == l && length(active) >= t) || error("cx needs l entries and active t")
+    At = zeros(n, t); ca = zeros(t); ds = zeros(t)
+    rc = GC.@preserve active A cx At ca ds ccall((:enlsip_gn_gather_active_constraints, LIB), Cint,
+        (Int64, Int64, Int64, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64}, Cint, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}),
+        l, n, t, active, A, max(l, 1), cx, Cint(scaling), At, max(n, 1), ca, ds)
+    rc == 0 || error("enlsip_gn_gather_active_constraints returned $rc")
+    return At, ca, ds
+end
+
+"""    add_constraints_batched_dev_hip(h, B, n, l, t_max, q, t, active, inactive, index_α_upp, take, scaling, dA, lda, strideA,
+                                    dcx_all, dAt, ldat, strideAt, dcx, ddiag_scale) -> (added, status)
+
+The walk above for every problem with `take[k] == 1` on the DEVICE buffer `dcx_all`, then (also for `take[k] == 2`) the padded
+slot of the ragged solve gathered from `dA` / `dcx_all` into `dAt`, `dcx`, `ddiag_scale`.  `q`, `t`, `index_α_upp`, `take`
+(`nothing`: 1 everywhere) are host vectors of `B` entries, `active` / `inactive` host matrices `l x B` (one column per problem);
+`t` and the lists of the walked problems are updated in place."""
+function add_constraints_batched_dev_hip(h::Handle, B::Integer, n::Integer, l::Integer, t_max::Integer, q::Vector{Int64},
+                                         t::Vector{Int64}, active::Matrix{Int64}, inactive::Matrix{Int64},
+                                         index_α_upp::Vector{Int64}, take::Union{Nothing,Vector{Int64}}, scaling::Bool,
+                                         dA::Ptr{Float64}, lda::Integer, strideA::Integer, dcx_all::Ptr{Float64}, dAt::Ptr{Float64},
+                                         ldat::Integer, strideAt::Integer, dcx::Ptr{Float64}, ddiag_scale::Ptr{Float64})
+    (length(q) == B && length(t) == B && length(index_α_upp) == B && (take === nothing || length(take) == B)) ||
+        error("q, t, index_α_upp and take need B entries")
+    (size(active) == (l, B) && size(inactive) == (l, B)) || error("active and inactive are l x B")
+    added = zeros(Int64, B); status = zeros(Int64, B)
+    tk = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    GC.@preserve q t active inactive index_α_upp take added status check(h, ccall((:enlsip_gn_add_constraints_batched_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Cint,
+         Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+        h.ptr, B, n, l, t_max, q, t, active, inactive, index_α_upp, tk, Cint(scaling), dA, lda, strideA, dcx_all, dAt, ldat,
+        strideAt, dcx, ddiag_scale, added, status))
+    return added, status
+end
+
+"""    addition_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last add_constraints call on `h`"""
+function addition_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_addition_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    upper_bound_steplength_hip(inactive, n_inactive, index_del, cx, Ap) -> (α_upp, index_α_upp)
 
 `upper_bound_steplength` (src/enlsip_functions.jl:2149-2178) on host data with `Ap = A * p` already formed, through the library's

@@ -160,6 +160,13 @@ PROTOTYPES = {
     "enlsip_gn_minrn": (C.c_int, [C.c_double] * 9 + [_dp, _dp]),
     "enlsip_gn_check_reduction": (C.c_int, [C.c_double] * 5 + [C.POINTER(C.c_int)]),
     "enlsip_gn_linesearch_fit_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64] + [C.c_void_p] * 20),
+    "enlsip_gn_evaluate_violated_constraints": (C.c_int, [_i64, _i64, _i64, _ip, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _ip, _ip]),
+    "enlsip_gn_gather_active_constraints": (C.c_int, [_i64, _i64, _i64, C.c_void_p, C.c_void_p, _i64, C.c_void_p, C.c_int,
+                                                      C.c_void_p, _i64, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_add_constraints_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64, C.c_void_p,
+                                                        C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_addition_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

@@ -81,6 +81,52 @@ def check_constraint_deletion(q: int, lam, scaling: bool, diag_scale, grad_res: 
     return int(s.value)
 
 
+def evaluate_violated_constraints(l: int, n: int, q: int, t: int, active, inactive, cx, index_alpha_upp: int):
+    """evaluate_violated_constraints (src/enlsip_functions.jl:608-650) on host data, through the library's host entry point (no
+    GPU): the routine the batched kernels run.  active / inactive: 1-based, the first t / l - t entries used; shorter arrays
+    (the reference's inactive has l - q entries) are zero-padded to l.  Returns (t, active (l,), inactive (l,), added, status);
+    status 1: the reference would repeat a swap pass for ever, the lists are in that unchanged state; 2: the pass cap."""
+    def padded(x, name):
+        a = np.asarray(x).astype(np.int64).ravel()
+        if a.size > l:
+            raise ValueError(f"{name} has more than l entries")
+        return np.ascontiguousarray(np.concatenate([a, np.zeros(l - a.size, dtype=np.int64)]))
+    av, iv = padded(active, "active"), padded(inactive, "inactive")
+    cv = np.ascontiguousarray(cx, dtype=np.float64)
+    if cv.size != l:
+        raise ValueError("cx needs l entries")
+    tt, added, status = C.c_int64(int(t)), C.c_int64(0), C.c_int64(0)
+    p = lambda a: _fptr(a) if a.size else None
+    rc = L.load().enlsip_gn_evaluate_violated_constraints(int(l), int(n), int(q), C.byref(tt), p(av), p(iv), p(cv),
+                                                          int(index_alpha_upp), C.byref(added), C.byref(status))
+    if rc:
+        raise GNError(f"enlsip_gn_evaluate_violated_constraints returned {rc}")
+    return int(tt.value), av, iv, bool(added.value), int(status.value)
+
+
+def gather_active_constraints(active, t: int, A, cx, scaling: bool, ldat: Optional[int] = None, out=None):
+    """active_C.cx / active_C.A of src/enlsip_functions.jl:2854-2855 with evaluate_scaling! (src/structures.jl:160-178) on host
+    data, through the library's host entry point (no GPU): the routine the batched kernels run.  A: (l, n); active: 1-based, the
+    first t entries count.  Returns (At (t, ldat): row c is column c of the n x t column-major A' block, cx_active (t,),
+    diag_scale (t,)); `out` = (At, cx_active, diag_scale) is written in place (only rows 0..n-1 of a column)."""
+    Af = np.asfortranarray(A, dtype=np.float64)
+    l, n = Af.shape
+    cv = np.ascontiguousarray(cx, dtype=np.float64)
+    av = np.ascontiguousarray(np.asarray(active).astype(np.int64))
+    if cv.size != l or av.size < t:
+        raise ValueError("cx needs l entries and active t")
+    ldat = n if ldat is None else int(ldat)
+    At, ca, ds = out if out is not None else (np.zeros((t, ldat)), np.zeros(t), np.zeros(t))
+    if not (At.flags.c_contiguous and At.dtype == np.float64 and At.shape == (t, ldat)) or ca.size < t or ds.size < t:
+        raise ValueError("out must be (At (t, ldat) C-contiguous float64, cx_active (t,), diag_scale (t,))")
+    p = lambda a: _fptr(a) if a.size else None
+    rc = L.load().enlsip_gn_gather_active_constraints(l, n, int(t), p(av), p(Af), max(l, 1), p(cv), int(bool(scaling)), p(At), ldat,
+                                                      p(ca), p(ds))
+    if rc:
+        raise GNError(f"enlsip_gn_gather_active_constraints returned {rc}")
+    return At, ca, ds
+
+
 def upper_bound_steplength(inactive, n_inactive: int, index_del: int, cx, Ap):
     """upper_bound_steplength (src/enlsip_functions.jl:2149-2178) on host data with Ap = A * p already formed, through the
     library's host entry point (no GPU): (alpha_upp, index_alpha_upp).  inactive: 1-based rows, 0 padding, of which the first
@@ -893,6 +939,35 @@ class GNSolver:
     def deletion_form(self) -> int:
         """Kernel form of the last delete / restore call: 0 general, 1 one wave per problem, -1 none yet."""
         return self._form("enlsip_gn_get_deletion_form")
+
+    # ---- the working-set additions and the rebuild of the active constraints on device buffers (:608-650, :2854-2855) --------------
+    def add_constraints_batched_dev(self, batch, n, l, t_max, q, t, active, inactive, index_alpha_upp, scaling, dA, lda, strideA,
+                                    dcx_all, dAt, ldat, strideAt, dcx, ddiag_scale, take=None):
+        """evaluate_violated_constraints per walked problem on dcx_all (l per problem), then the padded slot of the ragged solve
+        (dAt, dcx, ddiag_scale) gathered from dA / dcx_all by the active lists, scaled when `scaling`.  take (None: 1 everywhere):
+        0 leave the problem alone, 1 walk and rebuild, 2 rebuild only.  q, t (batch,), active, inactive (batch, l; 1-based, 0
+        padded) and index_alpha_upp (batch,; None: 0) are host arrays and are not modified.  Returns (t, active, inactive, added,
+        status) as new arrays: int64 (batch,), (batch, l), (batch, l), (batch,), (batch,); status 1: the reference would repeat a
+        swap pass for ever and the lists are in that unchanged state."""
+        q = self._host_i64(q, batch, "q")
+        t = self._host_i64(t, batch, "t").copy()
+        act = np.ascontiguousarray(np.asarray(active).astype(np.int64)).copy()
+        ina = np.ascontiguousarray(np.asarray(inactive).astype(np.int64)).copy()
+        if act.size != batch * l or ina.size != batch * l:
+            raise ValueError(f"active and inactive must have {batch} x {l} entries")
+        iau = None if index_alpha_upp is None else self._host_i64(index_alpha_upp, batch, "index_alpha_upp")
+        tk = None if take is None else self._host_i64(take, batch, "take")
+        added = np.zeros(batch, dtype=np.int64)
+        status = np.zeros(batch, dtype=np.int64)
+        self._chk(self._lib.enlsip_gn_add_constraints_batched_dev(
+            self._h, batch, n, l, t_max, _fptr(q), _fptr(t), _fptr(act) if act.size else None, _fptr(ina) if ina.size else None,
+            _fptr(iau), _fptr(tk), int(bool(scaling)), _dptr(dA), lda, strideA, _dptr(dcx_all), _dptr(dAt), ldat, strideAt,
+            _dptr(dcx), _dptr(ddiag_scale), _fptr(added), _fptr(status)))
+        return t, act.reshape(batch, l), ina.reshape(batch, l), added, status
+
+    def addition_form(self) -> int:
+        """Kernel form of the last add_constraints_batched_dev: 0 general, 1 one wave per problem, -1 none yet."""
+        return self._form("enlsip_gn_get_addition_form")
 
     # ---- the line-search set-up on device buffers (src/enlsip_functions.jl:2149-2178, :2226-2229, :1561-1584, :2269) ---------------
     def linesearch_setup_batched_dev(self, batch, m, n, l, dp, dA, lda, strideA, dcx, inactive, n_inactive, dAp, index_del=None,

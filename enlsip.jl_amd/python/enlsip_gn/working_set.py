@@ -362,7 +362,7 @@ def update_working_set_batched(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p
 
 
 # ---- the same with the batch resident in device buffers: nothing but s and info crosses PCIe between the stages -------------------
-def update_working_set_batched_dev(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p_gns, its, eps_rank: float):
+def update_working_set_batched_dev(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, Js, p_gns, its, eps_rank: float, built=None):
     """``update_working_set_batched`` with J, rx, A', cx, diag_scale, lambda, grad_res and p in device buffers (torch tensors) and
     only ``_dev`` entry points: the deletion test and the removal of a row (:574-603, :708-719, :748-756, :776-785) and the undo
     (:731-739) are ``delete_constraints_batched_dev`` / ``restore_constraints_batched_dev`` on those buffers.  Per stage only s and
@@ -371,15 +371,25 @@ def update_working_set_batched_dev(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, J
     follow by the same index.  Same arguments, mutations and return value as ``update_working_set_batched``; the undo puts back the
     row that was removed (the reference recomputes it from ``A`` and ``diag_scale``, :739: the same row), so ``A`` is not read.
     A batch may mix problems with and without row scaling: the test and the edit then run once per kind, each over its own
-    problems (``take``), on a diag_scale buffer of that kind."""
+    problems (``take``), on a diag_scale buffer of that kind.
+    ``built``: None, or ``(t_max, dAt, dcx, dds, ddsn)``, the slot ``add_constraints_batched_dev`` (below) left on the device: torch
+    float64 tensors (B, n * t_max), (B, t_max), (B, t_max), (B, t_max) with ldat = n (dds: the scaled problems' diag_scale, ones
+    elsewhere; ddsn: the row norms of the problems without row scaling).  The call then starts from these buffers, edits them in
+    place, and skips ``pack_ragged`` and the upload of A', cx and diag_scale; ``Cs`` must still hold the same rows on the host."""
     import torch
     B = len(Ws)
     m, n = Js[0].shape
     scal = np.array([1 if C.scaling else 0 for C in Cs], dtype=np.int64)
-    Ak = [np.asarray(C.A, dtype=np.float64).reshape(-1, n) for C in Cs]
-    At_h, cx_h, t = GNSolver.pack_ragged(Ak, [C.cx for C in Cs], n=n)
-    t = np.ascontiguousarray(t, dtype=np.int64)
-    t_max = At_h.shape[1]
+    if built is None:
+        Ak = [np.asarray(C.A, dtype=np.float64).reshape(-1, n) for C in Cs]
+        At_h, cx_h, t = GNSolver.pack_ragged(Ak, [C.cx for C in Cs], n=n)
+        t = np.ascontiguousarray(t, dtype=np.int64)
+        t_max = At_h.shape[1]
+    else:
+        t = np.array([W.t for W in Ws], dtype=np.int64)
+        t_max = int(built[0])
+        if t_max < 1 or t.max() > t_max:
+            raise ValueError("built: t_max must be at least 1 and no working set may exceed it")
     tm1 = max(t_max, 1)
     # diag_scale per kind: the scaled problems' (ones elsewhere: what the estimates' back-transform takes, as scales() of the host
     # flow), and that of the problems without row scaling, which only the deletion test reads (:592)
@@ -393,8 +403,11 @@ def update_working_set_batched_dev(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, J
     dJ = up(np.stack([np.asfortranarray(Jk, dtype=np.float64).T for Jk in Js]))       # (B, n, m): problem k column-major
     drx = up(np.stack([np.asarray(r, dtype=np.float64) for r in rxs]))
     dG = up(np.stack([np.asarray(g, dtype=np.float64) for g in grad_fxs]))
-    dAt, dcx, dds = up(At_h.reshape(B, -1) if t_max else np.zeros((B, 1))), up(cx_h if t_max else np.zeros((B, 1))), up(ds_h)
-    ddsn = up(dsn_h)
+    if built is None:
+        dAt, dcx, dds = up(At_h.reshape(B, -1) if t_max else np.zeros((B, 1))), up(cx_h if t_max else np.zeros((B, 1))), up(ds_h)
+        ddsn = up(dsn_h)
+    else:
+        dAt, dcx, dds, ddsn = built[1:]
     dlam, dlam2, dgres, dsaved = new(B, tm1), new(B, tm1), new(B), new(B, n + 3)
     dp, db, dd, dinfo = new(B, n), new(B, tm1), new(B, m), new(B, 6, dtype=torch.int64)
     torch.cuda.synchronize(dev)
@@ -482,3 +495,48 @@ def update_working_set_batched_dev(solver: GNSolver, Ws, rxs, A, Cs, grad_fxs, J
         it.grad_res = float(gres[k])
         it.lam = (lam2 if cand[k] else lam)[k, :W.t].copy()
     return [(solver.factor(FACTOR_A, k), solver.factor(FACTOR_L11, k), solver.factor(FACTOR_J2, k)) for k in range(B)]
+
+
+# ---- the additions after a step and the rebuild of the active constraints, on device buffers ------------------------------------------
+def add_constraints_batched_dev(solver: GNSolver, Ws, its_or_index_alpha_upp, dA, dcx_all, dAt, dcx, dds, *, n: int, t_max: int,
+                                scaling, lda=None, strideA=None, ldat=None, strideAt=None, take=None, ddsn=None):
+    """``evaluate_violated_constraints`` (src/enlsip_functions.jl:608-650) and the rebuild of ``active_C`` (:2854-2855 with
+    ``evaluate_scaling!``) for B problems of one shape through ``GNSolver.add_constraints_batched_dev``: the full ``A`` (l x n per
+    problem, column-major) and ``cx`` are the device buffers ``dA`` / ``dcx_all`` (raw pointers), and the padded slot of the ragged
+    solve is written to ``dAt`` / ``dcx`` / ``dds``.  ``its_or_index_alpha_upp``: the iteration records (their ``index_alpha_upp``
+    is read) or the indices themselves.  ``scaling``: one flag or one per problem; like the deletion driver a mixed batch runs once
+    per kind of row scaling, each over its own problems, the kind without scaling writing its row norms to ``ddsn`` (default
+    ``dds``).  ``take`` as in the entry point (None: walk and rebuild everywhere).  Updates ``W.t``, ``W.active`` and
+    ``W.inactive`` of every walked problem and returns ``(added, status)`` (int64, 0 where no walk ran); status 1 means the
+    reference would repeat a swap pass for ever there (the lists are in that unchanged state and the slot is built from them)."""
+    B = len(Ws)
+    l = Ws[0].l
+    if any(W.l != l for W in Ws):
+        raise ValueError("one shape per batch: every problem needs the same l")
+    iau = np.array([int(getattr(x, "index_alpha_upp", x)) for x in its_or_index_alpha_upp], dtype=np.int64)
+    scal = np.broadcast_to(np.asarray(scaling, dtype=bool), (B,)).astype(np.int64)
+    tk = np.ones(B, dtype=np.int64) if take is None else np.asarray(take).astype(np.int64)
+    q = np.array([W.q for W in Ws], dtype=np.int64)
+    t = np.array([W.t for W in Ws], dtype=np.int64)
+    act, ina = np.zeros((B, l), dtype=np.int64), np.zeros((B, l), dtype=np.int64)
+    for k, W in enumerate(Ws):      # the reference's inactive has l - q entries: zero-padded to l for the call
+        act[k, :] = W.active
+        ina[k, :l - W.q] = W.inactive
+    lda = max(l, 1) if lda is None else lda
+    ldat = max(n, 1) if ldat is None else ldat
+    strideA = lda * n if strideA is None else strideA
+    strideAt = ldat * t_max if strideAt is None else strideAt
+    added, status = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    for mask, flag, buf in ((scal, True, dds), (1 - scal, False, dds if ddsn is None else ddsn)):
+        kind = mask * tk
+        if not kind.any():
+            continue
+        t1, a1, i1, ad, st = solver.add_constraints_batched_dev(B, n, l, t_max, q, t, act, ina, iau, flag, dA, lda, strideA, dcx_all,
+                                                                dAt, ldat, strideAt, dcx, buf, take=kind)
+        for k in np.flatnonzero(kind == 1):
+            W = Ws[k]
+            W.t = int(t1[k])
+            W.active[:] = a1[k]
+            W.inactive[:] = i1[k, :l - W.q]
+            added[k], status[k] = ad[k], st[k]
+    return added, status

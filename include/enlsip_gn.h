@@ -763,6 +763,71 @@ int enlsip_gn_linesearch_fit_batched_dev(enlsip_gn_handle h, int64_t batch, int6
                                          const double* dJp, const double* dcx, const double* dcx_new, const double* dAp,
                                          const double* dw, double* sums, double* out, int* arm, double* psi_new);
 
+/* ---- the working-set additions of a batch and the rebuild of its active constraints, on the caller's device buffers -----------
+ * After new_point! the outer iteration runs evaluate_violated_constraints (src/enlsip_functions.jl:608-650), rebuilds
+ * active_C.cx / active_C.A from the full cx and A (:2854-2855) and scales them at the top of the next iteration
+ * (evaluate_scaling!, src/structures.jl:160-178, called at :2783).  These entry points do that where the full A (l x n per
+ * problem) and cx already are for enlsip_gn_linesearch_setup_batched_dev, and leave the padded slot of the ragged solve: the
+ * loop working-set update -> line search -> next update of a batch exchanges only per-problem scalars and index lists.
+ *
+ * enlsip_gn_evaluate_violated_constraints   the walk on HOST data, no handle and no GPU.  active, inactive: l entries each, the
+ *     first *t / l - *t used (1-based, sorted), 0 behind; cx: l entries.  eps = sqrt(DBL_EPSILON), delta = 0.1, bnd = min(l, n);
+ *     inactive[i] = k is violated when cx[k] < eps || (k == index_alpha_upp && cx[k] < delta): a NaN never is (nor is an entry
+ *     0).  At capacity (*t >= bnd) the worst active inequality is the FIRST maximum of cx over the positions q+1..t by a strict
+ *     >, and the swap happens only when worst_val > cx[k]; after the removal the inactive list is re-sorted and inactive[i],
+ *     whatever it now is, is added (the reference's behaviour, quirk included).  Both sorts are a single insertion into a sorted
+ *     list.  *added = 0 / 1; *status = 0 the walk ended as the reference's does; 1 a swap pass would put back the very
+ *     constraint it removes, so (active, inactive, t, i) would be unchanged and the reference would repeat that pass for ever:
+ *     the routine stops there with the lists in that unchanged state, *added is what earlier passes set; 2 the defensive cap of
+ *     (l+1)^2 passes was exceeded, the lists are as they are at the cap (never observed: the one-pass cycle is the only one
+ *     seen, not proved to be the only one).  Returns 0; -2 t, added or status NULL, l, n or q negative, q > *t or *t > l; -4
+ *     active, inactive or cx NULL while l > 0; -5 a list entry or index_alpha_upp outside 0..l.
+ * enlsip_gn_gather_active_constraints   the rebuild on HOST data: column c of At (n x t column-major, ldat >= n) is row active[c]
+ *     of A (l x n column-major, lda >= l); a list entry 0 gives a row of zeros.  row_i = sqrt of the sum of squares in ONE fixed
+ *     order that depends on n alone: 64 strided partials (s = j mod 64, ascending j), added by the butterfly of a wave
+ *     all-reduce (x[s] += x[s ^ mask], mask = 1, 2, 7, 15, 16, 32); products and additions rounded separately, one IEEE square
+ *     root.  scaling == 0: diag_scale = row_i, the row and cx are copied.  scaling != 0: row_i < DBL_EPSILON gives the divisor 1.0,
+ *     the row and cx are divided by the divisor (IEEE) and diag_scale = 1.0 / divisor.  Plain sums of squares: covered for
+ *     entries inside the 2^+-400 band, as the sums of the line-search set-up.  Nothing between rows n and ldat is written.
+ *     Returns 0; -2 a bad shape (l < 0, n < 1, t outside 0..l, lda < l, ldat < n); -4 a NULL while t > 0; -5 an entry outside 0..l.
+ * enlsip_gn_add_constraints_batched_dev   per problem k, by take[k] (HOST array, NULL = 1 everywhere): 0 nothing of problem k is
+ *     read or written; 1 the walk on dcx_all[k] (l per problem), then the rebuild; 2 the rebuild only, from the lists as given
+ *     (the first iteration after init_working_set, and the rebuild of :739).  q, t, active, inactive (batch x l each),
+ *     index_alpha_upp (NULL: 0) are HOST arrays; t, active, inactive come back updated where a walk ran (all l entries of a
+ *     row, 0 behind the used part), and added / status (HOST, batch entries; 0 for a problem without a walk) as above.  dA: problem
+ *     k's l x n column-major block at dA + k * strideA, as in the line-search set-up.  The rebuild writes the padded slot a
+ *     host caller would upload: columns 0..t[k]-1 of the block at dAt + k * strideAt gathered (and scaled when scaling != 0),
+ *     columns t[k]..t_max-1 0.0 in rows 0..n-1; dcx[k] (t_max per problem) likewise with 0.0 behind, ddiag_scale[k] with 1.0
+ *     behind.  No byte between rows n and ldat, behind ldat * t_max or of any input is written.  After a walk with status 1 or 2
+ *     the rebuild still runs on the lists as left.  The results are bitwise those of the two host routines on the same data in
+ *     both kernel forms and do not depend on the slot, the batch or the take of other problems; no floating-point atomics.
+ * enlsip_gn_get_addition_form   kernel form of the last call on this handle: 0 general (a walk kernel, one workgroup per problem
+ *     with one lane on LDS copies, l <= 1024 in this build; then a gather kernel per 64-column tile of A' and problem through a
+ *     padded LDS tile), 1 one wave per problem (n <= 64 and l <= 64: four problems per workgroup, one launch, cross-lane
+ *     operations), -1 none yet.
+ * The call needs no resident factors: it is legal in every handle state and touches nothing resident.  The number of launches
+ * does not depend on batch; one copy of the records goes up, one comes down, and the call returns after ONE synchronisation of
+ * the handle's stream.  l == 0 or t_max == 0 launches nothing.  Argument errors are raised before anything is launched and
+ * leave every buffer untouched (last_error names k):
+ *   -1 h NULL; -2 batch < 1 (or batch * ceil(t_max / 64) beyond the grid); -3 n < 1, l outside 0..1024, t_max outside 0..1024
+ *   or > l; -4 q, t, added or status NULL, active or inactive NULL while l > 0, a device pointer NULL while t_max > 0; -5 some
+ *   t[k] outside 0..t_max or, where take[k] == 1, max(t[k], min(l, n)) > t_max (the largest t a walk can leave, so that no
+ *   slot can overflow); -6 some q[k] outside 0..t[k]; -7 a list entry or index_alpha_upp[k] outside 0..l; -9 lda < l or
+ *   ldat < n; -10 strideA < lda * n or strideAt < ldat * t_max.  Problems with take[k] == 0 are not checked.
+ */
+int enlsip_gn_evaluate_violated_constraints(int64_t l, int64_t n, int64_t q, int64_t* t, int64_t* active, int64_t* inactive,
+                                            const double* cx, int64_t index_alpha_upp, int64_t* added, int64_t* status);
+int enlsip_gn_gather_active_constraints(int64_t l, int64_t n, int64_t t, const int64_t* active, const double* A, int64_t lda,
+                                        const double* cx, int scaling, double* At, int64_t ldat, double* cx_active,
+                                        double* diag_scale);
+int enlsip_gn_add_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t n, int64_t l, int64_t t_max,
+                                          const int64_t* q, int64_t* t, int64_t* active, int64_t* inactive,
+                                          const int64_t* index_alpha_upp, const int64_t* take, int scaling,
+                                          const double* dA, int64_t lda, int64_t strideA, const double* dcx_all,
+                                          double* dAt, int64_t ldat, int64_t strideAt, double* dcx, double* ddiag_scale,
+                                          int64_t* added, int64_t* status);
+int enlsip_gn_get_addition_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
