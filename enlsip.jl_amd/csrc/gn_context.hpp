@@ -262,6 +262,11 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf add_scr;
     gn::PinnedBuf h_add;
     int addition_form = -1;
+    // batched termination test (gn_termination_batched.inc): the records and both index lists of one call on the device and in
+    // pinned memory, the partial sums of rx.rx and the sums per problem, and the form of the last call; nothing resident
+    gn::DevBuf term_scr;
+    gn::PinnedBuf h_term;
+    int termination_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

@@ -12,6 +12,15 @@
 
 namespace gn {
 
+// One column of A' x in the order of k_gemv_t: lane ln adds rows ln, ln + 64, ... in ascending order, then the wave all-reduce.
+// Every lane returns the sum.  Shared with the termination call (gn_kernels_termination_batched.hpp), whose gradient is these bits.
+__device__ __forceinline__ double gemv_t_column(const double* __restrict__ col, const double* __restrict__ x, int rows, int ln) {
+    double s = 0.0;
+#pragma unroll 8
+    for (int r = ln; r < rows; r += WAVE) s += col[r] * x[r];
+    return wave_allsum(s);
+}
+
 // y_j[c] = sum_r A_j[r + c*ld] * x_j[r] for c < ncols_j (ncols_j = tk ? tk[j] : ncols), y_j[c] = 0 for ncols_j <= c < ncols.
 // grid (ceil(ncols / 4), count): one wave per column, lanes along rows, the order of k_gemv_t.
 __global__ __launch_bounds__(256) void k_gemv_t_batched(const double* __restrict__ A, long long ld, long long sA, int rows, int ncols,
@@ -29,10 +38,7 @@ __global__ __launch_bounds__(256) void k_gemv_t_batched(const double* __restrict
     }
     const double* col = A + j * sA + (size_t)c * ld;
     const double* xj = x + j * sx;
-    double s = 0.0;
-#pragma unroll 8
-    for (int r = ln; r < rows; r += WAVE) s += col[r] * xj[r];
-    s = wave_allsum(s);
+    const double s = gemv_t_column(col, xj, rows, ln);
     if (ln == 0) yj[c] = s;
 }
 

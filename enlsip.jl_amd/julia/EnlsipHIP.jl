@@ -789,6 +789,140 @@ function addition_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""what `check_termination_criteria` (src/enlsip_functions.jl:2399-2517) reads of one problem's host records: enlsip_gn_term_state"""
+struct TermState
+    restart::Int64                  # :2425  iter.restart (0 / 1)
+    code::Int64                     # :2425  iter.code
+    del::Int64                      # :2430  iter.del (0 / 1)
+    grad_res::Float64               # :2430  iter.grad_res
+    nb_iter::Int64                  # :2492  nb_iter
+    nb_newton_steps::Int64          # :2500  iter.nb_newton_steps
+    error_code::Int64               # :2496  error_code of search_direction_analys
+    psi_error::Int64                # :2503  Ψ_error of compute_steplength
+    delta_time::Float64             # :2511  Δ_time
+    q::Int64                        # :2437  W.q
+    t::Int64                        # :2431  W.t
+    l::Int64                        # :2431  W.l
+    dimJ2::Int64                    # :2448  iter.dimJ2
+    psi0::Float64                   # :2279  psi0 of compute_steplength (enters progress only)
+end
+
+"""max_iter and the four tolerances of one call: enlsip_gn_term_tol"""
+struct TermTol
+    max_iter::Int64                 # :2492
+    eps_abs::Float64                # :2456  ε_abs
+    eps_rel::Float64                # :2430  ε_rel
+    eps_x::Float64                  # :2460  ε_x
+    eps_c::Float64                  # :2430  ε_c
+end
+
+"""the scalars the device forms per problem: enlsip_gn_term_sums"""
+struct TermSums
+    rx_sum::Float64                 # :2828  dot(rx, rx)
+    grad_nrm::Float64               # :2430  norm(∇fx)
+    p_nrm::Float64                  # :2422  norm(iter.p)
+    active_cx_nrm::Float64          # :2430  norm(active_C.cx)
+    n_inactive_nonpos::Int64        # :2434  inactive cx that are not > 0
+    n_inactive_le0::Int64           # :2475  inactive cx that are <= 0
+    sigma_min::Float64              # :559   σ_min
+    lambda_abs_max::Float64         # :554   λ_abs_max
+    d1_sq::Float64                  # :2452  dot(d1, d1)
+    x_diff::Float64                 # :2449  norm(prev_iter.x - x)
+    x_nrm::Float64                  # :2460  norm(x)
+    Atcx_nrm::Float64               # :2488  norm(transpose(active_C.A) * active_C.cx)
+    active_penalty_sum::Float64     # :2489  dot(w[active], w[active])
+    whsum::Float64                  # :2279  sum of w[active] .* cx_new[active].^2
+    progress::Float64               # :2280  2 psi0 - rx_sum - whsum
+end
+
+"""    minmax_lagrangian_mult_hip(λ, q, t, diag_scale, scaling) -> (σ_min, λ_abs_max)
+
+`minmax_lagrangian_mult` (src/enlsip_functions.jl:540-564) on host data through the library's host entry point (no handle, no
+GPU): the routine the batched call below runs on the device.  A NaN among the `t` multipliers makes `λ_abs_max` NaN."""
+function minmax_lagrangian_mult_hip(λ::Vector{Float64}, q::Integer, t::Integer, diag_scale::Vector{Float64}, scaling::Bool)
+    (t <= q || (length(λ) >= t && length(diag_scale) >= t)) || error("λ and diag_scale need t entries")
+    smin = Ref{Float64}(0.0); lmax = Ref{Float64}(0.0)
+    rc = GC.@preserve λ diag_scale ccall((:enlsip_gn_minmax_lagrangian_mult, LIB), Cint,
+        (Int64, Int64, Ptr{Float64}, Ptr{Float64}, Cint, Ref{Float64}, Ref{Float64}), q, t, λ, diag_scale, Cint(scaling), smin, lmax)
+    rc == 0 || error("enlsip_gn_minmax_lagrangian_mult returned $rc")
+    return smin[], lmax[]
+end
+
+"""    check_termination_criteria_hip(state, sums, tol) -> exit_code
+
+The decision of `check_termination_criteria` (src/enlsip_functions.jl:2420-2516) on scalars, through the library's host entry
+point (no handle, no GPU)."""
+function check_termination_criteria_hip(state::TermState, sums::TermSums, tol::TermTol)
+    code = Ref{Int64}(0)
+    rc = @ccall LIB.enlsip_gn_check_termination_criteria(Ref(state)::Ptr{TermState}, Ref(sums)::Ptr{TermSums},
+                                                         Ref(tol)::Ptr{TermTol}, code::Ptr{Int64})::Cint
+    rc == 0 || error("enlsip_gn_check_termination_criteria returned $rc")
+    return Int(code[])
+end
+
+"""    termination_sums_hip(state, active, inactive, J, rx, cx_all, x, x_prev, p, d_gn, λ, cx_active, diag_scale, At, w, scaling)
+        -> (sums, ∇fx)
+
+The scalars of the termination test from host arrays of one problem, in the summation orders of the kernels (enlsip_gn_termination_sums);
+`q`, `t`, `dimJ2` and `psi0` are read from `state`.  `At` is the `n x t` matrix of the OLD active slot."""
+function termination_sums_hip(state::TermState, active::Vector{Int64}, inactive::Vector{Int64}, J::Matrix{Float64},
+                              rx::Vector{Float64}, cx_all::Vector{Float64}, x::Vector{Float64}, x_prev::Vector{Float64},
+                              p::Vector{Float64}, d_gn::Vector{Float64}, λ::Vector{Float64}, cx_active::Vector{Float64},
+                              diag_scale::Vector{Float64}, At::Matrix{Float64}, w::Vector{Float64}, scaling::Bool)
+    m, n = size(J)
+    l = length(cx_all)
+    sums = Ref(TermSums(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)); g = zeros(n)
+    none = Ptr{Float64}(C_NULL)
+    rc = GC.@preserve active inactive J rx cx_all x x_prev p d_gn λ cx_active diag_scale At w g @ccall LIB.enlsip_gn_termination_sums(
+        m::Int64, n::Int64, l::Int64, state.t::Int64, state.q::Int64, state.dimJ2::Int64, state.psi0::Float64,
+        pointer(active)::Ptr{Int64}, pointer(inactive)::Ptr{Int64}, pointer(J)::Ptr{Float64}, max(m, 1)::Int64,
+        pointer(rx)::Ptr{Float64}, pointer(cx_all)::Ptr{Float64}, pointer(x)::Ptr{Float64}, pointer(x_prev)::Ptr{Float64},
+        pointer(p)::Ptr{Float64}, pointer(d_gn)::Ptr{Float64}, pointer(λ)::Ptr{Float64}, pointer(cx_active)::Ptr{Float64},
+        pointer(diag_scale)::Ptr{Float64}, pointer(At)::Ptr{Float64}, max(n, 1)::Int64, pointer(w)::Ptr{Float64},
+        Cint(scaling)::Cint, none::Ptr{Float64}, none::Ptr{Float64}, pointer(g)::Ptr{Float64}, sums::Ptr{TermSums})::Cint
+    rc == 0 || error("enlsip_gn_termination_sums returned $rc")
+    return sums[], g
+end
+
+"""    termination_batched_dev_hip(h, m, n, l, t_max, states, tol, active, inactive, take, scaling, dJ, ldj, strideJ, drx, dcx_all,
+                                dx, dx_prev, dp, dd_gn, dλ, dcx_active, ddiag_scale, dAt, ldat, strideAt, dw, dgrad)
+        -> (sums, exit_code)
+
+What stands between `new_point!` and `evaluate_violated_constraints` (src/enlsip_functions.jl:2828-2839) for `B = length(states)`
+problems on DEVICE buffers in one call: `∇fx = J' rx` into `dgrad`, `rx_sum`, `minmax_lagrangian_mult` and every norm and count
+`check_termination_criteria` reads, then the decision on the host.  `active` / `inactive`: host matrices `l x B` (one column per
+problem, 0 behind the used part); `take` (`nothing`: all): `take[k] == 0` leaves problem `k` alone.  The slot (`dλ`, `dcx_active`,
+`ddiag_scale`, `dAt`) is the OLD active slot in the padded ragged layout.  `exit_code .== 0` is the take mask of the next
+iteration's batched calls."""
+function termination_batched_dev_hip(h::Handle, m::Integer, n::Integer, l::Integer, t_max::Integer, states::Vector{TermState},
+                                     tol::TermTol, active::Matrix{Int64}, inactive::Matrix{Int64},
+                                     take::Union{Nothing,Vector{Int64}}, scaling::Bool, dJ::Ptr{Float64}, ldj::Integer,
+                                     strideJ::Integer, drx::Ptr{Float64}, dcx_all::Ptr{Float64}, dx::Ptr{Float64},
+                                     dx_prev::Ptr{Float64}, dp::Ptr{Float64}, dd_gn::Ptr{Float64}, dλ::Ptr{Float64},
+                                     dcx_active::Ptr{Float64}, ddiag_scale::Ptr{Float64}, dAt::Ptr{Float64}, ldat::Integer,
+                                     strideAt::Integer, dw::Ptr{Float64}, dgrad::Ptr{Float64})
+    B = length(states)
+    (take === nothing || length(take) == B) || error("take must have one entry per problem")
+    (size(active) == (l, B) && size(inactive) == (l, B)) || error("active and inactive are l x B")
+    sums = fill(TermSums(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0), B); codes = zeros(Int64, B)
+    tk = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take)
+    GC.@preserve states active inactive take sums codes check(h, @ccall LIB.enlsip_gn_termination_batched_dev(
+        h.ptr::Ptr{Cvoid}, B::Int64, m::Int64, n::Int64, l::Int64, t_max::Int64, pointer(states)::Ptr{TermState},
+        Ref(tol)::Ptr{TermTol}, pointer(active)::Ptr{Int64}, pointer(inactive)::Ptr{Int64}, tk::Ptr{Int64}, Cint(scaling)::Cint,
+        dJ::Ptr{Float64}, ldj::Int64, strideJ::Int64, drx::Ptr{Float64}, dcx_all::Ptr{Float64}, dx::Ptr{Float64},
+        dx_prev::Ptr{Float64}, dp::Ptr{Float64}, dd_gn::Ptr{Float64}, dλ::Ptr{Float64}, dcx_active::Ptr{Float64},
+        ddiag_scale::Ptr{Float64}, dAt::Ptr{Float64}, ldat::Int64, strideAt::Int64, dw::Ptr{Float64}, dgrad::Ptr{Float64},
+        pointer(sums)::Ptr{TermSums}, pointer(codes)::Ptr{Int64})::Cint)
+    return sums, codes
+end
+
+"""    termination_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last termination call on `h`"""
+function termination_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, ccall((:enlsip_gn_get_termination_form, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}), h.ptr, f))
+    return Int(f[])
+end
+
 """    upper_bound_steplength_hip(inactive, n_inactive, index_del, cx, Ap) -> (α_upp, index_α_upp)
 
 `upper_bound_steplength` (src/enlsip_functions.jl:2149-2178) on host data with `Ap = A * p` already formed, through the library's

@@ -34,6 +34,28 @@ class SubspacePrev(C.Structure):
                 ("previous_alpha", C.c_double), ("constraint_progress", C.c_double), ("residual_progress", C.c_double)]
 
 
+class TermState(C.Structure):
+    """enlsip_gn_term_state: what check_termination_criteria (src/enlsip_functions.jl:2399-2517) reads of one problem's host records"""
+    _fields_ = [("restart", C.c_int64), ("code", C.c_int64), ("del", C.c_int64), ("grad_res", C.c_double),
+                ("nb_iter", C.c_int64), ("nb_newton_steps", C.c_int64), ("error_code", C.c_int64), ("psi_error", C.c_int64),
+                ("delta_time", C.c_double), ("q", C.c_int64), ("t", C.c_int64), ("l", C.c_int64), ("dimJ2", C.c_int64),
+                ("psi0", C.c_double)]
+
+
+class TermTol(C.Structure):
+    """enlsip_gn_term_tol: max_iter and the four tolerances of one call"""
+    _fields_ = [("max_iter", C.c_int64), ("eps_abs", C.c_double), ("eps_rel", C.c_double), ("eps_x", C.c_double),
+                ("eps_c", C.c_double)]
+
+
+class TermSums(C.Structure):
+    """enlsip_gn_term_sums: the scalars the device forms per problem"""
+    _fields_ = [("rx_sum", C.c_double), ("grad_nrm", C.c_double), ("p_nrm", C.c_double), ("active_cx_nrm", C.c_double),
+                ("n_inactive_nonpos", C.c_int64), ("n_inactive_le0", C.c_int64), ("sigma_min", C.c_double),
+                ("lambda_abs_max", C.c_double), ("d1_sq", C.c_double), ("x_diff", C.c_double), ("x_nrm", C.c_double),
+                ("Atcx_nrm", C.c_double), ("active_penalty_sum", C.c_double), ("whsum", C.c_double), ("progress", C.c_double)]
+
+
 # enlsip_gn_allgather_fn: int (*)(void* ctx, const void* dsend, void* drecv, size_t bytes_per_rank, void* hip_stream)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -167,6 +189,15 @@ PROTOTYPES = {
                                                         C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64, C.c_void_p,
                                                         C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_get_addition_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_minmax_lagrangian_mult": (C.c_int, [_i64, _i64, C.c_void_p, C.c_void_p, C.c_int, _dp, _dp]),
+    "enlsip_gn_check_termination_criteria": (C.c_int, [C.POINTER(TermState), C.POINTER(TermSums), C.POINTER(TermTol), _ip]),
+    "enlsip_gn_termination_sums": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, _i64]
+                                   + [C.c_void_p] * 10 + [_i64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                          C.POINTER(TermSums)]),
+    "enlsip_gn_termination_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, _i64, C.c_void_p, C.POINTER(TermTol), C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64] + [C.c_void_p] * 10
+                                          + [_i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_get_termination_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

@@ -828,6 +828,121 @@ int enlsip_gn_add_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int
                                           int64_t* added, int64_t* status);
 int enlsip_gn_get_addition_form(enlsip_gn_handle h, int* form);
 
+/* ---- the termination test of a batch, on the caller's device buffers ----------------------------------------------------------
+ * What stands between new_point! and evaluate_violated_constraints in the outer loop (src/enlsip_functions.jl:2828-2839): rx_sum,
+ * grad_fx = J' rx, minmax_lagrangian_mult (:540-564) and check_termination_criteria (:2399-2517), with iter.progress (:2279-2280).
+ * The exit code of a problem is also the take mask of every other batched call of the next iteration, and dgrad is the dgrad_fx
+ * of the next enlsip_gn_first_lagrange_batched_dev.  Delta_time, max_iter and the error_code / Psi_error bookkeeping stay with the
+ * caller as inputs.
+ *
+ * enlsip_gn_minmax_lagrangian_mult   :540-564 on HOST data, no handle and no GPU.  t <= q: *sigma_min = +Inf, *lambda_abs_max =
+ *     0.0.  Otherwise lambda_abs_max = max |lambda_i| over ALL t entries and sigma_min the smallest lambda_i of the positions
+ *     q+1..t with lambda_i * rows_i <= -sqrt(DBL_EPSILON) (strict < against the running minimum, in order), rows_i = 1.0 /
+ *     diag_scale_i (IEEE) when scaling != 0, diag_scale_i otherwise; +Inf when none passes.  A NaN never passes.  A NaN among the
+ *     t entries of lambda makes lambda_abs_max the quiet NaN (as Julia's maximum does), here and in both kernel forms.
+ *     Returns 0; -2 an output NULL, q < 0 or t < 0; -4 lambda or diag_scale NULL while t > q.
+ * enlsip_gn_check_termination_criteria   the decision of :2420-2516 on scalars, statement for statement: the preliminary
+ *     condition, the necessary conditions, the codes 10000 / 2000 / 300 / 40 summed, the feas negation of :2471-2481 (unreachable
+ *     in the reference, whose necessary condition already excludes it; kept, from n_inactive_le0), then the abnormal chain in its
+ *     order: -2, error_code (-3..-5), -9, -6, -10, -11.  alfnoi = DBL_EPSILON / (p_nrm + DBL_EPSILON); eps_rel^2 is eps_rel *
+ *     eps_rel.  Returns 0; -2 a NULL.
+ * enlsip_gn_termination_sums   fills enlsip_gn_term_sums from HOST arrays of ONE problem, in the orders of the kernels: every
+ *     n-, t- and l-length sum as 64 strided partials (s = j mod 64, ascending j, from +0.0) added by the butterfly of a wave
+ *     all-reduce (masks 1, 2, 7, 15, 16, 32), products and additions rounded separately; entry j of At * cx_active as a running
+ *     sum over the columns in ascending order; norms as a plain sum of squares and one IEEE square root (not nrm2's scaled form:
+ *     covered for operands inside the 2^+-400 band, as the sums of the line-search set-up and of the gather).  J: m x n
+ *     column-major, ldj; At: n x t column-major, ldat (the OLD active slot, as lambda, cx_active, diag_scale); active / inactive:
+ *     the first t / l - t entries used, 1-based, an entry 0 contributes nothing.  grad_in (n) / rx_sum_in: when not NULL the
+ *     gradient / rx_sum are taken as given (what the device formed: they follow k_gemv_t and the line-search set-up's dot(rx, rx),
+ *     which this routine does not restate bit for bit); otherwise both are formed in the strided order.  grad_out (n) may be NULL.
+ *     Returns 0; -2 sums NULL or a bad shape (m, l < 0, n < 1, t outside 0..l, q outside 0..t, dimJ2 outside 0..n, ldj < m,
+ *     ldat < n); -4 a NULL array that would be read; -5 a list entry outside 0..l; 998 out of host memory.
+ * enlsip_gn_termination_batched_dev   for every problem k with take[k] != 0 (HOST array, NULL = all; take[k] == 0: nothing of
+ *     problem k is read or written, sums[k] and exit_code[k] included), on the device: dgrad[k] = J_k' rx_k (n per problem) and the
+ *     fields of sums[k]; then, on the host inside the same call, exit_code[k] by enlsip_gn_check_termination_criteria on
+ *     (state[k], sums[k], tol): the decision has one implementation.  Padded ragged layout: dlambda, dcx_active, ddiag_scale hold
+ *     t_max entries per problem and dAt the n x t_max block at dAt + k * strideAt, of which problem k uses its first state[k].t;
+ *     they are the OLD active slot (what active_C holds at :2838).  dJ, drx, dcx_all (l), dx are the NEW point; dx_prev, dp, dd_gn
+ *     (n per problem, the first state[k].dimJ2 used), dw (l) belong to the iteration that just ended.  active / inactive: HOST,
+ *     batch x l, 1-based, 0 behind.  state[k].psi0 enters progress = 2 psi0 - rx_sum - whsum only.
+ *     Arithmetic: no floating-point atomics; every field is bitwise enlsip_gn_termination_sums on the same data given the dgrad
+ *     and the rx_sum the call produced, in both kernel forms, whatever the slot, the batch and the take of other problems.  dgrad
+ *     is bitwise what enlsip_gn_gradient_batched_dev returns once the same J, rx are resident; rx_sum is bitwise the dot(rx, rx)
+ *     of enlsip_gn_linesearch_setup_batched_dev on the same rx (which depends on the kernel form, as there).
+ * enlsip_gn_get_termination_form   kernel form of the last call on this handle: 0 general (the J' rx kernel, the partial sums of
+ *     rx, one workgroup per problem for every short reduction), 1 one wave per problem (n <= 64 and l <= 64: four problems per
+ *     workgroup, one launch, cross-lane operations only), -1 none yet.
+ * The call needs no resident factors: it is legal in every handle state and touches nothing resident.  The number of launches
+ * does not depend on batch; one copy of the records goes up, one comes down, and the call returns after ONE synchronisation of
+ * the handle's stream.  l == 0, t_max == 0 and m == 0 are legal (m == 0: rx_sum = 0.0 and dgrad = 0.0).  Argument errors are raised
+ * before anything is launched and leave every buffer untouched (last_error names k):
+ *   -1 h NULL; -2 batch < 1 (or batch * max(ceil(n / 4), partial-sum workgroups) beyond the grid); -3 m < 0, n < 1, l outside
+ *   0..1024, t_max outside 0..1024 or > l; -4 state, tol, sums or exit_code NULL, active or inactive NULL while l > 0, dJ or drx
+ *   NULL while m > 0, dcx_all or dw NULL while l > 0, dlambda, dcx_active, ddiag_scale or dAt NULL while t_max > 0, any of dx,
+ *   dx_prev, dp, dd_gn, dgrad NULL; -5 some state[k].t outside 0..t_max, or state[k].l != l; -6 some state[k].q outside
+ *   0..state[k].t; -7 a list entry outside 0..l; -8 some state[k].dimJ2 outside 0..n; -9 ldj < m or ldat < n; -10 strideJ <
+ *   ldj * n or strideAt < ldat * t_max.  Problems with take[k] == 0 are not checked.
+ */
+typedef struct enlsip_gn_term_state {
+    int64_t restart;              /* :2425  iter.restart (0 / 1)                                                  */
+    int64_t code;                 /* :2425  iter.code                                                             */
+    int64_t del;                  /* :2430  iter.del (0 / 1)                                                      */
+    double  grad_res;             /* :2430  iter.grad_res                                                         */
+    int64_t nb_iter;              /* :2492  nb_iter                                                               */
+    int64_t nb_newton_steps;      /* :2500  iter.nb_newton_steps                                                  */
+    int64_t error_code;           /* :2496  error_code of search_direction_analys                                 */
+    int64_t psi_error;            /* :2503  Psi_error of compute_steplength                                       */
+    double  delta_time;           /* :2511  Delta_time                                                            */
+    int64_t q;                    /* :2437  W.q                                                                   */
+    int64_t t;                    /* :2431  W.t                                                                   */
+    int64_t l;                    /* :2431  W.l                                                                   */
+    int64_t dimJ2;                /* :2448  iter.dimJ2                                                            */
+    double  psi0;                 /* :2279  psi0 of compute_steplength (enters progress only)                     */
+} enlsip_gn_term_state;
+typedef struct enlsip_gn_term_tol {
+    int64_t max_iter;             /* :2492  max_iter                                                              */
+    double  eps_abs;              /* :2456  eps_abs                                                               */
+    double  eps_rel;              /* :2430  eps_rel                                                               */
+    double  eps_x;                /* :2460  eps_x                                                                 */
+    double  eps_c;                /* :2430  eps_c                                                                 */
+} enlsip_gn_term_tol;
+typedef struct enlsip_gn_term_sums {
+    double  rx_sum;               /* :2828  dot(rx, rx)                                                           */
+    double  grad_nrm;             /* :2430  norm(grad_fx), grad_fx = J' rx (:2829)                                */
+    double  p_nrm;                /* :2422  norm(iter.p)                                                          */
+    double  active_cx_nrm;        /* :2430  norm(active_C.cx)                                                     */
+    int64_t n_inactive_nonpos;    /* :2434  inactive cx that are not > 0 (a NaN counts)                           */
+    int64_t n_inactive_le0;       /* :2475  inactive cx that are <= 0 (a NaN does not count)                      */
+    double  sigma_min;            /* :559   sigma_min of minmax_lagrangian_mult                                   */
+    double  lambda_abs_max;       /* :554   lambda_abs_max of minmax_lagrangian_mult                              */
+    double  d1_sq;                /* :2452  dot(d1, d1), d1 = iter.d_gn[1:dimJ2]                                  */
+    double  x_diff;               /* :2449  norm(prev_iter.x - x)                                                 */
+    double  x_nrm;                /* :2460  norm(x)                                                               */
+    double  Atcx_nrm;             /* :2488  norm(transpose(active_C.A) * active_C.cx)                             */
+    double  active_penalty_sum;   /* :2489  dot(w[active], w[active])                                             */
+    double  whsum;                /* :2279  sum of w[active] * cx_new[active]^2                                   */
+    double  progress;             /* :2280  2 psi0 - rx_sum - whsum                                               */
+} enlsip_gn_term_sums;
+int enlsip_gn_minmax_lagrangian_mult(int64_t q, int64_t t, const double* lambda, const double* diag_scale, int scaling,
+                                     double* sigma_min, double* lambda_abs_max);
+int enlsip_gn_check_termination_criteria(const enlsip_gn_term_state* s, const enlsip_gn_term_sums* v,
+                                         const enlsip_gn_term_tol* tol, int64_t* exit_code);
+int enlsip_gn_termination_sums(int64_t m, int64_t n, int64_t l, int64_t t, int64_t q, int64_t dimJ2, double psi0,
+                               const int64_t* active, const int64_t* inactive, const double* J, int64_t ldj, const double* rx,
+                               const double* cx_all, const double* x, const double* x_prev, const double* p, const double* d_gn,
+                               const double* lambda, const double* cx_active, const double* diag_scale, const double* At,
+                               int64_t ldat, const double* w, int scaling, const double* grad_in, const double* rx_sum_in,
+                               double* grad_out, enlsip_gn_term_sums* sums);
+int enlsip_gn_termination_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t l, int64_t t_max,
+                                      const enlsip_gn_term_state* state, const enlsip_gn_term_tol* tol, const int64_t* active,
+                                      const int64_t* inactive, const int64_t* take, int scaling, const double* dJ, int64_t ldj,
+                                      int64_t strideJ, const double* drx, const double* dcx_all, const double* dx,
+                                      const double* dx_prev, const double* dp, const double* dd_gn, const double* dlambda,
+                                      const double* dcx_active, const double* ddiag_scale, const double* dAt, int64_t ldat,
+                                      int64_t strideAt, const double* dw, double* dgrad, enlsip_gn_term_sums* sums,
+                                      int64_t* exit_code);
+int enlsip_gn_get_termination_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
