@@ -285,10 +285,6 @@ static void launch_factor(enlsip_gn_handle h, const CaqrArgs& a, int groups, hip
         // ceil(blocks / 2) registers per lane and column: the smaller forms issue fewer multiply-adds per step on rows that hold
         // nothing (the geometry of a node is the same in every form: slot ln + 64 i = block (ln >> 5) + 2 i)
         int rpl = h->plan.RPL;
-        if (rpl == 8 && ((h->factor_nw4 >= 1 && a.level == 0) || h->factor_nw4 >= 2)) {      // A/B: 4 waves x 8 columns
-            hipLaunchKernelGGL((k_caqr_factor<8, 4>), grid, dim3(256), 0, st, a);
-            return;
-        }
         if (a.level > 0 && groups == 1) {
             const int need = (a.nblocks + 1) / 2;
             const int fit = need <= 1 ? 1 : (need <= 2 ? 2 : (need <= 4 ? 4 : 8));
@@ -407,13 +403,13 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     };
     // few problems with many tiles each: the far update of a pair reads its grid XCD-locally, so that a tile's V stays in one L2
     // between the tile's column blocks (k_caqr_update_v4_pair); batches keep the native order (a problem's tiles are neighbours)
-    auto xmap_tiles = [&](int groups) -> int { return (h->xcd_map && P.batch <= 8 && groups >= 16 && !mixed) ? groups : 0; };
+    auto xmap_tiles = [&](int groups) -> int { return (P.batch <= 8 && groups >= 16 && !mixed) ? groups : 0; };
     // Look-ahead (chain-bound sweeps: one or a few problems with many tiles — C4): a pair's far update is split into the NEXT
     // pair's 64 columns (this stream) and the rest (second stream), so that the next pair's chain of small dependent launches
     // (two level-0 factorisations, their trees, the second panel's own columns) runs beside the bulk of the previous far update
     // instead of behind it.  Order: chain(K) -> E1 ; [wait E2(K-1)] near(K) ; second stream: wait E1, rest(K) -> E2.
     const long long far_wgs0 = P.batch * (((long long)mpad + 64 * P.RPL - 1) / (64 * P.RPL)) * ((n2_launch + 31) / 32);
-    const bool la = P.pair && use_mfma && h->lookahead && !mixed && !h->pair_debug && h->debug_stage < 0 &&
+    const bool la = P.pair && use_mfma && h->lookahead && !mixed &&
                     ((P.batch <= 8 && far_wgs0 >= 8192) || h->lookahead_forced);
     // The same idea for the PLAIN sweep of a chain-bound problem (a single C2 problem; a 32768-row shard of C4 where pairs do
     // not pay): the factorisations of a panel (tile level and tree levels: they only read the panel's own columns) run first,
@@ -423,7 +419,7 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
     // Measured (MI355X, round 4): it does NOT pay at the sizes it was meant for — a single C2 problem 4.18 -> 4.38 ms, four of them
     // 4.59 -> 4.80 ms, a 32768 x 1024 shard 15.66 -> 15.63 ms: two event hand-overs per panel cost what the overlap of a ~25 us
     // update with a ~75 us factor chain brings.  Kept behind ENLSIP_GN_LOOKAHEAD=1 (parity-tested in both sweeps), off by default.
-    const bool lap = !P.pair && use_mfma && h->lookahead && !mixed && h->debug_stage < 0 && npan >= 3 && h->lookahead_forced;
+    const bool lap = !P.pair && use_mfma && h->lookahead && !mixed && npan >= 3 && h->lookahead_forced;
     const hipStream_t sA = h->stream;
     hipStream_t sB = nullptr;
     if (la || lap) {
@@ -465,13 +461,7 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
         la_prev = e2;
         return 0;
     };
-    // Which parts of a step are issued.  Everything, but for the switches of the laboratory build (ENLSIP_GN_DEBUG_STAGE: parts
-    // 0..7 of a pair in the order of issue; ENLSIP_GN_DEBUG_MAXPAN: stop the sweep) and the A/B form ENLSIP_GN_PAIR=2: the same pair
-    // geometry, the far level-0 pass as two plain passes (first panel, then second).
-    auto live = [&](int part) { return h->debug_stage < 0 || part <= h->debug_stage; };
-    const bool far_pair_pass = live(4) && !h->pair_debug, far_plain_a = live(4) && h->pair_debug, far_plain_b = far_plain_a && live(5);
-    const int npan_run = h->debug_maxpan >= 0 ? std::min(npan, h->debug_maxpan) : npan;
-    for (int k = 0; k < npan_run;) {
+    for (int k = 0; k < npan;) {
         const int bwk = std::min(PB, kp_launch - k * PB);
         const int ntrail = n2_launch + 1 - (k * PB + bwk);  // trailing columns incl. the augmented one
         if (h->profiling && ntrail > 0) h->upd_all_bytes += (double)P.batch * btrail(k, ntrail);   // every column right of the panel
@@ -494,12 +484,11 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
                 a.win = 1;
                 return update_other(a, L, own, bwb, sA);
             };
-            if (live(0))
-                if (int rc = first_panel_level(LA[0])) return rc;
-            if (live(1)) launch_factor(h, caqr_args(h, kb, LB[0]), LB[0].groups);
-            for (size_t li = 1; li < LA.size() && live(2); ++li)
+            if (int rc = first_panel_level(LA[0])) return rc;
+            launch_factor(h, caqr_args(h, kb, LB[0]), LB[0].groups);
+            for (size_t li = 1; li < LA.size(); ++li)
                 if (int rc = first_panel_level(LA[li])) return rc;
-            for (size_t li = 1; li < LB.size() && live(3); ++li) launch_factor(h, caqr_args(h, kb, LB[li]), LB[li].groups);
+            for (size_t li = 1; li < LB.size(); ++li) launch_factor(h, caqr_args(h, kb, LB[li]), LB[li].groups);
             // window update (win = 2): both level-0 reflectors in one pass, then the first panel's tree levels, then the second's.
             // Grid of the first panel's launches.  A problem whose J2 ends inside the pair has bwb fewer pair
             // columns and as many more far columns than the launch shape says, so with mixed widths the grid spans ntrail and the
@@ -513,24 +502,19 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
                 const int far_grid = mixed ? ntrail : w.ncols;
                 CaqrArgs a = caqr_args(h, k, LA[0]);
                 a.win = 2;
-                if (far_pair_pass) {
-                    a.pair = 1; a.tOff2 = LB[0].tOff;
-                    a.xmap = xmap_tiles(LA[0].groups);
-                    int rc = timed(btrail(k, w.ncols) + btrail(kb, w.ncols), st, [&] { update_l0(a, LA[0], w, far_grid, st); });
-                    if (rc) return rc;
-                    if (mixed) {        // problems whose J2 ends before the second panel: the first panel alone, every trailing column
-                        a.pair = 2;
-                        update_l0(a, LA[0], w, ntrail, st);
-                    }
+                a.pair = 1; a.tOff2 = LB[0].tOff;
+                a.xmap = xmap_tiles(LA[0].groups);
+                if (int rc = timed(btrail(k, w.ncols) + btrail(kb, w.ncols), st, [&] { update_l0(a, LA[0], w, far_grid, st); })) return rc;
+                if (mixed) {        // problems whose J2 ends before the second panel: the first panel alone, every trailing column
+                    a.pair = 2;
+                    update_l0(a, LA[0], w, ntrail, st);
                 }
-                if (far_plain_a) update_l0(a, LA[0], w, ntrail, st);
-                if (far_plain_b) update_l0(caqr_args(h, kb, LB[0]), LB[0], w, nfar, st);
-                for (size_t li = 1; li < LA.size() && live(6); ++li) {
+                for (size_t li = 1; li < LA.size(); ++li) {
                     CaqrArgs t = caqr_args(h, k, LA[li]);
                     t.win = 2;
                     if (int rc = update_other(t, LA[li], w, far_grid, st)) return rc;
                 }
-                for (size_t li = 1; li < LB.size() && live(7); ++li)
+                for (size_t li = 1; li < LB.size(); ++li)
                     if (int rc = update_other(caqr_args(h, kb, LB[li]), LB[li], w, w.ncols, st)) return rc;
                 return 0;
             };
@@ -1457,38 +1441,8 @@ int enlsip_gn_create(enlsip_gn_handle* out, const enlsip_gn_opts* opts) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             h->cu_count = prop.multiProcessorCount;
-        h->trace = getenv("ENLSIP_GN_TRACE") != nullptr;
-        const char* pp = getenv("ENLSIP_GN_PAIR");            // 0: plain sweep, one panel per pass over the trailing matrix (A/B)
-        if (pp && pp[0] == '0') h->pair_enabled = false;
-        if (pp && pp[0] == '2') h->pair_debug = true;         // 2: pair geometry, but the far columns in two plain passes (A/B)
-        if (pp && (pp[0] == '1' || pp[0] == '2')) h->pair_forced = true;   // 1 / 2: pairs for every shape with three panels or more
-        const char* lk = getenv("ENLSIP_GN_LOOKAHEAD");      // 0: the pair sweep on one stream (A/B)
-        if (lk && lk[0] == '0') h->lookahead = false;
-        if (lk && lk[0] == '1') h->lookahead_forced = true;   // 1: for every paired sweep (tests)
-        const char* xm = getenv("ENLSIP_GN_XMAP");           // 0: native grid order for the far update of few problems with many tiles (A/B)
-        if (xm && xm[0] == '0') h->xcd_map = false;
-        const char* fs = getenv("ENLSIP_GN_FUSE_SMALL");     // 0: J*Q1 and the one-tile panel factorisation as two launches (A/B)
-        if (fs && fs[0] == '0') h->fuse_small = false;
-        const char* fh = getenv("ENLSIP_GN_SB_FORM_HINTS");   // 0: every block of the blocked pivoted QR in all of its forms (A/B)
-        if (fh && fh[0] == '0') h->sb_form_hints = false;
-        const char* hy = getenv("ENLSIP_GN_QRCP_HYBRID");     // 0: more than 512 rows = one launch per pivot step to the end (A/B)
-        if (hy && hy[0] == '0') h->qrcp_hybrid = false;
-#ifdef ENLSIP_GN_LAB       // laboratory build only (gn_device_utils.hpp): A/B and fault-location switches that no test of the suite uses
-        const char* f4 = getenv("ENLSIP_GN_FACTOR_NW4");
-        if (f4) h->factor_nw4 = atoi(f4);
-        const char* dm = getenv("ENLSIP_GN_DEBUG_MAXPAN");
-        if (dm) h->debug_maxpan = atoi(dm);
-        const char* ds = getenv("ENLSIP_GN_DEBUG_STAGE");
-        if (ds) h->debug_stage = atoi(ds);
-#endif
-        const char* rs = getenv("ENLSIP_GN_RESCALE");         // 0: no detection / rescaling of magnitudes beyond plain sums of squares (A/B, tests)
-        if (rs && rs[0] == '0') h->rescale_enabled = false;
-        const char* pl = getenv("ENLSIP_GN_PIPELINE");       // 0: never split a batch over two streams
-        if (pl && pl[0] == '0') h->pipeline = false;
-        if (pl && pl[0] == '1') h->pipeline_forced = true;    // 1: split even the small uniform shapes (A/B)
-        const char* ls = getenv("ENLSIP_GN_LAGRANGE_SMALL");  // 0: batched multiplier estimates always in the general form (A/B)
-        if (ls && ls[0] == '0') h->lagrange_small = false;
     }
+    gn::read_env_switches(h);
     if (opts && opts->panel_width != 0 && opts->panel_width != PB) {
         delete h;
         return -2;
@@ -1664,18 +1618,6 @@ int enlsip_gn_debug_copy_W(enlsip_gn_handle h, int64_t prob, double* out, int64_
     GN_HIP(hipMemcpy(out, h->W + prob * P.sW, need * 8, hipMemcpyDeviceToHost));
     return 0;
 }
-
-#ifdef ENLSIP_SB_STEP_STAMPS
-// diagnostic build only: phase sums of the blocked pivoted QR's step (100 MHz ticks; [8] = steps; [16..23] block-level phases), reset on read; out: 24 words
-extern "C" int enlsip_gn_debug_sb_phase(long long* out) {
-    long long z[16] = {0};
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(gn::g_sb_phase), sizeof(z)) != hipSuccess) return 1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(gn::g_sb_phase), z, sizeof(z)) != hipSuccess) return 1;
-    if (hipMemcpyFromSymbol(out + 16, HIP_SYMBOL(gn::g_sb_blk), 8 * sizeof(long long)) != hipSuccess) return 1;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(gn::g_sb_blk), z, 8 * sizeof(long long)) != hipSuccess) return 1;
-    return 0;
-}
-#endif
 
 int enlsip_gn_get_update_stats(enlsip_gn_handle h, float* avg_ms, int64_t* launches, double* bytes) {
     if (!h) return -1;

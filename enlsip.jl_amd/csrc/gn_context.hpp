@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -134,15 +135,12 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     // a child handle (own stream + workspace) driven by a host thread, so the latency-bound kernels of one half
     // overlap the bandwidth-bound kernels of the other.  Accessors route a problem index to the half that owns it.
     enlsip_gn_context* child = nullptr;
-    bool pair_debug = false, pair_forced = false;
+    bool pair_forced = false;           // ENLSIP_GN_PAIR=1: pairs for every shape with three panels or more
     bool lookahead_forced = false;
     bool lookahead = true;              // ENLSIP_GN_LOOKAHEAD=0: chain-bound pair sweeps on one stream
     hipStream_t stream2 = nullptr;      // second stream of the look-ahead sweep (the bulk of a pair's far update)
     std::vector<hipEvent_t> la_events;
-    bool xcd_map = true;                // ENLSIP_GN_XMAP=0: native grid order (A/B)
     bool fuse_small = true;             // ENLSIP_GN_FUSE_SMALL=0: two launches for J*Q1 + panel factorisation of one-tile problems
-    int factor_nw4 = 0;                 // ENLSIP_GN_FACTOR_NW4 (A/B): 1 = level-0 tiles factored by 4 waves x 8 columns, 2 = tree nodes too
-    int debug_maxpan = -1, debug_stage = -1;
     bool pair_enabled = true;           // ENLSIP_GN_PAIR=0: one panel per pass over the trailing matrix
     bool pipeline = true;               // ENLSIP_GN_PIPELINE=0 disables
     bool pipeline_forced = false;   // ENLSIP_GN_PIPELINE=1
@@ -292,3 +290,40 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     long long oth_launches = 0;
     double upd_all_bytes = 0.0;             // SURVEY 8d bytes of EVERY panel of the sweep on ALL its trailing columns
 };
+
+namespace gn {
+
+// The run-time switches of a handle: every environment variable the library reads when a handle is created (helper, child, rescue
+// and sub handles are created the same way and read them again), but for ENLSIP_GN_RCCL_LIB, which names a file (gn_tsqr.inc).
+// One row per (variable, value): a value whose first character is `value` stores `set` in `field`; value 0 = the variable is set
+// at all.  README.md lists the switches from this table.
+struct EnvSwitch {
+    const char* name;
+    char value;
+    bool enlsip_gn_context::*field;
+    bool set;
+};
+inline constexpr EnvSwitch ENV_SWITCHES[] = {
+    {"ENLSIP_GN_TRACE", 0, &enlsip_gn_context::trace, true},                     // stage names on stderr, a synchronisation after each
+    {"ENLSIP_GN_PAIR", '0', &enlsip_gn_context::pair_enabled, false},            // plain sweep: one panel per pass over the trailing matrix
+    {"ENLSIP_GN_PAIR", '1', &enlsip_gn_context::pair_forced, true},              // pairs for every shape with three panels or more
+    {"ENLSIP_GN_PAIR", '2', &enlsip_gn_context::pair_forced, true},              // (once an A/B form of the far update: now the same as 1)
+    {"ENLSIP_GN_LOOKAHEAD", '0', &enlsip_gn_context::lookahead, false},          // the pair sweep on one stream
+    {"ENLSIP_GN_LOOKAHEAD", '1', &enlsip_gn_context::lookahead_forced, true},    // look-ahead in every sweep, the plain one too (tests)
+    {"ENLSIP_GN_FUSE_SMALL", '0', &enlsip_gn_context::fuse_small, false},        // J*Q1 and the one-tile panel factorisation as two launches
+    {"ENLSIP_GN_SB_FORM_HINTS", '0', &enlsip_gn_context::sb_form_hints, false},  // every block of the blocked pivoted QR in all of its forms
+    {"ENLSIP_GN_QRCP_HYBRID", '0', &enlsip_gn_context::qrcp_hybrid, false},      // more than 512 rows: one launch per pivot step to the end
+    {"ENLSIP_GN_RESCALE", '0', &enlsip_gn_context::rescale_enabled, false},      // no detection / rescaling of magnitudes beyond plain sums of squares
+    {"ENLSIP_GN_PIPELINE", '0', &enlsip_gn_context::pipeline, false},            // never split a batch over two streams
+    {"ENLSIP_GN_PIPELINE", '1', &enlsip_gn_context::pipeline_forced, true},      // split even the small uniform shapes
+    {"ENLSIP_GN_LAGRANGE_SMALL", '0', &enlsip_gn_context::lagrange_small, false},  // batched multiplier estimates always in the general form
+};
+
+inline void read_env_switches(enlsip_gn_context* h) {
+    for (const EnvSwitch& sw : ENV_SWITCHES) {
+        const char* v = getenv(sw.name);
+        if (v && (sw.value == 0 || v[0] == sw.value)) h->*sw.field = sw.set;
+    }
+}
+
+}  // namespace gn

@@ -9,18 +9,6 @@ namespace gn {
 
 constexpr int WAVE = 64;
 
-// ENLSIP_GN_LAB (not set by build.sh): the laboratory build.  Only with it do the timing ablations (ENLSIP_V4_ABLATE,
-// ENLSIP_FACTOR_ABLATE: kernels whose RESULTS ARE WRONG by design), the phase-stamp macros (ENLSIP_V4_STAMPS,
-// ENLSIP_FACTOR_STAMPS, ENLSIP_SB_STEP_STAMPS, GN_PS_STAMPS) and the A/B run-time switches that no test of the suite uses
-// (ENLSIP_GN_FACTOR_NW4, ENLSIP_GN_DEBUG_MAXPAN, ENLSIP_GN_DEBUG_STAGE, ENLSIP_GN_JQ1_ROWS2) exist; the product build refuses the
-// macros and never reads those variables.  tests/microbench/*.hip and tests/probes/*.sh build with -DENLSIP_GN_LAB.
-#ifndef ENLSIP_GN_LAB
-#if (defined(ENLSIP_V4_ABLATE) && ENLSIP_V4_ABLATE != 0) || (defined(ENLSIP_FACTOR_ABLATE) && ENLSIP_FACTOR_ABLATE != 0) || \
-    defined(ENLSIP_V4_STAMPS) || defined(ENLSIP_FACTOR_STAMPS) || defined(ENLSIP_SB_STEP_STAMPS) || defined(GN_PS_STAMPS)
-#error "timing ablations and phase stamps are laboratory code: build with -DENLSIP_GN_LAB"
-#endif
-#endif
-
 // Host side: kernel-selection record of the solve that runs on this thread (include/enlsip_gn.h: ENLSIP_GN_ROUTE_*); the launch
 // helpers OR their bit in, solve_dev folds it into the handle.  A pipelined solve runs its second half on a thread of its own.
 inline thread_local unsigned long long gn_route_acc = 0;

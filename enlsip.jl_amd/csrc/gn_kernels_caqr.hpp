@@ -102,19 +102,6 @@ __device__ __forceinline__ long long caqr_block_row(const CaqrArgs& a, long long
 #ifndef ENLSIP_FACTOR_OCC16
 #define ENLSIP_FACTOR_OCC16 8
 #endif
-// timing experiments only (tests/microbench/factor_bench.hip; results wrong when != 0): 1 no reflector arithmetic (norm reduction,
-// dlarfg), 2 no reduction of the dot products, 3 no T factor, 4 no barrier inside the step loop, 5 no step loop, 6 no dot products /
-// column updates
-#ifndef ENLSIP_FACTOR_ABLATE
-#define ENLSIP_FACTOR_ABLATE 0
-#endif
-constexpr int FACTOR_ABLATE = ENLSIP_FACTOR_ABLATE;
-#ifdef ENLSIP_FACTOR_STAMPS     // harness only: phase stamps (100 MHz) of one workgroup
-__device__ long long g_factor_stamps[16];
-#define FACTOR_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x == 3 && blockIdx.y == 7 && threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); g_factor_stamps[i] = wall_clock64(); } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define FACTOR_STAMP(i) do { } while (0)
-#endif
 // The factorisation of one group with the tile in registers.  PRE = true: x already holds the tile (the fused small-problem
 // kernel gn_kernels_small_fused.hpp hands it over without the round trip through HBM).
 // All-reduce of the LAST `live` entries of dot (the columns of a wave that are still being updated), smallest transposed butterfly
@@ -160,8 +147,6 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
     const int w = __builtin_amdgcn_readfirstlane(wave_id());
     double* W = a.W + prob * a.sW;
     const bool tri = a.level > 0;
-
-    FACTOR_STAMP(0);
     if (GRAM)
         for (int e = threadIdx.x; e < PB * (PB + 1); e += NT) (&gsh[0][0])[e] = 0.0;
     if (threadIdx.x < PB) taush[threadIdx.x] = 0.0;
@@ -196,11 +181,10 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
         }
     }
     __syncthreads();
-    FACTOR_STAMP(1);
 
 #pragma unroll
     for (int jj = 0; jj < NC; ++jj) {
-        for (int jw = 0; jw < (FACTOR_ABLATE == 5 ? 0 : NW); ++jw) {
+        for (int jw = 0; jw < NW; ++jw) {
             int lnl = ln;                      // opaque per-iteration copy: keeps LICM from hoisting (and spilling) the row masks
             asm volatile("" : "+v"(lnl));
             const int j = NW * jj + jw;  // wave-uniform
@@ -214,9 +198,9 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
                     double xn2 = (lnl > dj) ? x[jj][0] * x[jj][0] : 0.0;
 #pragma unroll
                     for (int i = 1; i < RPL; ++i) xn2 += x[jj][i] * x[jj][i];
-                    if (FACTOR_ABLATE != 1) xn2 = wave_allsum(xn2);
-                    const double alpha = (FACTOR_ABLATE == 1) ? x[jj][0] : wave_bcast(x[jj][0], dj);
-                    const Reflector h = (FACTOR_ABLATE == 1) ? Reflector{0.5 * alpha, 1.5, 0.25 * xn2} : make_reflector(alpha, xn2);
+                    xn2 = wave_allsum(xn2);
+                    const double alpha = wave_bcast(x[jj][0], dj);
+                    const Reflector h = make_reflector(alpha, xn2);
                     {
                         const double v = (lnl > dj) ? x[jj][0] * h.scale : (lnl == dj ? 1.0 : 0.0);
                         vsh[buf][lnl] = v;
@@ -230,7 +214,7 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
                     }
                     if (lnl == 0) taush[j] = h.tau;
                 }
-                if (FACTOR_ABLATE != 4) __syncthreads();
+                __syncthreads();
                 double v[RPL];
 #pragma unroll
                 for (int i = 0; i < RPL; ++i) v[i] = vsh[buf][lnl + 64 * i];
@@ -242,14 +226,11 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
                     dot[cc] = 0.0;
                     if (cc >= cc_lo) {
 #pragma unroll
-                        for (int i = 0; i < (FACTOR_ABLATE == 6 ? 1 : RPL); ++i) dot[cc] += x[cc][i] * v[i];
+                        for (int i = 0; i < RPL; ++i) dot[cc] += x[cc][i] * v[i];
                     }
                 }
                 double ds[NC];
-                if (FACTOR_ABLATE == 2) {
-#pragma unroll
-                    for (int cc = 0; cc < NC; ++cc) ds[cc] = dot[cc];
-                } else if (GRAM) wave_allsumN(dot, ds);     // NC reductions sharing one transposed butterfly
+                if (GRAM) wave_allsumN(dot, ds);     // NC reductions sharing one transposed butterfly
                 else wave_allsum_last<NC>(dot, ds, NC - jj);
 #pragma unroll
                 for (int cc = 0; cc < NC; ++cc) {
@@ -258,7 +239,7 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
                     if (c > j) {
                         const double wd = tj * ds[cc];
 #pragma unroll
-                        for (int i = 0; i < (FACTOR_ABLATE == 6 ? 1 : RPL); ++i) x[cc][i] -= wd * v[i];
+                        for (int i = 0; i < RPL; ++i) x[cc][i] -= wd * v[i];
                     } else if (GRAM && c < j) {
                         // Gram entry v_c' v_j for the T factor: rows above slot j are masked by
                         // v (zero there), so the R entries held in x[cc] do not contribute
@@ -269,7 +250,6 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
         }
     }
     __syncthreads();
-    FACTOR_STAMP(2);
     // store the tile back (V below / R on and above the diagonal; tree levels: upper triangles).  The lane's slot geometry is formed
     // AGAIN here, from an opaque copy of the lane index: kept from the load phase, the 64-bit lane offset and the row masks stayed
     // live across the step loop — 27 of the 126 registers of the 8-wave form (now 99; the 4-wave forms 207 -> 171 and 124 -> 101).
@@ -290,7 +270,6 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
             }
         }
     }
-    FACTOR_STAMP(3);
     // T factor (dlarft forward/columnwise) by wave 0: lanes r and r + 32 build row r, each holding every second entry of it
     if (!GRAM) {
         if (w == 0) {                // diag(T) = tau, zeros elsewhere (lane r + 32 hh writes every second entry of row r)
@@ -307,7 +286,7 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
                 T[r + j * PB] = (r == j) ? tr : 0.0;
             }
         }
-    } else if (w == 0 && FACTOR_ABLATE != 3) {
+    } else if (w == 0) {
         double* T = a.Tbuf + prob * a.sT + (a.tOff + g) * (long long)(PB * PB);
         // Row r of T in registers, loops fully unrolled and branch-free: T is upper triangular, so trow[l] = 0 for l < r and the
         // plain sum over l < j is the dlarft sum over r <= l < j; gsh / taush are zero where no reflector exists.  (A lane-bounded
@@ -332,7 +311,6 @@ __device__ __forceinline__ void caqr_factor_core(const CaqrArgs& a, const int pr
             if ((j & 1) == hh) T[r + j * PB] = tv;
         }
     }
-    FACTOR_STAMP(4);
 }
 
 template <int RPL, int NW>

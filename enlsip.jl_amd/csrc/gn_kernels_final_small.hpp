@@ -14,12 +14,6 @@ namespace gn {
 // LDS (doubles): tmp[kpm * 65] vbuf[64] dg[64] pbuf[nv]
 inline size_t final_small_lds_bytes(int kpm, int nv) { return (size_t)(kpm * 65 + 64 + 64 + nv + 8) * 8; }
 
-#ifdef GN_PS_STAMPS   // timing-only build: phase stamps (100 MHz wall clock) of problem 0 in the last entries of d_out
-#define GN_PS_STAMP(i) do { if (prob == 0 && ln == 0 && a.d_out) stamps[i] = (double)wall_clock64(); } while (0)
-#else
-#define GN_PS_STAMP(i) do { } while (0)
-#endif
-
 template <int NR>
 #ifndef ENLSIP_PS_OCC
 #define ENLSIP_PS_OCC 0           // measured: 4 waves per SIMD (128 registers, 120 B scratch) more than doubles the kernel's time
@@ -29,7 +23,6 @@ template <int NR>
 #endif
 __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : ((NR == 64 && ENLSIP_PS64_OCC) ? ENLSIP_PS64_OCC : 1)) void k_pivot_small(FinalArgs a) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    double stamps[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const int prob = listed_prob(a.plist, blockIdx.x, a.prob0);
     ProbState* stp = a.state + prob;
     const int rankA = stp->rankA, n2 = stp->n2, kp = stp->kp;
@@ -51,7 +44,6 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : (
     const int ln = threadIdx.x;
     int status = 0;
 
-    GN_PS_STAMP(0);
     // ---- R0 (upper trapezoid) and z: columns through LDS so that the global loads run along rows ---------------
     // 32 independent loads in flight, then 32 LDS writes (the column registers are not live yet): with eight per round the 57
     // columns of a C3 problem were eight HBM round trips in a row, 21 us of the kernel's 119
@@ -89,9 +81,7 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : (
     q.rows = kp; q.k = kp; q.ncand = n2; q.npart = n2 + 1;
     q.tmp = tmp; q.vbuf = vbuf; q.dg = dg; q.F = Rt; q.ldf = ldr; q.tau = tauJ;
     int mypos = ln;
-    GN_PS_STAMP(1);
     if (kp > 0) wave_qrcp<NR, false>(x, q, ln, mypos);
-    GN_PS_STAMP(2);
 
     // ---- permutation, upper parts of the columns, rank ---------------------------------------------------------------
     if (ln < n2) jpvtJ[mypos] = ln + 1;
@@ -105,7 +95,6 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : (
     const int rankJ2 = wave_pseudo_rank(dg, kp, a.eps_rank, ln, pseudo_rank_abs_threshold(a.eps_rank, a.abs_shift));
     int dimJ2 = (a.dimJ2_override >= 0) ? a.dimJ2_override : rankJ2;
     dimJ2 = dimJ2 < kp ? dimJ2 : kp;      // as k_pivot_solve: never past the factor
-    GN_PS_STAMP(3);
 
     // ---- dp2 = U(Rt[1:dimJ2,1:dimJ2]) \ d[1:dimJ2]: lane r carries row r of the right-hand side ------------------------
     double zw = (ln < dimJ2 && ln < kp) ? tmp[ln * 65 + n2] : 0.0;
@@ -120,7 +109,6 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : (
         if (ln < i) zw -= tmp[ln * 65 + li] * yi;
     }
     status = __any(status) ? 1 : 0;
-    GN_PS_STAMP(4);
     // y = [p1 ; p2],  p2[pJ[i]-1] = (i < dimJ2 ? dp2[i] : 0)
     for (int i = ln; i < rankA; i += WAVE) pbuf[i] = p1[i];
     if (ln < n2) pbuf[rankA + lp] = (ln < dimJ2) ? zw : 0.0;
@@ -130,7 +118,6 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : (
     else if (n <= 128) wave_apply_reflectors_reg<false, 2>(FA, n, tauA, kA, n, pbuf);
     else wave_apply_reflectors<false>(FA, n, tauA, kA, n, pbuf);
     wave_mem_sync();
-    GN_PS_STAMP(5);
     if (a.p_out)
         for (int i = ln; i < n; i += WAVE) a.p_out[prob * a.sPo + i] = pbuf[i];
     if (a.b_out)
@@ -149,11 +136,6 @@ __global__ __launch_bounds__(64, (NR == 32 && ENLSIP_PS_OCC) ? ENLSIP_PS_OCC : (
         stp->dimJ2 = dimJ2;
         stp->status |= status;
     }
-#ifdef GN_PS_STAMPS
-    GN_PS_STAMP(6);
-    if (prob == 0 && ln == 0 && a.d_out)
-        for (int i = 0; i < 7; ++i) a.d_out[m - 8 + i] = stamps[i];
-#endif
 }
 
 

@@ -29,16 +29,6 @@
 #ifndef ENLSIP_JQ1_PREFETCH_VT
 #define ENLSIP_JQ1_PREFETCH_VT 1
 #endif
-#ifndef ENLSIP_JQ1_ABLATE
-#define ENLSIP_JQ1_ABLATE 0     // timing-only ablations for tests/microbench/jq1_bench.hip: 1 = no MFMAs, 2 = no J loads / W stores,
-#endif                          // 3 = no V staging (wrong results in every non-zero mode)
-
-#ifdef ENLSIP_JQ1_STAMPS        // harness only: phase stamps (100 MHz) of a few sample workgroups
-__device__ long long g_jq1_stamps[8 * 8];
-#define JQ1_STAMP(i) do { if (blockIdx.x == 37 && (blockIdx.y & 31) == 3 && blockIdx.y < 256 && threadIdx.x == 0) g_jq1_stamps[(blockIdx.y >> 5) * 8 + (i)] = wall_clock64(); } while (0)
-#else
-#define JQ1_STAMP(i) do { } while (0)
-#endif
 
 namespace gn {
 
@@ -105,8 +95,6 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
     const int w = __builtin_amdgcn_readfirstlane(wave_id());
     const int lr = ln & 15, lq = ln >> 4;
     double* Vs = ush + w * Q2_VS;
-
-    JQ1_STAMP(0);
     // ---- J tiles -> registers (shape restrictions of launch_jq1_v2: every tile and every row pair exists) -------
     // addresses = wave-uniform base + one 32-bit lane offset (saddr + voffset form, no 64-bit address registers)
     const unsigned jlane = (unsigned)(((size_t)lq * a.ldj + NP * lr) * 8);     // row (pair) NP lr, column lq of a 4-column step
@@ -127,9 +115,7 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
         for (int r = 0; r < 4; ++r)
         {
             const char* src = (const char*)(Jin + (size_t)(16 * (w + Q2_NW * T) + 4 * r) * a.ldj + row0) + jlane;
-            if (ENLSIP_JQ1_ABLATE == 2) {
-                jt[T][r][0] = (double)tid; jt[T][r][NP - 1] = 1.0;
-            } else if (NP == 2) {
+            if (NP == 2) {
                 const v4_d2 x = __builtin_nontemporal_load((const v4_d2*)src);     // J is streamed once
                 jt[T][r][0] = x[0];
                 jt[T][r][NP - 1] = x[1];
@@ -145,12 +131,10 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
         const int rp = ln & 7, jc = ln >> 3;
         const unsigned vlane = (unsigned)(((size_t)jc * n + 2 * rp) * 8);
         auto fetch_v = [&](int tile, v4_d2 (&x)[8]) {
-            if (ENLSIP_JQ1_ABLATE == 3) return;
 #pragma unroll
             for (int q = 0; q < 8; ++q) x[q] = *(const v4_d2*)((const char*)(FA + (size_t)(c0 + 8 * q) * n + 16 * tile) + vlane);
         };
         auto put_v = [&](int tile, const v4_d2 (&x)[8]) {
-            if (ENLSIP_JQ1_ABLATE == 3) return;
             const int gr = 16 * tile + 2 * rp;
             if (16 * tile >= c0 + KBLK) {          // tile below the trapezoid's triangle (wave-uniform): V is dense there
 #pragma unroll
@@ -167,12 +151,10 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
             }
         };
         auto fetch_vt = [&](int tile, v4_d2 (&x)[8]) {     // the same tile of Vt = V T' (dense: no structure to mask in)
-            if (ENLSIP_JQ1_ABLATE == 3) return;
 #pragma unroll
             for (int q = 0; q < 8; ++q) x[q] = *(const v4_d2*)((const char*)(VT + (size_t)(8 * q) * n + 16 * tile) + vlane);
         };
         auto put_vt = [&](int tile, const v4_d2 (&x)[8]) {
-            if (ENLSIP_JQ1_ABLATE == 3) return;
 #pragma unroll
             for (int q = 0; q < 8; ++q) *(v4_d2*)&Vs[(jc + 8 * q) * Q2_LDV + 2 * rp] = x[q];
         };
@@ -181,7 +163,6 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
             return T < NTW && 16 * tile + 15 >= c0;
         };
         // ---- phase 1: per-wave partial W1 = J V_b over the wave's tiles --------------------------------
-        JQ1_STAMP(1);
         mfma_d4 acc[NP][4];
 #pragma unroll
         for (int p = 0; p < NP; ++p)
@@ -206,8 +187,7 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
                         for (int p = 0; p < NP; ++p) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r)
-                                if (ENLSIP_JQ1_ABLATE == 1) acc[p][jg][r] += jt[T][r][p] + bv[r];
-                                else acc[p][jg] = __builtin_amdgcn_mfma_f64_16x16x4f64(jt[T][r][p], bv[r], acc[p][jg], 0, 0, 0);
+                                acc[p][jg] = __builtin_amdgcn_mfma_f64_16x16x4f64(jt[T][r][p], bv[r], acc[p][jg], 0, 0, 0);
                             __builtin_amdgcn_sched_barrier(0);     // keep the chain of 4 on one accumulator together
                         }
                     }
@@ -219,13 +199,11 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
         }
         // ---- phase 2: W1 = sum over waves (slots of waves 4..7, then += waves 0..3), W2 = -W1 T_b ------------
         // partial layout: lane-linear, index ((p * 4 + jg) * 4 + r) * 64 + ln
-        JQ1_STAMP(2);
         // the first Vt tile of phase 3 travels during the reduction (it used to be requested after it: one exposed L2 round trip
         // per workgroup)
         v4_d2 vx3[8];
         if (ENLSIP_JQ1_PREFETCH_VT && tile_on(0)) fetch_vt(w, vx3);
         __syncthreads();                                   // every wave is done with its V image
-        JQ1_STAMP(3);
         {
             double* ps = ush + (w % NS) * Q2_PS;
             if (w >= NS) {
@@ -263,7 +241,6 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
                 }
         }
         __syncthreads();
-        JQ1_STAMP(4);
         __builtin_amdgcn_sched_barrier(0);
         // ---- phase 3: tile^T += V_b W2^T  (D^T[i = column lq + 4 r][j = row pair lr]) -------------------------
         {
@@ -306,8 +283,7 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
                         for (int p = 0; p < NP; ++p) {
 #pragma unroll
                             for (int k4 = 0; k4 < 4; ++k4)
-                                if (ENLSIP_JQ1_ABLATE == 1) fr[p][k4] += av[k4] + bw[p][k4];
-                                else fr[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[k4], bw[p][k4], fr[p], 0, 0, 0);
+                                fr[p] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[k4], bw[p][k4], fr[p], 0, 0, 0);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
@@ -321,7 +297,6 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        JQ1_STAMP(5);
         __syncthreads();      // W2s and the V images are rewritten by the next block
     }
 
@@ -338,8 +313,7 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             char* dst = (char*)(W + (size_t)(16 * (w + Q2_NW * T) + 4 * r) * ldw + row0) + wlane;   // W 256-byte aligned
-            if (ENLSIP_JQ1_ABLATE == 2) { if (jt[T][r][0] == 1.2345) *(double*)dst = 0.0; }
-            else if (NP == 2) __builtin_nontemporal_store((v4_d2){jt[T][r][0], jt[T][r][NP - 1]}, (v4_d2*)dst);
+            if (NP == 2) __builtin_nontemporal_store((v4_d2){jt[T][r][0], jt[T][r][NP - 1]}, (v4_d2*)dst);
             else *(double*)dst = jt[T][r][0];
         }
 #pragma unroll
@@ -356,7 +330,6 @@ __global__ __launch_bounds__(64 * Q2_NW, 2) void k_jq1_v2(JQ1Args a) {
         for (int q = 0; q < Q2_NW; ++q) s += dred[q][tid];
         W[row + (size_t)n * ldw] = -s - rxv;
     }
-    JQ1_STAMP(6);
 }
 
 // The second form is the straight-line fast path for regular shapes: n a multiple of 128 (<= 512), m a multiple of

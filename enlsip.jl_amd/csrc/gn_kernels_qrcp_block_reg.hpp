@@ -17,12 +17,6 @@
 
 namespace gn {
 
-#ifdef ENLSIP_SB_STEP_STAMPS     // diagnostic build only (tests/probes/sb_step_probe.py): phase times of a pivot step, summed over the steps of wave 0 of problem prob0 (g_sb_phase: gn_kernels_qrcp_block.hpp)
-#define SB_PH(i) do { __builtin_amdgcn_sched_barrier(0); if (sb_st) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const long long t_ = wall_clock64(); sb_acc[i] += t_ - sb_t; sb_t = t_; } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define SB_PH(i) do { } while (0)
-#endif
-
 struct SbRegLds {             // bookkeeping of a block: keys, positions, candidates, the block's Gram / T entries
     double valk[SB_NMAX];
     int posk[SB_NMAX];
@@ -85,20 +79,9 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
     int* colat = a.q.colat + prob * 2 * a.q.sI;
     const double tol3z = 1.4901161193847656e-08;
 
-#ifdef ENLSIP_SB_STEP_STAMPS
-    long long bl_t = wall_clock64();
-    auto stamp = [&](int i) {        // block-level phases: time since the previous stamp -> g_sb_blk[i]
-        if (tid == 0 && prob == a.q.prob0) {
-            const long long t_ = wall_clock64();
-            atomicAdd((unsigned long long*)&g_sb_blk[i], (unsigned long long)(t_ - bl_t));
-            bl_t = t_;
-        }
-    };
-#else
     auto stamp = [&](int i) {
         if (a.dbg && tid == 0 && prob == a.q.prob0) a.dbg[a.blkid * 8 + i] = (long long)__builtin_amdgcn_s_memrealtime();
     };
-#endif
     stamp(0);
     // ---- 1. keys of the trailing columns --------------------------------------------------------
     for (int c = tid; c < n2; c += NT) {
@@ -287,14 +270,6 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
         am = search(0, ln);
         go = certain(am, 0);
     }
-#ifdef ENLSIP_SB_STEP_STAMPS
-#ifndef ENLSIP_SB_STAMP_WAVE
-#define ENLSIP_SB_STAMP_WAVE 0
-#endif
-    const bool sb_st = tid == 64 * ENLSIP_SB_STAMP_WAVE && prob == a.q.prob0;
-    long long sb_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    long long sb_t = wall_clock64();
-#endif
     while (go) {
         // opaque per-iteration copies of the lane / wave ids: without them loop-invariant code motion hoists every row
         // mask and LDS address of the unrolled columns out of the loop and spills them
@@ -334,9 +309,7 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
                 }
             }
         }
-        SB_PH(0);       // owner's part (wave 0 owns every 8th pivot)
         __syncthreads();
-        SB_PH(1);       // wait for the owner
         double v[RPL];
 #pragma unroll
         for (int i = 0; i < RPL; ++i) v[i] = L.vsh[rd][lnl + 64 * i];
@@ -360,7 +333,6 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
             for (int i = 0; i < RPL; ++i) dot[cc] += x[cc][i] * v[i];
         }
         wave_allsumN(dot, ds);
-        SB_PH(2);       // LDS reads, dot products, reduction
         // apply the reflector to the active candidates, WITHOUT branches per column: a column that is not live (slot beyond K,
         // the pivot itself, retired earlier) gets the factor 0 — 56 independent FMAs the scheduler can interleave instead of
         // eight compare / branch / multiply / update / broadcast sequences one behind the other (the column loop was the
@@ -400,7 +372,6 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
             const int aa = (-1 - pk_u) - j0;
             if (aa >= 0 && aa < 32 && s < 32) L.gram[aa * 33 + s] = dsu;
         }
-        SB_PH(3);       // column loop: updates, pivot-row entries, Gram entries
         // dlaqp2 norm downdate of the wave's active columns as ONE instruction stream: lane u < NCW <-> column u
         {
             const bool mine = mine_col && pk_u >= 0;
@@ -432,10 +403,9 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
             }
             if (mine) L.cvn1[wr][ku] = o1;
         }
-        SB_PH(4);       // norm downdate
         // position bookkeeping (wave 0): pivot at position q <-> column cj that sat at position j.  Wave 0 has the time: the two
         // waves of a SIMD share its issue slots and the older one (waves 0..3) has priority, so waves 4..7 reach the barrier
-        // ~0.5 us later anyway (phase stamps per wave, tests/probes/sb_step_probe.py); done by the owner's neighbour under the owner's
+        // ~0.5 us later anyway (measured with per-wave phase clocks); done by the owner's neighbour under the owner's
         // reflector construction instead, the step takes the same time.
         if (wl == 0) {
             const int pc = L.ccol[ci];
@@ -454,23 +424,14 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
                 L.pos_l[pc] = j;
             }
         }
-        SB_PH(5);       // bookkeeping
         __syncthreads();
-        SB_PH(6);       // wait for the slowest wave
         ++s;
         go = (j0 + s < kp) && (s < smax);
         if (go) {
             am = search(s, lnl);
             go = certain(am, s);
         }
-        SB_PH(7);       // pivot search of the next step
     }
-#ifdef ENLSIP_SB_STEP_STAMPS
-    if (sb_st) {
-        for (int i = 0; i < 8; ++i) atomicAdd((unsigned long long*)&g_sb_phase[i], (unsigned long long)sb_acc[i]);
-        atomicAdd((unsigned long long*)&g_sb_phase[8], (unsigned long long)s);
-    }
-#endif
     const int fin = s & 1;   // buffer holding the state after the last completed step
     stamp(3);
     // ---- 4b. T factor (dlarft, forward / columnwise) from the Gram entries gathered during the steps -------------
@@ -561,10 +522,6 @@ __global__ __launch_bounds__(64 * NWV, RPL <= 2 ? 4 : (RPL <= 4 ? 3 : 2)) void k
         SbInfo o = {j0 + s, s, a.blkid, j0, nact, {0, 0, 0}};
         *info = o;
     }
-#ifdef ENLSIP_SB_STEP_STAMPS
-    stamp(5);
-    if (tid == 0 && prob == a.q.prob0) atomicAdd((unsigned long long*)&g_sb_blk[7], 1ull);
-#endif
 }
 
 }  // namespace gn

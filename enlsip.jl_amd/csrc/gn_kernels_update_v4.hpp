@@ -44,19 +44,6 @@ typedef double v4_d4 __attribute__((ext_vector_type(4)));
 typedef v4_d4 mfma_d4;   // name used by the other MFMA kernels
 typedef double v4_d2 __attribute__((ext_vector_type(2)));
 
-#ifndef ENLSIP_V4_ABLATE
-#define ENLSIP_V4_ABLATE 0
-#endif
-// timing experiments only (results wrong when != 0): 2 no V loads, 3 no C traffic, 4 no MFMA, 5 MFMA only, 6 no C stores, 7 no C loads
-constexpr int V4_ABLATE = ENLSIP_V4_ABLATE;
-#ifdef ENLSIP_V4_STAMPS         // harness only (tests/microbench/update_bench.hip): phase stamps (100 MHz) of sample workgroups
-__device__ long long g_v4_stamps[8 * 8];
-__device__ int g_v4_stamp_x = 3;      // group index (blockIdx.x) of the sampled workgroups (tree levels with one group: 0)
-#define V4_STAMP(i) do { __builtin_amdgcn_sched_barrier(0); if (blockIdx.x == g_v4_stamp_x && blockIdx.y == 5 && (blockIdx.z & 31) == 7 && blockIdx.z < 256 && threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); g_v4_stamps[(blockIdx.z >> 5) * 8 + (i)] = wall_clock64(); } __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define V4_STAMP(i) do { } while (0)
-#endif
-
 #ifndef ENLSIP_V4_PREFETCH_NEXT
 #define ENLSIP_V4_PREFETCH_NEXT 1
 #endif
@@ -200,10 +187,7 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (V4_ABLATE == 3 || V4_ABLATE == 5 || V4_ABLATE == 7) cp[g][ct][r] = (v4_d2){(double)(g + r), (double)ct};
-                else cp[g][ct][r] = __builtin_nontemporal_load((const v4_d2*)cptr(g, ct, r));   // streamed once: keep it out of L2's way
-            }
+            for (int r = 0; r < 4; ++r) cp[g][ct][r] = __builtin_nontemporal_load((const v4_d2*)cptr(g, ct, r));   // streamed once: keep it out of L2's way
     };
     auto finish_c = [&](int g) {
         if (CFULL) return;
@@ -220,10 +204,7 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
     // V operands are fetched in halves of 4 contraction steps: vh[k4] = V[row pair][vcol 16 h + 4 k4 + lq]
     auto issue_v = [&](int ai, int g, int h, v4_d2 (&vh)[4]) {
 #pragma unroll
-        for (int k4 = 0; k4 < 4; ++k4) {
-            if (V4_ABLATE == 2 || V4_ABLATE == 5) vh[k4] = (v4_d2){(double)(g + k4), 1.0};
-            else vh[k4] = *(const v4_d2*)vptr(ai, g, 4 * h + k4);
-        }
+        for (int k4 = 0; k4 < 4; ++k4) vh[k4] = *(const v4_d2*)vptr(ai, g, 4 * h + k4);
     };
     // lrx / lqx: the calling phase's own (opaque) copy of the lane coordinates, so that the masks are recomputed per phase
     // instead of being kept — i.e. spilled — from product 1 to product 2
@@ -267,7 +248,6 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
         asm volatile("" : "+v"(lnp));
         const int lrp = lnp & 15, lqp = lnp >> 4;
         // ---- product 1: per-wave partial W1 = V' C ------------------------------------------------------------
-        if (first_app) V4_STAMP(0);
         v4_d4 acc[2][2];
 #pragma unroll
         for (int it = 0; it < 2; ++it)
@@ -351,16 +331,11 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
 #pragma unroll
                         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                            for (int k4 = 0; k4 < 4; ++k4) {
-                                if (V4_ABLATE == 4) acc[it][ct][k4] += av[it][k4] + bv[ct][k4];
-                                else acc[it][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[it][k4], bv[ct][k4], acc[it][ct], 0, 0, 0);
-                            }
+                            for (int k4 = 0; k4 < 4; ++k4) acc[it][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[it][k4], bv[ct][k4], acc[it][ct], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (first_app) V4_STAMP(1);
-        if (!first_app) V4_STAMP(3);          // pair: product 1 of the second pass done
         constexpr int VBD = ENLSIP_V4_VB_DEPTH;
         v4_d2 vb[VBD][4];                                    // ring over (unit, half)
         if (NGW > 0) issue_v(ai, 0, 0, vb[0]);               // travels during the reduction step
@@ -376,9 +351,7 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
             for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) stage[w][(16 * it + lqr + 4 * r) * PB + 16 * ct + lrr] = acc[it][ct][r];
-        if (first_app && NAP == 1) V4_STAMP(2);
         __syncthreads();
-        if (first_app && NAP == 1) V4_STAMP(3);
         {
             v4_d4 t = (v4_d4){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -393,8 +366,6 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
             for (int r = 0; r < 4; ++r) W2l[(16 * it2 + lqr + 4 * r) * PB + ((16 * ct2 + lrr) ^ (16 * (lqr & 1)))] = -t[r];   // swizzled, see the read
         }
         __syncthreads();
-        if (first_app) V4_STAMP(4);
-        if (!first_app) V4_STAMP(7);          // pair: second reduction done
 
         // ---- product 2: D^T[col][row pair] += W2^T V^T, even and odd rows of each unit; stored by the last pass,
         //      back into the registers otherwise ---------------------------------------------------------------------
@@ -407,9 +378,7 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
             for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if (V4_ABLATE == 3 || V4_ABLATE == 5 || V4_ABLATE == 6) {
-                        if (fr[0][ct][r] == 1.2345e301) c.C[0] = fr[1][ct][r];
-                    } else if (CFULL || ((smask >> (4 * ct + r)) & 1u)) {
+                    if (CFULL || ((smask >> (4 * ct + r)) & 1u)) {
                         if (!RMASK) {
                             if (ENLSIP_V4_NT_STORE) __builtin_nontemporal_store((v4_d2){fr[0][ct][r], fr[1][ct][r]}, (v4_d2*)cptr(g, ct, r));
                             else *(v4_d2*)cptr(g, ct, r) = (v4_d2){fr[0][ct][r], fr[1][ct][r]};
@@ -460,10 +429,7 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
 #pragma unroll
                     for (int p = 0; p < 2; ++p)
 #pragma unroll
-                        for (int k4 = 0; k4 < 4; ++k4) {
-                            if (V4_ABLATE == 4) fr[p][ct][k4] += a2[k4] + vb[u % VBD][k4][p];
-                            else fr[p][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[k4], vb[u % VBD][k4][p], fr[p][ct], 0, 0, 0);
-                        }
+                        for (int k4 = 0; k4 < 4; ++k4) fr[p][ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(a2[k4], vb[u % VBD][k4][p], fr[p][ct], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -472,7 +438,6 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
                 for (int p = 0; p < 2; ++p)
 #pragma unroll
                     for (int ct = 0; ct < 2; ++ct) cf[g][p][ct] = fr[p][ct];
-                if (g == NGW - 1) V4_STAMP(2);   // pair: product 2 of the first pass done
                 continue;
             }
             post(g, fr);
@@ -485,7 +450,6 @@ __device__ __forceinline__ void v4_body(const V4Ctx& c, const int w, double (*st
             __builtin_amdgcn_sched_barrier(0);
         }
     }
-    V4_STAMP(5);
 }
 
 template <int RPL, bool TRI, bool CFULL, int NCT, bool RMASK = false, class Post = V4NoPost, bool GATHER = false, int NAP = 1>
@@ -682,7 +646,6 @@ __global__ __launch_bounds__(256, ENLSIP_V4_CW == 16 ? 3 : 2) void k_caqr_update
     __shared__ __attribute__((aligned(16))) double stage[4][V4_STAGE];   // per-wave transpose images / W1 partials
     __shared__ __attribute__((aligned(16))) double W2l[PB * PB];         // W2 = -T' W1   [k][j]
 
-    V4_STAMP(6);
     if (!TRI && a.skip_rhs && blockIdx.y == gridDim.y - 1) {             // the carried right-hand side of this tile
         v4_rhs_body<RPL, false>(a, reinterpret_cast<double (*)[PB]>(&stage[0][0]), W2l, &stage[1][0], blockIdx.x);
         return;
@@ -709,7 +672,6 @@ __global__ __launch_bounds__(256, 2) void k_caqr_update_v4_pair(CaqrArgs a) {
     __shared__ __attribute__((aligned(16))) double stage[4][V4_STAGE];
     __shared__ __attribute__((aligned(16))) double W2l[PB * PB];
 
-    V4_STAMP(6);
     // Grid.  Batches: x = tile, y = column block, z = problem — the 8 tiles x ~13 column blocks of a problem are consecutive
     // workgroups and share the tile's V out of the XCD's L2.  ONE problem with hundreds of tiles (a.xmap: C4, a 32768-row shard):
     // in that order the 13 uses of a tile's V lie 511 workgroups = 131 MB of other tiles' V apart, every one of them a miss of the

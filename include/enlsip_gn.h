@@ -1214,10 +1214,9 @@ enum {
 };
 int enlsip_gn_get_route(enlsip_gn_handle h, uint64_t* mask);
 const char* enlsip_gn_route_name(int bit);
-/* Debugging aid (tests/probes/pair_probe_w*.py): copies the working matrix W of problem `prob` (ldw x (n + 1): J*Q1 with the CAQR factors of
- * [J2 | d] in place) as it stands to host memory; *ldw_out = its leading dimension; -3 when cap_doubles is too small.  Together with
- * ENLSIP_GN_DEBUG_MAXPAN / ENLSIP_GN_DEBUG_STAGE (stop the CAQR sweep after so many panels / inside the first pair) this is how an
- * orthogonality defect is located stage by stage. */
+/* Debugging aid: copies the working matrix W of problem `prob` (ldw x (n + 1): J*Q1 with the CAQR factors of [J2 | d] in place) as
+ * it stands after the last solve to host memory; *ldw_out = its leading dimension; -3 when cap_doubles is too small.  Comparing
+ * the copies of two handles (ENLSIP_GN_PAIR=0 against the default, say) locates a defect of the sweep panel by panel. */
 int enlsip_gn_debug_copy_W(enlsip_gn_handle h, int64_t prob, double* out, int64_t* ldw_out, int64_t cap_doubles);
 
 #ifdef __cplusplus

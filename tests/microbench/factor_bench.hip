@@ -1,7 +1,6 @@
 // Timing harness for the panel factorisation of the CAQR (k_caqr_factor<8,8>, gn_kernels_caqr.hpp) on the C2 geometry: `batch`
-// problems x 8 tiles of 512 x 32, timed with HIP events; the timing-only ablations (-DENLSIP_FACTOR_ABLATE=1..6, see the kernel
-// header) say where a step's time goes, -DENLSIP_FACTOR_STAMPS adds wall-clock stamps of one workgroup's phases.
-// Build: hipcc --offload-arch=gfx950 -O3 -w -std=c++17 -DENLSIP_GN_LAB -I enlsip.jl_amd/csrc -o tests/microbench/factor_bench tests/microbench/factor_bench.hip
+// problems x 8 tiles of 512 x 32, timed with HIP events.
+// Build: hipcc --offload-arch=gfx950 -O3 -w -std=c++17 -I enlsip.jl_amd/csrc -o tests/microbench/factor_bench tests/microbench/factor_bench.hip
 // Run  : factor_bench [batch=384] [tiles=8]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -48,12 +47,7 @@ int main(int argc, char** argv) {
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         if (r > 0) tot += ms;
     }
-    printf("ablate %d: k_caqr_factor<8,8> %d tiles x %d problems: %.1f us per launch (%.2f us per tile-slot round of 512)\n", ENLSIP_FACTOR_ABLATE,
+    printf("k_caqr_factor<8,8> %d tiles x %d problems: %.1f us per launch (%.2f us per tile-slot round of 512)\n",
            tiles, batch, 1e3 * tot / reps, 1e3 * tot / reps / ((double)tiles * batch / 512.0));
-#ifdef ENLSIP_FACTOR_STAMPS
-    long long st[16];
-    CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_factor_stamps), sizeof(st)));
-    printf("stamps of workgroup (3, 7) [us]: load %.2f  loop %.2f  store %.2f  T %.2f\n", (st[1] - st[0]) * 0.01, (st[2] - st[1]) * 0.01, (st[3] - st[2]) * 0.01, (st[4] - st[3]) * 0.01);
-#endif
     return 0;
 }

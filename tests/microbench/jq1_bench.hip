@@ -1,6 +1,5 @@
 // Stand-alone timing harness for k_jq1_v2 (gn_kernels_q1_v2.hpp) on synthetic data with the C2 geometry.
 // Build: hipcc --offload-arch=gfx950 -O3 -w -std=c++17 -I enlsip.jl_amd/csrc -o tests/microbench/jq1_bench tests/microbench/jq1_bench.hip
-//        (-DENLSIP_JQ1_ABLATE=1|2|3: timing-only ablations, see the kernel)
 // Run  : jq1_bench [batch=256]
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -35,13 +34,5 @@ int main(int argc, char** argv) {
     float ms; hipEventElapsedTime(&ms, e0, e1); ms /= 5;
     const double flop = 4.0 * m * n * t * batch, bytes = 16.0 * m * n * batch;
     printf("k_jq1_v2 batch %d: %.3f ms  %.1f TFLOP/s  %.2f TB/s  (%s)\n", batch, ms, flop / ms * 1e-9, bytes / ms * 1e-9, hipGetErrorString(hipGetLastError()));
-#ifdef ENLSIP_JQ1_STAMPS
-    long long st[64];
-    CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_jq1_stamps), sizeof(st)));
-    for (int g = 0; g < 8; ++g)
-        printf("wg (37, %3d): load-issue %5.2f us | phase1 %5.2f | wait %5.2f | reduce+T %5.2f | phase3 %5.2f | store+d %5.2f | total %5.2f\n", 32 * g + 3,
-               (st[g*8+1]-st[g*8])*0.01, (st[g*8+2]-st[g*8+1])*0.01, (st[g*8+3]-st[g*8+2])*0.01, (st[g*8+4]-st[g*8+3])*0.01,
-               (st[g*8+5]-st[g*8+4])*0.01, (st[g*8+6]-st[g*8+5])*0.01, (st[g*8+6]-st[g*8])*0.01);
-#endif
     return 0;
 }

@@ -2,9 +2,7 @@
 // (gn_kernels_update_v4.hpp) on synthetic data with the C2 geometry; the reflector-by-reflector kernel
 // of gn_kernels_caqr.hpp is timed beside it.  The check recomputes C - V (T' (V' C)) in plain host loops
 // for sampled columns of problem 0.
-// Build: hipcc --offload-arch=gfx950 -O3 -w -std=c++17 -DENLSIP_GN_LAB -I enlsip.jl_amd/csrc -o tests/microbench/update_bench tests/microbench/update_bench.hip
-//        (-DENLSIP_V4_ABLATE=2|3|4|5 for the timing-only ablations documented in the kernel header, -DENLSIP_V4_STAMPS for
-//        per-phase wall-clock stamps of sample workgroups; the stamps themselves cost ~25 %)
+// Build: hipcc --offload-arch=gfx950 -O3 -w -std=c++17 -I enlsip.jl_amd/csrc -o tests/microbench/update_bench tests/microbench/update_bench.hip
 // Run  : update_bench [batch=256] [panel=0] [level=0]
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -181,22 +179,7 @@ int main(int argc, char** argv) {
             const float t4 = timeit("pair, far columns", [&] { launch_update_v4(RPL, ap, groups, ntrail - ap.skip_rhs, batch, 0); }, bf);
             printf("  two plain passes %.3f ms   narrow + pair %.3f ms   ratio %.3f\n", t1 + t2, t3 + t4, (t3 + t4) / (t1 + t2));
         }
-#ifdef ENLSIP_V4_STAMPS
-        {
-        // the LAST kernel that ran was the pair's far update: entry 6 -> 0 start -> 1 product 1 (a) -> 4 reduction (a) -> 2 product 2 (a)
-        // -> 3 product 1 (b) -> 7 reduction (b) -> 5 product 2 (b) + stores
-        long long sp[64];
-        CK(hipMemcpyFromSymbol(sp, HIP_SYMBOL(g_v4_stamps), sizeof(sp)));
-        for (int g = 0; g < 8; ++g)
-            printf("PAIR wg (3, 5, %3d): setup %5.2f us | product 1 a %5.2f | reduce a %5.2f | product 2 a %5.2f | product 1 b %5.2f | reduce b %5.2f | product 2 b + stores %5.2f | total %5.2f\n",
-                   32 * g + 7, (sp[g*8+0]-sp[g*8+6])*0.01, (sp[g*8+1]-sp[g*8+0])*0.01, (sp[g*8+4]-sp[g*8+1])*0.01, (sp[g*8+2]-sp[g*8+4])*0.01,
-                   (sp[g*8+3]-sp[g*8+2])*0.01, (sp[g*8+7]-sp[g*8+3])*0.01, (sp[g*8+5]-sp[g*8+7])*0.01, (sp[g*8+5]-sp[g*8+6])*0.01);
-        }
-#endif
     }
-#ifdef ENLSIP_V4_STAMPS
-    if (groups <= 3) { const int zero = 0; CK(hipMemcpyToSymbol(HIP_SYMBOL(g_v4_stamp_x), &zero, sizeof(int))); }
-#endif
     const int reps = 5;
     const double rows_k = (double)nblocks * 32;
     const double bytes = (double)batch * 8.0 * (2.0 * rows_k * ntrail + rows_k * 32);
@@ -212,13 +195,5 @@ int main(int argc, char** argv) {
         printf("%s: %.3f ms / launch   %.0f GB/s algorithmic   (%.2f us per workgroup-slot)\n", which ? "v4  " : "refl", ms, bytes / ms * 1e-6,
                ms * 1e3 / ((double)groups * ((ntrail + 31) / 32) * batch / 256.0));
     }
-#ifdef ENLSIP_V4_STAMPS
-    long long st[64];
-    CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(g_v4_stamps), sizeof(st)));
-    for (int g = 0; g < 8; ++g)
-        printf("wg (3, 5, %3d): setup %5.2f us | product1 (C, V loads + MFMA) %5.2f | partial->LDS %5.2f | barrier %5.2f | T-MFMA + barrier %5.2f | product2 + stores %5.2f | total %5.2f\n",
-               32 * g + 7, (st[g*8+0]-st[g*8+6])*0.01, (st[g*8+1]-st[g*8+0])*0.01, (st[g*8+2]-st[g*8+1])*0.01, (st[g*8+3]-st[g*8+2])*0.01,
-               (st[g*8+4]-st[g*8+3])*0.01, (st[g*8+5]-st[g*8+4])*0.01, (st[g*8+5]-st[g*8+6])*0.01);
-#endif
     return 0;
 }

@@ -72,7 +72,7 @@ addt("lib3_pert1e-13_n640", [t * (1 + 1e-13 * pert.standard_normal(t.shape)) for
 addt("lib3_x2_n640", [2.0 * t for t in lib[:3]], 640)
 addt("lib3_x1.7_n640", [1.7 * t for t in lib[:3]], 640)
 np.savez("/tmp/min_stack.npz", **cases)
-for tag, env in (("plain", {"ENLSIP_GN_PAIR": "0"}), ("pair", {"ENLSIP_GN_PAIR": os.environ.get("PAIR_MODE", "1")})):
+for tag, env in (("plain", {"ENLSIP_GN_PAIR": "0"}), ("pair", {"ENLSIP_GN_PAIR": "1"})):
     e = dict(os.environ); e.update(env)
     subprocess.check_call([sys.executable, __file__, "child", tag], env=e)
 a, b = np.load("/tmp/min_pair.npz"), np.load("/tmp/min_plain.npz")
