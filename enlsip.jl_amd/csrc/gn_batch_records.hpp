@@ -1,7 +1,8 @@
 // The batched calls on the caller's device buffers (gn_deletion_batched.inc, gn_linesearch_batched.inc, gn_penalty_batched.inc,
-// gn_linesearch_fit_batched.inc, gn_addition_batched.inc, gn_termination_batched.inc): the records they upload and download, the checks and the packing of their host arguments, and
+// gn_linesearch_fit_batched.inc, gn_addition_batched.inc, gn_termination_batched.inc, gn_direction_batched.inc): the records they
+// upload and download, the checks and the packing of their host arguments, and
 // their scratch layouts.  Host-only, nothing of HIP: tests/batch_records_check.cpp runs all of it on the CPU
-// (the termination call's check and layout: tests/termination_check.cpp).  The
+// (the termination call's check and layout: tests/termination_check.cpp; the direction check's: tests/direction_check.cpp).  The
 // kernel headers include it for the records.
 #pragma once
 #include <algorithm>
@@ -66,6 +67,12 @@ struct TermMeta {
     double psi0;            // enters progress only
     int t, q, dimJ2;
     int take;               // 0 leaves the problem alone
+};
+
+struct DirMeta {
+    int t, q, dimA, dimJ2;
+    int k_prev;             // entries of d under d1_asprev_sq: max(prev_dimJ2 + prev_t - t - 1, 0), at most m
+    int take;               // 0 leaves the problem alone (not taken, or status 1)
 };
 
 constexpr int LS_SUM_ROWS = 1024;       // rows per partial-sum workgroup until nblk reaches LS_MAX_NBLK
@@ -228,6 +235,41 @@ inline int check_termination(std::string& err, const TerminationShape& s, const 
     if (s.ldat < s.n) return fail(err, -9, "ldat < n");
     if (s.strideJ < s.ldj * s.n) return fail(err, -10, "strideJ < ldj * n");
     if (s.strideAt < s.ldat * s.t_max) return fail(err, -10, "strideAt < ldat * t_max");
+    return 0;
+}
+
+// ---- the direction check: list = [active | inactive] as the termination call's, out = the sums as the header declares them, no
+// partial sums.  Its checks (the codes of include/enlsip_gn.h; tests/direction_check.cpp runs them on the CPU) ------------------------
+using DirectionScratch = RecordScratch<DirMeta, enlsip_gn_dir_sums>;
+struct DirectionShape { int64_t batch, m, n, l, t_max; };
+constexpr int64_t DIR_PREV_MAX = 1LL << 31;      // |prev_dimJ2| (a Newton step leaves t - n there): k_prev cannot overflow
+inline int check_direction(std::string& err, const DirectionShape& s, const enlsip_gn_dir_state* state, const int64_t* active,
+                           const int64_t* inactive, const int64_t* take, bool host_rest, bool dev_m, bool dev_l, bool dev_t) {
+    int rc;
+    if ((rc = check_batch(err, s.batch))) return rc;
+    if (s.m < 0 || s.m > 0x7fffffff) return fail(err, -3, "m must be in 0..2^31-1");
+    if (s.n < 1 || s.n > 0x3fffffff) return fail(err, -3, "n must be at least 1");
+    if (s.l < 0 || s.l > BATCH_MAX_T) return fail(err, -3, "l must be in 0..1024 in this build");
+    if ((rc = check_t_max(err, s.t_max))) return rc;
+    if (s.t_max > s.l) return fail(err, -3, "t_max > l");
+    if (!state || !host_rest) return fail(err, -4, "state, sums, method_code, beta and status are required");
+    if (s.l > 0 && (!active || !inactive)) return fail(err, -4, "active and inactive are host arrays of batch x l entries");
+    if (s.m > 0 && !dev_m) return fail(err, -4, "dd is required when m > 0");
+    if (s.l > 0 && !dev_l) return fail(err, -4, "dcx_all is required when l > 0");
+    if (s.t_max > 0 && !dev_t) return fail(err, -4, "db, dlambda and ddiag_scale are required when t_max > 0");
+    for (int64_t k = 0; k < s.batch; ++k) {      // per problem: the lower k wins; nothing of a problem that is not taken is read
+        if (!take_flag(take, k)) continue;
+        const enlsip_gn_dir_state& st = state[k];
+        if ((rc = check_count(err, -5, "state.t", k, st.t, {0, s.t_max, "0..t_max"})) ||
+            (rc = check_count(err, -5, "state.l", k, st.l, {s.l, s.l, "l"})) ||
+            (rc = check_count(err, -6, "state.q", k, st.q, {0, st.t, "0..t[k]"})) ||
+            (rc = check_list(err, -7, "active", k, active + k * s.l, st.t, {0, s.l, "0..l"})) ||
+            (rc = check_list(err, -7, "inactive", k, inactive + k * s.l, s.l - st.t, {0, s.l, "0..l"})) ||
+            (rc = check_count(err, -8, "state.dimA", k, st.dimA, {0, st.t, "0..t[k]"})) ||
+            (rc = check_count(err, -8, "state.dimJ2", k, st.dimJ2, {0, s.m, "0..m"})) ||
+            (rc = check_count(err, -8, "state.prev_t", k, st.prev_t, {0, s.l, "0..l"})) ||
+            (rc = check_count(err, -8, "state.prev_dimJ2", k, st.prev_dimJ2, {-DIR_PREV_MAX, DIR_PREV_MAX, "-2^31..2^31"}))) return rc;
+    }
     return 0;
 }
 

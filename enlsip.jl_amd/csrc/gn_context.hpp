@@ -265,6 +265,11 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf term_scr;
     gn::PinnedBuf h_term;
     int termination_form = -1;
+    // batched direction check (gn_direction_batched.inc): the records and both index lists of one call on the device and in pinned
+    // memory, the sums per problem, and the form of the last call; nothing resident
+    gn::DevBuf dir_scr;
+    gn::PinnedBuf h_dir;
+    int direction_form = -1;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

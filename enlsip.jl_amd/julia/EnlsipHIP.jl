@@ -923,6 +923,102 @@ function termination_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""what `check_gn_direction` (src/enlsip_functions.jl:943-1030) and the norms of `search_direction_analys` (:1222-1231) read of one
+problem's host records: enlsip_gn_dir_state"""
+struct DirState
+    iter_number::Int64              # :981   iter_number
+    restart::Int64                  # :974   current_iter.restart (0 / 1)
+    add::Int64                      # :983   current_iter.add (0 / 1)
+    del::Int64                      # :983   current_iter.del (0 / 1)
+    q::Int64                        # :998   W.q
+    t::Int64                        # :998   W.t
+    l::Int64                        # :1007  W.l
+    rankA::Int64                    # :1015  current_iter.rankA
+    dimA::Int64                     # :1222  current_iter.dimA
+    dimJ2::Int64                    # :1228  current_iter.dimJ2
+    prev_code::Int64                # :974   previous_iter.code
+    prev_dimJ2::Int64               # :1230  previous_iter.dimJ2
+    prev_t::Int64                   # :1230  previous_iter.t
+    prev_beta::Float64              # :984   previous_iter.β
+    prev_progress::Float64          # :985   previous_iter.progress
+    prev_predicted_reduction::Float64      # :985   previous_iter.predicted_reduction
+    prev_alpha::Float64             # :1020  previous_iter.α
+end
+
+"""the scalars the device forms per problem: enlsip_gn_dir_sums"""
+struct DirSums
+    b1_sq::Float64                  # :1222  dot(b1, b1)
+    d_sq::Float64                   # :1227  dot(d_gn, d_gn)
+    d1_sq::Float64                  # :1228  dot(d1, d1)
+    d1_asprev_sq::Float64           # :1231  the same over d_gn[1:k_prev]
+    active_c_sum::Float64           # :1013  active_cx_sum
+    n_lm_ge::Int64                  # :1004  multipliers of q+1..t with λ_i * rows_i >= -sqrt(eps)
+    n_lm_neg::Int64                 # :1004  multipliers of q+1..t below 0
+    n_inactive_lt_delta::Int64      # :1009  inactive cx below δ
+end
+
+"""    check_gn_direction_hip(state, sums, m, n) -> (method_code, β)
+
+The decision of `check_gn_direction` (src/enlsip_functions.jl:943-1030) on scalars, through the library's host entry point (no
+handle, no GPU)."""
+function check_gn_direction_hip(state::DirState, sums::DirSums, m::Integer, n::Integer)
+    code = Ref{Int64}(0); β = Ref{Float64}(0.0)
+    rc = @ccall LIB.enlsip_gn_check_gn_direction(Ref(state)::Ptr{DirState}, Ref(sums)::Ptr{DirSums}, m::Int64, n::Int64,
+                                                 code::Ptr{Int64}, β::Ptr{Float64})::Cint
+    rc == 0 || error("enlsip_gn_check_gn_direction returned $rc")
+    return Int(code[]), β[]
+end
+
+"""    direction_sums_hip(state, m, n, active, inactive, b, d, λ, diag_scale, cx_all, scaling) -> (sums, status)
+
+The scalars of the direction check from host arrays of one problem, in the summation order of the kernels
+(enlsip_gn_direction_sums).  `status == 1`: the reference would index `d_gn` past its end (:1231) and `sums` is all zero."""
+function direction_sums_hip(state::DirState, m::Integer, n::Integer, active::Vector{Int64}, inactive::Vector{Int64},
+                            b::Vector{Float64}, d::Vector{Float64}, λ::Vector{Float64}, diag_scale::Vector{Float64},
+                            cx_all::Vector{Float64}, scaling::Bool)
+    sums = Ref(DirSums(0, 0, 0, 0, 0, 0, 0, 0)); status = Ref{Int64}(0); sc = Cint(scaling)
+    rc = GC.@preserve active inactive b d λ diag_scale cx_all @ccall LIB.enlsip_gn_direction_sums(
+        m::Int64, n::Int64, length(cx_all)::Int64, Ref(state)::Ptr{DirState}, pointer(active)::Ptr{Int64},
+        pointer(inactive)::Ptr{Int64}, pointer(b)::Ptr{Float64}, pointer(d)::Ptr{Float64}, pointer(λ)::Ptr{Float64},
+        pointer(diag_scale)::Ptr{Float64}, pointer(cx_all)::Ptr{Float64}, sc::Cint, sums::Ptr{DirSums},
+        status::Ptr{Int64})::Cint
+    rc == 0 || error("enlsip_gn_direction_sums returned $rc")
+    return sums[], Int(status[])
+end
+
+"""    direction_check_batched_dev_hip(h, m, n, l, t_max, states, active, inactive, take, scaling, db, dd, dλ, ddiag_scale, dcx_all)
+        -> (sums, method_code, β, status)
+
+`search_direction_analys` (src/enlsip_functions.jl:1191-1291) up to its branch for `B = length(states)` problems on DEVICE buffers
+in one call: the norms of :1222-1231 and `check_gn_direction`.  `db`, `dd`, `dλ`, `ddiag_scale` are where the solve and the
+multiplier calls left them; `active` / `inactive`: host matrices `l x B`; `take` (`nothing`: all): `take[k] == 0` leaves problem
+`k` alone.  `method_code .== -1` is the take of `subspace_direction_batched_dev`, `method_code .== 2` that of the batched Newton
+direction.  `status[k] == 1`: the reference throws at :1231, no code; `2`: a prefix of `d_gn` reaches past `n - rankA`
+(`d_gn_prefix` would assert)."""
+function direction_check_batched_dev_hip(h::Handle, m::Integer, n::Integer, l::Integer, t_max::Integer, states::Vector{DirState},
+                                         active::Matrix{Int64}, inactive::Matrix{Int64}, take::Union{Nothing,Vector{Int64}},
+                                         scaling::Bool, db::Ptr{Float64}, dd::Ptr{Float64}, dλ::Ptr{Float64},
+                                         ddiag_scale::Ptr{Float64}, dcx_all::Ptr{Float64})
+    B = length(states)
+    (take === nothing || length(take) == B) || error("take must have one entry per problem")
+    (size(active) == (l, B) && size(inactive) == (l, B)) || error("active and inactive are l x B")
+    sums = fill(DirSums(0, 0, 0, 0, 0, 0, 0, 0), B); codes = zeros(Int64, B); β = fill(NaN, B); status = fill(Int64(-1), B)
+    tk = take === nothing ? Ptr{Int64}(C_NULL) : pointer(take); sc = Cint(scaling)
+    GC.@preserve states active inactive take sums codes β status check(h, @ccall LIB.enlsip_gn_direction_check_batched_dev(
+        h.ptr::Ptr{Cvoid}, B::Int64, m::Int64, n::Int64, l::Int64, t_max::Int64, pointer(states)::Ptr{DirState},
+        pointer(active)::Ptr{Int64}, pointer(inactive)::Ptr{Int64}, tk::Ptr{Int64}, sc::Cint, db::Ptr{Float64},
+        dd::Ptr{Float64}, dλ::Ptr{Float64}, ddiag_scale::Ptr{Float64}, dcx_all::Ptr{Float64}, pointer(sums)::Ptr{DirSums},
+        pointer(codes)::Ptr{Int64}, pointer(β)::Ptr{Float64}, pointer(status)::Ptr{Int64})::Cint)
+    return sums, codes, β, status
+end
+
+"""    direction_form_hip(h) -> 0 general, 1 one wave per problem, -1 none yet: the form of the last direction check on `h`"""
+function direction_form_hip(h::Handle)
+    f = Ref{Cint}(0)
+    check(h, @ccall LIB.enlsip_gn_get_direction_form(h.ptr::Ptr{Cvoid}, f::Ptr{Cint})::Cint)
+    return Int(f[])
+end
+
 """    upper_bound_steplength_hip(inactive, n_inactive, index_del, cx, Ap) -> (α_upp, index_α_upp)
 
 `upper_bound_steplength` (src/enlsip_functions.jl:2149-2178) on host data with `Ap = A * p` already formed, through the library's

@@ -5,3 +5,4 @@ from .api import evaluate_violated_constraints, gather_active_constraints  # noq
 from .api import linesearch_coefficients, linesearch_fit, minrn, check_reduction  # noqa: F401
 from ._lib import FACTOR_A, FACTOR_L11, FACTOR_J2, FLAG_UPDATE_MFMA, FLAG_UPDATE_REFLECTORS, LIB_PATH, DIM_HOLD  # noqa: F401
 from .termination import minmax_lagrangian_mult, check_termination_criteria, termination_sums  # noqa: F401
+from .direction import check_gn_direction, direction_sums  # noqa: F401

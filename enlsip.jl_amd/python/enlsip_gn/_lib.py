@@ -56,6 +56,21 @@ class TermSums(C.Structure):
                 ("Atcx_nrm", C.c_double), ("active_penalty_sum", C.c_double), ("whsum", C.c_double), ("progress", C.c_double)]
 
 
+class DirState(C.Structure):
+    """enlsip_gn_dir_state: what check_gn_direction (src/enlsip_functions.jl:943-1030) and the norms of :1222-1231 read of one
+    problem's host records"""
+    _fields_ = [("iter_number", C.c_int64), ("restart", C.c_int64), ("add", C.c_int64), ("del", C.c_int64), ("q", C.c_int64),
+                ("t", C.c_int64), ("l", C.c_int64), ("rankA", C.c_int64), ("dimA", C.c_int64), ("dimJ2", C.c_int64),
+                ("prev_code", C.c_int64), ("prev_dimJ2", C.c_int64), ("prev_t", C.c_int64), ("prev_beta", C.c_double),
+                ("prev_progress", C.c_double), ("prev_predicted_reduction", C.c_double), ("prev_alpha", C.c_double)]
+
+
+class DirSums(C.Structure):
+    """enlsip_gn_dir_sums: the scalars the device forms per problem"""
+    _fields_ = [("b1_sq", C.c_double), ("d_sq", C.c_double), ("d1_sq", C.c_double), ("d1_asprev_sq", C.c_double),
+                ("active_c_sum", C.c_double), ("n_lm_ge", C.c_int64), ("n_lm_neg", C.c_int64), ("n_inactive_lt_delta", C.c_int64)]
+
+
 # enlsip_gn_allgather_fn: int (*)(void* ctx, const void* dsend, void* drecv, size_t bytes_per_rank, void* hip_stream)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -198,6 +213,12 @@ PROTOTYPES = {
                                                     C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, _i64, _i64] + [C.c_void_p] * 10
                                           + [_i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_get_termination_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_check_gn_direction": (C.c_int, [C.POINTER(DirState), C.POINTER(DirSums), _i64, _i64, _ip, _dp]),
+    "enlsip_gn_direction_sums": (C.c_int, [_i64, _i64, _i64, C.POINTER(DirState)] + [C.c_void_p] * 7
+                                 + [C.c_int, C.POINTER(DirSums), _ip]),
+    "enlsip_gn_direction_check_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, _i64] + [C.c_void_p] * 4 + [C.c_int]
+                                              + [C.c_void_p] * 9),
+    "enlsip_gn_get_direction_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

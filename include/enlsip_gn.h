@@ -943,6 +943,94 @@ int enlsip_gn_termination_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t
                                       int64_t* exit_code);
 int enlsip_gn_get_termination_form(enlsip_gn_handle h, int* form);
 
+/* ---- the Gauss-Newton direction check of a batch, on the caller's device buffers ---------------------------------------------
+ * search_direction_analys (src/enlsip_functions.jl:1191-1291) up to its branch: the norms of :1222-1231 and check_gn_direction
+ * (:943-1030).  After a solve b, d, lambda, diag_scale and cx are on the device; this call forms every scalar of the decision
+ * there, brings one 64-byte record per problem down and makes the decision on the host inside the same call.  method_code == -1
+ * is the take of enlsip_gn_subspace_direction_batched_dev, method_code == 2 the take of enlsip_gn_newton_direction_batched_dev.
+ * Callbacks and the Hessian sums of the Newton branch stay with the caller.
+ *
+ * enlsip_gn_check_gn_direction   :943-1030 on scalars, statement for statement, HOST, no handle and no GPU.  b1nrm, d1nrm,
+ *     d1nrm_as_km1, dnrm = sqrt of b1_sq, d1_sq, d1_asprev_sq, d_sq (one IEEE square root each); *beta = sqrt(d1nrm * d1nrm +
+ *     b1nrm * b1nrm); c1..c5 = 0.5, 0.1, 4.0, 10.0, 0.05, delta = 0.1, eps = max(1e-2, 10 DBL_EPSILON).  lagrange_mult_cond =
+ *     n_lm_ge > 0 && n_lm_neg > 0 enters to_reduce only when q < t, n_inactive_lt_delta > 0 only when l - t > 0.  *method_code: 1
+ *     the Gauss-Newton direction is accepted, -1 subspace minimisation, 2 the method of Newton.  Returns 0; -2 a NULL.
+ * enlsip_gn_direction_sums   fills enlsip_gn_dir_sums from HOST arrays of ONE problem, in the order of the kernels: every sum as
+ *     64 strided partials (s = j mod 64, ascending j, from +0.0) added by the butterfly of a wave all-reduce (the masks of
+ *     enlsip_gn_termination_sums), products and additions rounded separately; norms are a plain sum of squares (covered for
+ *     operands inside the 2^+-400 band).  b: the first dimA entries are read, d: m, lambda and diag_scale: t, cx_all: l; active / inactive: the first
+ *     t / l - t entries used, 1-based, an entry 0 contributes nothing.  A NaN passes none of the three comparisons behind the
+ *     counts.  *status as status[k] below; with status 1 sums is left untouched.  Returns 0; -2 a NULL among s, sums, status or a
+ *     bad shape (m, l < 0, n < 1, s->l != l, t outside 0..l, q outside 0..t, dimA outside 0..t, dimJ2 outside 0..m, prev_t
+ *     outside 0..l, |prev_dimJ2| > 2^31); -4 a NULL
+ *     array that would be read; -5 a list entry outside 0..l.
+ * enlsip_gn_direction_check_batched_dev   for every problem k with take[k] != 0 (HOST array, NULL = all; take[k] == 0: nothing
+ *     of problem k is read, written or checked, sums[k], method_code[k], beta[k] and status[k] included), on the device the fields
+ *     of sums[k]; then, on the host inside the same call, method_code[k] and beta[k] by enlsip_gn_check_gn_direction on (state[k],
+ *     sums[k], m, n).  db, dd, dlambda, ddiag_scale are where the preceding solve and multiplier calls left them, in the padded
+ *     ragged layout: db + k * t_max, dd + k * m, dlambda and ddiag_scale + k * t_max; dcx_all holds l entries per problem.  state,
+ *     active, inactive (batch x l, 1-based, 0 behind the used part) are HOST arrays.
+ *     status[k]: 0 the decision was made; 1 k_prev = prev_dimJ2 + prev_t - t - 1 > m: the reference throws a BoundsError at
+ *     :1231, nothing but status[k] is written; 2 the decision was made, but a prefix of d (dimJ2 or k_prev entries) reaches past
+ *     n - rankA, where d is this library's and differs from LAPACK's by an orthogonal transform of the tail.
+ *     Arithmetic: no floating-point atomics; every field is bitwise enlsip_gn_direction_sums on the same data, in both kernel
+ *     forms, whatever the slot, the batch and the take of other problems.
+ * enlsip_gn_get_direction_form   kernel form of the last call on this handle: 0 general (one workgroup of four waves per
+ *     problem: one pass over d, b and the active list, the multiplier counts, the inactive count), 1 one wave per problem (m <=
+ *     1024, l <= 64 and t_max <= 64: four problems per workgroup, cross-lane operations only), -1 none yet.  One launch either
+ *     way; the bound on m changes no result.
+ * The call needs no resident factors: it is legal in every handle state and touches nothing resident.  One copy of the records
+ * goes up, one comes down, and the call returns after ONE synchronisation of the handle's stream.  l == 0, t_max == 0 and m == 0
+ * are legal.  Argument errors are raised before anything is launched and leave every buffer untouched (last_error names k):
+ *   -1 h NULL; -2 batch < 1; -3 m < 0, n < 1, l outside 0..1024, t_max outside 0..1024 or > l; -4 state, sums, method_code, beta
+ *   or status NULL, active or inactive NULL while l > 0, dd NULL while m > 0, dcx_all NULL while l > 0, db, dlambda or
+ *   ddiag_scale NULL while t_max > 0; -5 some state[k].t outside 0..t_max, or state[k].l != l; -6 some state[k].q outside
+ *   0..state[k].t; -7 a list entry outside 0..l; -8 some state[k].dimA outside 0..state[k].t, state[k].dimJ2 outside 0..m,
+ *   state[k].prev_t outside 0..l or |state[k].prev_dimJ2| > 2^31.
+ *   Problems with take[k] == 0 are not checked.
+ */
+typedef struct enlsip_gn_dir_state {
+    int64_t iter_number;               /* :981   iter_number                                                      */
+    int64_t restart;                   /* :974   current_iter.restart (0 / 1)                                     */
+    int64_t add;                       /* :983   current_iter.add (0 / 1)                                         */
+    int64_t del;                       /* :983   current_iter.del (0 / 1)                                         */
+    int64_t q;                         /* :998   W.q                                                              */
+    int64_t t;                         /* :998   W.t                                                              */
+    int64_t l;                         /* :1007  W.l                                                              */
+    int64_t rankA;                     /* :1015  current_iter.rankA                                               */
+    int64_t dimA;                      /* :1222  current_iter.dimA                                                */
+    int64_t dimJ2;                     /* :1228  current_iter.dimJ2                                               */
+    int64_t prev_code;                 /* :974   previous_iter.code                                               */
+    int64_t prev_dimJ2;                /* :1230  previous_iter.dimJ2                                              */
+    int64_t prev_t;                    /* :1230  previous_iter.t                                                  */
+    double  prev_beta;                 /* :984   previous_iter.beta                                               */
+    double  prev_progress;             /* :985   previous_iter.progress                                           */
+    double  prev_predicted_reduction;  /* :985   previous_iter.predicted_reduction                                */
+    double  prev_alpha;                /* :1020  previous_iter.alpha                                              */
+} enlsip_gn_dir_state;
+typedef struct enlsip_gn_dir_sums {
+    double  b1_sq;                     /* :1222  dot(b1, b1), b1 = b_gn[1:dimA]                                   */
+    double  d_sq;                      /* :1227  dot(d_gn, d_gn), all m entries                                   */
+    double  d1_sq;                     /* :1228  dot(d1, d1), d1 = d_gn[1:dimJ2]                                  */
+    double  d1_asprev_sq;              /* :1231  the same over d_gn[1:k_prev] (k_prev <= 0: 0.0)                  */
+    double  active_c_sum;              /* :1013  sum of cx[active]^2 (active_cx_sum)                              */
+    int64_t n_lm_ge;                   /* :1004  i in q+1..t with lambda_i * rows_i >= -sqrt(eps)                 */
+    int64_t n_lm_neg;                  /* :1004  i in q+1..t with lambda_i < 0                                    */
+    int64_t n_inactive_lt_delta;       /* :1009  inactive cx below delta = 0.1                                    */
+} enlsip_gn_dir_sums;
+int enlsip_gn_check_gn_direction(const enlsip_gn_dir_state* s, const enlsip_gn_dir_sums* v, int64_t m, int64_t n,
+                                 int64_t* method_code, double* beta);
+int enlsip_gn_direction_sums(int64_t m, int64_t n, int64_t l, const enlsip_gn_dir_state* s, const int64_t* active,
+                             const int64_t* inactive, const double* b, const double* d, const double* lambda,
+                             const double* diag_scale, const double* cx_all, int scaling, enlsip_gn_dir_sums* sums,
+                             int64_t* status);
+int enlsip_gn_direction_check_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t n, int64_t l, int64_t t_max,
+                                          const enlsip_gn_dir_state* state, const int64_t* active, const int64_t* inactive,
+                                          const int64_t* take, int scaling, const double* db, const double* dd,
+                                          const double* dlambda, const double* ddiag_scale, const double* dcx_all,
+                                          enlsip_gn_dir_sums* sums, int64_t* method_code, double* beta, int64_t* status);
+int enlsip_gn_get_direction_form(enlsip_gn_handle h, int* form);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
