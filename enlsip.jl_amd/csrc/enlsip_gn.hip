@@ -36,6 +36,7 @@
 #include "gn_kernels_addition_batched.hpp"
 #include "gn_kernels_termination_batched.hpp"
 #include "gn_kernels_direction_batched.hpp"
+#include "gn_kernels_hessian_batched.hpp"
 #include "gn_linesearch_fit.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_newton_batched.hpp"
@@ -1407,7 +1408,7 @@ static void tsqr_drop_comm(enlsip_gn_handle h);      // gn_tsqr.inc
 
 extern "C" {
 
-int enlsip_gn_version(void) { return 203; }
+int enlsip_gn_version(void) { return 204; }
 
 // why the last enlsip_gn_create of this thread failed (no handle exists to carry the message): enlsip_gn_last_error(NULL)
 static thread_local std::string g_create_err;
@@ -1495,9 +1496,10 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->add_scr.p) (void)hipFree(h->add_scr.p);
     if (h->term_scr.p) (void)hipFree(h->term_scr.p);
     if (h->dir_scr.p) (void)hipFree(h->dir_scr.p);
+    if (h->hess_scr.p) (void)hipFree(h->hess_scr.p);
     for (hipEvent_t e : h->nwb_ev)
         if (e) (void)hipEventDestroy(e);
-    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_pen, &h->h_add, &h->h_term, &h->h_dir, &h->h_nwflag, &h->h_lagflag})
+    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_pen, &h->h_add, &h->h_term, &h->h_dir, &h->h_hess, &h->h_nwflag, &h->h_lagflag})
         if (b->p) (void)hipHostFree(b->p);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);
@@ -2419,5 +2421,6 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_addition_batched.inc"
 #include "gn_termination_batched.inc"
 #include "gn_direction_batched.inc"
+#include "gn_hessian_batched.inc"
 #include "gn_newton.inc"
 #include "gn_newton_batched.inc"

@@ -1,8 +1,9 @@
 // The batched calls on the caller's device buffers (gn_deletion_batched.inc, gn_linesearch_batched.inc, gn_penalty_batched.inc,
-// gn_linesearch_fit_batched.inc, gn_addition_batched.inc, gn_termination_batched.inc, gn_direction_batched.inc): the records they
+// gn_linesearch_fit_batched.inc, gn_addition_batched.inc, gn_termination_batched.inc, gn_direction_batched.inc,
+// gn_hessian_batched.inc): the records they
 // upload and download, the checks and the packing of their host arguments, and
 // their scratch layouts.  Host-only, nothing of HIP: tests/batch_records_check.cpp runs all of it on the CPU
-// (the termination call's check and layout: tests/termination_check.cpp; the direction check's: tests/direction_check.cpp).  The
+// (the termination call's check and layout: tests/termination_check.cpp; the direction check's: tests/direction_check.cpp; the Hessian calls': tests/hessian_sums_check.cpp).  The
 // kernel headers include it for the records.
 #pragma once
 #include <algorithm>
@@ -73,6 +74,11 @@ struct DirMeta {
     int t, q, dimA, dimJ2;
     int k_prev;             // entries of d under d1_asprev_sq: max(prev_dimJ2 + prev_t - t - 1, 0), at most m
     int take;               // 0 leaves the problem alone (not taken, or status 1)
+};
+
+struct HessMeta {
+    int t;                  // used entries of the problem's active list; 0 for a problem that is left alone
+    int slot;               // the problem's Gamma is at Gamma + slot * strideG; < 0 leaves the problem alone
 };
 
 constexpr int LS_SUM_ROWS = 1024;       // rows per partial-sum workgroup until nblk reaches LS_MAX_NBLK
@@ -269,6 +275,65 @@ inline int check_direction(std::string& err, const DirectionShape& s, const enls
             (rc = check_count(err, -8, "state.dimJ2", k, st.dimJ2, {0, s.m, "0..m"})) ||
             (rc = check_count(err, -8, "state.prev_t", k, st.prev_t, {0, s.l, "0..l"})) ||
             (rc = check_count(err, -8, "state.prev_dimJ2", k, st.prev_dimJ2, {-DIR_PREV_MAX, DIR_PREV_MAX, "-2^31..2^31"}))) return rc;
+    }
+    return 0;
+}
+
+// ---- the Hessian sums: up [meta | active], nothing down, no partial sums.  Its checks and those of the points call (the codes of
+// include/enlsip_gn.h; tests/hessian_sums_check.cpp runs them on the CPU) ------------------------------------------------------------
+struct HessianScratch {
+    HessMeta* meta = nullptr;
+    int* list = nullptr;
+    size_t up_bytes = 0;
+    void carve(Carver& c, int64_t count, int64_t l, int64_t) {
+        c.take(meta, "meta", (size_t)count);
+        c.take(list, "list", (size_t)count * (size_t)l);
+        up_bytes = bytes_since(c, meta);
+    }
+};
+constexpr int64_t HESS_MAX_ELEMS = 1LL << 48;      // doubles of one evaluation or point buffer: every index stays far inside int64
+// the pair range [pair0, pair0 + npairs) inside the triangle of n, and count x npairs x 4 x width doubles addressable
+inline int check_hessian_range(std::string& err, int64_t count, int64_t n, int64_t pair0, int64_t npairs, int64_t width) {
+    if (count < 1 || count > 0x7fffffff) return fail(err, -2, "count must be in 1..2^31-1");
+    if (n < 1 || n > 0x7fffffff) return fail(err, -2, "n must be in 1..2^31-1");
+    if (npairs < 1 || pair0 < 0) return fail(err, -2, "npairs must be at least 1 and pair0 at least 0");
+    const int64_t pairs = n * (n + 1) / 2;
+    if (pair0 > pairs || npairs > pairs - pair0) return fail(err, -2, "pair0 + npairs > n (n + 1) / 2");
+    if (width > 0 && npairs > HESS_MAX_ELEMS / 4 / width / count) return fail(err, -2, "count x npairs x 4 x row length beyond 2^48 doubles");
+    return 0;
+}
+inline int check_hessian_points(std::string& err, int64_t count, int64_t n, int64_t pair0, int64_t npairs, bool x, bool X) {
+    int rc;
+    if ((rc = check_hessian_range(err, count, n, pair0, npairs, n))) return rc;
+    return !x || !X ? fail(err, -4, "x and X are required") : 0;
+}
+struct HessianShape { int64_t count, m, n, l, t_max, pair0, npairs, ldg, strideG; };
+inline int check_hessian_sums(std::string& err, const HessianShape& s, const int64_t* t, const int64_t* active, const int64_t* slot,
+                              bool x, bool F, bool rx, bool G, bool lambda, bool Gamma) {
+    int rc;
+    if (s.m < 0 || s.m > 0x7fffffff) return fail(err, -2, "m must be in 0..2^31-1");
+    if (s.l < 0 || s.l > (1LL << 27) || s.t_max < 0 || s.t_max > 0x7fffffff) return fail(err, -2, "l must be in 0..2^27 and t_max in 0..2^31-1");
+    if ((rc = check_hessian_range(err, s.count, s.n, s.pair0, s.npairs, std::max(s.m, s.l)))) return rc;
+    const int64_t t_top = std::min(s.l, s.t_max);
+    if (!t || !x || !Gamma) return fail(err, -4, "t, x and Gamma are required");
+    if (s.m > 0 && (!F || !rx)) return fail(err, -4, "F and rx are required when m > 0");
+    for (int64_t k = 0; k < s.count; ++k)        // nothing of a problem with slot[k] < 0 is read
+        if (!(slot && slot[k] < 0) && t[k] > 0 && (!active || !G || !lambda))
+            return fail(err, -4, "active, G and lambda are required when some t[k] > 0");
+    for (int64_t k = 0; k < s.count; ++k) {      // the lower k wins
+        if (slot && slot[k] < 0) continue;
+        if ((rc = check_count(err, -5, "t", k, t[k], {0, t_top, "0..min(l, t_max)"})) ||
+            (t[k] > 0 && (rc = check_list(err, -5, "active", k, active + k * s.l, t[k], {0, s.l, "0..l"}))) ||
+            (slot && (rc = check_count(err, -5, "slot", k, slot[k], {0, 0x7fffffff, "below 2^31"})))) return rc;
+    }
+    if (s.ldg < s.n) return fail(err, -5, "ldg < n");
+    if (s.ldg > INT64_MAX / s.n || s.strideG < s.ldg * s.n) return fail(err, -5, "strideG < ldg * n");
+    if (slot) {
+        std::vector<int64_t> used;
+        for (int64_t k = 0; k < s.count; ++k)
+            if (slot[k] >= 0) used.push_back(slot[k]);
+        std::sort(used.begin(), used.end());
+        if (std::adjacent_find(used.begin(), used.end()) != used.end()) return fail(err, -5, "two problems share a slot");
     }
     return 0;
 }

@@ -270,6 +270,10 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf dir_scr;
     gn::PinnedBuf h_dir;
     int direction_form = -1;
+    // batched Hessian sums of the Newton branch (gn_hessian_batched.inc): the per-problem counts and slots and the active lists of
+    // one call on the device and in pinned memory; nothing resident
+    gn::DevBuf hess_scr;
+    gn::PinnedBuf h_hess;
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

@@ -1019,6 +1019,69 @@ function direction_form_hip(h::Handle)
     return Int(f[])
 end
 
+"""    hessian_points_hip(x, pair0, npairs) -> X (n × 4 × npairs)
+
+The stencil points of `hessian_res!` / `hessian_cons!` (src/enlsip_functions.jl:259-265) for the pairs `pair0 .. pair0 + npairs - 1`
+(0-based pair index `P = k (k + 1) / 2 + j`, the loop order of :255 with 0-based `j ≤ k`), through the library's host entry point
+(no handle, no GPU): `X[:, s, q]` is `x_work` before evaluation `f_s` of pair `q`, bit for bit."""
+function hessian_points_hip(x::Vector{Float64}, pair0::Integer, npairs::Integer)
+    n = length(x)
+    X = zeros(n, 4, max(npairs, 0))
+    rc = GC.@preserve x X @ccall LIB.enlsip_gn_hessian_points(n::Int64, pair0::Int64, npairs::Int64, pointer(x)::Ptr{Float64},
+                                                               pointer(X)::Ptr{Float64})::Cint
+    rc == 0 || error("enlsip_gn_hessian_points returned $rc")
+    return X
+end
+
+"""    hessian_points_batched_dev_hip(h, B, n, pair0, npairs, dx, dX)
+
+The same for `B` problems on DEVICE buffers: `dx` (`n × B`) in, `dX` (`n × 4 × npairs × B`) out, in one launch."""
+function hessian_points_batched_dev_hip(h::Handle, B::Integer, n::Integer, pair0::Integer, npairs::Integer, dx::Ptr{Float64},
+                                        dX::Ptr{Float64})
+    check(h, @ccall LIB.enlsip_gn_hessian_points_batched_dev(h.ptr::Ptr{Cvoid}, B::Int64, n::Int64, pair0::Int64, npairs::Int64,
+                                                             dx::Ptr{Float64}, dX::Ptr{Float64})::Cint)
+    return nothing
+end
+
+"""    hessian_sums_hip!(Γ, x, F, rx, G, λ, active, t, pair0) -> Γ
+
+`Γ[k, j] = Γ[j, k] = r - c` (src/enlsip_functions.jl:268-272, :317-322, :393) for the pairs `pair0 .. pair0 + size(F, 3) - 1` from
+the evaluations `F` (`m × 4 × npairs`, the residuals) and `G` (`l × 4 × npairs`, all constraints) at the points of
+`hessian_points_hip`, through the library's host entry point.  The sums are taken in the library's documented order (64 strided
+partials and a butterfly), not left to right.  Only the entries of the pairs in the range are written."""
+function hessian_sums_hip!(Γ::Matrix{Float64}, x::Vector{Float64}, F::Array{Float64,3}, rx::Vector{Float64}, G::Array{Float64,3},
+                           λ::Vector{Float64}, active::Vector{Int64}, t::Integer, pair0::Integer)
+    n = length(x); m = length(rx); l = size(G, 1); npairs = size(F, 3); ldg = size(Γ, 1)
+    (size(F, 1) == m && size(F, 2) == 4 && size(G, 2) == 4 && size(G, 3) == npairs) || error("F is m x 4 x npairs, G l x 4 x npairs")
+    (size(Γ, 2) == n && ldg >= n && length(λ) >= t && length(active) >= t) || error("Γ has n columns; λ and active need t entries")
+    rc = GC.@preserve Γ x F rx G λ active @ccall LIB.enlsip_gn_hessian_sums(
+        m::Int64, n::Int64, l::Int64, t::Int64, pair0::Int64, npairs::Int64, pointer(active)::Ptr{Int64}, pointer(x)::Ptr{Float64},
+        pointer(F)::Ptr{Float64}, pointer(rx)::Ptr{Float64}, pointer(G)::Ptr{Float64}, pointer(λ)::Ptr{Float64},
+        pointer(Γ)::Ptr{Float64}, ldg::Int64)::Cint
+    rc == 0 || error("enlsip_gn_hessian_sums returned $rc")
+    return Γ
+end
+
+"""    hessian_sums_batched_dev_hip(h, m, n, l, t_max, pair0, npairs, t, active, slot, dx, dF, drx, dG, dλ, dΓ, ldg, strideΓ)
+
+The same for `B = length(t)` problems on DEVICE buffers in one launch: `Γ` of problem `k` is written column-major at
+`dΓ + slot[k] * strideΓ`, where the batched Newton direction reads it (`slot === nothing`: slot `k`; `slot[k] < 0` leaves problem
+`k` alone).  `active`: host matrix `l × B`, 1-based, 0 behind the used part."""
+function hessian_sums_batched_dev_hip(h::Handle, m::Integer, n::Integer, l::Integer, t_max::Integer, pair0::Integer, npairs::Integer,
+                                      t::Vector{Int64}, active::Matrix{Int64}, slot::Union{Nothing,Vector{Int64}},
+                                      dx::Ptr{Float64}, dF::Ptr{Float64}, drx::Ptr{Float64}, dG::Ptr{Float64}, dλ::Ptr{Float64},
+                                      dΓ::Ptr{Float64}, ldg::Integer, strideΓ::Integer)
+    B = length(t)
+    size(active) == (l, B) || error("active is l x B")
+    (slot === nothing || length(slot) == B) || error("slot must have one entry per problem")
+    sl = slot === nothing ? Ptr{Int64}(C_NULL) : pointer(slot)
+    GC.@preserve t active slot check(h, @ccall LIB.enlsip_gn_hessian_sums_batched_dev(
+        h.ptr::Ptr{Cvoid}, B::Int64, m::Int64, n::Int64, l::Int64, t_max::Int64, pair0::Int64, npairs::Int64, pointer(t)::Ptr{Int64},
+        pointer(active)::Ptr{Int64}, sl::Ptr{Int64}, dx::Ptr{Float64}, dF::Ptr{Float64}, drx::Ptr{Float64}, dG::Ptr{Float64},
+        dλ::Ptr{Float64}, dΓ::Ptr{Float64}, ldg::Int64, strideΓ::Int64)::Cint)
+    return nothing
+end
+
 """    upper_bound_steplength_hip(inactive, n_inactive, index_del, cx, Ap) -> (α_upp, index_α_upp)
 
 `upper_bound_steplength` (src/enlsip_functions.jl:2149-2178) on host data with `Ap = A * p` already formed, through the library's

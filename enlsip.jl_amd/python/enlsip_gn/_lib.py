@@ -219,6 +219,10 @@ PROTOTYPES = {
     "enlsip_gn_direction_check_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, _i64] + [C.c_void_p] * 4 + [C.c_int]
                                               + [C.c_void_p] * 9),
     "enlsip_gn_get_direction_form": (C.c_int, [_h, C.POINTER(C.c_int)]),
+    "enlsip_gn_hessian_points": (C.c_int, [_i64, _i64, _i64, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_hessian_points_batched_dev": (C.c_int, [_h, _i64, _i64, _i64, _i64, C.c_void_p, C.c_void_p]),
+    "enlsip_gn_hessian_sums": (C.c_int, [_i64] * 6 + [C.c_void_p] * 7 + [_i64]),
+    "enlsip_gn_hessian_sums_batched_dev": (C.c_int, [_h] + [_i64] * 7 + [C.c_void_p] * 9 + [_i64, _i64]),
     "enlsip_gn_newton_direction": (C.c_int, [_h, _i64, C.c_void_p, _i64, C.c_void_p, _ip]),
     "enlsip_gn_newton_direction_batched": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_newton_direction_batched_dev": (C.c_int, [_h, _i64, _i64, C.c_void_p, _i64, _i64, C.c_void_p, C.c_void_p,

@@ -1031,6 +1031,64 @@ int enlsip_gn_direction_check_batched_dev(enlsip_gn_handle h, int64_t batch, int
                                           enlsip_gn_dir_sums* sums, int64_t* method_code, double* beta, int64_t* status);
 int enlsip_gn_get_direction_form(enlsip_gn_handle h, int* form);
 
+/* ---- the finite-difference Hessian sums of the Newton branch, around the caller's evaluations ---------------------------------
+ * hessian_res! and hessian_cons! (src/enlsip_functions.jl:243-328) are callback-bound only in their evaluations: the stencil
+ * points and the contractions are streaming work.  A caller whose residuals and constraints are batched device functions forms
+ * the points of a pair range for every problem in one call, evaluates them all at once, and hands the evaluations to the sums
+ * call, which writes Gamma = r_mat - c_mat (:393) where enlsip_gn_newton_direction_batched_dev reads it.
+ *
+ * Pair index: a pair is (k, j), 0 <= j <= k < n, P = k (k + 1) / 2 + j (the loop order `for k in 1:n, j in 1:k` of :255).  Every
+ * call takes a pair range [pair0, pair0 + npairs), so the caller bounds the size of its evaluation buffers.
+ * Steps: eps1 = eps(Float64)^(1/3) (:252), formed once on the host as pow(DBL_EPSILON, 1.0 / 3.0); eps_k = max(|x[k]|, 1.0) * eps1
+ * (:256-257; a NaN in x[k] stays a NaN, as Julia's max).
+ *
+ * enlsip_gn_hessian_points   HOST, one problem, no handle and no GPU.  X (npairs, 4, n): slot s of pair (k, j) is x_work before
+ *     evaluation f_{s+1} (:259-265) bit for bit: a copy of x, entry j +- eps_j FIRST, then entry k +- eps_k, signs (+,+), (-,+),
+ *     (+,-), (-,-) in the order (j, k).  On the diagonal k == j these are two successive roundings of one entry (f2 is
+ *     (x[k] - eps) + eps, not x[k]).  Returns 0; -2 n < 1, npairs < 1, pair0 < 0 or pair0 + npairs > n (n + 1) / 2; -4 a NULL.
+ * enlsip_gn_hessian_points_batched_dev   the same for count problems on DEVICE buffers: dx (count, n) in, dX (count, npairs, 4,
+ *     n) out, bitwise the host routine's.  One launch, one synchronisation of the handle's stream.  -1 h NULL; -2 count < 1 or
+ *     a bad range as above; -4 dx or dX NULL.
+ * enlsip_gn_hessian_sums   HOST, one problem and one pair range.  F (npairs, 4, m) and G (npairs, 4, l) hold the residuals and ALL
+ *     l constraints at the points above; per pair
+ *         s_r = sum_{i<m} (((f1[i] - f2[i]) - f3[i]) + f4[i]) * rx[i]                          :268-271
+ *         r   = s_r / ((4 * eps_j) * eps_k)                                                    :272
+ *         s_c = sum_{i<t} (((g1[a] - g2[a]) - g3[a]) + g4[a]) * lambda[i], a = active[i] - 1   :317-321
+ *         c   = s_c / ((4.0 * eps_k) * eps_j)                                                  :322
+ *         Gamma[k, j] = Gamma[j, k] = r - c                                                    :393
+ *     every difference, product and divisor rounded as written (the two divisors associate differently in the reference; both
+ *     forms are kept).  The two sums are taken in the order of enlsip_gn_termination_sums: 64 strided partials (s = i mod 64,
+ *     ascending i, from +0.0) added by the butterfly of a wave all-reduce, NOT the reference's left-to-right order.  An active
+ *     entry 0 contributes nothing; with t == 0 c = +0.0 and G, lambda and active are not read.  Gamma is column-major with
+ *     ldg >= n; only the (k, j) and (j, k) entries of the pairs in the range are written.  Returns 0; -2 m < 0, n < 1, l < 0 or a
+ *     bad range; -4 x or Gamma NULL, F or rx NULL while m > 0, active, G or lambda NULL while t > 0; -5 t outside 0..l, an active
+ *     entry outside 0..l, or ldg < n.
+ * enlsip_gn_hessian_sums_batched_dev   the same for count problems on DEVICE buffers: dx (count, n), dF (count, npairs, 4, m), drx
+ *     (count, m), dG (count, npairs, 4, l), dlambda (count, t_max); t (count), active (count x l, 1-based, 0 behind the used
+ *     part) and slot (count) are HOST arrays.  Gamma of problem k is written column-major at dGamma + slot[k] * strideG (slot
+ *     NULL: slot[k] = k), the layout enlsip_gn_newton_direction_batched_dev reads, so a compacted list of problems can be run
+ *     against the Gamma slots of the resident batch.  slot[k] < 0 leaves problem k alone: nothing of it is read, written or
+ *     checked.  Rows >= n of a column (ldg > n) and the gap up to strideG are never touched.  Where no taken problem has t[k] > 0,
+ *     dG, dlambda and active may be NULL.  One wave owns one (problem, pair), four pairs per workgroup; no LDS, no barrier, no floating-point
+ *     atomics; every entry is bitwise enlsip_gn_hessian_sums on the same data, whatever the slot, the batch and the split of the
+ *     triangle into pair ranges.  One copy of the records goes up, one launch, one synchronisation of the handle's stream.
+ *     Argument errors are raised before anything is launched and leave every buffer untouched (last_error names k):
+ *       -1 h NULL; -2 count < 1, n < 1, m < 0, l < 0, t_max < 0, npairs < 1, pair0 < 0 or pair0 + npairs > n (n + 1) / 2 (also: a
+ *       buffer beyond 2^48 doubles); -4 t, dx or dGamma NULL, dF or drx NULL while m > 0, active, dG or dlambda NULL while some
+ *       taken t[k] > 0; -5 an active entry outside 0..l, t[k] outside 0..min(l, t_max), ldg < n, strideG < ldg * n, a slot
+ *       beyond 2^31 - 1, or two non-negative slot values equal.
+ * The batched calls need no resident factors: they are legal in every handle state and touch nothing resident. */
+int enlsip_gn_hessian_points(int64_t n, int64_t pair0, int64_t npairs, const double* x, double* X);
+int enlsip_gn_hessian_points_batched_dev(enlsip_gn_handle h, int64_t count, int64_t n, int64_t pair0, int64_t npairs,
+                                         const double* dx, double* dX);
+int enlsip_gn_hessian_sums(int64_t m, int64_t n, int64_t l, int64_t t, int64_t pair0, int64_t npairs, const int64_t* active,
+                           const double* x, const double* F, const double* rx, const double* G, const double* lambda,
+                           double* Gamma, int64_t ldg);
+int enlsip_gn_hessian_sums_batched_dev(enlsip_gn_handle h, int64_t count, int64_t m, int64_t n, int64_t l, int64_t t_max,
+                                       int64_t pair0, int64_t npairs, const int64_t* t, const int64_t* active,
+                                       const int64_t* slot, const double* dx, const double* dF, const double* drx,
+                                       const double* dG, const double* dlambda, double* dGamma, int64_t ldg, int64_t strideG);
+
 /* ---- Newton direction on the resident data of the last solve -------------------------------------------------
  * newton_search_direction (src/enlsip_functions.jl:348-423) after its two Hessian sums (:391-396), which are callback-bound and
  * stay with the caller: Gamma = r_mat - c_mat (n x n, host, column-major, ldg >= n).  Computes E = F_A.Q' Gamma F_A.Q (:398),
