@@ -118,12 +118,26 @@ template <class Layout, class... Shape>
 static int place_pinned(enlsip_gn_handle h, PinnedBuf& b, Layout& L, const Shape&... shape) {
     return place(L, [&](size_t bytes, void** base) { const int rc = grow_pinned(h, b, bytes); *base = b.p; return rc; }, shape...);
 }
-// The records of a call on the caller's buffers (gn_batch_records.hpp): the same layout in the device buffer and in pinned memory,
-// there without the partial sums (`part` per problem), which stay on the device.
+// The records of a call on the caller's buffers (gn_batch_records.hpp): the same layout in the handle's record scratch on the
+// device and in pinned memory, there without the partial sums (`part` per problem), which stay on the device.
 template <class Layout, class... Shape>
-static int place_records(enlsip_gn_handle h, DevBuf& d, PinnedBuf& p, Layout& D, Layout& H, int64_t part, const Shape&... shape) {
-    const int rc = place_dev(h, d, D, shape..., part);
-    return rc ? rc : place_pinned(h, p, H, shape..., (int64_t)0);
+static int place_records(enlsip_gn_handle h, Layout& D, Layout& H, int64_t part, const Shape&... shape) {
+    const int rc = place_dev(h, h->rec_scr, D, shape..., part);
+    return rc ? rc : place_pinned(h, h->h_rec, H, shape..., (int64_t)0);
+}
+// The round trip of such a call on h->stream: the uploaded arrays (they start at `meta` on both sides) in one copy, the call's
+// launches, `down_bytes` from `d_down` to `h_down` in one copy down (the same array of D and of H; none: nothing comes down), and
+// the synchronisation that frees the record scratch for the next call.  Errors as GN_HIP reports them.
+template <class Layout, class Launch>
+static int round_trip(enlsip_gn_handle h, const Layout& D, const Layout& H, Launch&& launch, void* h_down = nullptr,
+                      const void* d_down = nullptr, size_t down_bytes = 0) {
+    hipStream_t st = h->stream;
+    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
+    launch(st);
+    GN_HIP(hipGetLastError());
+    if (h_down) GN_HIP(hipMemcpyAsync(h_down, d_down, down_bytes, hipMemcpyDeviceToHost, st));
+    GN_HIP(hipStreamSynchronize(st));
+    return 0;
 }
 static_assert(PLAN_PB == PB && PLAN_KBLK == KBLK && PLAN_QD_CPW == QD_CPW && PLAN_QDCAND_BYTES == sizeof(QdCand) &&
               PLAN_SBINFO_BYTES == sizeof(SbInfo), "gn_plan.hpp sizes the workspaces with the kernels' constants");
@@ -1490,16 +1504,10 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->nwb_io.p) (void)hipFree(h->nwb_io.p);
     if (h->ssb_req.p) (void)hipFree(h->ssb_req.p);
     if (h->ssb_io.p) (void)hipFree(h->ssb_io.p);
-    if (h->del_scr.p) (void)hipFree(h->del_scr.p);
-    if (h->ls_scr.p) (void)hipFree(h->ls_scr.p);
-    if (h->pen_scr.p) (void)hipFree(h->pen_scr.p);
-    if (h->add_scr.p) (void)hipFree(h->add_scr.p);
-    if (h->term_scr.p) (void)hipFree(h->term_scr.p);
-    if (h->dir_scr.p) (void)hipFree(h->dir_scr.p);
-    if (h->hess_scr.p) (void)hipFree(h->hess_scr.p);
+    if (h->rec_scr.p) (void)hipFree(h->rec_scr.p);
     for (hipEvent_t e : h->nwb_ev)
         if (e) (void)hipEventDestroy(e);
-    for (PinnedBuf* b : {&h->h_ssb, &h->h_del, &h->h_ls, &h->h_pen, &h->h_add, &h->h_term, &h->h_dir, &h->h_hess, &h->h_nwflag, &h->h_lagflag})
+    for (PinnedBuf* b : {&h->h_ssb, &h->h_rec, &h->h_nwflag, &h->h_lagflag})
         if (b->p) (void)hipHostFree(b->p);
     if (h->cws.p) (void)hipFree(h->cws.p);
     if (h->plist_buf.p) (void)hipFree(h->plist_buf.p);

@@ -139,6 +139,13 @@ int stage_out(enlsip_gn_handle h, const Staged* a, int na) {
 // the NULL checks of the getters of what a batched call recorded on the handle
 #define GN_GETTER_CHECK(h, out) if (!(h)) return -1; if (!(out)) { (h)->err = #out " is NULL"; return -2; }
 
+// the ten enlsip_gn_get_*_form getters
+int get_form(enlsip_gn_handle h, Form which, int* form) {
+    GN_GETTER_CHECK(h, form)
+    *form = h->form[which];
+    return 0;
+}
+
 // the constraint count of problem `prob` of the resident batch: its own t after a ragged solve, the batch's t otherwise
 int prob_t(enlsip_gn_handle h, int64_t prob) {
     return h->h_tk.empty() ? (int)h->plan.t : h->h_tk[(size_t)prob];

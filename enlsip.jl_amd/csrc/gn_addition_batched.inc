@@ -1,7 +1,7 @@
 // The working-set additions of a batch and the rebuild of its active constraints on the caller's device buffers (kernels:
 // gn_kernels_addition_batched.hpp; the routines: gn_violated_constraints.hpp): evaluate_violated_constraints
 // (src/enlsip_functions.jl:608-650), active_C.cx / active_C.A of :2854-2855 and evaluate_scaling! (src/structures.jl:160-178).  The
-// call needs and touches nothing resident: the handle lends its device, its stream and a scratch for the records
+// call needs and touches nothing resident: the handle lends its device, its stream and its record scratch, in which the call places its records
 // (AdditionScratch: t, q, take, index_alpha_upp and both lists up; the lists, t, added and status down).  Included at the end of
 // enlsip_gn.hip.
 
@@ -52,58 +52,47 @@ int enlsip_gn_add_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, int
     const bool wave = addition_wave_form(n, l);
     const int64_t tiles = (t_max + 63) / 64;
     if (!wave && !grid_fits(batch, tiles)) { h->err = "batch * ceil(t_max / 64) exceeds the grid"; return -2; }
-    h->addition_form = wave ? 1 : 0;
+    h->form[FORM_ADDITION] = wave ? 1 : 0;
     std::fill(added, added + batch, (int64_t)0);
     std::fill(status, status + batch, (int64_t)0);
     if (l == 0 || t_max == 0) return 0;      // no slot to build and, by the check of t_max, no walk that could add
     GN_HIP(hipSetDevice(h->device));
     AdditionScratch D, H;
-    if ((rc = place_records(h, h->add_scr, h->h_add, D, H, 0, batch, 2 * l))) return rc;
-    int* const h_act = H.list;
-    int* const h_ina = H.list + batch * l;
-    std::vector<int64_t> n_act((size_t)batch), n_ina((size_t)batch);
+    if ((rc = place_records(h, D, H, 0, batch, 2 * l))) return rc;
+    const WorkingSets<int> Dw(D.list, batch, l), Hw(H.list, batch, l);
     for (int64_t k = 0; k < batch; ++k) {      // a problem that is not taken: counts of 0, so that nothing of its lists is read
         const int tk = addition_take(take, k);
         H.meta[k] = {tk ? (int)t[k] : 0, tk ? (int)q[k] : 0, tk, tk && index_alpha_upp ? (int)index_alpha_upp[k] : 0};
-        n_act[k] = tk ? t[k] : 0;
-        n_ina[k] = tk ? l - t[k] : 0;
+        pack_working_sets(H.list, batch, l, k, active, inactive, tk ? t[k] : -1);
     }
-    pack_rows(h_act, active, n_act.data(), batch, l);
-    pack_rows(h_ina, inactive, n_ina.data(), batch, l);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     AdditionArgs a{};
-    a.meta = D.meta; a.act = D.list; a.inact = D.list + batch * l; a.out = D.out;
+    a.meta = D.meta; a.act = Dw.act; a.inact = Dw.inact; a.out = D.out;
     a.count = (int)batch; a.n = (int)n; a.l = (int)l; a.t_max = (int)t_max; a.scaling = scaling != 0; a.tiles = (int)tiles;
     a.A = dA; a.lda = lda; a.strideA = strideA; a.cx_all = dcx_all;
     a.At = dAt; a.ldat = ldat; a.strideAt = strideAt; a.cx = dcx; a.diag_scale = ddiag_scale;
-    if (wave) {
-        hipLaunchKernelGGL(k_add_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(k_add_walk, dim3((unsigned)batch), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_add_gather, dim3((unsigned)(batch * tiles)), dim3(256), 0, st, a);
-    }
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.list, D.list, addition_down_bytes(H, batch), hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    auto launch = [&](hipStream_t st) {
+        if (wave) {
+            hipLaunchKernelGGL(k_add_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(k_add_walk, dim3((unsigned)batch), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_add_gather, dim3((unsigned)(batch * tiles)), dim3(256), 0, st, a);
+        }
+    };
+    if ((rc = round_trip(h, D, H, launch, H.list, D.list, addition_down_bytes(H, batch)))) return rc;
     for (int64_t k = 0; k < batch; ++k) {
         if (H.meta[k].take != 1) continue;      // only a walk changes the host records
         t[k] = H.out[k].t;
         added[k] = H.out[k].added;
         status[k] = H.out[k].status;
         for (int64_t i = 0; i < l; ++i) {
-            active[k * l + i] = h_act[k * l + i];
-            inactive[k * l + i] = h_ina[k * l + i];
+            active[k * l + i] = Hw.act[k * l + i];
+            inactive[k * l + i] = Hw.inact[k * l + i];
         }
     }
     return 0;
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_addition_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->addition_form;
-    return 0;
-}
+int enlsip_gn_get_addition_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_ADDITION, form); }
 
 }  // extern "C"

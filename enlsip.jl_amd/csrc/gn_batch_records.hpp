@@ -1,10 +1,10 @@
-// The batched calls on the caller's device buffers (gn_deletion_batched.inc, gn_linesearch_batched.inc, gn_penalty_batched.inc,
-// gn_linesearch_fit_batched.inc, gn_addition_batched.inc, gn_termination_batched.inc, gn_direction_batched.inc,
-// gn_hessian_batched.inc): the records they
-// upload and download, the checks and the packing of their host arguments, and
-// their scratch layouts.  Host-only, nothing of HIP: tests/batch_records_check.cpp runs all of it on the CPU
-// (the termination call's check and layout: tests/termination_check.cpp; the direction check's: tests/direction_check.cpp; the Hessian calls': tests/hessian_sums_check.cpp).  The
-// kernel headers include it for the records.
+// The eleven batched calls on the caller's device buffers (gn_deletion_batched.inc, gn_linesearch_batched.inc,
+// gn_penalty_batched.inc, gn_linesearch_fit_batched.inc, gn_addition_batched.inc, gn_termination_batched.inc,
+// gn_direction_batched.inc, gn_hessian_batched.inc): the records they upload and download, the checks and the packing of their
+// host arguments (the working-set lists among them), and the layouts they place in the handle's one record scratch (DESIGN.md
+// 5.7a).  Host-only, nothing of HIP: tests/batch_records_check.cpp runs the shared pieces on the CPU, tests/addition_walk_check.cpp,
+// termination_check.cpp, direction_check.cpp and hessian_sums_check.cpp the checks and layouts of their calls.  The kernel headers
+// include it for the records.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -95,11 +95,26 @@ inline int check_l(std::string& err, int64_t l) { return l < 0 || l > (1LL << 27
 inline int check_t_max(std::string& err, int64_t t_max) {
     return t_max < 0 || t_max > BATCH_MAX_T ? fail(err, -3, "t_max must be in 0..1024 in this build") : 0;
 }
+inline int check_m(std::string& err, int64_t m) { return m < 0 || m > 0x7fffffff ? fail(err, -3, "m must be in 0..2^31-1") : 0; }
+inline int check_n(std::string& err, int64_t n) { return n < 1 || n > 0x3fffffff ? fail(err, -3, "n must be at least 1") : 0; }
+// t_max in the build's range and no larger than l
+inline int check_t_max_in_l(std::string& err, int64_t t_max, int64_t l) {
+    const int rc = check_t_max(err, t_max);
+    return rc ? rc : t_max > l ? fail(err, -3, "t_max > l") : 0;
+}
 // the shape of the penalty, merit and fit calls
 inline int check_shape(std::string& err, int64_t batch, int64_t l, int64_t t_max) {
     int rc;
-    if ((rc = check_batch(err, batch)) || (rc = check_l(err, l)) || (rc = check_t_max(err, t_max))) return rc;
-    return t_max > l ? fail(err, -3, "t_max > l") : 0;
+    if ((rc = check_batch(err, batch)) || (rc = check_l(err, l))) return rc;
+    return check_t_max_in_l(err, t_max, l);
+}
+// the shape of the calls that take both working-set lists with stride l (addition, termination, direction check), whose general
+// forms keep a list in LDS: l is bounded like t_max.  The addition call has no m and passes 0.
+inline int check_working_set_shape(std::string& err, int64_t batch, int64_t m, int64_t n, int64_t l, int64_t t_max) {
+    int rc;
+    if ((rc = check_batch(err, batch)) || (rc = check_m(err, m)) || (rc = check_n(err, n))) return rc;
+    if (l < 0 || l > BATCH_MAX_T) return fail(err, -3, "l must be in 0..1024 in this build");
+    return check_t_max_in_l(err, t_max, l);
 }
 
 struct Range { int64_t lo, hi; const char* text; };     // lo..hi, and what a message calls it ("0..t_max")
@@ -120,14 +135,37 @@ inline int check_list(std::string& err, int code, const char* name, int64_t k, c
     return 0;
 }
 
-// batch rows of `stride` ints: the first cnt[k] entries of row k of src, 0 behind them
+// problem k's working set of the calls above: t active entries, l - t inactive ones, all in 0..l (code -7)
+inline int check_working_set(std::string& err, int64_t k, const int64_t* active, const int64_t* inactive, int64_t l, int64_t t) {
+    const int rc = check_list(err, -7, "active", k, active + k * l, t, {0, l, "0..l"});
+    return rc ? rc : check_list(err, -7, "inactive", k, inactive + k * l, l - t, {0, l, "0..l"});
+}
+
+// row k of `stride` ints: the first cnt entries of row k of src, 0 behind them; with cnt == 0 nothing of src is touched
+inline void pack_row(int* dst, const int64_t* src, int64_t k, int64_t cnt, int64_t stride) {
+    int* to = dst + k * stride;
+    const int64_t* from = cnt > 0 ? src + k * stride : nullptr;
+    for (int64_t i = 0; i < cnt; ++i) to[i] = (int)from[i];
+    std::fill(to + cnt, to + stride, 0);
+}
+// batch such rows, row k with cnt[k] entries
 inline void pack_rows(int* dst, const int64_t* src, const int64_t* cnt, int64_t batch, int64_t stride) {
-    for (int64_t k = 0; k < batch; ++k) {
-        const int64_t* from = src + k * stride;
-        int* to = dst + k * stride;
-        for (int64_t i = 0; i < cnt[k]; ++i) to[i] = (int)from[i];
-        std::fill(to + cnt[k], to + stride, 0);
-    }
+    for (int64_t k = 0; k < batch; ++k) pack_row(dst, src, k, cnt[k], stride);
+}
+
+// A working-set list as the addition, termination and direction calls move it: [active, batch rows of l | inactive, batch rows of
+// l].  The two halves of `list`, on either side (T: int in the scratch).
+template <class T>
+struct WorkingSets {
+    T *act, *inact;
+    WorkingSets(T* list, int64_t batch, int64_t l) : act(list), inact(list + batch * l) {}
+};
+// problem k's two rows of it from the caller's arrays: t active entries and l - t inactive ones.  t < 0, a problem that is not
+// taken: two zero rows, and nothing of its source rows is read.  (The Hessian sums pack the active half alone: pack_row.)
+inline void pack_working_sets(int* list, int64_t batch, int64_t l, int64_t k, const int64_t* active, const int64_t* inactive, int64_t t) {
+    const WorkingSets<int> w(list, batch, l);
+    pack_row(w.act, active, k, t < 0 ? 0 : t, l);
+    pack_row(w.inact, inactive, k, t < 0 ? 0 : l - t, l);
 }
 
 inline int take_flag(const int64_t* take, int64_t k) { return (take && take[k] == 0) ? 0 : 1; }     // no array: every problem
@@ -178,11 +216,7 @@ inline int check_addition(std::string& err, const AdditionShape& s, const int64_
                           const int64_t* inactive, const int64_t* index_alpha_upp, const int64_t* take, bool host_outputs,
                           bool device_inputs, bool device_outputs) {
     int rc;
-    if ((rc = check_batch(err, s.batch))) return rc;
-    if (s.n < 1 || s.n > 0x3fffffff) return fail(err, -3, "n must be at least 1");
-    if (s.l < 0 || s.l > BATCH_MAX_T) return fail(err, -3, "l must be in 0..1024 in this build");
-    if ((rc = check_t_max(err, s.t_max))) return rc;
-    if (s.t_max > s.l) return fail(err, -3, "t_max > l");
+    if ((rc = check_working_set_shape(err, s.batch, 0, s.n, s.l, s.t_max))) return rc;
     if (!q || !t || !host_outputs) return fail(err, -4, "q, t, added and status are host arrays of batch entries");
     if (s.l > 0 && (!active || !inactive)) return fail(err, -4, "active and inactive are host arrays of batch x l entries");
     if (s.t_max > 0 && (!device_inputs || !device_outputs))
@@ -196,8 +230,7 @@ inline int check_addition(std::string& err, const AdditionShape& s, const int64_
             return fail(err, -5, "t_max < max(t[" + std::to_string(k) + "], min(l, n)): the walk of problem " + std::to_string(k) +
                                      " could outgrow its slot");
         if ((rc = check_count(err, -6, "q", k, q[k], {0, t[k], "0..t[k]"})) ||
-            (rc = check_list(err, -7, "active", k, active + k * s.l, t[k], {0, s.l, "0..l"})) ||
-            (rc = check_list(err, -7, "inactive", k, inactive + k * s.l, s.l - t[k], {0, s.l, "0..l"})) ||
+            (rc = check_working_set(err, k, active, inactive, s.l, t[k])) ||
             (index_alpha_upp && (rc = check_count(err, -7, "index_alpha_upp", k, index_alpha_upp[k], {0, s.l, "0..l"})))) return rc;
     }
     if (s.lda < s.l) return fail(err, -9, "lda < l");
@@ -215,12 +248,7 @@ inline int check_termination(std::string& err, const TerminationShape& s, const 
                              const int64_t* inactive, const int64_t* take, bool host_rest, bool dev_m, bool dev_l, bool dev_t,
                              bool dev_n) {
     int rc;
-    if ((rc = check_batch(err, s.batch))) return rc;
-    if (s.m < 0 || s.m > 0x7fffffff) return fail(err, -3, "m must be in 0..2^31-1");
-    if (s.n < 1 || s.n > 0x3fffffff) return fail(err, -3, "n must be at least 1");
-    if (s.l < 0 || s.l > BATCH_MAX_T) return fail(err, -3, "l must be in 0..1024 in this build");
-    if ((rc = check_t_max(err, s.t_max))) return rc;
-    if (s.t_max > s.l) return fail(err, -3, "t_max > l");
+    if ((rc = check_working_set_shape(err, s.batch, s.m, s.n, s.l, s.t_max))) return rc;
     if (!state || !host_rest) return fail(err, -4, "state, tol, sums and exit_code are required");
     if (s.l > 0 && (!active || !inactive)) return fail(err, -4, "active and inactive are host arrays of batch x l entries");
     if (s.m > 0 && !dev_m) return fail(err, -4, "dJ and drx are required when m > 0");
@@ -233,8 +261,7 @@ inline int check_termination(std::string& err, const TerminationShape& s, const 
         if ((rc = check_count(err, -5, "state.t", k, st.t, {0, s.t_max, "0..t_max"})) ||
             (rc = check_count(err, -5, "state.l", k, st.l, {s.l, s.l, "l"})) ||
             (rc = check_count(err, -6, "state.q", k, st.q, {0, st.t, "0..t[k]"})) ||
-            (rc = check_list(err, -7, "active", k, active + k * s.l, st.t, {0, s.l, "0..l"})) ||
-            (rc = check_list(err, -7, "inactive", k, inactive + k * s.l, s.l - st.t, {0, s.l, "0..l"})) ||
+            (rc = check_working_set(err, k, active, inactive, s.l, st.t)) ||
             (rc = check_count(err, -8, "state.dimJ2", k, st.dimJ2, {0, s.n, "0..n"}))) return rc;
     }
     if (s.ldj < s.m) return fail(err, -9, "ldj < m");
@@ -252,12 +279,7 @@ constexpr int64_t DIR_PREV_MAX = 1LL << 31;      // |prev_dimJ2| (a Newton step 
 inline int check_direction(std::string& err, const DirectionShape& s, const enlsip_gn_dir_state* state, const int64_t* active,
                            const int64_t* inactive, const int64_t* take, bool host_rest, bool dev_m, bool dev_l, bool dev_t) {
     int rc;
-    if ((rc = check_batch(err, s.batch))) return rc;
-    if (s.m < 0 || s.m > 0x7fffffff) return fail(err, -3, "m must be in 0..2^31-1");
-    if (s.n < 1 || s.n > 0x3fffffff) return fail(err, -3, "n must be at least 1");
-    if (s.l < 0 || s.l > BATCH_MAX_T) return fail(err, -3, "l must be in 0..1024 in this build");
-    if ((rc = check_t_max(err, s.t_max))) return rc;
-    if (s.t_max > s.l) return fail(err, -3, "t_max > l");
+    if ((rc = check_working_set_shape(err, s.batch, s.m, s.n, s.l, s.t_max))) return rc;
     if (!state || !host_rest) return fail(err, -4, "state, sums, method_code, beta and status are required");
     if (s.l > 0 && (!active || !inactive)) return fail(err, -4, "active and inactive are host arrays of batch x l entries");
     if (s.m > 0 && !dev_m) return fail(err, -4, "dd is required when m > 0");
@@ -269,8 +291,7 @@ inline int check_direction(std::string& err, const DirectionShape& s, const enls
         if ((rc = check_count(err, -5, "state.t", k, st.t, {0, s.t_max, "0..t_max"})) ||
             (rc = check_count(err, -5, "state.l", k, st.l, {s.l, s.l, "l"})) ||
             (rc = check_count(err, -6, "state.q", k, st.q, {0, st.t, "0..t[k]"})) ||
-            (rc = check_list(err, -7, "active", k, active + k * s.l, st.t, {0, s.l, "0..l"})) ||
-            (rc = check_list(err, -7, "inactive", k, inactive + k * s.l, s.l - st.t, {0, s.l, "0..l"})) ||
+            (rc = check_working_set(err, k, active, inactive, s.l, st.t)) ||
             (rc = check_count(err, -8, "state.dimA", k, st.dimA, {0, st.t, "0..t[k]"})) ||
             (rc = check_count(err, -8, "state.dimJ2", k, st.dimJ2, {0, s.m, "0..m"})) ||
             (rc = check_count(err, -8, "state.prev_t", k, st.prev_t, {0, s.l, "0..l"})) ||
@@ -311,7 +332,7 @@ struct HessianShape { int64_t count, m, n, l, t_max, pair0, npairs, ldg, strideG
 inline int check_hessian_sums(std::string& err, const HessianShape& s, const int64_t* t, const int64_t* active, const int64_t* slot,
                               bool x, bool F, bool rx, bool G, bool lambda, bool Gamma) {
     int rc;
-    if (s.m < 0 || s.m > 0x7fffffff) return fail(err, -2, "m must be in 0..2^31-1");
+    if (s.m < 0 || s.m > 0x7fffffff) return fail(err, -2, "m must be in 0..2^31-1");      // -2 here, not check_m's -3
     if (s.l < 0 || s.l > (1LL << 27) || s.t_max < 0 || s.t_max > 0x7fffffff) return fail(err, -2, "l must be in 0..2^27 and t_max in 0..2^31-1");
     if ((rc = check_hessian_range(err, s.count, s.n, s.pair0, s.npairs, std::max(s.m, s.l)))) return rc;
     const int64_t t_top = std::min(s.l, s.t_max);

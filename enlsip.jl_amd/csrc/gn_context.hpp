@@ -95,6 +95,10 @@ struct SolveMode {
     SolveMode fresh() const { return {Fresh, nullptr, false, dimA_ov, dimJ2_ov, eps_rank, abs_shift}; }
 };
 
+// the families whose last kernel form a handle records (enlsip_gn_context::form)
+enum Form { FORM_CONSUMER, FORM_RESOLVE, FORM_NEWTON, FORM_SUBSPACE, FORM_DELETION, FORM_LINESEARCH, FORM_PENALTY, FORM_ADDITION,
+            FORM_TERMINATION, FORM_DIRECTION, FORM_COUNT };
+
 }  // namespace gn
 
 struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed main workspace
@@ -215,65 +219,36 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     gn::DevBuf lagb_io, lagb_scr;
     gn::PinnedBuf h_lagflag;
     bool lagrange_small = true;         // ENLSIP_GN_LAGRANGE_SMALL=0: batched multiplier estimates in the general form only (A/B)
-    int consumer_form = -1;             // form of the last batched multiplier estimate (enlsip_gn_get_consumer_form), -1: none yet
-    // batched re-solve (gn_resolve_batched.inc): per-slot requests on the device, staging of the host-buffer form, the form of the
-    // last call, and per resident problem the (code, dimA) of a held call whose p1 and Q3' d_temp are still in p1 / vec (code 0: none)
+    // batched re-solve (gn_resolve_batched.inc): per-slot requests on the device, staging of the host-buffer form, and per
+    // resident problem the (code, dimA) of a held call whose p1 and Q3' d_temp are still in p1 / vec (code 0: none)
     gn::DevBuf rsb_dims, rsb_io;
-    int resolve_form = -1;
     hipEvent_t rsb_ev[2] = {};          // profiling on: around the Q0' launches of the last batched re-solve on this handle
     bool rsb_timed = false;
     float resolve_q0_ms = 0.f;          // ... summed over the handles that ran a part of the range
     struct Held { int code = 0, dimA = 0; };
     std::vector<Held> held;
-    // batched Newton direction (gn_newton_batched.inc): device temporaries of a segment, staging of the host-buffer form, the form of
-    // the last call, HIP events around its four stages (profiling on) and their times summed over the handles that ran a part
+    // batched Newton direction (gn_newton_batched.inc): device temporaries of a segment, staging of the host-buffer form, HIP
+    // events around its four stages (profiling on) and their times summed over the handles that ran a part
     gn::DevBuf nwb_ws, nwb_io;
     gn::PinnedBuf h_nwflag;             // pinned "some slot flagged" word of the last launch on this handle
-    int newton_form = -1;
     hipEvent_t nwb_ev[5] = {};
     bool nwb_timed = false;
     float newton_ms[4] = {};
     // one-call subspace minimisation (gn_subspace_batched.inc): requests and previous iterates on the device, staging of the
-    // host-buffer form, the pinned copy of the final requests (chosen dimensions, status) and the form of the last call
+    // host-buffer form and the pinned copy of the final requests (chosen dimensions, status)
     gn::DevBuf ssb_req, ssb_io;
     gn::PinnedBuf h_ssb;
-    int subspace_form = -1;
-    // batched deletion test and working-set edit (gn_deletion_batched.inc): t / q / take / s of one call on the device and in pinned
-    // memory, and the form of the last call; nothing of the resident state
-    gn::DevBuf del_scr;
-    gn::PinnedBuf h_del;
-    int deletion_form = -1;
-    // batched line-search set-up (gn_linesearch_batched.inc): the inactive lists and per-problem records of one call on the device
-    // and in pinned memory, the partial sums and the five scalars per problem, and the form of the last call; nothing resident
-    gn::DevBuf ls_scr;
-    gn::PinnedBuf h_ls;
-    int linesearch_form = -1;
-    // batched penalty weights and merit function (gn_penalty_batched.inc): the active / inactive lists and per-problem records of one
-    // call on the device and in pinned memory, the partial sums of rx.rx and the scalars per problem (the two calls lay the same
-    // buffers out for themselves, and so does the polynomial fit of gn_linesearch_fit_batched.inc), and the form of the last
-    // penalty-weight call; nothing resident
-    gn::DevBuf pen_scr;
-    gn::PinnedBuf h_pen;
-    int penalty_form = -1;
-    // batched working-set additions and rebuild of the active constraints (gn_addition_batched.inc): the records and both index
-    // lists of one call on the device and in pinned memory, and the form of the last call; nothing resident
-    gn::DevBuf add_scr;
-    gn::PinnedBuf h_add;
-    int addition_form = -1;
-    // batched termination test (gn_termination_batched.inc): the records and both index lists of one call on the device and in
-    // pinned memory, the partial sums of rx.rx and the sums per problem, and the form of the last call; nothing resident
-    gn::DevBuf term_scr;
-    gn::PinnedBuf h_term;
-    int termination_form = -1;
-    // batched direction check (gn_direction_batched.inc): the records and both index lists of one call on the device and in pinned
-    // memory, the sums per problem, and the form of the last call; nothing resident
-    gn::DevBuf dir_scr;
-    gn::PinnedBuf h_dir;
-    int direction_form = -1;
-    // batched Hessian sums of the Newton branch (gn_hessian_batched.inc): the per-problem counts and slots and the active lists of
-    // one call on the device and in pinned memory; nothing resident
-    gn::DevBuf hess_scr;
-    gn::PinnedBuf h_hess;
+    // The one record scratch of the eleven calls on the caller's device buffers (gn_batch_records.hpp): delete and
+    // restore, line-search set-up, penalty weights, merit, fit, additions, termination test, direction check, Hessian sums (the
+    // Hessian points need none).  A device buffer and its pinned mirror, grown and never shrunk, shared on this invariant: every
+    // such call places its own layout at its start (place_records), nothing in the scratch is read before the call has written
+    // it, and the call synchronises h->stream before it returns (round_trip).  So nothing in it outlives a call and nothing of
+    // the resident state is in it.
+    gn::DevBuf rec_scr;
+    gn::PinnedBuf h_rec;
+    // the kernel form the last call of each family took (1 wave / small, 0 general; the enlsip_gn_get_*_form getters), -1: none yet
+    int form[gn::FORM_COUNT] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+    static_assert(gn::FORM_COUNT == 10, "one -1 per family in the initialiser of form");
     gn::ProbState* h_state = nullptr;   // pinned
     size_t h_state_cap = 0;
     // device-pointer inputs of the last solve (resolve, Newton direction, J*Q1, gradient, multiplier estimates)

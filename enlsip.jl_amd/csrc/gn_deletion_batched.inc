@@ -1,8 +1,8 @@
 // The deletion test and the working-set edit of a batch on the caller's device buffers (kernels: gn_kernels_deletion_batched.hpp; the
 // test: gn_deletion_test.hpp): check_constraint_deletion (src/enlsip_functions.jl:574-603) with the removal of :708-719 / :748-756 /
 // :776-785, and the re-insertion of :731-739.  Neither call needs or touches anything resident: the handle lends its device, its
-// stream and a small scratch for t / q / take / s (DeletionScratch: the records up, the decisions down; the restore brings
-// nothing down).  Included at the end of enlsip_gn.hip.
+// stream and its record scratch, in which each call places t / q / take / s for itself (DeletionScratch: the records up, the
+// decisions down; the restore brings nothing down).  Included at the end of enlsip_gn.hip.
 
 namespace {
 
@@ -10,9 +10,7 @@ namespace {
 int deletion_check_shape(enlsip_gn_handle h, int64_t batch, int64_t n, int64_t t_max, const int64_t* t, const double* dlambda,
                          const double* ddiag_scale, const double* dAt, int64_t ldat, int64_t strideAt, const double* dcx) {
     int rc;
-    if ((rc = check_batch(h->err, batch))) return rc;
-    if (n < 1 || n > 0x3fffffff) { h->err = "n must be at least 1"; return -3; }
-    if ((rc = check_t_max(h->err, t_max))) return rc;
+    if ((rc = check_batch(h->err, batch)) || (rc = check_n(h->err, n)) || (rc = check_t_max(h->err, t_max))) return rc;
     if (!t) { h->err = "t is a host array of batch entries"; return -4; }
     if (t_max > 0 && (!dlambda || !ddiag_scale || !dAt || !dcx)) {
         h->err = "dlambda, ddiag_scale, dAt and dcx are required when t_max > 0";
@@ -64,19 +62,17 @@ int enlsip_gn_delete_constraints_batched_dev(enlsip_gn_handle h, int64_t batch, 
     }
     GN_HIP(hipSetDevice(h->device));
     DeletionScratch D, H;
-    if ((rc = place_records(h, h->del_scr, h->h_del, D, H, 0, batch, (int64_t)0))) return rc;
+    if ((rc = place_records(h, D, H, 0, batch, (int64_t)0))) return rc;
     for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], (int)q[k], take_flag(take, k), 0};
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     DeletionArgs a = deletion_args(batch, n, t_max, scaling, dlambda, ddiag_scale, dgrad_res, dAt, ldat, strideAt, dcx, dsaved);
     a.meta = D.meta; a.s_out = D.out;
     const bool wave = deletion_wave_form(n, t_max);
-    h->deletion_form = wave ? 1 : 0;
-    if (wave) hipLaunchKernelGGL(k_delete_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_delete_general, dim3((unsigned)batch), dim3(256), 0, st, a);
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    h->form[FORM_DELETION] = wave ? 1 : 0;
+    auto launch = [&](hipStream_t st) {
+        if (wave) hipLaunchKernelGGL(k_delete_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_delete_general, dim3((unsigned)batch), dim3(256), 0, st, a);
+    };
+    if ((rc = round_trip(h, D, H, launch, H.out, D.out, H.down_bytes))) return rc;
     std::copy(H.out, H.out + batch, s);
     return 0;
     GN_CATCH(h)
@@ -101,26 +97,19 @@ int enlsip_gn_restore_constraints_batched_dev(enlsip_gn_handle h, int64_t batch,
     if (!dsaved) { h->err = "dsaved is NULL while some s[k] != 0"; return -12; }
     GN_HIP(hipSetDevice(h->device));
     DeletionScratch D, H;
-    if ((rc = place_records(h, h->del_scr, h->h_del, D, H, 0, batch, (int64_t)0))) return rc;
+    if ((rc = place_records(h, D, H, 0, batch, (int64_t)0))) return rc;
     for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], 0, 1, (int)s[k]};
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     DeletionArgs a = deletion_args(batch, n, t_max, 0, dlambda, ddiag_scale, nullptr, dAt, ldat, strideAt, dcx, (double*)dsaved);
     a.meta = D.meta;
     const bool wave = deletion_wave_form(n, t_max);
-    h->deletion_form = wave ? 1 : 0;
-    if (wave) hipLaunchKernelGGL(k_restore_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_restore_general, dim3((unsigned)batch), dim3(256), 0, st, a);
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipStreamSynchronize(st));
-    return 0;
+    h->form[FORM_DELETION] = wave ? 1 : 0;
+    return round_trip(h, D, H, [&](hipStream_t st) {      // nothing comes down
+        if (wave) hipLaunchKernelGGL(k_restore_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_restore_general, dim3((unsigned)batch), dim3(256), 0, st, a);
+    });
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_deletion_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->deletion_form;
-    return 0;
-}
+int enlsip_gn_get_deletion_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_DELETION, form); }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // The Gauss-Newton direction check of a batch on the caller's device buffers (kernels: gn_kernels_direction_batched.hpp; the
 // routines: gn_direction_check.hpp): the norms of search_direction_analys (src/enlsip_functions.jl:1222-1231) and what
 // check_gn_direction (:943-1030) reads of lambda, diag_scale and cx.  The call needs and touches nothing resident: the handle lends
-// its device, its stream and a scratch for the records (DirectionScratch: the per-problem counts and both lists up; the sums down).
+// its device, its stream and its record scratch, in which the call places its records (DirectionScratch: the per-problem counts and both lists up; the sums down).
 // The method codes are formed on the host from the downloaded sums by dir_decide, the one implementation of the decision.
 // Included at the end of enlsip_gn.hip.
 
@@ -54,32 +54,27 @@ int enlsip_gn_direction_check_batched_dev(enlsip_gn_handle h, int64_t batch, int
                              dd != nullptr, dcx_all != nullptr, db && dlambda && ddiag_scale);
     if (rc) return rc;
     const bool wave = direction_wave_form(m, l, t_max);
-    h->direction_form = wave ? 1 : 0;
+    h->form[FORM_DIRECTION] = wave ? 1 : 0;
     GN_HIP(hipSetDevice(h->device));
     DirectionScratch D, H;
-    if ((rc = place_records(h, h->dir_scr, h->h_dir, D, H, 0, batch, 2 * l))) return rc;
-    std::vector<int64_t> n_act((size_t)batch), n_ina((size_t)batch);
+    if ((rc = place_records(h, D, H, 0, batch, 2 * l))) return rc;
     for (int64_t k = 0; k < batch; ++k) {      // not taken, or status 1: counts of 0, so that nothing of the problem is read
         const enlsip_gn_dir_state& s = state[k];
         const int tk = take_flag(take, k) && dir_status(s, m, n) != 1;
         const int64_t kp = tk ? std::max<int64_t>(dir_k_prev(s), 0) : 0;
         H.meta[k] = tk ? DirMeta{(int)s.t, (int)s.q, (int)s.dimA, (int)s.dimJ2, (int)kp, 1} : DirMeta{0, 0, 0, 0, 0, 0};
-        n_act[k] = tk ? s.t : 0;
-        n_ina[k] = tk ? l - s.t : 0;
+        pack_working_sets(H.list, batch, l, k, active, inactive, tk ? s.t : -1);
     }
-    pack_rows(H.list, active, n_act.data(), batch, l);
-    pack_rows(H.list + batch * l, inactive, n_ina.data(), batch, l);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
+    const WorkingSets<int> Dw(D.list, batch, l);
     DirectionArgs a{};
-    a.meta = D.meta; a.act = D.list; a.inact = D.list + batch * l; a.out = D.out;
+    a.meta = D.meta; a.act = Dw.act; a.inact = Dw.inact; a.out = D.out;
     a.count = (int)batch; a.m = (int)m; a.l = (int)l; a.t_max = (int)t_max; a.scaling = scaling != 0;
     a.b = db; a.d = dd; a.lambda = dlambda; a.diag_scale = ddiag_scale; a.cx_all = dcx_all;
-    if (wave) hipLaunchKernelGGL(k_dir_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_dir_general, dim3((unsigned)batch), dim3(256), 0, st, a);
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    auto launch = [&](hipStream_t st) {
+        if (wave) hipLaunchKernelGGL(k_dir_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_dir_general, dim3((unsigned)batch), dim3(256), 0, st, a);
+    };
+    if ((rc = round_trip(h, D, H, launch, H.out, D.out, H.down_bytes))) return rc;
     for (int64_t k = 0; k < batch; ++k) {
         if (!take_flag(take, k)) continue;
         status[k] = dir_status(state[k], m, n);
@@ -93,10 +88,6 @@ int enlsip_gn_direction_check_batched_dev(enlsip_gn_handle h, int64_t batch, int
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_direction_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->direction_form;
-    return 0;
-}
+int enlsip_gn_get_direction_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_DIRECTION, form); }
 
 }  // extern "C"

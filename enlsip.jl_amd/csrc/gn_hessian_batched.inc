@@ -1,7 +1,7 @@
 // The finite-difference Hessian sums of the Newton branch (src/enlsip_functions.jl:243-328) around the caller's evaluations, on
 // the host for one problem and for a batch on the caller's device buffers (kernels: gn_kernels_hessian_batched.hpp; the routines:
-// gn_hessian_sums.hpp).  The batched calls need and touch nothing resident: the handle lends its device, its stream and a scratch
-// for the records of the sums call (HessianScratch: the per-problem counts and slots and the active lists up; nothing comes down).
+// gn_hessian_sums.hpp).  The batched calls need and touch nothing resident: the handle lends its device, its stream and its record
+// scratch, in which the sums call places its records (HessianScratch: the per-problem counts and slots and the active lists up; nothing comes down).
 // eps1 is formed on the host, once per call, and handed to the kernels.  Included at the end of enlsip_gn.hip.
 
 extern "C" {
@@ -56,26 +56,21 @@ int enlsip_gn_hessian_sums_batched_dev(enlsip_gn_handle h, int64_t count, int64_
     if (rc) return rc;
     GN_HIP(hipSetDevice(h->device));
     HessianScratch D, H;
-    if ((rc = place_records(h, h->hess_scr, h->h_hess, D, H, 0, count, l))) return rc;
-    std::vector<int64_t> n_act((size_t)count);
+    if ((rc = place_records(h, D, H, 0, count, l))) return rc;
     for (int64_t k = 0; k < count; ++k) {      // slot[k] < 0: a count of 0, so that nothing of the problem is read
         const bool tk = !slot || slot[k] >= 0;
         H.meta[k] = tk ? HessMeta{(int)t[k], (int)(slot ? slot[k] : k)} : HessMeta{0, -1};
-        n_act[k] = tk ? t[k] : 0;
+        if (active) pack_row(H.list, active, k, tk ? t[k] : 0, l);      // the active half of a working-set list
     }
-    if (l > 0 && active) pack_rows(H.list, active, n_act.data(), count, l);
-    else if (l > 0) std::fill(H.list, H.list + count * l, 0);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
+    if (!active) std::fill(H.list, H.list + count * l, 0);             // no active array (every count is 0): zeros
     HessianSumsArgs a{};
     a.meta = D.meta; a.act = D.list;
     a.m = (int)m; a.n = (int)n; a.l = (int)l; a.t_max = (int)t_max; a.pair0 = pair0; a.npairs = npairs; a.eps1 = hess_eps1();
     a.x = dx; a.F = dF; a.rx = drx; a.G = dG; a.lambda = dlambda; a.Gamma = dGamma; a.ldg = ldg; a.strideG = strideG;
     const int64_t blocks = (npairs + HESS_PAIRS_PER_WG - 1) / HESS_PAIRS_PER_WG;
-    hipLaunchKernelGGL(k_hessian_sums, dim3((unsigned)count, (unsigned)std::min<int64_t>(blocks, HESS_MAX_GRID_Y)), dim3(256), 0, st, a);
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipStreamSynchronize(st));      // the pinned records are free again when the call returns
-    return 0;
+    return round_trip(h, D, H, [&](hipStream_t st) {      // nothing comes down
+        hipLaunchKernelGGL(k_hessian_sums, dim3((unsigned)count, (unsigned)std::min<int64_t>(blocks, HESS_MAX_GRID_Y)), dim3(256), 0, st, a);
+    });
     GN_CATCH(h)
 }
 

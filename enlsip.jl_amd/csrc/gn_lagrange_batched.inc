@@ -228,7 +228,7 @@ int consumer_dev(enlsip_gn_handle h, int kind, int64_t prob0, int64_t count, con
     }
     GN_HIP(hipSetDevice(h->device));
     const bool small = h->lagrange_small && P.n <= 64 && P.t <= 64;
-    if (est) h->consumer_form = small ? 1 : 0;
+    if (est) h->form[FORM_CONSUMER] = small ? 1 : 0;
     rc = for_each_segment(h, r, [&](const ResidentSeg& sg) { return consumer_launch(sg.hh, kind, sg, io, small); });
     if (rc) return rc;
     bool flagged = false;
@@ -339,10 +339,6 @@ int enlsip_gn_second_lagrange_batched(enlsip_gn_handle h, int64_t prob0, int64_t
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_consumer_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->consumer_form;
-    return 0;
-}
+int enlsip_gn_get_consumer_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_CONSUMER, form); }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // The line-search set-up of a batch on the caller's device buffers (kernels: gn_kernels_linesearch_batched.hpp; the bound:
 // gn_steplength_bound.hpp): Ap = A * p of src/enlsip_functions.jl:2227, upper_bound_steplength (:2149-2178) and the three sums of
-// :1561-1584 / :2269.  The call needs and touches nothing resident: the handle lends its device, its stream and a scratch for the
-// host records, the partial sums and the five scalars per problem (LinesearchScratch).  Included at the end of enlsip_gn.hip.
+// :1561-1584 / :2269.  The call needs and touches nothing resident: the handle lends its device, its stream and its record scratch,
+// in which the call places the host records, the partial sums and the five scalars per problem (LinesearchScratch).  Included at the end of enlsip_gn.hip.
 
 namespace {
 
@@ -58,7 +58,7 @@ int enlsip_gn_linesearch_setup_batched_dev(enlsip_gn_handle h, int64_t batch, in
         h->err = "batch * max(ceil(l / 256), partial-sum workgroups) exceeds the grid";
         return -2;
     }
-    h->linesearch_form = wave ? 1 : 0;
+    h->form[FORM_LINESEARCH] = wave ? 1 : 0;
     if (l == 0 && !want_sums) {      // no constraint anywhere and no sums: nothing to launch
         std::fill(alpha_upp, alpha_upp + batch, GN_STEPLENGTH_CAP);
         std::fill(index_alpha_upp, index_alpha_upp + batch, (int64_t)0);
@@ -66,26 +66,24 @@ int enlsip_gn_linesearch_setup_batched_dev(enlsip_gn_handle h, int64_t batch, in
     }
     GN_HIP(hipSetDevice(h->device));
     LinesearchScratch D, H;      // the partial sums: the general form's only
-    if ((rc = place_records(h, h->ls_scr, h->h_ls, D, H, wave ? 0 : 3 * nblk, batch, l))) return rc;
+    if ((rc = place_records(h, D, H, wave ? 0 : 3 * nblk, batch, l))) return rc;
     for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)n_inactive[k], index_del ? (int)index_del[k] : 0};
     pack_rows(H.list, inactive, n_inactive, batch, l);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     LinesearchArgs a{};
     a.meta = D.meta; a.list = D.list; a.out = D.out; a.part = D.part;
     a.count = (int)batch; a.n = (int)n; a.l = (int)l; a.m = want_sums ? (int)m : 0;
     a.row_blocks = (int)row_blocks; a.nblk = (int)nblk;
     a.p = dp; a.A = dA; a.lda = lda; a.strideA = strideA; a.cx = dcx; a.Jp = dJp; a.rx = drx; a.Ap = dAp;
-    if (wave) {
-        hipLaunchKernelGGL(k_ls_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    } else {
-        if (l > 0) hipLaunchKernelGGL(k_ls_product, dim3((unsigned)(batch * row_blocks)), dim3(256), 0, st, a);
-        if (want_sums) hipLaunchKernelGGL(k_ls_sums_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_ls_bound, dim3((unsigned)batch), dim3(256), 0, st, a);
-    }
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    auto launch = [&](hipStream_t st) {
+        if (wave) {
+            hipLaunchKernelGGL(k_ls_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        } else {
+            if (l > 0) hipLaunchKernelGGL(k_ls_product, dim3((unsigned)(batch * row_blocks)), dim3(256), 0, st, a);
+            if (want_sums) hipLaunchKernelGGL(k_ls_sums_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_ls_bound, dim3((unsigned)batch), dim3(256), 0, st, a);
+        }
+    };
+    if ((rc = round_trip(h, D, H, launch, H.out, D.out, H.down_bytes))) return rc;
     for (int64_t k = 0; k < batch; ++k) {
         alpha_upp[k] = H.out[k].alpha_upp;
         index_alpha_upp[k] = H.out[k].index_alpha_upp;
@@ -95,10 +93,6 @@ int enlsip_gn_linesearch_setup_batched_dev(enlsip_gn_handle h, int64_t batch, in
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_linesearch_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->linesearch_form;
-    return 0;
-}
+int enlsip_gn_get_linesearch_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_LINESEARCH, form); }
 
 }  // extern "C"

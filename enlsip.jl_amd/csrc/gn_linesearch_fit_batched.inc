@@ -5,8 +5,8 @@
 // the last place and the routine branches on their results, so a device copy could not be pinned to the host routine, and the
 // step length has to reach the host for the next callback evaluation anyway.  With psi_new the merit kernels of
 // gn_kernels_penalty_batched.hpp run on (drx_new, dcx_new, dw) from the same uploaded records.  The call needs or touches nothing
-// resident: the handle lends its device, its stream and the scratch of the merit call (MeritScratch with fit).  Included at the
-// end of enlsip_gn.hip.
+// resident: the handle lends its device, its stream and its record scratch, in which the call places the layout of the merit call
+// with the fit's arrays (MeritScratch with fit).  Included at the end of enlsip_gn.hip.
 
 extern "C" {
 
@@ -61,7 +61,7 @@ int enlsip_gn_linesearch_fit_batched_dev(enlsip_gn_handle h, int64_t batch, int6
     GN_TRY
     int rc = check_shape(h->err, batch, l, t_max);
     if (rc) return rc;
-    if (m < 0 || m > 0x7fffffff) { h->err = "m must be in 0..2^31-1"; return -3; }
+    if ((rc = check_m(h->err, m))) return rc;
     if (!t || !n_inactive || !alpha_k || !x_min || !alpha_min || !alpha_max || !sums || !out || !arm) {
         h->err = "t, n_inactive, alpha_k, x_min, alpha_min, alpha_max, sums, out and arm are host arrays of batch (6 x batch) entries";
         return -4;
@@ -84,23 +84,21 @@ int enlsip_gn_linesearch_fit_batched_dev(enlsip_gn_handle h, int64_t batch, int6
     if (!grid_fits(batch, nblk)) { h->err = "batch * partial-sum workgroups exceeds the grid"; return -2; }
     GN_HIP(hipSetDevice(h->device));
     MeritScratch D, H;
-    if ((rc = place_records(h, h->pen_scr, h->h_pen, D, H, nblk, batch, t_max, l, true))) return rc;
+    if ((rc = place_records(h, D, H, nblk, batch, t_max, l, true))) return rc;
     for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], (int)n_inactive[k], take_flag(take, k), 0};
     pack_rows(H.act, active, t, batch, t_max);
     pack_rows(H.inact, inactive, n_inactive, batch, l);
     std::copy(alpha_k, alpha_k + batch, H.alpha);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     FitArgs a{};
     a.meta = D.meta; a.act = D.act; a.inact = D.inact; a.alpha = D.alpha; a.part = D.part; a.out = D.sums;
     a.count = (int)batch; a.m = (int)m; a.l = (int)l; a.t_max = (int)t_max; a.nblk = (int)nblk;
     a.rx = drx; a.rx_new = drx_new; a.Jp = dJp; a.cx = dcx; a.cx_new = dcx_new; a.Ap = dAp; a.w = dw;
-    if (nblk > 0) hipLaunchKernelGGL(k_fit_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_fit_total, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    if (psi_new) launch_merit(st, {D.meta, D.act, D.inact, D.mpart, D.psi, a.count, a.m, a.l, a.t_max, a.nblk, drx_new, dcx_new, dw});
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.sums, D.sums, H.down_bytes - (psi_new ? 0 : H.psi_bytes), hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    auto launch = [&](hipStream_t st) {
+        if (nblk > 0) hipLaunchKernelGGL(k_fit_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_fit_total, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        if (psi_new) launch_merit(st, {D.meta, D.act, D.inact, D.mpart, D.psi, a.count, a.m, a.l, a.t_max, a.nblk, drx_new, dcx_new, dw});
+    };
+    if ((rc = round_trip(h, D, H, launch, H.sums, D.sums, H.down_bytes - (psi_new ? 0 : H.psi_bytes)))) return rc;
     for (int64_t k = 0; k < batch; ++k) {
         double* o = out + 6 * k;
         double* s = sums + 6 * k;

@@ -133,7 +133,7 @@ int newton_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const NewtonIO&
         }
     GN_HIP(hipSetDevice(h->device));
     const bool small = P.n <= 64;
-    h->newton_form = small ? 1 : 0;
+    h->form[FORM_NEWTON] = small ? 1 : 0;
     std::vector<std::vector<int>> packs(r.seg.size());      // one per segment, alive until the streams are synchronised
     rc = for_each_segment(h, r, [&](const ResidentSeg& sg) {
         return newton_launch(sg.hh, sg, req.data() + sg.j0, io, small, h->profiling, packs[(size_t)(&sg - r.seg.data())]);
@@ -214,11 +214,7 @@ int enlsip_gn_newton_direction_batched(enlsip_gn_handle h, int64_t prob0, int64_
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_newton_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->newton_form;
-    return 0;
-}
+int enlsip_gn_get_newton_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_NEWTON, form); }
 
 int enlsip_gn_get_newton_stage_ms(enlsip_gn_handle h, float* ms) {
     GN_GETTER_CHECK(h, ms)

@@ -1,8 +1,8 @@
 // The penalty weights and the merit function of a batch on the caller's device buffers (kernels: gn_kernels_penalty_batched.hpp;
 // the routine: gn_penalty_weights.hpp): penalty_weight_update (src/enlsip_functions.jl:1545-1629) with psi(0) of :2243 and atwa of
 // :2268, and psi of :1307-1340 on evaluated trial points.  Neither call needs or touches anything resident: the handle lends its
-// device, its stream and a scratch for the host records, the partial sums and the scalars (PenaltyScratch, MeritScratch).  Included
-// at the end of enlsip_gn.hip.
+// device, its stream and its record scratch, in which each call places the host records, the partial sums and the scalars
+// (PenaltyScratch, MeritScratch).  Included at the end of enlsip_gn.hip.
 
 namespace {
 
@@ -95,24 +95,22 @@ int enlsip_gn_penalty_weights_batched_dev(enlsip_gn_handle h, int64_t batch, int
         if ((rc = check_count(h->err, -6, "dimA", k, dimA[k], {0, t[k], "0..t[k]"})) ||
             (rc = check_list(h->err, -6, "active", k, active + k * t_max, t[k], {1, l, "1..l"}))) return rc;
     const bool wave = penalty_wave_form(t_max, l);
-    h->penalty_form = wave ? 1 : 0;
+    h->form[FORM_PENALTY] = wave ? 1 : 0;
     GN_HIP(hipSetDevice(h->device));
     PenaltyScratch D, H;
-    if ((rc = place_records(h, h->pen_scr, h->h_pen, D, H, 0, batch, t_max))) return rc;
+    if ((rc = place_records(h, D, H, 0, batch, t_max))) return rc;
     for (int64_t k = 0; k < batch; ++k)
         H.meta[k] = {{sums[3 * k], sums[3 * k + 1], sums[3 * k + 2]}, (int)t[k], (int)dimA[k], take_flag(take, k), 0};
     pack_rows(H.list, active, t, batch, t_max);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
     PenaltyArgs a{};
     a.meta = D.meta; a.list = D.list; a.out = D.out;
     a.count = (int)batch; a.l = (int)l; a.t_max = (int)t_max; a.norm_code = norm_code; a.scaling = scaling != 0;
     a.w_old = dw_old; a.active_Ap = dactive_Ap; a.diag_scale = ddiag_scale; a.cx = dcx; a.K = dK; a.w = dw;
-    if (wave) hipLaunchKernelGGL((k_penalty<64, 64>), dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_penalty<256, PW_MAX_T>), dim3((unsigned)batch), dim3(256), 0, st, a);
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    auto launch = [&](hipStream_t st) {
+        if (wave) hipLaunchKernelGGL((k_penalty<64, 64>), dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_penalty<256, PW_MAX_T>), dim3((unsigned)batch), dim3(256), 0, st, a);
+    };
+    if ((rc = round_trip(h, D, H, launch, H.out, D.out, H.down_bytes))) return rc;
     for (int64_t k = 0; k < batch; ++k) {
         const bool taken = H.meta[k].take != 0;
         for (int q = 0; q < 3; ++q) scalars[3 * k + q] = taken ? H.out[k].scalars[q] : 0.0;
@@ -122,11 +120,7 @@ int enlsip_gn_penalty_weights_batched_dev(enlsip_gn_handle h, int64_t batch, int
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_penalty_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->penalty_form;
-    return 0;
-}
+int enlsip_gn_get_penalty_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_PENALTY, form); }
 
 int enlsip_gn_merit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, int64_t l, int64_t t_max, const int64_t* t,
                                 const int64_t* active, const int64_t* inactive, const int64_t* n_inactive, const int64_t* take,
@@ -135,7 +129,7 @@ int enlsip_gn_merit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
     GN_TRY
     int rc = check_shape(h->err, batch, l, t_max);
     if (rc) return rc;
-    if (m < 0 || m > 0x7fffffff) { h->err = "m must be in 0..2^31-1"; return -3; }
+    if ((rc = check_m(h->err, m))) return rc;
     if (!t || !n_inactive || !psi) { h->err = "t, n_inactive and psi are host arrays of batch entries"; return -4; }
     if (m > 0 && !drx) { h->err = "drx is required when m > 0"; return -4; }
     if (l > 0 && (!dcx || !dw || !inactive)) { h->err = "dcx, dw and inactive are required when l > 0"; return -4; }
@@ -150,16 +144,12 @@ int enlsip_gn_merit_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t m, in
     if (!grid_fits(batch, nblk)) { h->err = "batch * partial-sum workgroups exceeds the grid"; return -2; }
     GN_HIP(hipSetDevice(h->device));
     MeritScratch D, H;
-    if ((rc = place_records(h, h->pen_scr, h->h_pen, D, H, nblk, batch, t_max, l, false))) return rc;
+    if ((rc = place_records(h, D, H, nblk, batch, t_max, l, false))) return rc;
     for (int64_t k = 0; k < batch; ++k) H.meta[k] = {(int)t[k], (int)n_inactive[k], take_flag(take, k), 0};
     pack_rows(H.act, active, t, batch, t_max);
     pack_rows(H.inact, inactive, n_inactive, batch, l);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
-    launch_merit(st, {D.meta, D.act, D.inact, D.mpart, D.psi, (int)batch, (int)m, (int)l, (int)t_max, (int)nblk, drx, dcx, dw});
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.psi, D.psi, H.down_bytes, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    const MeritArgs a{D.meta, D.act, D.inact, D.mpart, D.psi, (int)batch, (int)m, (int)l, (int)t_max, (int)nblk, drx, dcx, dw};
+    if ((rc = round_trip(h, D, H, [&](hipStream_t st) { launch_merit(st, a); }, H.psi, D.psi, H.down_bytes))) return rc;
     std::copy(H.psi, H.psi + batch, psi);
     return 0;
     GN_CATCH(h)

@@ -200,7 +200,7 @@ int resolve_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t*
     }
     GN_HIP(hipSetDevice(h->device));
     const bool small = resolve_small(P);
-    h->resolve_form = small ? 1 : 0;
+    h->form[FORM_RESOLVE] = small ? 1 : 0;
     // the first call of the reference's flow asks for b alone (:1251): no d pointer and every request held — F_J2.Q' is not applied
     bool b_only = io.d == nullptr;
     for (const ResolveDims& d : dims)
@@ -334,10 +334,6 @@ int enlsip_gn_get_resolve_q0_ms(enlsip_gn_handle h, float* ms) {
     return 0;
 }
 
-int enlsip_gn_get_resolve_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->resolve_form;
-    return 0;
-}
+int enlsip_gn_get_resolve_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_RESOLVE, form); }
 
 }  // extern "C"

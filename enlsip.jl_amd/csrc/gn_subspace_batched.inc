@@ -171,7 +171,7 @@ int subspace_dev(enlsip_gn_handle h, int64_t prob0, int64_t count, const int64_t
     }
     GN_HIP(hipSetDevice(h->device));
     const bool small = resolve_small(P);
-    h->subspace_form = small ? 1 : 0;
+    h->form[FORM_SUBSPACE] = small ? 1 : 0;
     std::vector<std::vector<char>> packs(r.seg.size());      // one per segment, alive until the streams are synchronised
     rc = for_each_segment(h, r, [&](const ResidentSeg& sg) {
         return subspace_launch(sg.hh, sg, dims.data() + sg.j0, pvs.data() + sg.j0, io, small, packs[(size_t)(&sg - r.seg.data())]);
@@ -254,10 +254,6 @@ int enlsip_gn_subspace_direction_batched(enlsip_gn_handle h, int64_t prob0, int6
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_subspace_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->subspace_form;
-    return 0;
-}
+int enlsip_gn_get_subspace_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_SUBSPACE, form); }
 
 }  // extern "C"

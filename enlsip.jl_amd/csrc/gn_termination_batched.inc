@@ -1,6 +1,6 @@
 // The termination test of a batch on the caller's device buffers (kernels: gn_kernels_termination_batched.hpp; the routines:
 // gn_termination.hpp): what stands between new_point! and evaluate_violated_constraints in src/enlsip_functions.jl:2828-2839.  The
-// call needs and touches nothing resident: the handle lends its device, its stream and a scratch for the records
+// call needs and touches nothing resident: the handle lends its device, its stream and its record scratch, in which the call places its records
 // (TerminationScratch: the per-problem counts, psi0 and both lists up; the sums down; the partial sums of rx.rx stay on the device).
 // The exit codes are formed on the host from the downloaded sums by term_decide, the one implementation of the decision.
 // Included at the end of enlsip_gn.hip.
@@ -76,39 +76,34 @@ int enlsip_gn_termination_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t
         h->err = "batch * max(ceil(n / 4), partial-sum workgroups) exceeds the grid";
         return -2;
     }
-    h->termination_form = wave ? 1 : 0;
+    h->form[FORM_TERMINATION] = wave ? 1 : 0;
     GN_HIP(hipSetDevice(h->device));
     TerminationScratch D, H;      // the partial sums: the general form's only
-    if ((rc = place_records(h, h->term_scr, h->h_term, D, H, wave ? 0 : nblk, batch, 2 * l))) return rc;
-    std::vector<int64_t> n_act((size_t)batch), n_ina((size_t)batch);
+    if ((rc = place_records(h, D, H, wave ? 0 : nblk, batch, 2 * l))) return rc;
     for (int64_t k = 0; k < batch; ++k) {      // a problem that is not taken: counts of 0, so that nothing of its lists is read
         const int tk = take_flag(take, k);
         const enlsip_gn_term_state& s = state[k];
         H.meta[k] = tk ? TermMeta{s.psi0, (int)s.t, (int)s.q, (int)s.dimJ2, 1} : TermMeta{0.0, 0, 0, 0, 0};
-        n_act[k] = tk ? s.t : 0;
-        n_ina[k] = tk ? l - s.t : 0;
+        pack_working_sets(H.list, batch, l, k, active, inactive, tk ? s.t : -1);
     }
-    pack_rows(H.list, active, n_act.data(), batch, l);
-    pack_rows(H.list + batch * l, inactive, n_ina.data(), batch, l);
-    hipStream_t st = h->stream;
-    GN_HIP(hipMemcpyAsync(D.meta, H.meta, H.up_bytes, hipMemcpyHostToDevice, st));
+    const WorkingSets<int> Dw(D.list, batch, l);
     TerminationArgs a{};
-    a.meta = D.meta; a.act = D.list; a.inact = D.list + batch * l; a.out = D.out; a.part = D.part;
+    a.meta = D.meta; a.act = Dw.act; a.inact = Dw.inact; a.out = D.out; a.part = D.part;
     a.count = (int)batch; a.m = (int)m; a.n = (int)n; a.l = (int)l; a.t_max = (int)t_max; a.scaling = scaling != 0;
     a.nblk = (int)nblk; a.col_blocks = (int)col_blocks;
     a.J = dJ; a.ldj = ldj; a.strideJ = strideJ; a.rx = drx; a.cx_all = dcx_all; a.x = dx; a.x_prev = dx_prev; a.p = dp; a.d_gn = dd_gn;
     a.lambda = dlambda; a.cx_active = dcx_active; a.diag_scale = ddiag_scale; a.At = dAt; a.ldat = ldat; a.strideAt = strideAt;
     a.w = dw; a.grad = dgrad;
-    if (wave) {
-        hipLaunchKernelGGL(k_term_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(k_term_grad, dim3((unsigned)(batch * col_blocks)), dim3(256), 0, st, a);
-        if (m > 0) hipLaunchKernelGGL(k_term_rx_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_term_short, dim3((unsigned)batch), dim3(256), 0, st, a);
-    }
-    GN_HIP(hipGetLastError());
-    GN_HIP(hipMemcpyAsync(H.out, D.out, H.down_bytes, hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
+    auto launch = [&](hipStream_t st) {
+        if (wave) {
+            hipLaunchKernelGGL(k_term_wave, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, a);
+        } else {
+            hipLaunchKernelGGL(k_term_grad, dim3((unsigned)(batch * col_blocks)), dim3(256), 0, st, a);
+            if (m > 0) hipLaunchKernelGGL(k_term_rx_part, dim3((unsigned)(batch * nblk)), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_term_short, dim3((unsigned)batch), dim3(256), 0, st, a);
+        }
+    };
+    if ((rc = round_trip(h, D, H, launch, H.out, D.out, H.down_bytes))) return rc;
     for (int64_t k = 0; k < batch; ++k) {
         if (!H.meta[k].take) continue;
         sums[k] = H.out[k];
@@ -118,10 +113,6 @@ int enlsip_gn_termination_batched_dev(enlsip_gn_handle h, int64_t batch, int64_t
     GN_CATCH(h)
 }
 
-int enlsip_gn_get_termination_form(enlsip_gn_handle h, int* form) {
-    GN_GETTER_CHECK(h, form)
-    *form = h->termination_form;
-    return 0;
-}
+int enlsip_gn_get_termination_form(enlsip_gn_handle h, int* form) { return get_form(h, FORM_TERMINATION, form); }
 
 }  // extern "C"

@@ -284,6 +284,144 @@ static void layouts() {
     }
 }
 
+// ---- the working-set lists [active | inactive] of the addition, termination and direction calls -------------------------------------
+// source rows of stride l of which row k holds cnt[k] entries 10 (k + 1) + i and INT64_MIN behind them; the last row ends with its
+// used part
+static std::vector<int64_t> ragged_source(int64_t batch, int64_t l, const std::vector<int64_t>& cnt) {
+    std::vector<int64_t> src((size_t)((batch - 1) * l + cnt[(size_t)batch - 1]), INT64_MIN);
+    for (int64_t k = 0; k < batch; ++k)
+        for (int64_t i = 0; i < cnt[(size_t)k]; ++i) src[(size_t)(k * l + i)] = 10 * (k + 1) + i;
+    return src;
+}
+
+static void working_sets() {
+    {
+        int one[1] = {0};
+        const WorkingSets<int> w(one, 1, 1), e(one, 1, 0);      // batch = 1; and l = 0, where both halves are empty and coincide
+        EXPECT(w.act == one && w.inact == one + 1 && e.act == one && e.inact == one);
+        const int64_t big[1] = {0};
+        const WorkingSets<const int64_t> c(big, 7, 0);
+        EXPECT(c.act == big && c.inact == big);
+        std::vector<int> list(2 * 5 * 3);
+        const WorkingSets<int> g(list.data(), 5, 3);
+        EXPECT(g.act == list.data() && g.inact == list.data() + 15 && g.inact + 15 == list.data() + list.size());
+    }
+    group("working_sets_halves");
+    {
+        // t = l (no inactive entry), a problem that is not taken, t = 0 (no active entry), one in between; the sources of the
+        // problem that is not taken hold legal-looking entries, which must not arrive
+        const int64_t batch = 4, l = 3, t[4] = {3, -1, 0, 2};
+        std::vector<int64_t> n_act, n_ina;
+        for (int64_t k = 0; k < batch; ++k) { n_act.push_back(t[k] < 0 ? l : t[k]); n_ina.push_back(t[k] < 0 ? l : l - t[k]); }
+        std::vector<int64_t> act = ragged_source(batch, l, n_act), ina = ragged_source(batch, l, n_ina);
+        std::vector<int> list((size_t)(2 * batch * l), -7);      // exactly both halves
+        for (int64_t k = 0; k < batch; ++k) pack_working_sets(list.data(), batch, l, k, act.data(), ina.data(), t[k]);
+        const WorkingSets<int> w(list.data(), batch, l);
+        bool used = true, padded = true, untaken = true;
+        for (int64_t k = 0; k < batch; ++k)
+            for (int64_t i = 0; i < l; ++i) {
+                const int a = w.act[k * l + i], b = w.inact[k * l + i];
+                if (t[k] < 0) { untaken = untaken && a == 0 && b == 0; continue; }
+                if (i < t[k]) used = used && a == 10 * (k + 1) + i; else padded = padded && a == 0;
+                if (i < l - t[k]) used = used && b == 10 * (k + 1) + i; else padded = padded && b == 0;
+            }
+        EXPECT(used && padded);
+        group("pack_working_sets_t_0_and_t_l");
+        EXPECT(untaken);
+        group("pack_working_sets_not_taken_rows_are_zero");
+    }
+    {
+        // nothing behind a used count is read: the problem that is not taken comes last and its source rows do not exist
+        const int64_t batch = 2, l = 4, t[2] = {1, -1};
+        std::vector<int64_t> act = ragged_source(batch, l, {1, 0}), ina = ragged_source(batch, l, {3, 0});
+        EXPECT(act.size() == 4 && ina.size() == 4);
+        std::vector<int> list((size_t)(2 * batch * l), -7);
+        for (int64_t k = 0; k < batch; ++k) pack_working_sets(list.data(), batch, l, k, act.data(), ina.data(), t[k]);
+        const int want[16] = {10, 0, 0, 0, 0, 0, 0, 0, 10, 11, 12, 0, 0, 0, 0, 0};
+        EXPECT(!memcmp(list.data(), want, sizeof want));
+        group("pack_working_sets_reads_only_the_used_entries");
+    }
+    {
+        std::vector<int> none;
+        for (int64_t k = 0; k < 3; ++k) pack_working_sets(none.data(), 3, 0, k, nullptr, nullptr, k == 1 ? -1 : 0);      // l = 0
+        group("pack_working_sets_l_0");
+    }
+    {
+        // the closing pair of the three per-problem loops: code -7, entries 0..l, active before inactive, the used entries only
+        const int64_t batch = 2, l = 3;
+        std::vector<int64_t> act = ragged_source(batch, l, {2, 1}), ina = ragged_source(batch, l, {1, 2});
+        for (auto* v : {&act, &ina})
+            for (int64_t& x : *v) if (x != INT64_MIN) x = x % (l + 1);
+        std::string e;
+        EXPECT(check_working_set(e, 0, act.data(), ina.data(), l, 2) == 0 && check_working_set(e, 1, act.data(), ina.data(), l, 1) == 0 && e.empty());
+        ina[(size_t)(1 * l + 1)] = l + 1;
+        EXPECT(check_working_set(e, 1, act.data(), ina.data(), l, 1) == -7 && e == "inactive[1][1] outside 0..l");
+        act[(size_t)(1 * l)] = -1;
+        EXPECT(check_working_set(e, 1, act.data(), ina.data(), l, 1) == -7 && e == "active[1][0] outside 0..l");
+        e.clear();
+        EXPECT(check_working_set(e, 0, act.data(), ina.data(), l, 2) == 0 && e.empty());
+        EXPECT(check_working_set(e, 0, nullptr, nullptr, 0, 0) == 0 && e.empty());
+        group("check_working_set");
+    }
+}
+
+// the preamble of check_addition / check_termination / check_direction: batch, m, n, l <= 1024, t_max, t_max > l in this order, with
+// the messages and codes that tests/addition_walk_check.cpp, termination_check.cpp and direction_check.cpp pin for the callers; each
+// caller gives exactly the preamble's answer (nothing else of its arguments is looked at before)
+static void working_set_shape() {
+    struct Case { int64_t batch, m, n, l, t_max; int rc; const char* msg; };
+    const Case cases[] = {
+        {2, 9, 4, 5, 3, 0, ""},
+        {1, 0, 1, 0, 0, 0, ""},
+        {1, 0x7fffffff, 0x3fffffff, 1024, 1024, 0, ""},
+        {0, 9, 4, 5, 3, -2, "batch must be in 1..2^31-1"},
+        {0x80000000LL, 9, 4, 5, 3, -2, "batch must be in 1..2^31-1"},
+        {2, -1, 4, 5, 3, -3, "m must be in 0..2^31-1"},
+        {2, 0x80000000LL, 4, 5, 3, -3, "m must be in 0..2^31-1"},
+        {2, 9, 0, 5, 3, -3, "n must be at least 1"},
+        {2, 9, 0x40000000, 5, 3, -3, "n must be at least 1"},
+        {2, 9, 4, -1, 0, -3, "l must be in 0..1024 in this build"},
+        {2, 9, 4, 1025, 3, -3, "l must be in 0..1024 in this build"},
+        {2, 9, 4, 5, -1, -3, "t_max must be in 0..1024 in this build"},
+        {2, 9, 4, 5, 6, -3, "t_max > l"},
+        // two faults at once: the earlier one of the order wins
+        {0, -1, 0, 1025, 1025, -2, "batch must be in 1..2^31-1"},
+        {2, -1, 0, 1025, 1025, -3, "m must be in 0..2^31-1"},
+        {2, 9, 0, 1025, 1025, -3, "n must be at least 1"},
+        {2, 9, 4, 1025, 1026, -3, "l must be in 0..1024 in this build"},
+        {2, 9, 4, 1024, 1025, -3, "t_max must be in 0..1024 in this build"},
+    };
+    bool pre = true, add = true, term = true, dir = true;
+    for (const Case& c : cases) {
+        std::string e;
+        pre = pre && check_working_set_shape(e, c.batch, c.m, c.n, c.l, c.t_max) == c.rc && e == c.msg;
+        if (c.rc == 0) continue;      // a good shape goes on to the callers' own arguments: their own groups
+        e.clear();
+        term = term && check_termination(e, {c.batch, c.m, c.n, c.l, c.t_max, 0, 0, 0, 0}, nullptr, nullptr, nullptr, nullptr, false,
+                                         false, false, false, false) == c.rc && e == c.msg;
+        e.clear();
+        dir = dir && check_direction(e, {c.batch, c.m, c.n, c.l, c.t_max}, nullptr, nullptr, nullptr, nullptr, false, false, false,
+                                     false) == c.rc && e == c.msg;
+        if (c.m < 0 || c.m > 0x7fffffff) continue;      // the addition call has no m
+        e.clear();
+        add = add && check_addition(e, {c.batch, c.n, c.l, c.t_max, 0, 0, 0, 0}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                    false, false, false) == c.rc && e == c.msg;
+    }
+    EXPECT(pre);
+    group("working_set_shape");
+    EXPECT(add);
+    group("working_set_shape_of_check_addition");
+    EXPECT(term);
+    group("working_set_shape_of_check_termination");
+    EXPECT(dir);
+    group("working_set_shape_of_check_direction");
+    std::string e;
+    EXPECT(check_m(e, 0) == 0 && check_n(e, 1) == 0 && check_t_max_in_l(e, 0, 0) == 0 && check_t_max_in_l(e, 1024, 1024) == 0 && e.empty());
+    EXPECT(check_t_max_in_l(e, 1025, 1024) == -3 && e == "t_max must be in 0..1024 in this build");
+    EXPECT(check_t_max_in_l(e, 3, 2) == -3 && e == "t_max > l");
+    group("shape_pieces");
+}
+
 int main() {
     records();
     shape_checks();
@@ -292,6 +430,8 @@ int main() {
     pack();
     take_and_blocks();
     layouts();
+    working_sets();
+    working_set_shape();
     printf("%d failures\n", failures);
     return failures ? 1 : 0;
 }

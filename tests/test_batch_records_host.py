@@ -22,6 +22,10 @@ GROUPS = (["record_" + r for r in ("DeletionMeta", "LsMeta", "LsOut", "PenaltyMe
            "list_check_lo_is_an_argument", "list_check_null_list_of_stride_0", "pack_copies_the_used_part", "pack_zero_pads",
            "pack_stride_0", "take_flag", "sum_blocks", "grid_fits"])
 LAYOUTS = ["layout_" + n for n in ("deletion", "linesearch", "penalty", "merit", "fit", "merit_prefix_is_the_fit_prefix")]
+WORKING_SETS = (["working_sets_halves"] +
+                ["pack_working_sets_" + n for n in ("t_0_and_t_l", "not_taken_rows_are_zero", "reads_only_the_used_entries", "l_0")] +
+                ["check_working_set", "working_set_shape"] +
+                ["working_set_shape_of_check_" + n for n in ("addition", "termination", "direction")] + ["shape_pieces"])
 
 
 @pytest.fixture(scope="module")
@@ -55,5 +59,6 @@ def test_every_named_assertion_ran_and_held(lines):
     assert [ln for ln in lines if ln.startswith("FAIL")] == []
     ok = [ln.split()[1] for ln in lines if ln.startswith("ok ")]
     assert ok[:len(GROUPS)] == GROUPS
-    assert ok[len(GROUPS):] == LAYOUTS * 4          # the four shapes (batch, t_max, l, nblk) of the program
+    assert ok[len(GROUPS):len(GROUPS) + 4 * len(LAYOUTS)] == LAYOUTS * 4          # the four shapes (batch, t_max, l, nblk) of the program
+    assert ok[len(GROUPS) + 4 * len(LAYOUTS):] == WORKING_SETS
     assert lines[-1] == "0 failures"

@@ -226,9 +226,11 @@ def family_sequence(s, shape, sol, pv, Gam, small, whole):
 
 @pytest.mark.parametrize("name", ["wave", "general", "halves"])
 def test_interleaved_families_match_a_pregrown_handle(name, monkeypatch):
-    """The re-solve, the Newton direction, the multipliers, the deletion step and the subspace call keep a per-call scratch EACH
-    (rsb_dims / rsb_io, nwb_ws / nwb_io, lagb_scr / lagb_io, del_scr, ssb_req / ssb_io, with their pinned copies): no buffer is
-    shared between two families, what they share is the code that grows and stages them.  On X every family is called over a small
+    """The re-solve, the Newton direction, the multipliers and the subspace call keep a per-call scratch EACH (rsb_dims / rsb_io,
+    nwb_ws / nwb_io, lagb_scr / lagb_io, ssb_req / ssb_io, with their pinned copies): no buffer is shared between two of these
+    families, what they share is the code that grows and stages them.  The deletion step places its records in rec_scr / h_rec, the
+    one record scratch of the calls on the caller's buffers, which none of the other four touches
+    (tests/test_gpu_record_scratch.py runs the calls that do share it).  On X every family is called over a small
     range and then over the whole one, with the other families' calls in between, so each family's own scratch grows between its two
     calls; on Y one whole-range call of every family came first, so nothing grows later.  Every output of the same sequence is bit
     for bit the same on both, every slot is answered in full, and the guard rows around the host outputs keep their fill.
