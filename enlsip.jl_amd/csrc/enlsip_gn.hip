@@ -27,6 +27,7 @@
 #include "gn_kernels_misc.hpp"
 #include "gn_kernels_lagrange.hpp"
 #include "gn_kernels_lagrange_batched.hpp"
+#include "gn_kernels_tsqr_products.hpp"
 #include "gn_kernels_resolve_batched.hpp"
 #include "gn_kernels_subspace_batched.hpp"
 #include "gn_kernels_deletion_batched.hpp"
@@ -164,6 +165,7 @@ static int make_plan(enlsip_gn_handle h, long long batch, long long m, long long
     }
     h->have_plan = true;
     h->factors_valid = false;
+    h->tsqr_stage = 0;
     return 0;
 }
 
@@ -1087,6 +1089,7 @@ static void begin_whole_part(enlsip_gn_handle h, const BatchOperands& inputs, bo
     h->split = 0;
     h->chunk0 = 0;
     h->factors_valid = false;
+    h->tsqr_stage = 0;
     h->held.clear();
     h->last = inputs;
     h->sc_eJ = 0;
@@ -1411,6 +1414,7 @@ static int solve_dev(enlsip_gn_handle h, const BatchOperands& v, SolveMode mode)
         if (rc) return rc;
     }
     h->factors_valid = true;
+    h->tsqr_stage = 0;
     h->route = gn_route_acc;
     return 0;
 }
@@ -1515,6 +1519,7 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
     if (h->scratch.p) (void)hipFree(h->scratch.p);
     if (h->xbuf.p) (void)hipFree(h->xbuf.p);
     if (h->tsqr_part.p) (void)hipFree(h->tsqr_part.p);
+    if (h->tsqr_prod.p) (void)hipFree(h->tsqr_prod.p);
     tsqr_drop_comm(h);
     if (h->h_state) (void)hipHostFree(h->h_state);
     if (h->h_sbinfo) (void)hipHostFree(h->h_sbinfo);
@@ -1904,6 +1909,7 @@ static int factor_one_dev(enlsip_gn_handle h, long long m, long long n, long lon
         if (rc) return rc;
     }
     h->factors_valid = true;
+    h->tsqr_stage = 0;
     h->constraints_only = true;
     v.hinfo = info;
     return publish_info(h, v, {1}, true);
@@ -2049,6 +2055,7 @@ static int factor_dev(enlsip_gn_handle h, const BatchOperands& v, double eps_ran
     rc = publish_info(h, v, cov, true);
     if (rc) return rc;
     h->factors_valid = true;
+    h->tsqr_stage = 0;
     h->constraints_only = true;
     h->route = gn_route_acc;
     return 0;
@@ -2419,6 +2426,7 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_accessors.inc"
 #include "gn_tsqr.inc"
 #include "gn_lagrange.inc"
+#include "gn_tsqr_products.inc"
 #include "gn_lagrange_batched.inc"
 #include "gn_resolve_batched.inc"
 #include "gn_subspace_batched.inc"

@@ -211,6 +211,12 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     int tsqr_transport = 0;             // what moved the triangles in the last enlsip_gn_solve_tsqr (ENLSIP_GN_TRANSPORT_*)
     gn::DevBuf xbuf;                    // send message + G received messages
     gn::DevBuf tsqr_part;               // per-workgroup partial sums of the TSQR stages' ordered sums of squares
+    // What of a row shard is resident (beside factors_valid, which stays false for a shard): 0 nothing, 1 the local stage of
+    // this handle's last tsqr_local, 2 local stage AND combine (enlsip_gn_solve_tsqr, enlsip_gn_tsqr_combine(_scaled)_dev): F_A,
+    // tauA, the pivots of A' and `last` are those of the shard — what the enlsip_gn_tsqr_products family needs.  Every other
+    // solve entry sets it back to 0.
+    int tsqr_stage = 0;
+    gn::DevBuf tsqr_prod;               // scratch and messages of the enlsip_gn_tsqr_products family
     float tsqr_ms[3] = {};              // local / exchange / combine of the last enlsip_gn_solve_tsqr (profiling on)
     // staging for the host-pointer API
     gn::DevBuf in_stage, out_stage, scratch, lag, newton;

@@ -314,6 +314,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     hipStream_t s = h->stream;
     h->eps_rank = eps_rank;
     h->factors_valid = false;
+    h->tsqr_stage = 0;
     h->held.clear();
     h->last = {1, m_loc, n, t, dJ, ldj, 0, drx, dAt, ldat, 0, dcx};
     // same routing as a solve (register / distributed forms of F_A for the shapes that need them)
@@ -350,6 +351,7 @@ int tsqr_local_core(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, con
     }
     h->tsqr_n2 = h->h_state[0].n2;
     h->route = gn_route_acc;
+    h->tsqr_stage = 1;
     return 0;
 }
 
@@ -406,6 +408,7 @@ int tsqr_combine_core(enlsip_gn_handle h, int64_t G, int64_t n2, double eps_rank
     if (info) *info = {st.rankA, sinfo.rankJ2, st.code, st.dimA, sinfo.dimJ2, (int64_t)(st.status | sinfo.status)};
     h->tsqr_E = E;
     if (E != 0 || h->tsqr_e != 0) h->route |= (1ull << ENLSIP_GN_ROUTE_RESCALED);
+    if (h->tsqr_stage == 1) h->tsqr_stage = 2;       // the shard's local stage of THIS handle went into the combine
     return 0;
 }
 
@@ -603,6 +606,32 @@ int enlsip_gn_tsqr_set_exchange(enlsip_gn_handle h, enlsip_gn_allgather_fn fn, v
     GN_CATCH(h)
 }
 
+// The one exchange step of a collective on the handle's communicator (enlsip_gn_solve_tsqr, the enlsip_gn_tsqr_products family):
+// every rank's `send` (msg_len doubles, device) into `recv` (ranks x msg_len, rank-major), on the handle's stream.
+// An attached RCCL communicator is USED, also with one rank (a self-gather of a few MB): the prototype, the datatype
+// constant and the count are then exercised on every box, not for the first time on an 8-GPU node.
+static int tsqr_exchange_step(enlsip_gn_handle h, const double* send, double* recv, size_t msg_len) {
+    hipStream_t s = h->stream;
+    if (h->tsqr_comm) {
+        RcclApi& r = rccl();
+        const int e = r.AllGather(send, recv, msg_len, GN_NCCL_FLOAT64, h->tsqr_comm, s);
+        if (e != 0) {
+            h->err = std::string("ncclAllGather: ") + (r.GetErrorString ? r.GetErrorString(e) : "error");
+            return 995;
+        }
+        h->tsqr_transport = ENLSIP_GN_TRANSPORT_RCCL;
+    } else if (h->tsqr_ranks > 1) {
+        GN_HIP(hipStreamSynchronize(s));
+        const int e = h->tsqr_xfn(h->tsqr_xctx, send, recv, msg_len * 8, (void*)s);
+        if (e != 0) { h->err = "the caller's all-gather reported error " + std::to_string(e); return 994; }
+        h->tsqr_transport = ENLSIP_GN_TRANSPORT_CALLBACK;
+    } else {
+        GN_HIP(hipMemcpyAsync(recv, send, msg_len * 8, hipMemcpyDeviceToDevice, s));
+        h->tsqr_transport = ENLSIP_GN_TRANSPORT_NONE;
+    }
+    return 0;
+}
+
 int enlsip_gn_solve_tsqr(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t, const double* dJ, int64_t ldj,
                          const double* drx, const double* dAt, int64_t ldat, const double* dcx, double eps_rank,
                          double* p, double* dlead, double* d_norm, enlsip_gn_info* info, int64_t* jpvtJ2) {
@@ -643,25 +672,8 @@ int enlsip_gn_solve_tsqr(enlsip_gn_handle h, int64_t m_loc, int64_t n, int64_t t
     GN_HIP(hipGetLastError());
     if (ev) GN_HIP(hipEventRecord(ev[6], s));
     // ---- the one exchange step -----------------------------------------------------------------------------------------------
-    // an attached RCCL communicator is USED, also with one rank (a self-gather of a few MB): the prototype, the datatype
-    // constant and the count are then exercised on every box, not for the first time on an 8-GPU node
-    if (h->tsqr_comm) {
-        RcclApi& r = rccl();
-        const int e = r.AllGather(send, recv, msg_len, GN_NCCL_FLOAT64, h->tsqr_comm, s);
-        if (e != 0) {
-            h->err = std::string("ncclAllGather: ") + (r.GetErrorString ? r.GetErrorString(e) : "error");
-            return 995;
-        }
-        h->tsqr_transport = ENLSIP_GN_TRANSPORT_RCCL;
-    } else if (G > 1) {
-        GN_HIP(hipStreamSynchronize(s));
-        const int e = h->tsqr_xfn(h->tsqr_xctx, send, recv, msg_len * 8, (void*)s);
-        if (e != 0) { h->err = "the caller's all-gather reported error " + std::to_string(e); return 994; }
-        h->tsqr_transport = ENLSIP_GN_TRANSPORT_CALLBACK;
-    } else {
-        GN_HIP(hipMemcpyAsync(recv, send, msg_len * 8, hipMemcpyDeviceToDevice, s));
-        h->tsqr_transport = ENLSIP_GN_TRANSPORT_NONE;
-    }
+    rc = tsqr_exchange_step(h, send, recv, msg_len);
+    if (rc) return rc;
     if (ev) GN_HIP(hipEventRecord(ev[7], s));
     // ---- combine, redundantly on every rank ----------------------------------------------------------------------------------
     TsqrScratch T;

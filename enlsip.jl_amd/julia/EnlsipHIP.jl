@@ -1383,4 +1383,73 @@ function gn_search_direction_tsqr_hip(h::Handle, dJ::Ptr{Float64}, ldj::Integer,
     return p, dlead[1:n2], dn[], info[], jJ[1:n2]
 end
 
+# ---- the consumers around the subproblem on a row-sharded J: every rank calls them after `gn_search_direction_tsqr_hip` ------
+# The shard (dJ, drx, dAt, dcx) of that call must still be alive and unchanged.  Each call is ONE exchange of n + 3 doubles per
+# rank and every rank returns the same bits.  They are outside the magnitude contract (code -15 after a rescaled sharded solve).
+
+"""    tsqr_products_hip(h, n, t, p=nothing; dJp=C_NULL) -> (grad, sums, Ap)
+
+`grad = J'(rx + J p)` over all ranks (`p === nothing`: `J' rx`, src/enlsip_functions.jl:2690), `sums = (dot(rx,rx), dot(Jp,Jp),
+dot(Jp,rx))` (:1561-1584, :2269), `Ap = C.A p` on the active rows (:2227; empty without `p`).  `dJp`: device pointer to `m_loc`
+doubles that receive this rank's rows of `J p` (:2226), or C_NULL."""
+function tsqr_products_hip(h::Handle, n::Integer, t::Integer, p::Union{Nothing,Vector{Float64}}=nothing;
+                           dJp::Ptr{Float64}=Ptr{Float64}(C_NULL))
+    grad = zeros(Float64, n); sums = zeros(Float64, 3)
+    Ap = zeros(Float64, p === nothing ? 0 : t)
+    pp = p === nothing ? Ptr{Float64}(C_NULL) : pointer(p)
+    pa = isempty(Ap) ? Ptr{Float64}(C_NULL) : pointer(Ap)
+    GC.@preserve p grad sums Ap check(h, ccall((:enlsip_gn_tsqr_products, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h.ptr, pp, dJp, grad, sums, pa))
+    return grad, sums, Ap
+end
+
+"""    tsqr_first_lagrange_hip(h, t, ε_rank; grad_fx=nothing, diag_scale=nothing) -> (λ, grad_res)
+
+`first_lagrange_mult_estimate!` (src/enlsip_functions.jl:461-508) on the replicated `F_A` of the sharded solve; without `grad_fx`
+the gradient `J' rx` is formed over the ranks (collective)."""
+function tsqr_first_lagrange_hip(h::Handle, t::Integer, ε_rank::Float64; grad_fx::Union{Nothing,Vector{Float64}}=nothing,
+                                 diag_scale::Union{Nothing,Vector{Float64}}=nothing)
+    λ = zeros(Float64, t); gres = Ref{Float64}(0.0)
+    pg = grad_fx === nothing ? Ptr{Float64}(C_NULL) : pointer(grad_fx)
+    pd = diag_scale === nothing ? Ptr{Float64}(C_NULL) : pointer(diag_scale)
+    GC.@preserve grad_fx diag_scale λ check(h, ccall((:enlsip_gn_tsqr_first_lagrange, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ref{Float64}), h.ptr, pg, pd, ε_rank, λ, gres))
+    return λ, gres[]
+end
+
+"""    tsqr_second_lagrange_hip(h, t, p_gn, ε_rank; diag_scale=nothing) -> λ
+
+`second_lagrange_mult_estimate!` (src/enlsip_functions.jl:514-537), collective: `J1'(rx + J p_gn)` is formed as
+`(F_A.Q' (J'(rx + J p_gn)))[1:t]` from the shards' products."""
+function tsqr_second_lagrange_hip(h::Handle, t::Integer, p_gn::Vector{Float64}, ε_rank::Float64;
+                                  diag_scale::Union{Nothing,Vector{Float64}}=nothing)
+    λ = zeros(Float64, t)
+    pd = diag_scale === nothing ? Ptr{Float64}(C_NULL) : pointer(diag_scale)
+    GC.@preserve p_gn diag_scale λ check(h, ccall((:enlsip_gn_tsqr_second_lagrange, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}), h.ptr, p_gn, pd, ε_rank, λ))
+    return λ
+end
+
+"""    tsqr_products_local_hip!(h, dJ, ldj, drx, dp, dJp, dmsg, m_loc, n)
+
+The local stage alone, for callers that move the messages themselves: device pointers in, the shard's message
+(`tsqr_products_msg_len(n)` doubles) in `dmsg`.  `dp`, `dJp` may be C_NULL."""
+function tsqr_products_local_hip!(h::Handle, dJ::Ptr{Float64}, ldj::Integer, drx::Ptr{Float64}, dp::Ptr{Float64},
+                                  dJp::Ptr{Float64}, dmsg::Ptr{Float64}, m_loc::Integer, n::Integer)
+    check(h, ccall((:enlsip_gn_tsqr_products_local_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        h.ptr, m_loc, n, dJ, ldj, drx, dp, dJp, dmsg))
+end
+
+"""    tsqr_products_combine_hip(h, dmsgs, G, n) -> (grad, sums): the G gathered messages (device, rank-major) added in rank order"""
+function tsqr_products_combine_hip(h::Handle, dmsgs::Ptr{Float64}, G::Integer, n::Integer)
+    grad = zeros(Float64, n); sums = zeros(Float64, 3)
+    GC.@preserve grad sums check(h, ccall((:enlsip_gn_tsqr_products_combine_dev, LIB), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), h.ptr, G, n, dmsgs, grad, sums))
+    return grad, sums
+end
+
+"""    tsqr_products_msg_len(n): doubles per message — header (4), g (n), three sums, rounded up to 16-byte granules"""
+tsqr_products_msg_len(n::Integer) = (4 + n + 3 + 1) & ~1
+
 end # module

@@ -399,3 +399,175 @@ def tsqr_solve_shards(solver: GNSolver, J, rx, A_active, cx, G: int, eps_rank: f
     Atd = torch.tensor(np.ascontiguousarray(A_active), dtype=torch.float64, device=dev) if t else None
     cxd = torch.tensor(np.asarray(cx), dtype=torch.float64, device=dev) if t else None
     return tsqr_solve_shards_dev(solver, Jd, rxd, Atd, cxd, G, eps_rank, scaled=scaled, row_blocks=row_blocks, in_place=in_place)
+
+
+# ---- the consumers around the subproblem on a row-sharded J (enlsip_gn_tsqr_products*) ----------------------------------------
+PRODUCTS_HDR = 4          # [rank + 1 | rank count | n | 0], then g (n), then dot(rx,rx), dot(Jp,Jp), dot(Jp,rx)
+
+
+def tsqr_products_msg_len(n: int) -> int:
+    """Doubles per message (enlsip_gn_tsqr_products_msg_len): header, n, three sums, rounded up to 16-byte granules."""
+    return (PRODUCTS_HDR + n + 3 + 1) & ~1
+
+
+@dataclass
+class TSQRProducts:
+    grad: np.ndarray                 # J' (rx + J p) over all ranks (p None: J' rx)
+    sums: np.ndarray                 # dot(rx,rx), dot(Jp,Jp), dot(Jp,rx) over all ranks
+    Ap: Optional[np.ndarray] = None  # C.A p on the active rows (library collective with p and t > 0)
+    Jp: object = None                # this rank's J_g p (device tensor), or the whole J p in the rehearsal
+
+
+def _host(x, count=None):
+    if x is None:
+        return None, None
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    assert count is None or a.shape == (count,), (a.shape, count)
+    return a, a.ctypes.data_as(C.c_void_p)
+
+
+def tsqr_products_lib(solver: GNSolver, n: int, t: int, p=None, Jp_out=None) -> TSQRProducts:
+    """``enlsip_gn_tsqr_products``: collective on the shard and communicator of the handle's last ``tsqr_solve_lib``.  ``p`` (n) or
+    None; ``Jp_out``: a device tensor of m_loc doubles that receives this rank's J_g p, or None."""
+    pa, pp = _host(p, n)
+    grad, sums = np.zeros(n), np.zeros(3)
+    Ap = np.zeros(t) if (pa is not None and t > 0) else None
+    solver._chk(solver._lib.enlsip_gn_tsqr_products(
+        solver._h, pp, C.c_void_p(Jp_out.data_ptr()) if Jp_out is not None else None, grad.ctypes.data_as(C.c_void_p),
+        sums.ctypes.data_as(C.c_void_p), Ap.ctypes.data_as(C.c_void_p) if Ap is not None else None))
+    return TSQRProducts(grad=grad, sums=sums, Ap=Ap, Jp=Jp_out)
+
+
+def tsqr_first_lagrange_lib(solver: GNSolver, n: int, t: int, grad_fx=None, diag_scale=None, eps_rank: float = SQRT_EPS):
+    """``enlsip_gn_tsqr_first_lagrange`` -> (lambda (t), grad_res).  ``grad_fx`` None: J' rx over the ranks (collective)."""
+    ga, gp = _host(grad_fx, n)
+    da, dp = _host(diag_scale, t)
+    lam = np.zeros(t)
+    gres = C.c_double(0.0)
+    solver._chk(solver._lib.enlsip_gn_tsqr_first_lagrange(solver._h, gp, dp, eps_rank, lam.ctypes.data_as(C.c_void_p),
+                                                          C.byref(gres)))
+    return lam, float(gres.value)
+
+
+def tsqr_second_lagrange_lib(solver: GNSolver, n: int, t: int, p_gn, diag_scale=None, eps_rank: float = SQRT_EPS):
+    """``enlsip_gn_tsqr_second_lagrange`` -> lambda (t).  Collective."""
+    pa, pp = _host(p_gn, n)
+    da, dp = _host(diag_scale, t)
+    lam = np.zeros(t)
+    solver._chk(solver._lib.enlsip_gn_tsqr_second_lagrange(solver._h, pp, dp, eps_rank, lam.ctypes.data_as(C.c_void_p)))
+    return lam
+
+
+def hip_products_local(solver: GNSolver, m_loc, n, dJ, ldj, drx, dp, dJp, dmsg):
+    """enlsip_gn_tsqr_products_local_dev on raw device pointers (0: NULL)."""
+    v = lambda x: C.c_void_p(x) if x else None
+    solver._chk(solver._lib.enlsip_gn_tsqr_products_local_dev(solver._h, m_loc, n, v(dJ), ldj, v(drx), v(dp), v(dJp), v(dmsg)))
+
+
+def hip_products_combine(solver: GNSolver, G, n, dmsgs):
+    grad, sums = np.zeros(n), np.zeros(3)
+    solver._chk(solver._lib.enlsip_gn_tsqr_products_combine_dev(solver._h, G, n, C.c_void_p(dmsgs) if dmsgs else None,
+                                                                grad.ctypes.data_as(C.c_void_p), sums.ctypes.data_as(C.c_void_p)))
+    return grad, sums
+
+
+def products_combine_host(msgs: np.ndarray, G: int, n: int):
+    """The combine on the host: the G messages added in rank order, rank 0's value first, with plain additions — the same IEEE
+    operations in the same order as the device combine, hence the same bits.  Raises on a header that does not fit."""
+    L = tsqr_products_msg_len(n)
+    M = np.asarray(msgs, dtype=np.float64).reshape(G, L)
+    for g in range(G):
+        rk, cnt, nn = M[g, 0], M[g, 1], M[g, 2]
+        if nn != n or cnt not in (0.0, float(G)) or rk not in (0.0, float(g + 1)):
+            raise ValueError(f"message {g}: header (rank+1, ranks, n) = ({rk}, {cnt}, {nn}) does not fit slot {g} of {G}, n = {n}")
+    acc = M[0, PRODUCTS_HDR:PRODUCTS_HDR + n + 3].copy()
+    for g in range(1, G):
+        acc = acc + M[g, PRODUCTS_HDR:PRODUCTS_HDR + n + 3]
+    return acc[:n].copy(), acc[n:n + 3].copy()
+
+
+def tsqr_products(solver: Optional[GNSolver], J_loc, rx_loc, p, group=None, local_stage: Callable = None) -> TSQRProducts:
+    """The stage form, collective over ``group``: local products, ONE all-gather of the messages, the combine on every rank.
+    ``J_loc`` (n, m_loc) C-order == column-major m_loc x n, ``rx_loc`` (m_loc): torch tensors on this rank's device; ``p``: (n)
+    array-like or None.  ``local_stage(J_loc, rx_loc, p, msg)`` fills the message tensor (body; the header's n) and returns this
+    rank's J p or None — a NumPy stage can stand in without a GPU; the combine then runs on the host.  Every rank returns the same
+    bits."""
+    import torch
+    import torch.distributed as dist
+    G = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    n, m_loc = J_loc.shape
+    dev = J_loc.device
+    L = tsqr_products_msg_len(n)
+    msg = torch.zeros((L,), dtype=torch.float64, device=dev)
+    Jp = None
+    if local_stage is None:
+        pd = torch.as_tensor(np.asarray(p, dtype=np.float64), device=dev) if p is not None else None
+        Jp = torch.empty((max(m_loc, 1),), dtype=torch.float64, device=dev)[:m_loc] if p is not None else None
+        if dev.type == "cuda":
+            torch.cuda.current_stream(dev).synchronize()      # the library runs on its own stream
+        hip_products_local(solver, m_loc, n, J_loc.data_ptr() if m_loc else 0, max(m_loc, 0), rx_loc.data_ptr() if m_loc else 0,
+                           pd.data_ptr() if pd is not None else 0, Jp.data_ptr() if (Jp is not None and m_loc) else 0,
+                           msg.data_ptr())
+    else:
+        Jp = local_stage(J_loc, rx_loc, p, msg)
+    msg[0], msg[1], msg[2] = float(rank + 1), float(G), float(n)      # the sender states its slot and the count it believes in
+    every = torch.empty((G * L,), dtype=torch.float64, device=dev)
+    if G > 1:
+        if dev.type == "cuda" and dist.get_backend(group) != "nccl":   # rehearsal: several ranks on one GPU under gloo
+            ec = torch.empty((G * L,), dtype=torch.float64)
+            dist.all_gather_into_tensor(ec, msg.cpu().contiguous(), group=group)
+            every.copy_(ec)
+        else:
+            dist.all_gather_into_tensor(every, msg.contiguous(), group=group)
+    else:
+        every.copy_(msg)
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()
+    if local_stage is None:
+        grad, sums = hip_products_combine(solver, G, n, every.data_ptr())
+    else:
+        grad, sums = products_combine_host(every.cpu().numpy(), G, n)
+    return TSQRProducts(grad=grad, sums=sums, Jp=Jp)
+
+
+def tsqr_products_shards_dev(solver: GNSolver, Jd, rxd, p, G: int, row_blocks=None, in_place: bool = False) -> TSQRProducts:
+    """Single-process rehearsal on ONE GPU: ``Jd`` (n, m) C-order == column-major m x n, ``rxd`` (m) in HBM.  The G row blocks go
+    through ``enlsip_gn_tsqr_products_local_dev`` one after the other on the same handle, each message stated as rank g of G, and
+    ``enlsip_gn_tsqr_products_combine_dev`` adds them as the all-gather would have stacked them.  ``row_blocks``: the G block
+    heights (zero allowed; default ``row_range``).  ``in_place``: block g is read where it lies, ``J + lo`` with ``ldj = m``."""
+    import torch
+    n, m = Jd.shape
+    if in_place and not (Jd.is_contiguous() and rxd.is_contiguous() and Jd.dtype == rxd.dtype == torch.float64):
+        raise ValueError("in_place needs contiguous float64 Jd and rxd")
+    dev = Jd.device
+    if row_blocks is None:
+        edges = [row_range(m, G, g) for g in range(G)]
+    else:
+        if len(row_blocks) != G or sum(row_blocks) != m or min(row_blocks) < 0:
+            raise ValueError("row_blocks must be G non-negative heights that add up to m")
+        ends = np.cumsum(row_blocks)
+        edges = [(int(b - a), int(b)) for a, b in zip(row_blocks, ends)]
+    L = tsqr_products_msg_len(n)
+    msgs = torch.zeros((G, L), dtype=torch.float64, device=dev)
+    pd = torch.as_tensor(np.asarray(p, dtype=np.float64), device=dev) if p is not None else None
+    Jp = torch.zeros((m,), dtype=torch.float64, device=dev) if p is not None else None
+    for g in range(G):
+        lo, hi = edges[g]
+        ml = hi - lo
+        if in_place:
+            Jl, rl = None, None
+            pJ, ldj, prx = Jd.data_ptr() + 8 * lo, m, rxd.data_ptr() + 8 * lo
+        else:
+            Jl = Jd[:, lo:hi].contiguous()
+            rl = rxd[lo:hi].contiguous()
+            pJ, ldj, prx = Jl.data_ptr(), ml, rl.data_ptr()
+        torch.cuda.synchronize(dev)                    # the library runs on its own stream
+        hip_products_local(solver, ml, n, pJ if ml else 0, ldj if ml else 0, prx if ml else 0, pd.data_ptr() if pd is not None else 0,
+                           (Jp.data_ptr() + 8 * lo) if (Jp is not None and ml) else 0, msgs[g].data_ptr())
+        del Jl, rl
+    msgs[:, 0] = torch.arange(1, G + 1, dtype=torch.float64, device=dev)
+    msgs[:, 1] = float(G)
+    torch.cuda.synchronize(dev)
+    grad, sums = hip_products_combine(solver, G, n, msgs.data_ptr())
+    return TSQRProducts(grad=grad, sums=sums, Jp=Jp)

@@ -1259,6 +1259,61 @@ int enlsip_gn_tsqr_get_transport(enlsip_gn_handle h, int* transport);
  * on every rank is "RCCL moved one message from each of N distinct ranks" (bench.py --config C4 prints and asserts it). */
 int enlsip_gn_tsqr_get_exchange(enlsip_gn_handle h, int* transport, int* ranks, int* rank_tags_seen);
 
+/* ---- the consumers around the subproblem on a row-sharded J -------------------------------------------------------------------
+ * What Enlsip runs around the subproblem, for a J whose rows stay on their ranks: grad = J' (rx + J p) (p NULL: J' rx,
+ * src/enlsip_functions.jl:2690, :2734, :2830), J p and A p of the line-search set-up (:2226-2229), the three sums dot(rx,rx),
+ * dot(Jp,Jp), dot(Jp,rx) (:1561-1584, :2269) and the two multiplier estimates (:461-508, :514-537).  Rank g forms the products of its
+ * shard (J_g p is row-local and stays on the rank), packs ONE message
+ *     [ rank + 1 | rank count | n | 0 | g_g = J_g' v_g (n) | dot(rx_g,rx_g) | dot(Jp_g,Jp_g) | dot(Jp_g,rx_g) ]   v_g = rx_g + J_g p
+ * of enlsip_gn_tsqr_products_msg_len(n) doubles (a multiple of two: 16-byte granules; the length depends on n alone), the messages
+ * move in ONE exchange step the way the triangles of enlsip_gn_solve_tsqr move (RCCL where a communicator is attached, also with one
+ * rank; the callback otherwise; a device copy for one rank without a communicator; errors 994 / 995 as there), and every rank adds the
+ * G messages in RANK order, 0 first, with plain additions: every rank holds the same bits.  A message whose header names another n,
+ * another rank count than G or another slot than the one it lies in returns -13 (rank and rank count 0 = "not stated" pass).
+ *
+ * Order of summation: fixed by m_loc, n, ldj and the operands alone (chunks of a fixed height, 64 strided partial sums and a
+ * butterfly inside a chunk, chunks ascending, ranks ascending; no floating-point atomics): a call repeats its bits on any handle and
+ * after any history, and a shard read in place (any start row, ldj = the whole height; only the 8-byte alignment of a double is
+ * assumed) gives the bits of a copy of its rows.  Two different splits of the same rows differ by rounding.
+ *
+ * Magnitudes: these calls compute plainly on the caller's data and are OUTSIDE the magnitude contract above, like the stage pair
+ * enlsip_gn_tsqr_local_dev / _combine_dev.  When the handle's last sharded solve was rescaled (enlsip_gn_tsqr_get_scale not (0, 0),
+ * or A', cx were factored on a scaled copy) the resident F_A may belong to a scaled copy: the collective forms return -15 and
+ * compute nothing.  enlsip_gn_tsqr_products_local_dev is stateless and unaffected.
+ *
+ * enlsip_gn_tsqr_products_local_dev    the local stage alone, for callers that move the messages themselves; needs NOTHING resident and
+ *     leaves the handle's resident data alone.  dJ (m_loc x n, column-major, ldj >= m_loc), drx (m_loc), dp (n) or NULL, dJp (m_loc;
+ *     receives J_g p when dp is given, else untouched) or NULL, dmsg (msg_len doubles): device.  m_loc = 0 is legal and gives a zero
+ *     message.  The header carries the rank and rank count of the handle's communicator, or 0 / 0 without one (the caller may fill
+ *     them in).  Returns 0; before anything is launched: -2 m_loc, -3 n (1..1024), -4 dJ NULL, -5 ldj < m_loc, -6 drx NULL,
+ *     -8 dmsg NULL.
+ * enlsip_gn_tsqr_products_combine_dev  dmsgs: G messages, rank-major (device); grad (n) and sums (3): host, either may be NULL.
+ *     -2 G, -3 n, -4 dmsgs NULL, -13 a header does not fit (nothing is written).
+ * The collective forms work on the shard (dJ, drx, dAt, dcx: kept alive and unchanged by the caller, as for the one-GPU consumers)
+ * and the communicator of the handle's last successful enlsip_gn_solve_tsqr, or enlsip_gn_tsqr_combine_dev / _combine_scaled_dev after a
+ * local stage on the same handle; every other solve entry withdraws that.  Without it they return -7 and launch nothing.  Every rank
+ * calls them; a rank that fails before the exchange leaves its peers waiting, as in the solve.  One synchronisation of the handle's
+ * stream per call (the callback transport adds the one before it calls out).
+ * enlsip_gn_tsqr_products         p (host n) or NULL; dJp (device m_loc, receives this rank's J_g p) or NULL; grad (host n), sums
+ *     (host 3), Ap (host t: C.A p on the active rows, from the replicated A' of the solve, no exchange; needs p) or NULL each.
+ * enlsip_gn_tsqr_first_lagrange   first_lagrange_mult_estimate! (:461-508) on the resident F_A: grad_fx (host n), or NULL for J' rx
+ *     over the ranks (then collective); diag_scale (host t) or NULL; lambda (host t), grad_res.  The arithmetic is that of
+ *     enlsip_gn_first_lagrange.  Returns 1 for a singular triangular system.
+ * enlsip_gn_tsqr_second_lagrange  second_lagrange_mult_estimate! (:514-537), collective: b = J1' (rx + J p_gn) with
+ *     J1 = (J F_A.Q)[:, 1:t] is formed as (F_A.Q' (J' (rx + J p_gn)))[1:t], from the product above and F_A.Q' on an n-vector.  It
+ *     reads no factored workspace, so the -7 of enlsip_gn_second_lagrange has no counterpart; the ROUNDING ORDER differs from the
+ *     one-GPU call (which forms J1 first), the results agree within the bound of either.
+ */
+int64_t enlsip_gn_tsqr_products_msg_len(int64_t n);
+int enlsip_gn_tsqr_products_local_dev(enlsip_gn_handle h, int64_t m_loc, int64_t n, const double* dJ, int64_t ldj, const double* drx,
+                                      const double* dp, double* dJp, double* dmsg);
+int enlsip_gn_tsqr_products_combine_dev(enlsip_gn_handle h, int64_t G, int64_t n, const double* dmsgs, double* grad, double* sums);
+int enlsip_gn_tsqr_products(enlsip_gn_handle h, const double* p, double* dJp, double* grad, double* sums, double* Ap);
+int enlsip_gn_tsqr_first_lagrange(enlsip_gn_handle h, const double* grad_fx, const double* diag_scale, double eps_rank,
+                                  double* lambda, double* grad_res);
+int enlsip_gn_tsqr_second_lagrange(enlsip_gn_handle h, const double* p_gn, const double* diag_scale, double eps_rank,
+                                   double* lambda);
+
 /* ---- instrumentation: HIP-event time (ms) of the stages of the last solve ------------------ */
 enum {
     ENLSIP_GN_STAGE_CONSTRAINT = 0, /* F_A, F_L11, p1, T factor            */
