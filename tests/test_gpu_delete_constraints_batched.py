@@ -128,18 +128,18 @@ def batch_t_q(t_max, seed, batch=BATCH):
 
 
 # ---- 1. decision and edit, 3. restore ----------------------------------------------------------------------------------------------
-def edit_cases(n, t_max, padded):
+def edit_cases(n, t_max, padded, batch=BATCH):
     """The inputs of test 1 / 3 with what the host routine and the NumPy model say about them (no GPU involved): per case the
     buffers, scaling, take, the expected s, the expected images after the delete and the rows to put back."""
-    t, q = batch_t_q(t_max, seed=n * 1000 + t_max)
+    t, q = batch_t_q(t_max, seed=n * 1000 + t_max, batch=batch)
     rng = np.random.default_rng(5)
     cases = []
-    for scaling, take, gres, record in ((True, None, True, True), (False, (rng.random(BATCH) < 0.6).astype(np.int64), True, True),
+    for scaling, take, gres, record in ((True, None, True, True), (False, (rng.random(batch) < 0.6).astype(np.int64), True, True),
                                         (True, None, False, False)):      # the last: the second-order form, no record
         buf = Buffers(n, t_max, t, padded, seed=n + 7 * t_max + int(scaling) + 2 * int(gres))
         want = buf.images()
         s_want = np.array([host_s(int(q[k]), buf.lam[k, :t[k]], scaling, buf.ds[k, :t[k]], buf.gres[k] if gres else 0.0)
-                           if (take is None or take[k]) else 0 for k in range(BATCH)], dtype=np.int64)
+                           if (take is None or take[k]) else 0 for k in range(batch)], dtype=np.int64)
         assert s_want.any() and not s_want.all()
         model_delete(buf, want, s_want, t, with_saved=record)
         back = None
@@ -147,7 +147,7 @@ def edit_cases(n, t_max, padded):
             hit = np.flatnonzero(s_want)
             assert hit.size >= 2
             pick = rng.permutation(hit)[:max(1, hit.size // 2)]
-            back = np.zeros(BATCH, dtype=np.int64)
+            back = np.zeros(batch, dtype=np.int64)
             back[pick] = s_want[pick]
         cases.append(dict(buf=buf, t=t, q=q, scaling=scaling, take=take, gres=gres, record=record, s=s_want, want=want, back=back))
     return cases
