@@ -522,6 +522,7 @@ static int run_caqr(enlsip_gn_handle h, int n2_launch) {
                 a.win = 2;
                 a.pair = 1; a.tOff2 = LB[0].tOff;
                 a.xmap = xmap_tiles(LA[0].groups);
+                if (a.xmap) GN_ROUTE(ENLSIP_GN_ROUTE_SWEEP_XMAP);
                 if (int rc = timed(btrail(k, w.ncols) + btrail(kb, w.ncols), st, [&] { update_l0(a, LA[0], w, far_grid, st); })) return rc;
                 if (mixed) {        // problems whose J2 ends before the second panel: the first panel alone, every trailing column
                     a.pair = 2;
@@ -1652,7 +1653,7 @@ int enlsip_gn_get_route(enlsip_gn_handle h, uint64_t* mask) {
 }
 
 const char* enlsip_gn_route_name(int bit) {
-    static_assert(ENLSIP_GN_ROUTE_COUNT == 51, "one name per route bit");
+    static_assert(ENLSIP_GN_ROUTE_COUNT == 52, "one name per route bit");
     static const char* const names[ENLSIP_GN_ROUTE_COUNT] = {
         "constraint_wave32", "constraint_wave64", "constraint_lds_r1_256", "constraint_lds_r1_512", "constraint_lds_r2",
         "constraint_lds_r4", "constraint_lds_r8", "constraint_lds_r16", "constraint_global", "constraint_reg4", "constraint_reg8", "constraint_dist",
@@ -1661,7 +1662,7 @@ const char* enlsip_gn_route_name(int bit) {
         "sweep_tile256", "sweep_tile512", "sweep_reflectors", "sweep_upper_input", "pivot_wave32", "pivot_wave64", "pivot_wave2",
         "pivot_lds_r1_256", "pivot_lds_r1_512", "pivot_lds_r2", "pivot_lds_r4", "pivot_lds_r8", "pivot_lds_r16", "pivot_blocks",
         "pivot_blocks_448", "pivot_blocks_512", "pivot_blocks_256", "pivot_blocks_128", "pivot_hybrid", "pivot_steps",
-        "pipeline_split", "chunked", "second_attempt", "rescaled"};
+        "pipeline_split", "chunked", "second_attempt", "rescaled", "sweep_xmap"};
     return (bit >= 0 && bit < ENLSIP_GN_ROUTE_COUNT) ? names[bit] : nullptr;
 }
 

@@ -1411,6 +1411,7 @@ enum {
     ENLSIP_GN_ROUTE_SECOND_ATTEMPT,          /* some A was rank deficient: J2 wider than speculated, redone            */
     ENLSIP_GN_ROUTE_RESCALED,                /* inputs beyond the range of plain sums of squares: solved on a copy     */
                                              /* scaled by a power of two (LAPACK's dnrm2 / dlarfg behaviour)           */
+    ENLSIP_GN_ROUTE_SWEEP_XMAP,              /* a pair's far update read its grid XCD-locally (batch <= 8, >= 16 tiles) */
     ENLSIP_GN_ROUTE_COUNT
 };
 int enlsip_gn_get_route(enlsip_gn_handle h, uint64_t* mask);

@@ -159,11 +159,12 @@ def _col_err(X, Y, nrm) -> float:
     return float(np.sqrt((D * D).sum(axis=0)).max()) / nrm if D.size else 0.0
 
 
-def check_solve_identities(acc, J, rx, A, cx, out, *, kind="full", cols=None, rows_defined=None) -> dict:
+def check_solve_identities(acc, J, rx, A, cx, out, *, kind="full", cols=None, rows_defined=None, cols_J2=None) -> dict:
     """Every identity of one solved problem, from `acc` alone (SolverAccess / OracleAccess); out: its p, d, rankA (GNResult,
     GNSolution or anything with those fields).  Exact properties (shapes, diagonals, permutations) are asserted here; the residuals
     come back in a dict for assert_within — keys orth, A.qt / A.q / A.gram, L11.*, J2.*, W, JQ1, d and d_cond (the conditioning
-    term of the d bound, eps ||J1||_2 ||p|| / ||d||, see assert_within)."""
+    term of the d bound, eps ||J1||_2 ||p|| / ||d||, see assert_within).  cols_J2: the columns of F_J2 to check where they are
+    not those of `cols` (tests/test_gpu_sweep_edges.py: every column of F_J2, the sampled ones of the small factors)."""
     J = np.asarray(J, dtype=np.float64)
     m, n = J.shape
     A = np.asarray(A, dtype=np.float64).reshape(-1, n)
@@ -194,7 +195,7 @@ def check_solve_identities(acc, J, rx, A, cx, out, *, kind="full", cols=None, ro
     JQ = np.asarray(J.astype(np.longdouble) @ QA.astype(np.longdouble), dtype=np.float64)
     nJ = _norm2(J)
     J1, J2 = JQ[:, :rankA], JQ[:, rankA:]
-    res["J2.qt"], res["J2.q"], res["J2.gram"] = check_factor_identity(FJ, J2, cols=cols, rows_defined=rows_defined,
+    res["J2.qt"], res["J2.q"], res["J2.gram"] = check_factor_identity(FJ, J2, cols=cols if cols_J2 is None else cols_J2, rows_defined=rows_defined,
                                                                       gram=kind != "graded")
     # the J1 columns the routed J*Q1 kernel wrote (the sweep starts at column rankA: k_caqr_update_refl's col0; the re-solve reads
     # them there: k_dtemp_batched), and get_JQ1

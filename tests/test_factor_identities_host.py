@@ -18,11 +18,11 @@ def test_case_list_covers_every_reachable_route_bit():
     assert fi.covered_bits(by_rule) == fi.reachable_bits()
     # below the size cap, on default handles: everything but the bits another test asserts and the bits that need a large batch
     assert names - fi.covered_bits(by_rule) == set(dg.COVERED_ELSEWHERE) | fi.NEED_LARGE_BATCH == {
-        "jq1_rows64", "jq1_plain", "sweep_reflectors", "sweep_lookahead", "sweep_upper_input", "pivot_steps", "chunked", "rescaled",
-        "pipeline_split", "sweep_pairs"}
+        "jq1_rows64", "jq1_plain", "sweep_reflectors", "sweep_lookahead", "sweep_xmap", "sweep_upper_input", "pivot_steps", "chunked",
+        "rescaled", "pipeline_split", "sweep_pairs"}
     # with the forced variants and the batch of 128: what no case of this list reaches at all
     assert fi.covered_bits(cs) <= names
-    assert names - fi.covered_bits(cs) == {"jq1_rows64", "sweep_lookahead", "sweep_upper_input", "chunked", "rescaled"}
+    assert names - fi.covered_bits(cs) == {"jq1_rows64", "sweep_lookahead", "sweep_xmap", "sweep_upper_input", "chunked", "rescaled"}
     # every kind of the grid that fits, every forced variant, the index cases
     pool_kinds = {(c["batch"], c["m"], c["n"], c["t"], c["kind"]) for c in dg.grid()
                   if c["kind"] != "full" and c["batch"] <= fi.BATCH_CAP and c["m"] * c["n"] <= fi.SIZE_CAP}

@@ -24,8 +24,11 @@ SHAPES = [(256, 32, 4), (40, 32, 4), (300, 64, 1), (192, 128, 64), (320, 256, 64
           (600, 91, 0), (700, 129, 3), (900, 257, 1), (1000, 449, 1), (1100, 513, 0), (700, 600, 20), (20, 100, 4)]
 # bits no default handle reaches at a small size: (environment set before the handle is created, handle flags)
 OWN_HANDLE = {"sweep_pairs": ({"ENLSIP_GN_PAIR": "1"}, 0), "sweep_lookahead": ({"ENLSIP_GN_PAIR": "1", "ENLSIP_GN_LOOKAHEAD": "1"}, 0),
-              "jq1_plain": ({}, 2), "sweep_reflectors": ({}, 2), "pivot_steps": ({"ENLSIP_GN_QRCP_HYBRID": "0"}, 0)}
-OWN_SHAPE = {"pivot_steps": (1100, 600, 8)}        # more than 512 rows of R0; the others: (1100, 200, 8)
+              "jq1_plain": ({}, 2), "sweep_reflectors": ({}, 2), "pivot_steps": ({"ENLSIP_GN_QRCP_HYBRID": "0"}, 0),
+              "sweep_xmap": ({"ENLSIP_GN_PAIR": "1", "ENLSIP_GN_LOOKAHEAD": "0"}, 0)}
+# more than 512 rows of R0; 16 tiles for the XCD-local grid of a pair's far update (at most 8 problems); the others: (1100, 200, 8)
+OWN_SHAPE = {"pivot_steps": (1100, 600, 8), "sweep_xmap": (8192, 100, 8)}
+UNIFORM = {"sweep_lookahead", "sweep_xmap"}        # both need one width for the whole part
 
 
 @pytest.fixture(scope="module")
@@ -118,8 +121,8 @@ def route_cases():
             continue
         if route in OWN_HANDLE:
             m, n, tm = OWN_SHAPE.get(route, (1100, 200, 8))
-            # the look-ahead sweep needs one width for the whole part: every problem ends with t_max rows (t_min = -1)
-            cases.append(pytest.param(route, m, n, tm, 5, -1 if route == "sweep_lookahead" else 0, id=f"{route}-{m}x{n}x{tm}"))
+            # the look-ahead sweep and the grid remap need one width for the whole part: every problem ends with t_max rows (t_min = -1)
+            cases.append(pytest.param(route, m, n, tm, 5, -1 if route in UNIFORM else 0, id=f"{route}-{m}x{n}x{tm}"))
             continue
         c = case_for(route)
         if c is not None:
@@ -214,7 +217,7 @@ def test_routes_bitwise_against_ragged(route, m, n, t_max, B, t_min, monkeypatch
 
 def test_every_jacobian_route_has_a_case():
     have = {c.values[0] for c in route_cases()}
-    assert len(JAC_ROUTES) == 35
+    assert len(JAC_ROUTES) == 36
     assert set(JAC_ROUTES) - NOT_RUN == have, set(JAC_ROUTES) - NOT_RUN - have
 
 
