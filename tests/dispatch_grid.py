@@ -64,8 +64,10 @@ def _rows_bucket(prefix: str, rows: int) -> str:
     return f"{prefix}_r16"
 
 
-def expected_route(batch: int, m: int, n: int, t: int, rank_deficient_A: bool = False, tile_rows: int = 512) -> set:
-    """Route bits a fresh default handle must report for a batch of (m, n, t) problems whose A has full rank."""
+def expected_route(batch: int, m: int, n: int, t: int, rank_deficient_A: bool = False, tile_rows: int = 512, layout=None) -> set:
+    """Route bits a fresh default handle must report for a batch of (m, n, t) problems whose A has full rank.  layout: (ldj,
+    strideJ, address of J in bytes) of the caller's buffer, None for a tight, aligned one: the fast J*Q1 kernel takes only the
+    layouts that pass the guard of launch_jq1_v2 (tests/layout_cases.py: v2_layout_ok), the general kernel the others."""
     r = set()
     kA = min(n, t)
     n2 = n - kA
@@ -100,7 +102,7 @@ def expected_route(batch: int, m: int, n: int, t: int, rank_deficient_A: bool = 
         r.add("jq1_fused_small")
     elif n <= 64 and kA <= Q1R_MAXK:
         r.add("jq1_rows32" if n <= 32 else "jq1_rows2")
-    elif n <= 512 and n % 128 == 0 and m % 32 == 0 and kA == KBLK and _vt_fits(m, n):
+    elif n <= 512 and n % 128 == 0 and m % 32 == 0 and kA == KBLK and _vt_fits(m, n) and _layout_fits(layout):
         r.add(f"jq1_v2_n{n}")
     else:
         r.add("jq1_mfma")
@@ -150,6 +152,13 @@ def expected_route(batch: int, m: int, n: int, t: int, rank_deficient_A: bool = 
     if rank_deficient_A:
         r.add("second_attempt")
     return r
+
+
+def _layout_fits(layout) -> bool:
+    if layout is None:
+        return True
+    from layout_cases import v2_layout_ok          # layout_cases imports this module for its constants
+    return v2_layout_ok(*layout)
 
 
 def _vt_fits(m: int, n: int) -> bool:
