@@ -41,6 +41,7 @@
 #include "gn_linesearch_fit.hpp"
 #include "gn_kernels_newton.hpp"
 #include "gn_kernels_newton_batched.hpp"
+#include "gn_kernels_newton_wide.hpp"
 #include "gn_kernels_qrcp_dist.hpp"
 #include "gn_kernels_qrcp_block.hpp"
 #include "gn_kernels_qrcp_block_reg.hpp"
@@ -1507,6 +1508,8 @@ int enlsip_gn_destroy(enlsip_gn_handle h) {
         if (e) (void)hipEventDestroy(e);
     if (h->nwb_ws.p) (void)hipFree(h->nwb_ws.p);
     if (h->nwb_io.p) (void)hipFree(h->nwb_io.p);
+    if (h->tnw_ws.p) (void)hipFree(h->tnw_ws.p);
+    if (h->tnw_io.p) (void)hipFree(h->tnw_io.p);
     if (h->ssb_req.p) (void)hipFree(h->ssb_req.p);
     if (h->ssb_io.p) (void)hipFree(h->ssb_io.p);
     if (h->rec_scr.p) (void)hipFree(h->rec_scr.p);
@@ -2441,3 +2444,4 @@ int enlsip_gn_solve(enlsip_gn_handle h, int64_t m, int64_t n, int64_t t, const d
 #include "gn_hessian_batched.inc"
 #include "gn_newton.inc"
 #include "gn_newton_batched.inc"
+#include "gn_tsqr_newton.inc"

@@ -240,6 +240,10 @@ struct enlsip_gn_context : gn::WsLayout {      // h->W, h->FA, ... : the placed 
     hipEvent_t nwb_ev[5] = {};
     bool nwb_timed = false;
     float newton_ms[4] = {};
+    // Newton direction on a row shard (gn_tsqr_newton.inc): the call's temporaries and the staging of its host form; the form of
+    // its factorisation, ENLSIP_GN_NEWTON_WIDE=0 never / =1 always the device-wide one (default: from an n2 threshold on)
+    gn::DevBuf tnw_ws, tnw_io;
+    bool newton_wide = true, newton_wide_forced = false;
     // one-call subspace minimisation (gn_subspace_batched.inc): requests and previous iterates on the device, staging of the
     // host-buffer form and the pinned copy of the final requests (chosen dimensions, status)
     gn::DevBuf ssb_req, ssb_io;
@@ -307,6 +311,8 @@ inline constexpr EnvSwitch ENV_SWITCHES[] = {
     {"ENLSIP_GN_PIPELINE", '0', &enlsip_gn_context::pipeline, false},            // never split a batch over two streams
     {"ENLSIP_GN_PIPELINE", '1', &enlsip_gn_context::pipeline_forced, true},      // split even the small uniform shapes
     {"ENLSIP_GN_LAGRANGE_SMALL", '0', &enlsip_gn_context::lagrange_small, false},  // batched multiplier estimates always in the general form
+    {"ENLSIP_GN_NEWTON_WIDE", '0', &enlsip_gn_context::newton_wide, false},        // sharded Newton direction: never the device-wide Cholesky
+    {"ENLSIP_GN_NEWTON_WIDE", '1', &enlsip_gn_context::newton_wide_forced, true},  // ... always
 };
 
 inline void read_env_switches(enlsip_gn_context* h) {

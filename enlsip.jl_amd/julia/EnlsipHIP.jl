@@ -1430,6 +1430,21 @@ function tsqr_second_lagrange_hip(h::Handle, t::Integer, p_gn::Vector{Float64}, 
     return λ
 end
 
+"""    tsqr_newton_direction(h, Γ) -> (p, not_posdef)
+
+`newton_search_direction` (src/enlsip_functions.jl:348-423) after its Hessian sums on the resident result of the handle's last
+sharded solve: `Γ = r_mat - c_mat` (n x n).  Nothing is exchanged and no shard is read; ranks that pass the same `Γ` get the same
+bits.  `not_posdef` is the reference's `error = true` (then `p` is zero)."""
+function tsqr_newton_direction(h::Handle, Γ::Matrix{Float64})
+    n = size(Γ, 1)
+    size(Γ, 2) == n || throw(DimensionMismatch("Γ must be square"))
+    p = zeros(Float64, n)
+    bad = Ref{Int64}(0)
+    GC.@preserve Γ p check(h, ccall((:enlsip_gn_tsqr_newton_direction, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Int64}), h.ptr, Γ, n, p, bad))
+    return p, bad[] != 0
+end
+
 """    tsqr_products_local_hip!(h, dJ, ldj, drx, dp, dJp, dmsg, m_loc, n)
 
 The local stage alone, for callers that move the messages themselves: device pointers in, the shard's message

@@ -254,6 +254,8 @@ PROTOTYPES = {
     "enlsip_gn_tsqr_products": (C.c_int, [_h, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "enlsip_gn_tsqr_first_lagrange": (C.c_int, [_h, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, _dp]),
     "enlsip_gn_tsqr_second_lagrange": (C.c_int, [_h, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "enlsip_gn_tsqr_newton_direction": (C.c_int, [_h, C.c_void_p, _i64, C.c_void_p, C.POINTER(C.c_int64)]),
+    "enlsip_gn_tsqr_newton_direction_dev": (C.c_int, [_h, C.c_void_p, _i64, C.c_void_p, C.c_void_p]),
     "enlsip_gn_set_profiling": (C.c_int, [_h, C.c_int]),
     "enlsip_gn_get_stage_ms": (C.c_int, [_h, C.POINTER(C.c_float)]),
     "enlsip_gn_get_update_stats": (C.c_int, [_h, C.POINTER(C.c_float), _ip, _dp]),

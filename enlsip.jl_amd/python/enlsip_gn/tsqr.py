@@ -458,6 +458,36 @@ def tsqr_second_lagrange_lib(solver: GNSolver, n: int, t: int, p_gn, diag_scale=
     return lam
 
 
+def tsqr_newton_direction_lib(solver: GNSolver, n: int, Gamma):
+    """``enlsip_gn_tsqr_newton_direction`` -> (p (n), not_posdef): newton_search_direction after its Hessian sums on the resident
+    result of the handle's last sharded solve.  ``Gamma`` = r_mat - c_mat, (n, n); NumPy's C order is transposed into the column-major
+    layout of the C ABI.  Not collective: nothing is exchanged, and ranks that pass the same Gamma get the same bits."""
+    G = np.ascontiguousarray(np.asarray(Gamma, dtype=np.float64).T)
+    assert G.shape == (n, n), (G.shape, n)
+    p = np.zeros(n)
+    bad = C.c_int64(0)
+    solver._chk(solver._lib.enlsip_gn_tsqr_newton_direction(solver._h, G.ctypes.data_as(C.c_void_p), n, p.ctypes.data_as(C.c_void_p),
+                                                            C.byref(bad)))
+    return p, bool(bad.value)
+
+
+def tsqr_newton_direction_dev(solver: GNSolver, n: int, Gamma_d, p_d=None, status_d=None, ldg: Optional[int] = None):
+    """``enlsip_gn_tsqr_newton_direction_dev`` on torch device tensors -> (p_d, status_d).  ``Gamma_d``: float64, column-major n x n
+    with leading dimension ``ldg`` (default n), i.e. a C-order (n, ldg) tensor holding Gamma'.  ``p_d`` (n, float64) and
+    ``status_d`` (1, int32) are allocated when not given; status 1 = the symmetrised W22 is not positive definite, p = 0.  The inputs
+    must be complete (the library runs on its own stream); the call returns after one synchronisation of that stream."""
+    import torch
+    dev = Gamma_d.device
+    if p_d is None:
+        p_d = torch.zeros(n, dtype=torch.float64, device=dev)
+    if status_d is None:
+        status_d = torch.zeros(1, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(dev)
+    solver._chk(solver._lib.enlsip_gn_tsqr_newton_direction_dev(solver._h, C.c_void_p(Gamma_d.data_ptr()), n if ldg is None else ldg,
+                                                                C.c_void_p(p_d.data_ptr()), C.c_void_p(status_d.data_ptr())))
+    return p_d, status_d
+
+
 def hip_products_local(solver: GNSolver, m_loc, n, dJ, ldj, drx, dp, dJp, dmsg):
     """enlsip_gn_tsqr_products_local_dev on raw device pointers (0: NULL)."""
     v = lambda x: C.c_void_p(x) if x else None

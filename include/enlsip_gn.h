@@ -1138,7 +1138,8 @@ int enlsip_gn_newton_direction(enlsip_gn_handle h, int64_t prob, const double* G
  *   Workspace: 2 n^2 + n + ldw doubles per problem of each pipelined half (1.5 GiB for 384 problems of n = 512), kept on the
  *   handle until it is destroyed.
  * enlsip_gn_get_newton_form      kernel form of the last enlsip_gn_newton_direction_batched* on this handle: 0 general (256
- *     threads per problem in the factorisation), 1 one wave per problem (n <= 64), -1 none yet.
+ *     threads per problem in the factorisation), 1 one wave per problem (n <= 64), -1 none yet; after
+ *     enlsip_gn_tsqr_newton_direction* also 2, the device-wide factorisation of its one matrix.
  * enlsip_gn_get_newton_stage_ms  HIP-event times (ms) of the four stages of the last call (b / p1 / d with the default
  *     dimensions; E; W22 and the right-hand side; factorisation, solves and p), summed over the pipelined halves that ran a part of
  *     the range; zeros unless enlsip_gn_set_profiling was on.  ms: 4 floats.
@@ -1313,6 +1314,44 @@ int enlsip_gn_tsqr_first_lagrange(enlsip_gn_handle h, const double* grad_fx, con
                                   double* lambda, double* grad_res);
 int enlsip_gn_tsqr_second_lagrange(enlsip_gn_handle h, const double* p_gn, const double* diag_scale, double eps_rank,
                                    double* lambda);
+
+/* ---- Newton direction on a row-sharded J --------------------------------------------------------------------------------------
+ * newton_search_direction (src/enlsip_functions.jl:348-423) after its Hessian sums, for the sharded caller whose
+ * check_gn_direction answered method_code == 2.  Gamma = r_mat - c_mat (n x n, column-major, ldg >= n; the Hessian sums stay with
+ * the caller, as everywhere else).  The step is the batched one (enlsip_gn_newton_direction_batched above) on what the combine stage
+ * of a sharded solve leaves resident on EVERY rank, replicated and bitwise equal:
+ *     from the handle:      F_A, tauA, F_L11.p, p1 and rankA, n2, code, dimA of its state record
+ *     from its sub-handle:  R and Pi of the stacked problem (J2 Pi = Q R), d = F_J2.Q' d_stack carried beside R, rankJ2, dimJ2
+ *     E = F_A.Q' Gamma F_A.Q, sW22 = sym(E22) + Pi R'R Pi', rhs = -E21 p1 + Pi R' d[1:kp], cholesky, two solves, p = F_A.Q [p1; p2]
+ * No row of any shard is read and NOTHING IS EXCHANGED: the call is not collective, a rank may call it alone, and ranks that pass the
+ * same Gamma get the same bits.  Special cases as in the batched form: rankA == n returns p1 as it is (:379-381); a rank-deficient
+ * working set with t >= n > rankA takes E = E[F_L11.p, F_L11.p] (:396-399).
+ *
+ * It works on the resident result of the handle's last successful enlsip_gn_solve_tsqr, or enlsip_gn_tsqr_combine_dev /
+ * _combine_scaled_dev after a local stage on the same handle; every other solve entry withdraws that, as for the
+ * enlsip_gn_tsqr_products family.  Nothing resident is rewritten: F_A, p1, both state records, the sub-handle's factors, pivots and
+ * carried d, the shard pointers and what the enlsip_gn_tsqr_products family answers stay as they were.  The call has a workspace of
+ * its own (2 n^2 + n doubles and a few words), kept on the handle until it is destroyed.
+ *
+ * Host form: Gamma, p (n), not_posdef (may be NULL) on the host, Gamma staged in and p out through a buffer of the call, one copy
+ * each way.  *not_posdef = 1 with p = 0 when the symmetrised W22 is not positive definite (:413-421; LAPACK dpotrf semantics: a pivot
+ * <= 0 or NaN), else 0.  _dev form: dGamma, dp (n) and dstatus (one int, 0 or 1; may be NULL) are DEVICE buffers.  Either form
+ * returns after one synchronisation of the handle's stream.
+ * Returns 0, or, before anything is launched and with nothing written: -1 h is NULL, -3 Gamma is NULL, -5 p is NULL, -7 no sharded
+ * solve is resident, -4 ldg < n (n is the resident sharded solve's, so this is tested after -7: without one the answer is -7 whatever
+ * ldg is), -15 the sharded solve was rescaled (enlsip_gn_tsqr_get_scale not (0, 0), or A', cx factored on
+ * a scaled copy: the rule and the reason of enlsip_gn_tsqr_products), -8 rank-deficient working set with t < n (the reference
+ * indexes out of bounds there; enlsip_gn_newton_direction's -7).
+ *
+ * The factorisation of the one n2 x n2 matrix takes one of two forms: the one-workgroup kernel of the batched call (one problem), or
+ * a right-looking blocked Cholesky spread over the device, two launches per 32-column panel and no synchronisation but the kernel
+ * boundary.  ENLSIP_GN_NEWTON_WIDE=0 / 1 (read at handle creation) never / always takes the device-wide form; DESIGN.md section 7
+ * has the measurement behind the default.  enlsip_gn_get_newton_form reports 2 after a call that took the device-wide form, else 0 / 1
+ * as above (a call with rankA == n factors nothing and reports 0 / 1 under either setting); enlsip_gn_get_newton_stage_ms returns the four stage times (set-up; E; W22 and the right-hand side; factorisation, solves
+ * and p) when profiling is on.  The two forms agree to rounding, not bit for bit.
+ */
+int enlsip_gn_tsqr_newton_direction(enlsip_gn_handle h, const double* Gamma, int64_t ldg, double* p, int64_t* not_posdef);
+int enlsip_gn_tsqr_newton_direction_dev(enlsip_gn_handle h, const double* dGamma, int64_t ldg, double* dp, int* dstatus);
 
 /* ---- instrumentation: HIP-event time (ms) of the stages of the last solve ------------------ */
 enum {
